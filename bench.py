@@ -12,7 +12,9 @@ GPU in one launch, sharded over ranks with no data-path collective (scaling "wea
 collective is the RCCL all-reduce of the metric vector.
 
 Contract: W untimed warmup steps, then exactly K timed steps between barrier +
-torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE JSON line.
+torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE JSON line
+(ms_per_step = the wall-clock of the K steps / K).  --dump-outputs DIR: rank 0 writes what the last
+timed step computed as .npy files (dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -57,6 +59,26 @@ def make_engine(N, Engine, learners, device_id, seed):
     e.fill_synthetic(CAP, seed=seed + 17)
     e.sync()
     return e
+
+
+DUMP_LEARNERS = 64      # learners whose parameters --dump-outputs writes: 64 x 54 020 params x 2 kinds x 4 B = 27.7 MB
+
+
+def dump_outputs(N, e, stats, out_dir):
+    """--dump-outputs: what the last timed learn() hands its caller, as float32 .npy files under out_dir — the stats of
+    every learner (stats.npy, [P, 1, FRL_STAT_COUNT]) and the online / target parameters of both nets
+    (<actor|critic>_<online|target>.npy, [learners, num_params]) for every learner up to DUMP_LEARNERS of them, above that
+    for a fixed sample (seed 0, ascending learner order).  The same arguments give the same inputs, run after run."""
+    os.makedirs(out_dir, exist_ok=True)
+    pick = np.arange(e.P)
+    if e.P > DUMP_LEARNERS:
+        pick = np.sort(np.random.default_rng(0).choice(e.P, DUMP_LEARNERS, replace=False))
+    arrays = {"stats": stats}
+    for net, name in ((0, "actor"), (1, "critic")):
+        for kind, kname in ((N.PARAM_ONLINE, "online"), (N.PARAM_TARGET, "target")):
+            arrays["%s_%s" % (name, kname)] = np.stack([e.get_params(net, kind, learner=int(p)) for p in pick])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 # ------------------------------------------------------------------------------------------ CPU baselines (same box)
@@ -374,6 +396,9 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="profiling runs: only the P-learner engine (no P = 1 engine, no CPU baseline), so that rocprofv3's "
                          "per-kernel averages are averages over the headline launches")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last of them computed to DIR/<name>.npy "
+                         "(float32: every learner's stats, the parameters of up to %d learners)" % DUMP_LEARNERS)
     args = ap.parse_args()
     if args.cpu_worker:
         return _cpu_worker(args.cpu_worker, args.cpu_budget, args.cpu_seed)
@@ -384,6 +409,9 @@ def main():
     from freerl_amd import dist as fdist
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
+    # before the rendezvous: a rank of a mismatched launch would otherwise wait there for ranks that never come
+    if launched and int(os.environ["WORLD_SIZE"]) != args.gpus:
+        raise SystemExit("bench.py --gpus %d but the launcher started WORLD_SIZE=%s ranks" % (args.gpus, os.environ["WORLD_SIZE"]))
     if not launched and (args.gpus > 1 or args.spawn):
         # started without a launcher: become the launcher — N ranks of this script, one per GPU, under torch.distributed.run
         have = N.device_count()
@@ -404,8 +432,6 @@ def main():
     if not torch.cuda.is_available() or N.device_count() == 0:
         raise SystemExit("bench.py needs a HIP device: the engine has no CPU fallback")
     rank, world, local_rank = fdist.init()      # under a launcher: the engine's RCCL communicator (frl_comm_create) + a gloo control plane
-    if world != args.gpus:
-        raise SystemExit("bench.py --gpus %d but the launcher started WORLD_SIZE=%d ranks" % (args.gpus, world))
     if local_rank >= N.device_count():
         raise SystemExit("rank %d: LOCAL_RANK %d but only %d HIP devices visible" % (rank, local_rank, N.device_count()))
     torch.cuda.set_device(local_rank)
@@ -431,6 +457,8 @@ def main():
     barrier()
     stats = e.stats()
     assert np.all(np.isfinite(stats)), "non-finite losses"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(N, e, stats, args.dump_outputs)
 
     # per-kernel durations of the launch chain (HIP events around every launch), outside the timed region
     e.profile(True)
