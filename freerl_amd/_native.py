@@ -24,7 +24,7 @@ FRL_COMM_ID_BYTES = 128
 FRL_COMM_MAX_VALUES = 64
 
 # enum frl_algo
-ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO = -1, 0, 1, 2, 3, 4, 5
+ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE = -1, 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
 ACT_RAW, ACT_ARGMAX, ACT_TANHHEAD, ACT_SAC_SAMPLE, ACT_PPO_SAMPLE, ACT_CAT_SAMPLE = 0, 1, 2, 3, 4, 5

@@ -36,6 +36,7 @@
 #include "kernels_c51.hip"
 #include "kernels_solo.hip"
 #include "kernels_solow.hip"
+#include "kernels_sacd.hip"
 #endif
 
 using namespace frl;
@@ -227,7 +228,7 @@ static void build_record(RecordDesc& R, const frl_config& c) {
     R.obs_total = off;
     for (int j = 0; j < c.n_agents; ++j) {
         R.act_off[j] = off;
-        R.act_dim[j] = c.discrete ? 1 : c.act_dim[j];
+        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE) ? 1 : c.act_dim[j];     // (discrete SAC: always the index)
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
@@ -326,7 +327,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_PPO) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_SAC_DISCRETE) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -356,7 +357,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     h.capacity = c.capacity;
     h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
     h.seed = c.seed;
-    h.n_discrete = (c.algo == FRL_ALGO_DQN || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    if (c.algo == FRL_ALGO_SAC_DISCRETE) {      // what kernels_sacd.hip handles: one thread per row walks the action columns
+        if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: %d actions > %d (kernels_sacd.hip)", c.act_dim[0], kSacdMaxActions); }
+        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
+    }
     build_record(h.rec, c);
     const RecordDesc& R = h.rec;
     const int H = h.hidden;
@@ -373,6 +378,13 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         build_net(h.net[0], {{H, c.obs_dim[0]}, {(c.act_dim[0] + (c.dueling ? 1 : 0)) * per_out, H}}, 1, ACT_RELU, ACT_NONE, 0,
                   c.noisy ? 1 : 0);                                                                      // MLP, DQN.py:32-45
         h.noisy_split = c.dueling ? per_out : h.net[0].L[1].n_pad;
+    } else if (c.algo == FRL_ALGO_SAC_DISCRETE) {
+        // Actor_discrete_hands_on (SAC_add_discrete.py:137-150): O -> H -> H -> A, softmax on the head (in the kernels);
+        // Critic_discrete_hands_on (:152-177): two heads l1-l3 / l4-l6 on obs only, one value per action
+        h.n_nets = 2;
+        const int O = c.obs_dim[0], A = c.act_dim[0];
+        build_net(h.net[0], {{H, O}, {H, H}, {A, H}}, 1, ACT_RELU, ACT_NONE, 0);
+        build_net(h.net[1], {{H, O}, {H, H}, {A, H}, {H, O}, {H, H}, {A, H}}, 2, ACT_RELU, ACT_NONE, 0);
     } else if (c.algo == FRL_ALGO_PPO) {
         h.n_nets = 2;
         if (c.discrete && c.actor_dist == 2) h.cat_logits = 1;     // PPO_file/PPO.py:78-90,176,257: raw logits into Categorical(logits=)
@@ -480,6 +492,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_PPO && c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, pad16(c.act_dim[0]));   // logits' delta staging
     if (c.algo == FRL_ALGO_PPO && c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
     if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
+    if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -487,7 +500,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
     // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
     // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024) h.rc = 32;
+    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE) h.rc = 32;
     // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
@@ -497,6 +510,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
     if (lds_bytes_for(h, h.rc) > 160 * 1024) { delete e; return fail(FRL_ERR_INVALID, "network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc)); }
+    if (c.algo == FRL_ALGO_SAC_DISCRETE && lds_bytes_for(h, h.rc) > 80 * 1024) {
+        delete e;
+        return fail(FRL_ERR_INVALID, "discrete SAC: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
+    }
     e->lds_bytes = lds_bytes_for(h, h.rc);
     // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
     // ceil(units * s / slots) rounds of n_chunks / s chunk-times on the chip's resident-workgroup slots, and the reduce
@@ -551,7 +568,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(dalloc_zero(&h.grad, P * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
-        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO)
+        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE)
             CREATE_TRY(dalloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
         h.Gmax = 1;
         for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
@@ -667,6 +684,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(hipFuncSetAttribute((const void*)dqn_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)ac_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)ac_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+        CREATE_TRY(hipFuncSetAttribute((const void*)sacd_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+        CREATE_TRY(hipFuncSetAttribute((const void*)sacd_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) {
@@ -1220,6 +1239,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
+    if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_act_explore: discrete SAC acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * O, out_n = rows * nout;
@@ -1462,7 +1482,7 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnArgs a, int s
     const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
     const int units = pc * h.n_agents;
     const dim3 grid_chunks(((units + 7) / 8) * 8 * ns), grid_units(units), blk(256), grid_adam(units * h.Gmax);
-    const bool sac = h.algo == ALGO_SAC, maddpg = h.algo == ALGO_MADDPG;
+    const bool sac = h.algo == ALGO_SAC || h.algo == ALGO_SAC_DISCRETE, maddpg = h.algo == ALGO_MADDPG;
     AdamArgs ad;
     memset(&ad, 0, sizeof ad);
     ad.ns = ns; ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm;
@@ -1590,6 +1610,7 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnArgs a, int s
         prof_begin(e, PK_GRAD_CRITIC);
         if (h.algo == ALGO_DQN && h.c51_atoms) hipLaunchKernelGGL(c51_grad_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
         else if (h.algo == ALGO_DQN) hipLaunchKernelGGL(dqn_grad_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
+        else if (h.algo == ALGO_SAC_DISCRETE) hipLaunchKernelGGL(sacd_critic_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
         else hipLaunchKernelGGL(ac_critic_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
         prof_end(e);
         ad.which = 0; ad.lr = a.critic_lr; ad.wd = a.critic_wd;
@@ -1638,7 +1659,8 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnArgs a, int s
             return;
         }
         prof_begin(e, PK_GRAD_ACTOR);
-        hipLaunchKernelGGL(ac_actor_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
+        if (h.algo == ALGO_SAC_DISCRETE) hipLaunchKernelGGL(sacd_actor_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
+        else hipLaunchKernelGGL(ac_actor_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
         prof_end(e);
         ad.which = 1; ad.lr = a.actor_lr; ad.wd = 0.f; ad.soft = maddpg ? 0 : 1; ad.sac_alpha = sac ? 1 : 0;
         prof_begin(e, PK_ADAM_ACTOR);
@@ -1662,7 +1684,8 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
-    if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG))
+    if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
+          h.algo == ALGO_SAC_DISCRETE))
         return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn)", h.algo);
     if (args->batch < 1 || args->batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d outside [1,%d]", args->batch, h.batch_max);
     int min_size = h.capacity;
@@ -1704,6 +1727,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     if (args->loss_kind == FRL_LOSS_HUBER) {
         if (!(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "Huber loss needs huber_delta > 0");
         if (h.c51_atoms) return fail(FRL_ERR_STATE, "the Categorical head's loss is a cross-entropy: no Huber variant");
+        if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_INVALID, "discrete SAC's critic loss is F.mse_loss (SAC_add_discrete.py:313-314): no Huber variant");
         a.huber = 1; a.huber_delta = args->huber_delta;
     }
     a.rng_counter = e->rng_counter++;
@@ -1765,6 +1789,18 @@ extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, doub
         const double m = macs(N, 0, N.n_layers);
         fl = 2 * B * m * (1 + 1 + 2);                  // target fwd, online fwd, bwd (dX+dW)
         by = 4 * B * (2 * R.obs_total + R.act_total + 2) + 24.0 * N.n_params + 8.0 * N.n_params;
+    } else if (h.algo == ALGO_SAC_DISCRETE) {
+        // kernels_sacd.hip: online actor fwd on s', target critic fwd (both heads) on s', critic fwd + bwd (dX + dW);
+        // actor stage: critic fwd (both heads, no backward), actor fwd + bwd.  No target-actor pass, no dX through the critic
+        const NetDesc &NA = h.net[0], &NC = h.net[1];
+        const double ma = macs(NA, 0, NA.n_layers), mc = macs(NC, 0, NC.n_layers);
+        double f = ma + mc + 3 * mc;
+        by = 4 * B * (2 * R.obs_total + R.act_total + 2) + 24.0 * NC.n_params;
+        if (do_actor) {
+            f += mc + 3 * ma;
+            by += 4 * B * R.obs_total + 24.0 * NA.n_params + 8.0 * (NA.n_params + NC.n_params);
+        }
+        fl = 2 * B * f;
     } else if (h.algo == ALGO_PPO) {
         fl = 0; by = 0;
     } else {
@@ -1812,6 +1848,13 @@ extern "C" int frl_learn_work_executed(const frl_engine* e, int batch, int do_ac
         const NetDesc& N = h.net[0];
         const double m = macs(N, 0, N.n_layers);
         fl = 2 * B * (m + m + m + (m - first(N)));     // target fwd, online fwd, dW, dX from the second layer up
+    } else if (h.algo == ALGO_SAC_DISCRETE) {
+        // actor fwd (s') + target critic fwd + critic fwd + dW + dX (layers 2..); actor stage: critic fwd + actor fwd + dW + dX (layers 2..)
+        const NetDesc &NA = h.net[0], &NC = h.net[1];
+        const double ma = macs(NA, 0, NA.n_layers), mc = macs(NC, 0, NC.n_layers);
+        double f = ma + mc + mc + mc + (mc - first(NC));
+        if (do_actor) f += mc + ma + ma + (ma - first(NA));
+        fl = 2 * B * f;
     } else if (h.algo != ALGO_PPO) {
         const int n = h.n_agents;
         for (int ag = 0; ag < n; ++ag) {

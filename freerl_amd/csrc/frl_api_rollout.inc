@@ -221,6 +221,7 @@ static float decayed_scale(const frl_rollout_args* ra, const frl::EnvPool* pool,
 // host_explore = 1 is round 1's loop: obs H2D, action D2H, exploration by a host generator, records staged from the host.
 extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args* ra, frl_rollout_stats* out) {
     ENG(e);
+    if (e->h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for discrete SAC engines");
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;

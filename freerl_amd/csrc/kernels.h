@@ -136,6 +136,11 @@ __global__ void c51_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, 
 // kernels_critic.hip
 __global__ void ac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 
+// kernels_sacd.hip: discrete SAC (SAC_file/SAC_add_discrete.py), row-chunk gradient kernels
+constexpr int kSacdMaxActions = 64;
+__global__ void sacd_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void sacd_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

@@ -38,7 +38,9 @@ enum frl_algo {
     FRL_ALGO_TD3 = 2,          /* TD3_file/TD3.py:150-256 */
     FRL_ALGO_SAC = 3,          /* SAC_file/SAC.py:171-282 */
     FRL_ALGO_MADDPG = 4,       /* MADDPG_file/MADDPG_simple.py:107-210 */
-    FRL_ALGO_PPO = 5           /* PPO_file/PPO_with_tricks.py:211-374, PPO.py */
+    FRL_ALGO_PPO = 5,          /* PPO_file/PPO_with_tricks.py:211-374, PPO.py */
+    FRL_ALGO_SAC_DISCRETE = 6  /* SAC_file/SAC_add_discrete.py:137-348 (is_continue=False): softmax actor, twin critics with one
+                                  value per action; one agent, actions stored as one float index, act_dim[0] = number of actions */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2 };
