@@ -15,6 +15,9 @@ Contract: W untimed warmup steps, then exactly K timed steps between barrier +
 torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints ONE JSON line
 (ms_per_step = the wall-clock of the K steps / K).  --dump-outputs DIR: rank 0 writes what the last
 timed step computed as .npy files (dump_outputs), so that two builds can be compared output for output.
+That is all a plain run does.  --full adds everything else the benchmark measures, each figure from runs of its own after the
+timed steps: per-kernel times and the roofline of the headline engine, the rollout loop, single learners, BASELINE configs 4 and 5,
+the DQN roofline and loop, the drop-in classes and the CPU baselines.
 """
 import argparse
 import json
@@ -366,6 +369,62 @@ def fifty_x_statement(gpu_by_rows, cpu_loops):
     return {"ratio_by_ring_rows": {("%d" % n): r for n, r in pts}, "ring_rows_for_50x": cross, "statement": text}
 
 
+def single_learner_figures(N, Engine, device_id):
+    """Single-learner latency (P = 1): the reference's own case — one learn() per env step (TD3.py:403-450).  One learner of this
+    shape runs kernels_solo.hip (sixteen workgroups per learner, slab sum + Adam behind a grid barrier).  Returns (TD3 updates/s,
+    detail)."""
+    single = None
+    single_detail = {"unit": "us per learn(), one learner, asynchronous calls", "batch": BATCH}
+    for name, algo, twin, kw in (("td3", N.ALGO_TD3, True, None), ("ddpg", N.ALGO_DDPG, False, {}),
+                                 ("sac", N.ALGO_SAC, True, dict(alpha_lr=1e-4, target_entropy=-float(ACT)))):
+        if name == "td3":
+            e1 = make_engine(N, Engine, 1, device_id, seed=7)
+        else:
+            e1 = Engine(algo, OBS, ACT, 100_000, n_learners=1, twin_critic=twin, batch_max=BATCH, hidden=HIDDEN, device_id=device_id, seed=7)
+            g1 = np.random.default_rng(7)
+            for net in range(2):
+                flat = (g1.standard_normal(e1.num_params(net)) * 0.05).astype(np.float32)
+                e1.set_params(net, flat, N.PARAM_ONLINE); e1.set_params(net, flat, N.PARAM_TARGET)
+            if algo == N.ALGO_SAC:
+                e1.set_alpha_state([np.log(0.01), 0, 0, 0.01])
+            e1.fill_synthetic(100_000, seed=5)
+        call = (lambda k: e1.learn(BATCH, **td3_kwargs(k))) if name == "td3" else \
+            (lambda k: e1.learn(BATCH, gamma=0.99, tau=0.005, actor_lr=1e-3, critic_lr=1e-3, **kw))
+        for k in range(20):
+            call(k)
+        e1.sync()
+        t1 = time.perf_counter()
+        n1 = 1000
+        for k in range(n1):
+            call(k)
+        e1.sync()
+        dt1 = (time.perf_counter() - t1) / n1
+        path = e1.learn_path(BATCH)
+        single_detail[name] = dt1 * 1e6
+        single_detail["kernel_family"] = "solo: 16 workgroups per learner (kernels_solo.hip)" if path[2] == 16 and path[0] else ("chained" if path[0] else "row-chunk")
+        if name == "td3":
+            single = 1.0 / dt1
+        e1.close()
+    # ... and sixteen learners: the largest population of the same kernels (16 x 16 workgroups = every CU of the chip)
+    try:
+        e16 = make_engine(N, Engine, 16, device_id, seed=7)
+        for k in range(20):
+            e16.learn(BATCH, **td3_kwargs(k))
+        e16.sync()
+        t1 = time.perf_counter()
+        for k in range(400):
+            e16.learn(BATCH, **td3_kwargs(k))
+        e16.sync()
+        dt16 = (time.perf_counter() - t1) / 400
+        p16 = e16.learn_path(BATCH)
+        single_detail["td3_16_learners"] = {"us_per_learn": dt16 * 1e6, "updates_per_sec": 16 / dt16,
+                                            "kernel_family": "solo" if p16[2] == 16 and p16[0] else ("chained" if p16[0] else "row-chunk")}
+        e16.close()
+    except Exception as ex:                       # a detail of the report, never the reason a bench line is missing
+        single_detail["td3_16_learners"] = {"error": str(ex)[:200]}
+    return single, single_detail
+
+
 def traffic_figure():
     """HBM bytes per ac_critic_kernel launch from the PMC passes (profiles/traffic.json, written by tools/pmc_summary.py
     --traffic together with a digest of the kernel sources it was measured on).  Returns (bytes | None, stale)."""
@@ -380,6 +439,48 @@ def traffic_figure():
     return t.get("hbm_bytes_per_launch"), (t.get("kernel_source_digest") != kernel_source_digest())
 
 
+def roofline_figures(e, prof, kernel_ms, steps):
+    """The headline engine against the fp32 MFMA roofline: the dominant kernel's per-launch duration from the profile pass (`prof`,
+    HIP events around every launch), the step's from the timed launches (`kernel_ms`, MAX over ranks), flops from frl_learn_work."""
+    fl_a, by_a = e.learn_work(BATCH, True)
+    fl_c, by_c = e.learn_work(BATCH, False)
+    fx_a, fx_c = e.learn_work_executed(BATCH, True), e.learn_work_executed(BATCH, False)
+    n_act = sum(1 for k in range(steps) if k % 2 == 1)
+    step_s = kernel_ms * 1e-3 / steps
+    kern = {k: {"avg_ms": v[0] / v[1], "launches": v[1]} for k, v in prof.items()}
+    # dominant kernel: the critic stage.  At this population it is ac_critic_v2_twin_nv_kernel (kernels_critic2.hip; _nv = the
+    # record layout allows 16-byte row loads): targets, twin-critic forward / backward, clip + Adam + soft update of one learner per
+    # eight-wave workgroup in ONE launch ("adam_critic" absent from the per-kernel times); up to 128 learners ac_critic_kernel +
+    # adam_fused_kernel.  Its flops are the same
+    # algorithmic figure either way (frl_learn_work): the Adam / soft-update phase adds HBM bytes, not flops.
+    fused = "adam_critic" not in kern
+    dominant = "ac_critic_v2_twin_nv_kernel" if fused else "ac_critic_kernel"
+    launch_s = kern["grad_critic"]["avg_ms"] * 1e-3
+    stage_s = launch_s + (0.0 if fused else kern["adam_critic"]["avg_ms"] * 1e-3)
+    achieved = fl_c / launch_s / 1e12
+    flops, abytes = fl_c, by_c
+    traffic, traffic_stale = traffic_figure()
+    return {"bound": "mfma", "achieved": achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_stale": traffic_stale,
+            "kernel": dominant, "avg_launch_ms": launch_s * 1e3,
+            "critic_stage_ms": stage_s * 1e3, "critic_stage_tflops": fl_c / stage_s / 1e12,
+            "note": "round 6: eight-wave workgroups (two waves per SIMD, every wave inside 256 registers) - FRL_CHAIN_WAVES=4 runs "
+                    "rounds 2-5's four-wave kernels on the same box; the clip + Adam phase (~17 % of the launch) streams "
+                    "theta / m / v at the chip's HBM rate with every CU in it at once and is not overlapped with MFMA work",
+            "flops_per_launch": flops, "algorithmic_bytes_per_launch": abytes,
+            "flops_convention": "achieved / frac: SURVEY 8(d)'s formula, 2 B sum(in x out) x (#fwd + 2 x #bwd) (frl_learn_work); "
+                                "*_executed: the flops autograd and these kernels execute - no first-layer dX of a trained net, "
+                                "action columns only for dQ/da (frl_learn_work_executed)",
+            "flops_executed_per_launch": fx_c, "achieved_executed": fx_c / launch_s / 1e12,
+            "frac_executed": fx_c / launch_s / 1e12 / FP32_MFMA_PEAK_TFLOPS,
+            "step_tflops_executed": (fx_a * n_act + fx_c * (steps - n_act)) / steps / step_s / 1e12,
+            "hbm_bound_frac": abytes / launch_s / 1e9 / HBM_PEAK_GBS,
+            "step_flops_avg": (fl_a * n_act + fl_c * (steps - n_act)) / steps,
+            "step_ms_avg": step_s * 1e3,
+            "step_tflops": (fl_a * n_act + fl_c * (steps - n_act)) / steps / step_s / 1e12,
+            "kernels": kern}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -387,15 +488,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--learners", type=int, default=int(os.environ.get("FRL_BENCH_LEARNERS", "512")),
                     help="independent learners (seeds) per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (per-kernel times, roofline, rollout loop, single "
+                         "learners, configs 4 and 5, DQN, drop-in classes, CPU baselines); off: set up, warm up, time, dump, print")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baselines")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)       # internal: one CPU-baseline worker process
     ap.add_argument("--cpu-budget", type=float, default=6.0, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-seed", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--spawn", action="store_true",
                     help="go through the launcher even for --gpus 1 (RCCL init + the metric all-reduce with one rank)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="profiling runs: only the P-learner engine (no P = 1 engine, no CPU baseline), so that rocprofv3's "
-                         "per-kernel averages are averages over the headline launches")
+                    help="profiling runs with --full: only the P-learner engine's figures (per-kernel times, roofline, rollout; no "
+                         "P = 1 engine, no CPU baseline), so that rocprofv3's per-kernel averages are averages over the headline launches")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 writes what the last of them computed to DIR/<name>.npy "
                          "(float32: every learner's stats, the parameters of up to %d learners)" % DUMP_LEARNERS)
@@ -460,112 +564,46 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(N, e, stats, args.dump_outputs)
 
-    # per-kernel durations of the launch chain (HIP events around every launch), outside the timed region
-    e.profile(True)
-    for k in range(args.steps):
-        e.learn(BATCH, **td3_kwargs(k))
-    prof = e.profile_read()
-    e.profile(False)
+    if args.full:
+        # per-kernel durations of the launch chain (HIP events around every launch), outside the timed region
+        e.profile(True)
+        for k in range(args.steps):
+            e.learn(BATCH, **td3_kwargs(k))
+        prof = e.profile_read()
+        e.profile(False)
 
-    # env-steps/s: the full rollout-and-update loop (act + exploration on the device -> env.step on the host pool ->
-    # add -> learn, one env per learner = the reference's UTD 1) on the synthetic obs-8/act-2 task
-    from freerl_amd.envpool import EnvPool, rollout
-    pool = EnvPool("SynLinear-v0", P, n_threads=8, seed=1000 + rank)
-    rollout(e, pool, max(args.warmup, 20), start_steps=0, batch=BATCH)
-    barrier()
-    # the loop is host-paced (env workers, launch latency): one short sample is noise (537 k / 615 k / 661 k for one build in round 3),
-    # so the reported figure is the MEDIAN of five rollouts of >= 200 vector steps each, with the spread next to it
-    ro_runs = [rollout(e, pool, max(200, args.steps), start_steps=0, batch=BATCH) for _ in range(5)]
-    ro_runs.sort(key=lambda r: r["env_steps"] / r["seconds"])
-    ro = ro_runs[len(ro_runs) // 2]
-    ro_rates = [r["env_steps"] / r["seconds"] for r in ro_runs]
-    pool.close()
+        # env-steps/s: the full rollout-and-update loop (act + exploration on the device -> env.step on the host pool ->
+        # add -> learn, one env per learner = the reference's UTD 1) on the synthetic obs-8/act-2 task
+        from freerl_amd.envpool import EnvPool, rollout
+        pool = EnvPool("SynLinear-v0", P, n_threads=8, seed=1000 + rank)
+        rollout(e, pool, max(args.warmup, 20), start_steps=0, batch=BATCH)
+        barrier()
+        # the loop is host-paced (env workers, launch latency): one short sample is noise (537 k / 615 k / 661 k for one build in round 3),
+        # so the reported figure is the MEDIAN of five rollouts of >= 200 vector steps each, with the spread next to it
+        ro_runs = [rollout(e, pool, max(200, args.steps), start_steps=0, batch=BATCH) for _ in range(5)]
+        ro_runs.sort(key=lambda r: r["env_steps"] / r["seconds"])
+        ro = ro_runs[len(ro_runs) // 2]
+        ro_rates = [r["env_steps"] / r["seconds"] for r in ro_runs]
+        pool.close()
 
     # the path's only collective: the metric vector, summed over ranks / wall-clock maxed (RCCL over xGMI)
     learn_m = fdist.allreduce_metrics(env_steps=0.0, updates=float(P * args.steps), return_sum=0.0, episodes=0.0,
                                       loss_sum=float(np.mean(stats[:, 0, N.STAT_CRITIC_LOSS])), wall_s=dt, extra_max=[kernel_ms])
-    roll_m = fdist.allreduce_metrics(env_steps=float(ro["env_steps"]), updates=float(ro["updates"]), return_sum=ro["return_sum"],
-                                     episodes=float(ro["episodes"]), loss_sum=0.0, wall_s=ro["seconds"])
     dt_max, total_updates, kernel_ms = learn_m["wall_s_max"], learn_m["updates"], learn_m["extra_max"][0]
-    env_sps = fdist.throughput(roll_m)["env_steps_per_sec"]
-    ro_ups = fdist.throughput(roll_m)["updates_per_sec"]
+    if args.full:
+        roll_m = fdist.allreduce_metrics(env_steps=float(ro["env_steps"]), updates=float(ro["updates"]), return_sum=ro["return_sum"],
+                                         episodes=float(ro["episodes"]), loss_sum=0.0, wall_s=ro["seconds"])
+        env_sps = fdist.throughput(roll_m)["env_steps_per_sec"]
+        ro_ups = fdist.throughput(roll_m)["updates_per_sec"]
     backend = fdist.collective_name()
     fdist.finalize()          # every rank leaves the collective window here; what follows is rank 0's own work
 
     if rank == 0:
-        fl_a, by_a = e.learn_work(BATCH, True)
-        fl_c, by_c = e.learn_work(BATCH, False)
-        fx_a, fx_c = e.learn_work_executed(BATCH, True), e.learn_work_executed(BATCH, False)
-        n_act = sum(1 for k in range(args.steps) if k % 2 == 1)
-        step_s = kernel_ms * 1e-3 / args.steps
-        kern = {k: {"avg_ms": v[0] / v[1], "launches": v[1]} for k, v in prof.items()}
-        # dominant kernel: the critic stage.  At this population it is ac_critic_v2_twin_nv_kernel (kernels_critic2.hip; _nv = the
-        # record layout allows 16-byte row loads): targets, twin-critic forward / backward, clip + Adam + soft update of one learner per
-        # eight-wave workgroup in ONE launch ("adam_critic" absent from the per-kernel times); up to 128 learners ac_critic_kernel +
-        # adam_fused_kernel.  Its flops are the same
-        # algorithmic figure either way (frl_learn_work): the Adam / soft-update phase adds HBM bytes, not flops.
-        fused = "adam_critic" not in kern
-        dominant = "ac_critic_v2_twin_nv_kernel" if fused else "ac_critic_kernel"
-        launch_s = kern["grad_critic"]["avg_ms"] * 1e-3
-        stage_s = launch_s + (0.0 if fused else kern["adam_critic"]["avg_ms"] * 1e-3)
-        achieved = fl_c / launch_s / 1e12
-        flops, abytes = fl_c, by_c
         chained, lds, rc = e.learn_path(BATCH)
+        if args.full:
+            roofline = roofline_figures(e, prof, kernel_ms, args.steps)
     e.close()
     if rank == 0:
-        # single-learner latency (P = 1): the reference's own case — one learn() per env step (TD3.py:403-450).  One learner of this
-        # shape runs kernels_solo.hip (sixteen workgroups per learner, slab sum + Adam behind a grid barrier)
-        single, single_detail = None, None
-        if not args.headline_only:
-            single_detail = {"unit": "us per learn(), one learner, asynchronous calls", "batch": BATCH}
-            for name, algo, twin, kw in (("td3", N.ALGO_TD3, True, None), ("ddpg", N.ALGO_DDPG, False, {}),
-                                         ("sac", N.ALGO_SAC, True, dict(alpha_lr=1e-4, target_entropy=-float(ACT)))):
-                if name == "td3":
-                    e1 = make_engine(N, Engine, 1, local_rank, seed=7)
-                else:
-                    e1 = Engine(algo, OBS, ACT, 100_000, n_learners=1, twin_critic=twin, batch_max=BATCH, hidden=HIDDEN, device_id=local_rank, seed=7)
-                    g1 = np.random.default_rng(7)
-                    for net in range(2):
-                        flat = (g1.standard_normal(e1.num_params(net)) * 0.05).astype(np.float32)
-                        e1.set_params(net, flat, N.PARAM_ONLINE); e1.set_params(net, flat, N.PARAM_TARGET)
-                    if algo == N.ALGO_SAC:
-                        e1.set_alpha_state([np.log(0.01), 0, 0, 0.01])
-                    e1.fill_synthetic(100_000, seed=5)
-                call = (lambda k: e1.learn(BATCH, **td3_kwargs(k))) if name == "td3" else \
-                    (lambda k: e1.learn(BATCH, gamma=0.99, tau=0.005, actor_lr=1e-3, critic_lr=1e-3, **kw))
-                for k in range(20):
-                    call(k)
-                e1.sync()
-                t1 = time.perf_counter()
-                n1 = 1000
-                for k in range(n1):
-                    call(k)
-                e1.sync()
-                dt1 = (time.perf_counter() - t1) / n1
-                path = e1.learn_path(BATCH)
-                single_detail[name] = dt1 * 1e6
-                single_detail["kernel_family"] = "solo: 16 workgroups per learner (kernels_solo.hip)" if path[2] == 16 and path[0] else ("chained" if path[0] else "row-chunk")
-                if name == "td3":
-                    single = 1.0 / dt1
-                e1.close()
-            # ... and sixteen learners: the largest population of the same kernels (16 x 16 workgroups = every CU of the chip)
-            try:
-                e16 = make_engine(N, Engine, 16, local_rank, seed=7)
-                for k in range(20):
-                    e16.learn(BATCH, **td3_kwargs(k))
-                e16.sync()
-                t1 = time.perf_counter()
-                for k in range(400):
-                    e16.learn(BATCH, **td3_kwargs(k))
-                e16.sync()
-                dt16 = (time.perf_counter() - t1) / 400
-                p16 = e16.learn_path(BATCH)
-                single_detail["td3_16_learners"] = {"us_per_learn": dt16 * 1e6, "updates_per_sec": 16 / dt16,
-                                                    "kernel_family": "solo" if p16[2] == 16 and p16[0] else ("chained" if p16[0] else "row-chunk")}
-                e16.close()
-            except Exception as ex:                       # a detail of the report, never the reason a bench line is missing
-                single_detail["td3_16_learners"] = {"error": str(ex)[:200]}
-        traffic, traffic_stale = traffic_figure()
         line = {
             "metric": "learner_updates_per_sec", "value": total_updates / dt_max, "unit": "updates/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt_max * 1e3 / args.steps,
@@ -577,46 +615,32 @@ def main():
                        "rows_per_workgroup": rc, "lds_bytes": lds,
                        "parallelism": "seeds sharded over %d GPU(s), no data-path collective" % world,
                        "collective": "metric all-reduce: %s" % backend},
-            "env_steps_per_sec": env_sps,
-            "rollout": {"env": "SynLinear-v0 (obs 8, act 2)", "envs_per_learner": 1, "env_workers": 8,
-                        "updates_per_sec_in_loop": ro_ups,
-                        "sample": "median of 5 rollouts of %d vector steps (this rank: min %.0f, median %.0f, max %.0f env-steps/s)"
-                                  % (max(200, args.steps), ro_rates[0], ro_rates[len(ro_rates) // 2], ro_rates[-1]),
-                        "loop": "act kernel with device-side exploration -> D2H actions -> host env pool step -> staged add "
-                                "(one H2D) -> learn"},
-            "single_learner_updates_per_sec": single, "single_learner": single_detail,
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / FP32_MFMA_PEAK_TFLOPS, "traffic": traffic, "traffic_stale": traffic_stale,
-                         "kernel": dominant, "avg_launch_ms": launch_s * 1e3,
-                         "critic_stage_ms": stage_s * 1e3, "critic_stage_tflops": fl_c / stage_s / 1e12,
-                         "note": "round 6: eight-wave workgroups (two waves per SIMD, every wave inside 256 registers) - FRL_CHAIN_WAVES=4 runs "
-                                 "rounds 2-5's four-wave kernels on the same box; the clip + Adam phase (~17 % of the launch) streams "
-                                 "theta / m / v at the chip's HBM rate with every CU in it at once and is not overlapped with MFMA work",
-                         "flops_per_launch": flops, "algorithmic_bytes_per_launch": abytes,
-                         "flops_convention": "achieved / frac: SURVEY 8(d)'s formula, 2 B sum(in x out) x (#fwd + 2 x #bwd) (frl_learn_work); "
-                                             "*_executed: the flops autograd and these kernels execute - no first-layer dX of a trained net, "
-                                             "action columns only for dQ/da (frl_learn_work_executed)",
-                         "flops_executed_per_launch": fx_c, "achieved_executed": fx_c / launch_s / 1e12,
-                         "frac_executed": fx_c / launch_s / 1e12 / FP32_MFMA_PEAK_TFLOPS,
-                         "step_tflops_executed": (fx_a * n_act + fx_c * (args.steps - n_act)) / args.steps / step_s / 1e12,
-                         "hbm_bound_frac": abytes / launch_s / 1e9 / HBM_PEAK_GBS,
-                         "step_flops_avg": (fl_a * n_act + fl_c * (args.steps - n_act)) / args.steps,
-                         "step_ms_avg": step_s * 1e3,
-                         "step_tflops": (fl_a * n_act + fl_c * (args.steps - n_act)) / args.steps / step_s / 1e12,
-                         "kernels": kern},
-            "baseline_configs_one_learner": None if args.headline_only else baseline_configs_one_learner(local_rank),
-            "roofline_dqn": None if args.headline_only else dqn_roofline(local_rank),
-            "dropin_classes": None if args.headline_only else dropin_classes(),
-            "dqn_single_learner_loop": None if args.headline_only else dqn_single_learner_loop(args.learners),
-            "cpu_baseline": None if (args.no_cpu_baseline or args.headline_only) else cpu_baseline(),
         }
-        cb, dl = line["cpu_baseline"], line["dqn_single_learner_loop"]
-        if cb and dl:     # north_star's ">= 50x the reference CPU env-steps/s": same loop, same box, same ring, GPU engine / CPU port
-            dl["vs_cpu_port_same_box"] = fifty_x_statement(dl["by_ring_rows"], cb["dqn_loop_env_steps_per_sec"])
-            small, full = cb["dqn_loop_env_steps_per_sec"]["replay %d rows" % DQN_LOOP_ROWS[0]], cb["dqn_loop_env_steps_per_sec"]["replay %d rows" % DQN_LOOP_ROWS[-1]]
-            dl["vs_cpu_port_same_box"]["population_vs_all_cores"] = {
-                "ring 1e5 rows on the GPU / 1e4 on the CPU (its fastest)": dl["population"]["env_steps_per_sec"] / small["all_cores"],
-                "ring 1e5 rows on the GPU / 1e6 on the CPU": dl["population"]["env_steps_per_sec"] / full["all_cores"]}
+        if args.full:
+            single, single_detail = (None, None) if args.headline_only else single_learner_figures(N, Engine, local_rank)
+            line.update({
+                "env_steps_per_sec": env_sps,
+                "rollout": {"env": "SynLinear-v0 (obs 8, act 2)", "envs_per_learner": 1, "env_workers": 8,
+                            "updates_per_sec_in_loop": ro_ups,
+                            "sample": "median of 5 rollouts of %d vector steps (this rank: min %.0f, median %.0f, max %.0f env-steps/s)"
+                                      % (max(200, args.steps), ro_rates[0], ro_rates[len(ro_rates) // 2], ro_rates[-1]),
+                            "loop": "act kernel with device-side exploration -> D2H actions -> host env pool step -> staged add "
+                                    "(one H2D) -> learn"},
+                "single_learner_updates_per_sec": single, "single_learner": single_detail,
+                "roofline": roofline,
+                "baseline_configs_one_learner": None if args.headline_only else baseline_configs_one_learner(local_rank),
+                "roofline_dqn": None if args.headline_only else dqn_roofline(local_rank),
+                "dropin_classes": None if args.headline_only else dropin_classes(),
+                "dqn_single_learner_loop": None if args.headline_only else dqn_single_learner_loop(args.learners),
+                "cpu_baseline": None if (args.no_cpu_baseline or args.headline_only) else cpu_baseline(),
+            })
+            cb, dl = line["cpu_baseline"], line["dqn_single_learner_loop"]
+            if cb and dl:     # north_star's ">= 50x the reference CPU env-steps/s": same loop, same box, same ring, GPU engine / CPU port
+                dl["vs_cpu_port_same_box"] = fifty_x_statement(dl["by_ring_rows"], cb["dqn_loop_env_steps_per_sec"])
+                small, full = cb["dqn_loop_env_steps_per_sec"]["replay %d rows" % DQN_LOOP_ROWS[0]], cb["dqn_loop_env_steps_per_sec"]["replay %d rows" % DQN_LOOP_ROWS[-1]]
+                dl["vs_cpu_port_same_box"]["population_vs_all_cores"] = {
+                    "ring 1e5 rows on the GPU / 1e4 on the CPU (its fastest)": dl["population"]["env_steps_per_sec"] / small["all_cores"],
+                    "ring 1e5 rows on the GPU / 1e6 on the CPU": dl["population"]["env_steps_per_sec"] / full["all_cores"]}
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(line) + "\n").encode())
 

@@ -3,7 +3,7 @@
 # ("" = the product library; anything else = FRL_HIP_VARIANT).  Prints updates/s, ms per step, the critic stage's fraction, per-kernel ms.
 R=$(cd "$(dirname "$0")/.." && pwd)
 for v in "$@"; do
-  FRL_HIP_VARIANT=$v python $R/bench.py --headline-only --steps ${STEPS:-20} --warmup 3 2>/dev/null | python -c "
+  FRL_HIP_VARIANT=$v python $R/bench.py --full --headline-only --steps ${STEPS:-20} --warmup 3 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/dev; rm -rf $O; mkdir -p $O; cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1 < /dev/null; grep -E "passed|failed" $O/pytest.log | tail -n 2; grep -E "^(FAILED|ERROR)" $O/pytest.log | head
 for i in 1 2; do
-timeout 300 python bench.py --headline-only --steps 40 --warmup 4 > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null
+timeout 300 python bench.py --full --headline-only --steps 40 --warmup 4 > $O/bench_headline.json 2> $O/bench_headline.err < /dev/null
 python - <<'PY'
 import json
 d=json.load(open('gpurun_out/dev/bench_headline.json')); r=d['roofline']

@@ -3,7 +3,7 @@
 #   gpurun --timeout 900 -- 'bash tools/population_sweep.sh'
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/sweep; mkdir -p $O; cd $R
 for P in 64 128 256 384 512 768 1024 1536; do
-  timeout 300 python bench.py --headline-only --steps 30 --warmup 4 --learners $P > $O/b_$P.json 2> $O/b_$P.err < /dev/null
+  timeout 300 python bench.py --full --headline-only --steps 30 --warmup 4 --learners $P > $O/b_$P.json 2> $O/b_$P.err < /dev/null
   P=$P python - <<'PY'
 import json, os
 P = os.environ['P']

@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/prof
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 20 --warmup 2 --headline-only"
+BENCH="python $R/bench.py --full --steps 20 --warmup 2 --headline-only"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- $BENCH > $O/stats.log 2>&1
 cp $(ls $O/stats/*/*kernel_stats.csv | head -1) $O/kernel_stats.csv
 i=0
@@ -41,8 +41,8 @@ for a in td3 ddpg sac; do FRL_HIP_VARIANT=solot timeout 120 python tools/solo_ti
 timeout 300 python tools/critic2_timing.py 512 > $O/critic2_timing.txt 2>&1
 FRL_CHAIN_WAVES=4 timeout 300 python tools/critic2_timing.py 512 > $O/critic2_timing_w4.txt 2>&1        # (round 5's four-wave kernel, same box)
 FRL_HIP_VARIANT=bwdt timeout 300 python tools/bwd_timing.py 512 > $O/bwd_timing.txt 2>&1 < /dev/null   # FRL_UNIT_OUT=bwdt FRL_UNIT_FLAGS=-DFRL_BWD_TIMING bash tools/build_unit_timing.sh kernels_critic2
-FRL_CHAIN_WAVES=4 timeout 300 python bench.py --headline-only --steps 60 --warmup 3 > $O/bench_headline_w4.json 2>/dev/null   # the A/B of the round: four-wave kernels ...
-timeout 300 python bench.py --headline-only --steps 60 --warmup 3 > $O/bench_headline_w8.json 2>/dev/null                      # ... against the eight-wave ones
+FRL_CHAIN_WAVES=4 timeout 300 python bench.py --full --headline-only --steps 60 --warmup 3 > $O/bench_headline_w4.json 2>/dev/null   # the A/B of the round: four-wave kernels ...
+timeout 300 python bench.py --full --headline-only --steps 60 --warmup 3 > $O/bench_headline_w8.json 2>/dev/null                      # ... against the eight-wave ones
 timeout 120 $R/tools/_bin/lds_put > $O/lds_put.txt 2>&1
 timeout 300 python tools/actor2_timing.py 512 td3 > $O/actor2_timing.txt 2>&1
 timeout 300 python tools/actor2_timing.py 512 sac >> $O/actor2_timing.txt 2>&1
@@ -68,7 +68,7 @@ timeout 300 python tools/ppo_bench.py 1 64 256 > $O/ppo_bench.txt 2>&1
 timeout 600 python tools/rollout_bench.py 1 512 > $O/rollout_bench.txt 2>&1
 timeout 300 python tools/config4_rollout.py 1 8 32 > $O/config4_rollout.txt 2>&1
 FRL_CRITIC_V2=0 FRL_HIP_VARIANT=phase FRL_HIPCC_FLAGS=-DFRL_PHASE_TIMING timeout 200 python tools/phase_timing.py 1 > $O/phase_critic_p1.txt 2>&1 < /dev/null
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 300 python bench.py --spawn --headline-only --steps 10 --warmup 2 > $O/bench_spawn1.json 2> $O/bench_spawn1.err
 rm -rf $O/stats $O/stats_solo $O/stats_ppo $O/stats_dqn $O/stats_cfg $O/pmc[0-9]     # keep the summaries only (gpurun_out is size-capped)
 ls -la $O
