@@ -54,17 +54,4 @@ __device__ __forceinline__ f32x4 mfma4(f32x4 acc, const f32x4& a, const f32x4& b
     return acc;
 }
 
-// torch's single-tensor Adam on one element (clip coefficient already folded into g).  The moments are exact fp32
-// fma chains like everywhere else; the step itself, step * m / (sqrt(v) / sqrt(bc2) + eps), uses the hardware's 1-ulp
-// sqrt and reciprocal instead of the correctly rounded sequences (3 x ~10 VALU instructions per element, 88 elements per
-// lane and step: the difference between a 28 k and an 8 k cycle Adam phase).  Its relative error (<= ~3 ulp of the UPDATE,
-// which is itself ~lr times smaller than the parameter) is below the rounding of the subtraction that applies it.
-__device__ __forceinline__ float adam_elem(float th, float g, float& m, float& v, float w1, float w2, float b2, float inv_bc2s,
-                                           float eps, float step) {
-    m = m + (g - m) * w1;
-    v = v * b2 + (w2 * g) * g;
-    const float denom = __builtin_amdgcn_sqrtf(v) * inv_bc2s + eps;
-    return th - step * (m * __builtin_amdgcn_rcpf(denom));
-}
-
 }  // namespace frl

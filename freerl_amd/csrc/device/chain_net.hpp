@@ -62,10 +62,6 @@ struct HeadGradT {
 };
 using HeadGrad = HeadGradT<4>;
 
-// (no flags in here: the update runs inside MFMA chains, where a branch would cut the scheduling region — the soft target update is
-// a template argument of the functions below, weight decay is applied unconditionally: g + 0 * theta = g)
-struct AdamCoef { float coef, step, inv_bc2s, w1, w2, beta2, eps, wd, tk, tau; };
-
 // The four parameter arrays of one net of one learner as raw buffer resources: the update addresses them as
 // buffer_load/store_dwordx4 v, <lane offset VGPR>, s[rsrc], <tile offset: SGPR / literal> — one VGPR of address state for the
 // whole update instead of a 64-bit pointer per array and tile (which the register allocator spilled inside the MFMA chains).

@@ -10,6 +10,7 @@
 // plain read-modify-write).  Parameters / Adam state / targets are streamed once per step by the Adam kernels.
 #pragma once
 #include "../frl_desc.h"
+#include "adam.hpp"
 #include "rng.hpp"
 #include "tile.hpp"
 
@@ -535,17 +536,6 @@ __device__ __forceinline__ void zero_cols(lds_f X, int ldx, int rc, int c0, int 
     }
 }
 
-// beta^t in double by repeated squaring (torch computes `beta ** step` in Python floats)
-__device__ __forceinline__ double powi_d(double b, int t) {
-    double r = 1.0;
-    while (t > 0) {
-        if (t & 1) r *= b;
-        b *= b;
-        t >>= 1;
-    }
-    return r;
-}
-
 // Global-norm clip + Adam (+ optional soft target update) over one net's parameter block.
 // torch semantics: clip_grad_norm_(params, clip) then optim.Adam.step() (single-tensor order),
 // then theta_t <- theta_t*(1-tau) + theta*tau.  Returns the pre-clip gradient norm.
@@ -563,43 +553,29 @@ __device__ __forceinline__ float adam_net(int size, g_f theta, g_f m, g_f v, g_c
     }
     for (int i = 4 * n4 + threadIdx.x; i < size; i += kWG) ss += g[i] * g[i];
     const float total = sqrtf(block_sum(ss, red));
-    float coef = 1.f;
-    if (clip_norm > 0.f) coef = fminf(clip_norm / (total + 1e-6f), 1.f);
-    const double bc1 = 1.0 - powi_d((double)b1, t_new);
-    const double bc2 = 1.0 - powi_d((double)b2, t_new);
-    const float step = (float)((double)lr / bc1);
-    const float bc2s = (float)sqrt(bc2);
-    const float w1 = 1.f - b1, w2 = 1.f - b2, tk = 1.f - tau;
+    const AdamCoef c = adam_coef(total, clip_norm, t_new, lr, b1, b2, eps, wd, tau);
     FRL_GLB f32x4* th4 = (FRL_GLB f32x4*)theta;
     FRL_GLB f32x4* m4 = (FRL_GLB f32x4*)m;
     FRL_GLB f32x4* v4 = (FRL_GLB f32x4*)v;
     FRL_GLB f32x4* t4 = (FRL_GLB f32x4*)target;
 #pragma unroll 4
     for (int i = threadIdx.x; i < n4; i += kWG) {
-        f32x4 gi = g4[i] * coef, th = th4[i], mi = m4[i], vi = v4[i];
+        f32x4 gi = g4[i] * c.coef, th = th4[i], mi = m4[i], vi = v4[i];
         if (wd != 0.f) gi += wd * th;
-        mi = mi + (gi - mi) * w1;
-        vi = vi * b2 + (w2 * gi) * gi;
-        f32x4 denom;
-        denom.x = sqrtf(vi.x) / bc2s + eps; denom.y = sqrtf(vi.y) / bc2s + eps;
-        denom.z = sqrtf(vi.z) / bc2s + eps; denom.w = sqrtf(vi.w) / bc2s + eps;
-        th = th - step * (mi / denom);
+        th = adam_exact4(th, gi, mi, vi, c.w1, c.w2, b2, c.bc2s, eps, c.step);
         m4[i] = mi; v4[i] = vi; th4[i] = th;
-        if (target) t4[i] = t4[i] * tk + th * tau;
+        if (target) t4[i] = t4[i] * c.tk + th * tau;
     }
     for (int i = 4 * n4 + threadIdx.x; i < size; i += kWG) {
-        float gi = g[i] * coef;
+        float gi = g[i] * c.coef;
         float th = theta[i];
         if (wd != 0.f) gi += wd * th;
-        float mi = m[i];
-        mi = mi + (gi - mi) * w1;
-        const float vi = v[i] * b2 + (w2 * gi) * gi;
-        const float denom = sqrtf(vi) / bc2s + eps;
-        th = th - step * (mi / denom);
+        float mi = m[i], vi = v[i];
+        th = adam_exact1(th, gi, mi, vi, c.w1, c.w2, b2, c.bc2s, eps, c.step);
         m[i] = mi;
         v[i] = vi;
         theta[i] = th;
-        if (target) target[i] = target[i] * tk + th * tau;
+        if (target) target[i] = target[i] * c.tk + th * tau;
     }
     return total;
 }

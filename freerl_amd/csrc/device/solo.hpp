@@ -489,24 +489,16 @@ __device__ __forceinline__ float solo_update(const SoloArgs& s, const LearnArgs&
 #pragma unroll
     for (int sb = 0; sb < W; ++sb) tot += red[80 + sb];
     const float total = sqrtf(tot);
-    const float coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
-    const double bc1 = 1.0 - powi_d((double)a.beta1, u.t_new), bc2 = 1.0 - powi_d((double)a.beta2, u.t_new);
-    const float step = (float)((double)u.lr / bc1), bc2s = (float)sqrt(bc2);
-    const float w1 = 1.f - a.beta1, w2 = 1.f - a.beta2, tk = 1.f - a.tau;
+    const AdamCoef c = adam_coef(total, a.clip_norm, u.t_new, u.lr, a.beta1, a.beta2, a.adam_eps, u.wd, a.tau);
 #pragma unroll
     for (int k = 0; k < KM; ++k) {
         const int i = i0 + tid + kWG * k;
         if (i < i1) {
-            f32x4 gi = g[k] * coef, t4 = th[k], m4 = mi[k], v4 = vi[k];
+            f32x4 gi = g[k] * c.coef, t4 = th[k], m4 = mi[k], v4 = vi[k];
             if (u.wd != 0.f) gi += u.wd * t4;
-            m4 = m4 + (gi - m4) * w1;
-            v4 = v4 * a.beta2 + (w2 * gi) * gi;
-            f32x4 den;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) den[r] = sqrtf(v4[r]) / bc2s + a.adam_eps;
-            t4 = t4 - step * (m4 / den);
+            t4 = adam_exact4(t4, gi, m4, v4, c.w1, c.w2, a.beta2, c.bc2s, a.adam_eps, c.step);
             st4(u.th + 4 * i, t4); st4(u.mm + 4 * i, m4); st4(u.vv + 4 * i, v4);
-            if (u.soft) st4(u.tg + 4 * i, tg[k] * tk + t4 * a.tau);
+            if (u.soft) st4(u.tg + 4 * i, tg[k] * c.tk + t4 * a.tau);
         }
     }
     return total;

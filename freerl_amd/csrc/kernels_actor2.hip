@@ -271,6 +271,8 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
     const float qtot = red_sum(8);
     const float lptot = red_sum(16);
     const int t = __float_as_int(S.red[56]) + 1;
+    // (filled here rather than by adam_coef: the bias corrections ahead of the clip coefficient, the order this kernel's register
+    // allocation was tuned with — adam_coef's order costs the four-wave instance two registers)
     const double bc1 = 1.0 - powi_d((double)a.beta1, t), bc2 = 1.0 - powi_d((double)a.beta2, t);
     AdamCoef co;
     co.coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
@@ -284,28 +286,9 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
     if (tid == 0) {
         steps[0] = t;
         float* st = D.stats + (size_t)p * ST_COUNT;
-        st[ST_ACTOR_LOSS] = sac ? (-(qtot * 0.5f) + alpha * lptot) * invB : -qtot * invB;   // SAC.py:251: (alpha log pi - Q).mean()
+        st[ST_ACTOR_LOSS] = actor_loss_stat(sac, qtot, lptot, alpha, invB);
         st[ST_ACTOR_GNORM] = total;
-        if (sac) {                                                     // alpha step on the batch's entropy (SAC.py:154-169,257-260)
-            float* al = D.alpha + p * 4;
-            const float ent_mean = -lptot * invB;
-            const float mean_term = ent_mean - a.target_entropy;
-            const float gl = alpha * mean_term;                        // d alpha_loss / d log_alpha
-            const int ta = steps[kMaxNets] + 1;
-            float mi = al[1], vi = al[2];
-            mi = mi + (gl - mi) * (1.f - a.beta1);
-            vi = vi * a.beta2 + ((1.f - a.beta2) * gl) * gl;
-            const double b1 = 1.0 - powi_d((double)a.beta1, ta), b2 = 1.0 - powi_d((double)a.beta2, ta);
-            const float denom = sqrtf(vi) / (float)sqrt(b2) + 1e-8f;
-            al[0] = al[0] - (float)((double)a.alpha_lr / b1) * (mi / denom);
-            al[1] = mi;
-            al[2] = vi;
-            al[3] = expf(al[0]);
-            steps[kMaxNets] = ta;
-            st[ST_ALPHA_LOSS] = alpha * mean_term;
-            st[ST_ALPHA] = al[3];
-            st[ST_ENTROPY] = ent_mean;
-        }
+        if (sac) sac_alpha_step(D.alpha + p * 4, st, steps, alpha, -lptot * invB, a.target_entropy, a.beta1, a.beta2, a.alpha_lr);
     }
 }
 

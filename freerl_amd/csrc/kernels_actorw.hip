@@ -286,12 +286,7 @@ __device__ __forceinline__ void ac_actor_wide_body(const EngineDesc& D, const Le
     const float qtot = ((S.red[8] + S.red[9]) + S.red[10]) + S.red[11];
     const float lptot = ((S.red[12] + S.red[13]) + S.red[14]) + S.red[15];
     const int tstep = __float_as_int(S.red[32]) + 1;
-    const double bc1 = 1.0 - powi_d((double)a.beta1, tstep), bc2 = 1.0 - powi_d((double)a.beta2, tstep);
-    AdamCoef co;
-    co.coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
-    co.step = (float)((double)a.actor_lr / bc1); co.inv_bc2s = 1.f / (float)sqrt(bc2);
-    co.w1 = 1.f - a.beta1; co.w2 = 1.f - a.beta2; co.beta2 = a.beta2; co.eps = a.adam_eps; co.wd = 0.f;
-    co.tk = 1.f - a.tau; co.tau = a.tau;
+    const AdamCoef co = adam_coef(total, a.clip_norm, tstep, a.actor_lr, a.beta1, a.beta2, a.adam_eps, 0.f, a.tau);
     WIDE_T(9);
     if (nag == 1) W.adam_stream<true>(thA, mA, vA, tgA, (g_cf)grA, NA.size >> 2, co);
     else W.adam_stream<false>(thA, mA, vA, tgA, (g_cf)grA, NA.size >> 2, co);
@@ -300,28 +295,9 @@ __device__ __forceinline__ void ac_actor_wide_body(const EngineDesc& D, const Le
     if (tid == 0) {
         steps[2 * ag] = tstep;
         float* st = D.stats + ((size_t)p * nag + ag) * ST_COUNT;
-        st[ST_ACTOR_LOSS] = sac ? (-(qtot * 0.5f) + alpha * lptot) * invB : -qtot * invB;   // SAC.py:251: (alpha log pi - Q).mean()
+        st[ST_ACTOR_LOSS] = actor_loss_stat(sac, qtot, lptot, alpha, invB);
         st[ST_ACTOR_GNORM] = total;
-        if (sac) {                                                     // alpha step on the batch's entropy (SAC.py:154-169,257-260)
-            float* al = D.alpha + p * 4;
-            const float ent_mean = -lptot * invB;
-            const float mean_term = ent_mean - a.target_entropy;
-            const float gl = alpha * mean_term;                        // d alpha_loss / d log_alpha
-            const int ta = steps[kMaxNets] + 1;
-            float mi = al[1], vi = al[2];
-            mi = mi + (gl - mi) * (1.f - a.beta1);
-            vi = vi * a.beta2 + ((1.f - a.beta2) * gl) * gl;
-            const double b1 = 1.0 - powi_d((double)a.beta1, ta), b2 = 1.0 - powi_d((double)a.beta2, ta);
-            const float denom = sqrtf(vi) / (float)sqrt(b2) + 1e-8f;
-            al[0] = al[0] - (float)((double)a.alpha_lr / b1) * (mi / denom);
-            al[1] = mi;
-            al[2] = vi;
-            al[3] = expf(al[0]);
-            steps[kMaxNets] = ta;
-            st[ST_ALPHA_LOSS] = alpha * mean_term;
-            st[ST_ALPHA] = al[3];
-            st[ST_ENTROPY] = ent_mean;
-        }
+        if (sac) sac_alpha_step(D.alpha + p * 4, st, steps, alpha, -lptot * invB, a.target_entropy, a.beta1, a.beta2, a.alpha_lr);
     }
 }
 

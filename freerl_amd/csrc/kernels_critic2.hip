@@ -344,12 +344,7 @@ __device__ __forceinline__ void ac_critic_v2_body(const EngineDesc& D, const Lea
     for (int i = 1; i < NW; ++i) { tot2 += S.red[i]; loss += S.red[8 + i]; }
     const float total = sqrtf(tot2);
     const int t = __float_as_int(S.red[16]) + 1;
-    const double bc1 = 1.0 - powi_d((double)a.beta1, t), bc2 = 1.0 - powi_d((double)a.beta2, t);
-    AdamCoef co;
-    co.coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
-    co.step = (float)((double)a.critic_lr / bc1); co.inv_bc2s = 1.f / (float)sqrt(bc2);
-    co.w1 = 1.f - a.beta1; co.w2 = 1.f - a.beta2; co.beta2 = a.beta2; co.eps = a.adam_eps; co.wd = a.critic_wd;
-    co.tk = 1.f - a.tau; co.tau = a.tau;
+    const AdamCoef co = adam_coef(total, a.clip_norm, t, a.critic_lr, a.beta1, a.beta2, a.adam_eps, a.critic_wd, a.tau);
 #if !(FRL_ABL & 1)
     if (a.do_actor != 0) {                                             // TD3: targets move with the delayed policy step (TD3.py:224-233)
         static_for<0, NH>([&](auto hd) { C.template adam_head<true, decltype(hd)::value, decltype(hd)::value == NH - 1>(G[decltype(hd)::value], thC, mC, vC, tgCw, co); });

@@ -238,12 +238,7 @@ __device__ __forceinline__ void ac_critic_wide_body(const EngineDesc& D, const L
     const float total = sqrtf(((S.red[0] + S.red[1]) + S.red[2]) + S.red[3]);
     const float loss = ((S.red[8] + S.red[9]) + S.red[10]) + S.red[11];
     const int tstep = __float_as_int(S.red[16]) + 1;
-    const double bc1 = 1.0 - powi_d((double)a.beta1, tstep), bc2 = 1.0 - powi_d((double)a.beta2, tstep);
-    AdamCoef co;
-    co.coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
-    co.step = (float)((double)a.critic_lr / bc1); co.inv_bc2s = 1.f / (float)sqrt(bc2);
-    co.w1 = 1.f - a.beta1; co.w2 = 1.f - a.beta2; co.beta2 = a.beta2; co.eps = a.adam_eps; co.wd = a.critic_wd;
-    co.tk = 1.f - a.tau; co.tau = a.tau;
+    const AdamCoef co = adam_coef(total, a.clip_norm, tstep, a.critic_lr, a.beta1, a.beta2, a.adam_eps, a.critic_wd, a.tau);
     WIDE_T(9);
     // single agent: the target moves here (TD3: with the delayed policy step, TD3.py:224-233); MADDPG: soft_update_kernel afterwards
     // (every agent's workgroups read every target actor)

@@ -242,6 +242,8 @@ __device__ __forceinline__ void ac_critic_x_body(const EngineDesc& D, const Lear
     const float total = sqrtf(((N.red[0] + N.red[1]) + N.red[2]) + N.red[3]);
     const float loss = ((N.red[8] + N.red[9]) + N.red[10]) + N.red[11];
     const int tstep = __float_as_int(N.red[16]) + 1;
+    // (filled here rather than by adam_coef: the bias corrections ahead of the clip coefficient, the order this kernel's register
+    // allocation was tuned with — adam_coef's order moves its SGPR spills and spill code)
     const double bc1 = 1.0 - powi_d((double)a.beta1, tstep), bc2 = 1.0 - powi_d((double)a.beta2, tstep);
     AdamCoef co;
     co.coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;

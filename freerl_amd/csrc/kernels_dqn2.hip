@@ -480,17 +480,12 @@ __global__ __launch_bounds__(256, 2) void dqn_fused_kernel(const EngineDesc* __r
     const float total = sqrtf(((S.red[0] + S.red[1]) + S.red[2]) + S.red[3]);
     const float loss = ((S.red[8] + S.red[9]) + S.red[10]) + S.red[11];
     const int t = __float_as_int(S.red[16]) + 1;
-    const float coef = a.clip_norm > 0.f ? fminf(a.clip_norm / (total + 1e-6f), 1.f) : 1.f;
-    const double bc1 = 1.0 - powi_d((double)a.beta1, t), bc2 = 1.0 - powi_d((double)a.beta2, t);
-    const float step = (float)((double)a.critic_lr / bc1), bc2s = (float)sqrt(bc2);
-    const float w1 = 1.f - a.beta1, w2 = 1.f - a.beta2, tk = 1.f - a.tau;
+    const AdamCoef co = adam_coef(total, a.clip_norm, t, a.critic_lr, a.beta1, a.beta2, a.adam_eps, a.critic_wd, a.tau);
     auto adam1 = [&](float gi, float& thi, float& mi, float& vi, float& tgi) {
-        gi *= coef;
+        gi *= co.coef;
         if (a.critic_wd != 0.f) gi += a.critic_wd * thi;
-        mi = mi + (gi - mi) * w1;
-        vi = vi * a.beta2 + (w2 * gi) * gi;
-        thi = thi - step * (mi / (sqrtf(vi) / bc2s + a.adam_eps));
-        tgi = tgi * tk + thi * a.tau;
+        thi = adam_exact1(thi, gi, mi, vi, co.w1, co.w2, a.beta2, co.bc2s, a.adam_eps, co.step);
+        tgi = tgi * co.tk + thi * a.tau;
     };
     // (s.act: the updated weights also go into the online net's LDS image — this lane's four values sit in four 16-byte
     // slots of its fragment tile, the owner-write pattern of device/chain.hpp)

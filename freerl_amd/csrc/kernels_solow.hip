@@ -540,28 +540,9 @@ __device__ __forceinline__ void solow_actor_body(const EngineDesc& D, const Lear
         }
         steps[2 * ag] = t_new;
         float* sts = D.stats + (size_t)unit * ST_COUNT;
-        sts[ST_ACTOR_LOSS] = sac ? (-(qtot * 0.5f) + alpha * lptot) * invB : -qtot * invB;   // SAC.py:251: (alpha log pi - Q).mean()
+        sts[ST_ACTOR_LOSS] = actor_loss_stat(sac, qtot, lptot, alpha, invB);
         sts[ST_ACTOR_GNORM] = total;
-        if (sac) {                                                         // alpha step on the batch's entropy (SAC.py:154-169,257-260)
-            float* al = D.alpha + p * 4;
-            const float ent_mean = -lptot * invB;
-            const float mean_term = ent_mean - a.target_entropy;
-            const float gl = alpha * mean_term;                            // d alpha_loss / d log_alpha
-            const int ta = steps[kMaxNets] + 1;
-            float mi = al[1], vi = al[2];
-            mi = mi + (gl - mi) * (1.f - a.beta1);
-            vi = vi * a.beta2 + ((1.f - a.beta2) * gl) * gl;
-            const double b1 = 1.0 - powi_d((double)a.beta1, ta), b2 = 1.0 - powi_d((double)a.beta2, ta);
-            const float denom = sqrtf(vi) / (float)sqrt(b2) + 1e-8f;
-            al[0] = al[0] - (float)((double)a.alpha_lr / b1) * (mi / denom);
-            al[1] = mi;
-            al[2] = vi;
-            al[3] = expf(al[0]);
-            steps[kMaxNets] = ta;
-            sts[ST_ALPHA_LOSS] = alpha * mean_term;
-            sts[ST_ALPHA] = al[3];
-            sts[ST_ENTROPY] = ent_mean;
-        }
+        if (sac) sac_alpha_step(D.alpha + p * 4, sts, steps, alpha, -lptot * invB, a.target_entropy, a.beta1, a.beta2, a.alpha_lr);
     }
 }
 

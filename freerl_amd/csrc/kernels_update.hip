@@ -126,24 +126,7 @@ __device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs
     st[a.which == 0 ? ST_CRITIC_GNORM : ST_ACTOR_GNORM] = total;
     if (a.sac_alpha) {
         float* al = D.alpha + p * 4;
-        const float alpha = al[3];
-        const float ent_mean = l1 * invB;
-        const float mean_term = ent_mean - a.target_entropy;
-        const float gl = alpha * mean_term;            // d alpha_loss / d log_alpha
-        const int ta = steps[kMaxNets] + 1;
-        float mi = al[1], vi = al[2];
-        mi = mi + (gl - mi) * (1.f - a.beta1);
-        vi = vi * a.beta2 + ((1.f - a.beta2) * gl) * gl;
-        const double b1 = 1.0 - powi_d((double)a.beta1, ta), b2 = 1.0 - powi_d((double)a.beta2, ta);
-        const float denom = sqrtf(vi) / (float)sqrt(b2) + 1e-8f;
-        al[0] = al[0] - (float)((double)a.alpha_lr / b1) * (mi / denom);
-        al[1] = mi;
-        al[2] = vi;
-        al[3] = expf(al[0]);
-        steps[kMaxNets] = ta;
-        st[ST_ALPHA_LOSS] = alpha * mean_term;
-        st[ST_ALPHA] = al[3];
-        st[ST_ENTROPY] = ent_mean;
+        sac_alpha_step(al, st, steps, al[3], l1 * invB, a.target_entropy, a.beta1, a.beta2, a.alpha_lr);
     }
 }
 
@@ -210,6 +193,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict_
     float ss = 0.f;
     for (int k = 0; k < Gn; ++k) ss += D.gsq[(size_t)unit * D.Gmax + k];      // same order in every workgroup
     const float total = sqrtf(ss);
+    // (adam_coef's arithmetic written out: adam_coef would put the step count's load ahead of the clip coefficient, which changes this
+    // kernel's register allocation)
     float coef = 1.f;
     if (a.clip > 0.f) coef = fminf(a.clip / (total + 1e-6f), 1.f);
     int* steps = D.steps + (size_t)p * (kMaxNets + 1);
@@ -229,12 +214,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict_
         if (i < n4) {
             f32x4 gi = g[i] * coef, thi = th[i], mi = m[i], vi = v[i];
             if (a.wd != 0.f) gi += a.wd * thi;
-            mi = mi + (gi - mi) * w1;
-            vi = vi * a.beta2 + (w2 * gi) * gi;
-            f32x4 denom;
-            denom.x = sqrtf(vi.x) / bc2s + a.eps; denom.y = sqrtf(vi.y) / bc2s + a.eps;
-            denom.z = sqrtf(vi.z) / bc2s + a.eps; denom.w = sqrtf(vi.w) / bc2s + a.eps;
-            thi = thi - step * (mi / denom);
+            thi = adam_exact4(thi, gi, mi, vi, w1, w2, a.beta2, bc2s, a.eps, step);
             m[i] = mi; v[i] = vi; th[i] = thi;
             if (a.soft) tg[i] = tg[i] * tk + thi * a.tau;
         }
@@ -320,11 +300,7 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
 #pragma unroll
     for (int w = 0; w < kFusedThreads / 64; ++w) tot += red[w];
     const float total = sqrtf(tot);
-    float coef = 1.f;
-    if (a.clip > 0.f) coef = fminf(a.clip / (total + 1e-6f), 1.f);
-    const double bc1 = 1.0 - powi_d((double)a.beta1, t), bc2 = 1.0 - powi_d((double)a.beta2, t);
-    const float step = (float)((double)a.lr / bc1), bc2s = (float)sqrt(bc2);
-    const float w1 = 1.f - a.beta1, w2 = 1.f - a.beta2, tk = 1.f - a.tau;
+    const AdamCoef c = adam_coef(total, a.clip, t, a.lr, a.beta1, a.beta2, a.eps, a.wd, a.tau);
     FRL_GLB f32x4* th = (FRL_GLB f32x4*)(D.theta + off);
     FRL_GLB f32x4* m = (FRL_GLB f32x4*)(D.m + off);
     FRL_GLB f32x4* v = (FRL_GLB f32x4*)(D.v + off);
@@ -333,16 +309,11 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
     for (int j = 0; j < VEC; ++j) {
         const int i = j * kFusedThreads + threadIdx.x;
         if (i < n4) {
-            f32x4 gi = g[j] * coef, thi = th[i], mi = m[i], vi = v[i];
+            f32x4 gi = g[j] * c.coef, thi = th[i], mi = m[i], vi = v[i];
             if (a.wd != 0.f) gi += a.wd * thi;
-            mi = mi + (gi - mi) * w1;
-            vi = vi * a.beta2 + (w2 * gi) * gi;
-            f32x4 denom;
-            denom.x = sqrtf(vi.x) / bc2s + a.eps; denom.y = sqrtf(vi.y) / bc2s + a.eps;
-            denom.z = sqrtf(vi.z) / bc2s + a.eps; denom.w = sqrtf(vi.w) / bc2s + a.eps;
-            thi = thi - step * (mi / denom);
+            thi = adam_exact4(thi, gi, mi, vi, c.w1, c.w2, a.beta2, c.bc2s, a.eps, c.step);
             m[i] = mi; v[i] = vi; th[i] = thi;
-            if (a.soft) tg[i] = tg[i] * tk + thi * a.tau;
+            if (a.soft) tg[i] = tg[i] * c.tk + thi * a.tau;
         }
     }
     if (threadIdx.x == 0) {
