@@ -24,7 +24,7 @@ FRL_COMM_ID_BYTES = 128
 FRL_COMM_MAX_VALUES = 64
 
 # enum frl_algo
-ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE = -1, 0, 1, 2, 3, 4, 5, 6
+ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE, ALGO_REINFORCE = -1, 0, 1, 2, 3, 4, 5, 6, 7
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
 ACT_RAW, ACT_ARGMAX, ACT_TANHHEAD, ACT_SAC_SAMPLE, ACT_PPO_SAMPLE, ACT_CAT_SAMPLE = 0, 1, 2, 3, 4, 5
@@ -72,6 +72,11 @@ class PpoArgs(C.Structure):
                 ("optimizer", C.c_int), ("perms", C.POINTER(C.c_int64)), ("loss_trace_out", C.POINTER(C.c_float)),
                 ("adv_out", C.POINTER(C.c_float)), ("vtarget_out", C.POINTER(C.c_float)),
                 ("gae_mode", C.c_int), ("last_value", C.POINTER(C.c_float)), ("gae_gamma", C.c_double), ("gae_lmbda", C.c_double)]
+
+
+class ReinforceArgs(C.Structure):
+    _fields_ = [("n_steps", C.POINTER(C.c_int)), ("gamma", C.c_double), ("lr", C.c_float), ("adam_eps", C.c_float),
+                ("loss_out", C.POINTER(C.c_float)), ("returns_out", C.POINTER(C.c_float))]
 
 
 class ExploreArgs(C.Structure):
@@ -156,6 +161,7 @@ SIGNATURES = {
     "frl_solo_debug_read": (_i, [_vp, _fp, _i]),
     "frl_learn_work_executed": (_i, [_vp, _i, _i, _P(C.c_double)]),
     "frl_ppo_learn": (_i, [_vp, _P(PpoArgs)]),
+    "frl_reinforce_learn": (_i, [_vp, _P(ReinforceArgs)]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

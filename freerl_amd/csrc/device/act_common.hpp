@@ -83,8 +83,13 @@ __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs&
             }
             a.out[row] = (float)best;
             if (a.env_out) a.env_out[row] = (float)best;
-            if (a.out_logp) a.out_logp[row] = D.cat_logits ? (outb[r * op + best] - mx) - logf(sum)          // Categorical(logits=)
-                                                           : logf(fminf(fmaxf(pbest / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f));
+            if (a.out_logp) {
+                const float qc = fminf(fmaxf(pbest / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f);
+                // (REINFORCE records this value as the step's log-prob: the correctly rounded logarithm, so that a clamped row reads
+                // log(eps) / log(1 - eps) to the bit as it does in the reference; logf is one ulp off at eps)
+                a.out_logp[row] = D.cat_logits ? (outb[r * op + best] - mx) - logf(sum)          // Categorical(logits=)
+                                               : (D.algo == ALGO_REINFORCE ? (float)log((double)qc) : logf(qc));
+            }
         }
         return;
     }

@@ -37,6 +37,7 @@
 #include "kernels_solo.hip"
 #include "kernels_solow.hip"
 #include "kernels_sacd.hip"
+#include "kernels_reinforce.hip"
 #endif
 
 using namespace frl;
@@ -136,6 +137,10 @@ struct frl_engine {
     double per_beta = 0.4, per_beta_inc = 0.001;
     std::vector<int> bucket_cursor;
     std::vector<int> size_flushed;        // rows valid per learner as of the last flush (PER_Buffer.add's `len(self.buffer) == 0`)
+    // frl_reinforce_learn: the learners' row counts of a call, staged in two alternating pinned slots (the call does not wait for the stream)
+    int* h_ep_n = nullptr;                // [2][P] pinned
+    hipEvent_t ev_ep[2] = {nullptr, nullptr};
+    unsigned ep_seq = 0;
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
     int lds_per_cu = 160 * 1024;          // LDS bytes of one compute unit
@@ -228,7 +233,7 @@ static void build_record(RecordDesc& R, const frl_config& c) {
     R.obs_total = off;
     for (int j = 0; j < c.n_agents; ++j) {
         R.act_off[j] = off;
-        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE) ? 1 : c.act_dim[j];     // (discrete SAC: always the index)
+        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE) ? 1 : c.act_dim[j];     // (discrete SAC, REINFORCE: always the index)
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
@@ -279,6 +284,9 @@ extern "C" int frl_destroy(frl_engine* e) {
     if (e->d_solo_bar) hipFree(e->d_solo_bar);
     if (e->d_solow_bar2) hipFree(e->d_solow_bar2);
     if (e->h_solo_err) hipHostFree(e->h_solo_err);
+    if (e->h_ep_n) hipHostFree(e->h_ep_n);
+    if (e->h.ep_n) hipFree(e->h.ep_n);
+    for (hipEvent_t ev : e->ev_ep) if (ev) hipEventDestroy(ev);
     float* dev[] = {e->h.act_spill, e->h.theta_eff, e->h.noisy_eps, e->h.isw, e->h.td_err, e->h.theta, e->h.target, e->h.m, e->h.v, e->h.grad, e->h.replay, e->h.noise, e->h.stats, e->h.alpha,
                     e->d_stage_rows, e->d_act_in, e->d_act_eps, e->d_act_out, e->d_act_logp, e->d_ppo, e->d_act_wk, e->h.wide_scr};
     for (float* p : dev) if (p) hipFree(p);
@@ -327,7 +335,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_SAC_DISCRETE) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_REINFORCE) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -356,8 +364,13 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (h.hidden % 16) { delete e; return fail(FRL_ERR_INVALID, "hidden must be a multiple of 16"); }
     h.capacity = c.capacity;
     h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
+    if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;
-    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    if (c.algo == FRL_ALGO_REINFORCE) {         // what kernels_reinforce.hip handles: discrete SAC's limits, for the same reasons
+        if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: %d actions > %d (kernels_reinforce.hip)", c.act_dim[0], kSacdMaxActions); }
+        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
+    }
     if (c.algo == FRL_ALGO_SAC_DISCRETE) {      // what kernels_sacd.hip handles: one thread per row walks the action columns
         if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: %d actions > %d (kernels_sacd.hip)", c.act_dim[0], kSacdMaxActions); }
         if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
@@ -385,6 +398,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         const int O = c.obs_dim[0], A = c.act_dim[0];
         build_net(h.net[0], {{H, O}, {H, H}, {A, H}}, 1, ACT_RELU, ACT_NONE, 0);
         build_net(h.net[1], {{H, O}, {H, H}, {A, H}, {H, O}, {H, H}, {A, H}}, 2, ACT_RELU, ACT_NONE, 0);
+    } else if (c.algo == FRL_ALGO_REINFORCE) {
+        h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
+        build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
     } else if (c.algo == FRL_ALGO_PPO) {
         h.n_nets = 2;
         if (c.discrete && c.actor_dist == 2) h.cat_logits = 1;     // PPO_file/PPO.py:78-90,176,257: raw logits into Categorical(logits=)
@@ -500,7 +516,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
     // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
     // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE) h.rc = 32;
+    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE) h.rc = 32;
     // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
@@ -513,6 +529,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_SAC_DISCRETE && lds_bytes_for(h, h.rc) > 80 * 1024) {
         delete e;
         return fail(FRL_ERR_INVALID, "discrete SAC: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
+    }
+    if (c.algo == FRL_ALGO_REINFORCE && lds_bytes_for(h, h.rc) > 80 * 1024) {
+        delete e;
+        return fail(FRL_ERR_INVALID, "REINFORCE: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
     }
     e->lds_bytes = lds_bytes_for(h, h.rc);
     // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
@@ -568,7 +588,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(dalloc_zero(&h.grad, P * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
-        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE)
+        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE)
             CREATE_TRY(dalloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
         h.Gmax = 1;
         for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
@@ -591,6 +611,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(dalloc_zero(&h.steps, P * (kMaxNets + 1), e->stream));
         CREATE_TRY(dalloc_zero(&h.ticket, P + 1, e->stream));
         CREATE_TRY(dalloc_zero(&h.alpha, P * 4, e->stream));
+        if (c.algo == FRL_ALGO_REINFORCE) {
+            CREATE_TRY(dalloc_zero(&h.ep_n, P, e->stream));
+            CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
+            for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
         if (h.solo || h.solow) {
             e->solo_stride = 0;
             for (int i = 0; i < h.n_nets; ++i) e->solo_stride = std::max(e->solo_stride, h.net[i].size);
@@ -686,6 +711,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(hipFuncSetAttribute((const void*)ac_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)sacd_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)sacd_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+        CREATE_TRY(hipFuncSetAttribute((const void*)reinforce_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) {
@@ -753,6 +779,7 @@ static int dqn_split_for(const EngineDesc& h, int batch, int pc) {
 extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, int* bytes_out, int* rows_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     if (e->h.algo == ALGO_PPO) return fail(FRL_ERR_INVALID, "frl_learn_path describes frl_learn(); PPO updates go through frl_ppo_learn");
+    if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_path describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
     if (batch <= 0 || batch > e->h.batch_max) return fail(FRL_ERR_INVALID, "batch out of range");
     if (dqn_fused_path(e->h, batch, e->per_on)) {           // kernels_dqn2.hip
         if (chained_out) *chained_out = 1;
@@ -1240,6 +1267,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     const EngineDesc& h = e->h;
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_act_explore: discrete SAC acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
+    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_act_explore: REINFORCE acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * O, out_n = rows * nout;
@@ -1686,7 +1714,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     const EngineDesc& h = e->h;
     if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
           h.algo == ALGO_SAC_DISCRETE))
-        return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn)", h.algo);
+        return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn, REINFORCE: frl_reinforce_learn)", h.algo);
     if (args->batch < 1 || args->batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d outside [1,%d]", args->batch, h.batch_max);
     int min_size = h.capacity;
     for (int p = 0; p < h.P; ++p) min_size = std::min(min_size, e->size[p]);
@@ -1780,6 +1808,7 @@ extern "C" int frl_learn(frl_engine* e, const frl_learn_args* args) { return lea
 extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, double* flops_out, double* bytes_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
     auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
     double fl = 0, by = 0;
     const double B = batch;
@@ -1835,6 +1864,7 @@ extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, doub
 extern "C" int frl_learn_work_executed(const frl_engine* e, int batch, int do_actor, double* flops_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work_executed describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
     auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
     auto first = [](const NetDesc& N) {            // the first layers of all heads
         const int nl = N.n_layers / std::max(1, N.heads);
@@ -2087,5 +2117,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 }
 #endif
 #include "frl_api_ppo.inc"
+#include "frl_api_reinforce.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

@@ -9,7 +9,8 @@ constexpr int kMaxAgents = 8;
 constexpr int kMaxNets = 2 * kMaxAgents;
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
-enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6 };
+enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
+                  ALGO_REINFORCE = 7 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -177,6 +178,8 @@ struct EngineDesc {
                           // columns, heads of up to 32 outputs, batches of up to 256 rows, <= kSoloMaxP learners); every net in fragment-image order
     int solo;             // > 0 (the workgroups per learner: 16 / 8): DDPG / TD3 / SAC updates of this engine run on kernels_solo.hip (<= kSoloMaxP learners of the narrow standard
                           // shape, sixteen workgroups per learner); parameters in fragment-image order like the chained family's
+    int* ep_n;            // [P] REINFORCE: ring rows 0..ep_n[p]-1 are learner p's batch of the current frl_reinforce_learn call (0: it sits
+                          // the call out); the normalised returns of those rows are in isw
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -118,6 +118,8 @@ struct CommitArgs {
 struct AdamArgs {
     int which, ns, batch, soft, sac_alpha, G, p0;
     float lr, eps, beta1, beta2, wd, clip, tau, alpha_lr, target_entropy;
+    int ragged;          // 1 (frl_reinforce_learn): learner p's batch is its own EngineDesc::ep_n[p] rows — its slabs are the workgroups that
+                         // had rows, and a learner with none is skipped whole (slabs, step count, moments, statistics untouched)
 };
 constexpr int kAdamVec = 8;                              // float4 per thread per workgroup (reduce_kernel / adam_kernel)
 constexpr int kFusedThreads = 1024, kFusedVec = 12;      // adam_fused_kernel: one workgroup per net, gradient in registers
@@ -140,6 +142,10 @@ __global__ void ac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a,
 constexpr int kSacdMaxActions = 64;
 __global__ void sacd_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 __global__ void sacd_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+
+// kernels_reinforce.hip: REINFORCE (REINFORCE_file/REINFORCE.py), the episode's return scan and the policy-gradient kernel
+__global__ void reinforce_returns_kernel(const EngineDesc* __restrict__ Dp, double gamma);
+__global__ void reinforce_grad_kernel(const EngineDesc* __restrict__ Dp, int p0, int p_count, int ns);
 
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);

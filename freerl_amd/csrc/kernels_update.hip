@@ -114,12 +114,19 @@ __device__ __forceinline__ int adam_net_index(const EngineDesc& D, int which, in
     return (D.algo == ALGO_DQN) ? 0 : (which == 0 ? 2 * ag + 1 : 2 * ag);
 }
 
+// gradient slabs of learner p in this launch: the launch's, or (AdamArgs::ragged) those of the learner's own row count — 0: it sits
+// the call out and its workgroups return before they touch anything
+__device__ __forceinline__ int adam_unit_ns(const EngineDesc& D, const AdamArgs& a, int p) {
+    if (!a.ragged) return a.ns;
+    return ((D.ep_n[p] + D.rc - 1) / D.rc + D.cps - 1) / D.cps;
+}
+
 // thread 0 of a unit's first Adam workgroup: losses of the step, SAC's alpha update (SAC.py:154-169,257-260)
-__device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs& a, int p, int ag, float total, int* steps) {
+__device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs& a, int ns, int p, int ag, float total, int* steps) {
     const int n = D.n_agents;
     const float* pt = D.part + ((size_t)p * n + ag) * D.S * 4;
     float l0 = 0.f, l1 = 0.f;
-    for (int k = 0; k < a.ns; ++k) { l0 += pt[4 * k]; l1 += pt[4 * k + 1]; }
+    for (int k = 0; k < ns; ++k) { l0 += pt[4 * k]; l1 += pt[4 * k + 1]; }
     float* st = D.stats + ((size_t)p * n + ag) * ST_COUNT;
     const float invB = 1.f / (float)a.batch;
     st[a.which == 0 ? ST_CRITIC_LOSS : ST_ACTOR_LOSS] = l0 * invB;
@@ -137,6 +144,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const EngineDesc* __restric
     const int n = D.n_agents, wg = blockIdx.x % a.G;
     const int p = a.p0 + (blockIdx.x / a.G) / n, ag = (blockIdx.x / a.G) % n, unit = p * n + ag;
     const int net = adam_net_index(D, a.which, ag);
+    const int ns = adam_unit_ns(D, a, p);
+    if (ns == 0) return;
     const NetDesc& N = D.net[net];
     const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
     const int n4 = N.size / 4;
@@ -161,7 +170,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const EngineDesc* __restric
             const bool sig_w = i >= sw0 && i < sw1, sig_b = i >= sb0 && i < sb1;
             const int src = sig_w ? H.w_off / 4 + (i - sw0) : (sig_b ? H.b_off / 4 + (i - sb0) : i);
             f32x4 s = slab[src];
-            for (int k = 1; k < a.ns; ++k) s += slab[(size_t)k * ls4 + src];
+            for (int k = 1; k < ns; ++k) s += slab[(size_t)k * ls4 + src];
             if (sig_w) {
                 const int e0 = 4 * (i - sw0), kk = e0 / H.n_pad, n0 = e0 - kk * H.n_pad;        // Wk[k][n]: four outputs of one input
                 s.x *= noisy_eps_w(eps, H, D.noisy_split, kk, n0); s.y *= noisy_eps_w(eps, H, D.noisy_split, kk, n0 + 1);
@@ -187,6 +196,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict_
     const int n = D.n_agents, wg = blockIdx.x % a.G;
     const int p = a.p0 + (blockIdx.x / a.G) / n, ag = (blockIdx.x / a.G) % n, unit = p * n + ag;
     const int net = adam_net_index(D, a.which, ag);
+    const int ns = adam_unit_ns(D, a, p);
+    if (ns == 0) return;
     const NetDesc& N = D.net[net];
     const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
     const int n4 = N.size / 4, Gn = (n4 + kWG * kAdamVec - 1) / (kWG * kAdamVec);
@@ -219,7 +230,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict_
             if (a.soft) tg[i] = tg[i] * tk + thi * a.tau;
         }
     }
-    if (wg == 0 && threadIdx.x == 0) adam_publish(D, a, p, ag, total, steps);
+    if (wg == 0 && threadIdx.x == 0) adam_publish(D, a, ns, p, ag, total, steps);
 }
 
 // One launch instead of reduce_kernel + adam_kernel when a net's gradient fits in the registers of ONE 1024-thread
@@ -231,6 +242,8 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
     const int n = D.n_agents;
     const int p = a.p0 + blockIdx.x / n, ag = blockIdx.x % n;
     const int net = adam_net_index(D, a.which, ag);
+    const int ns = adam_unit_ns(D, a, p);
+    if (ns == 0) return;
     const NetDesc& N = D.net[net];
     const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
     const int n4 = N.size / 4;
@@ -247,7 +260,7 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
             const int i = j * kFusedThreads + threadIdx.x;
             g[j] = (i < n4) ? slab[i] : f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        for (int k = 1; k < a.ns; ++k) {
+        for (int k = 1; k < ns; ++k) {
             const FRL_GLB f32x4* sk = slab + (size_t)k * ls4;
             f32x4 tmp[VEC];
 #pragma unroll
@@ -276,7 +289,7 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
                 const bool sig_w = i >= sw0 && i < sw1, sig_b = i >= sb0 && i < sb1;
                 const int src = sig_w ? H.w_off / 4 + (i - sw0) : (sig_b ? H.b_off / 4 + (i - sb0) : i);
                 sv = slab[src];
-                for (int k = 1; k < a.ns; ++k) sv += slab[(size_t)k * ls4 + src];
+                for (int k = 1; k < ns; ++k) sv += slab[(size_t)k * ls4 + src];
                 if (sig_w) {
                     const int e0 = 4 * (i - sw0), kk = e0 / H.n_pad, n0 = e0 - kk * H.n_pad;
                     sv.x *= noisy_eps_w(eps, H, D.noisy_split, kk, n0); sv.y *= noisy_eps_w(eps, H, D.noisy_split, kk, n0 + 1);
@@ -318,7 +331,7 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
     }
     if (threadIdx.x == 0) {
         steps[net] = t;
-        adam_publish(D, a, p, ag, total, steps);
+        adam_publish(D, a, ns, p, ag, total, steps);
     }
 }
 

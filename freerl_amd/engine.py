@@ -342,6 +342,26 @@ class Engine:
         N.check(self._L.frl_ppo_learn(self._h, C.byref(a)))
         return out
 
+    def reinforce_learn(self, *, gamma, lr, n_steps=None, adam_eps=1e-8, want_loss=False, want_returns=False):
+        """REINFORCE.learn(gamma) for every learner (frl_reinforce_learn): learner p trains on ring rows 0..n_steps[p]-1
+        (None: its cursor size; 0: it sits the call out).  -> dict with `loss` [P] and / or `returns` [P][capacity]
+        (normalised returns; rows past a learner's length, and learners that sat out, are NaN); empty and asynchronous when
+        neither is asked for."""
+        a = N.ReinforceArgs()
+        a.gamma, a.lr, a.adam_eps = float(gamma), float(lr), float(adam_eps)
+        if n_steps is not None:
+            ns = np.ascontiguousarray(np.broadcast_to(np.asarray(n_steps, dtype=np.int32).reshape(-1), (self.P,)))
+            a.n_steps = ns.ctypes.data_as(C.POINTER(C.c_int))
+        out = {}
+        if want_loss:
+            out["loss"] = np.full(self.P, np.nan, dtype=F32)
+            a.loss_out = _fp(out["loss"])
+        if want_returns:
+            out["returns"] = np.full((self.P, self.capacity), np.nan, dtype=F32)
+            a.returns_out = _fp(out["returns"])
+        N.check(self._L.frl_reinforce_learn(self._h, C.byref(a)))
+        return out
+
     # ------------------------------------------------------------------ timing
     def ppo_work(self, horizon, k_epochs):
         fl, by = C.c_double(0), C.c_double(0)

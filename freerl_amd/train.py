@@ -1,6 +1,7 @@
 """Training loops: the counterpart of the `__main__` blocks of the reference scripts
 (`DQN_file/DQN.py:227-349`, `DDPG_file/DDPG_simple.py:238-362`, `TD3_file/TD3.py:315-456`,
 `SAC_file/SAC.py:429-586`, `SAC_file/SAC_add_discrete.py:461-580`, `PPO_file/PPO_with_tricks.py:435-584`,
+`REINFORCE_file/REINFORCE.py:227-329`,
 `MADDPG_file/MADDPG_simple.py:268-395`), driving freerl_amd's GPU-backed policies.
 
     python -m freerl_amd.train td3 --env_name Pendulum-v1 --seed 0 --max_episodes 500
@@ -52,6 +53,11 @@ FLAGS = {
     "sac_discrete": dict(env_name="CartPole-v1", policy_name="SAC_add_discrete", device="cpu", is_dis_to_con=False,
                          flags=_COMMON + _AC + _REPLAY, overrides=dict(random_steps=500),
                          trick={"Batch_ObsNorm": True}),
+    # REINFORCE.py:228-248: CartPole, seed 100, one learn() per learn_episodes_interval finished episodes (no tau, no buffer)
+    "reinforce": dict(env_name="CartPole-v1", policy_name="REINFORCE", device="cuda", is_dis_to_con=False,
+                      flags=[("seed", int, 100), ("max_episodes", int, 1000), ("save_freq", int, 500 // 4), ("start_steps", int, 500),
+                             ("random_steps", int, 0), ("learn_steps_interval", int, 1), ("learn_episodes_interval", int, 1),
+                             ("gamma", float, 0.99), ("policy_net_lr", float, 1e-3)], trick=None),
     "ppo": dict(env_name="CartPole-v1", policy_name="PPO", device="cpu", is_dis_to_con=False,
                 flags=_COMMON + _AC + [("horizon", int, 2048), ("clip_param", float, 0.2), ("K_epochs", int, 10),
                                        ("entropy_coefficient", float, 0.01), ("minibatch_size", int, 64),
@@ -344,6 +350,29 @@ class _SACDiscreteHooks(_Hooks):
                     np.array([ms.mean.numpy(), ms.std.numpy()]))
 
 
+class _ReinforceHooks(_Hooks):
+    """REINFORCE.py:289-323: every action is a Categorical draw; add(reward, terminated); learn(gamma) right after the reset that
+    ends every learn_episodes_interval-th episode, between the two save points of the loop."""
+    due = False
+
+    def act(self, step, obs):
+        action = self.policy.select_action(obs)
+        return action, action, None
+
+    def store(self, obs, action, reward, next_obs, terminated, done, extra):
+        self.policy.add(reward, terminated)                          # :299
+
+    def episode_end(self, episode_num):
+        self.due = (episode_num + 1) % self.args.learn_episodes_interval == 0      # :318
+
+    def learn_due(self, step):
+        due, self.due = self.due, False
+        return due
+
+    def learn(self, episode_num):
+        self.policy.learn(self.args.gamma)
+
+
 class _PPOHooks(_Hooks):
     def begin(self, obs):
         t = self.args.trick
@@ -541,6 +570,13 @@ def run(algo, argv=None, env=None, log=print):
             raise ValueError("sac_discrete trains on discrete action spaces (SAC_add_discrete.py); %s is continuous" % args.env_name)
         policy = SAC(dim_info, False, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick, **kw)
         hooks = _SACDiscreteHooks(args, env, policy, dim_info, max_action)
+    elif algo == "reinforce":
+        from .REINFORCE import REINFORCE
+        # the steps between two learn() calls: learn_episodes_interval episodes of at most the env's time limit each
+        limit = getattr(env, "max_episode_steps", None) or getattr(getattr(env, "spec", None), "max_episode_steps", None) or 1000
+        policy = REINFORCE(dim_info, is_continue, args.policy_net_lr, device, trick=args.trick,
+                           max_steps=max(2048, int(limit) * args.learn_episodes_interval), seed=args.seed)
+        hooks = _ReinforceHooks(args, env, policy, dim_info, max_action)
     elif algo == "ppo":
         from .PPO import PPO
         policy = PPO(dim_info, is_continue, args.actor_lr, args.critic_lr, args.horizon, device, trick=args.trick,

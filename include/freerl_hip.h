@@ -39,8 +39,13 @@ enum frl_algo {
     FRL_ALGO_SAC = 3,          /* SAC_file/SAC.py:171-282 */
     FRL_ALGO_MADDPG = 4,       /* MADDPG_file/MADDPG_simple.py:107-210 */
     FRL_ALGO_PPO = 5,          /* PPO_file/PPO_with_tricks.py:211-374, PPO.py */
-    FRL_ALGO_SAC_DISCRETE = 6  /* SAC_file/SAC_add_discrete.py:137-348 (is_continue=False): softmax actor, twin critics with one
+    FRL_ALGO_SAC_DISCRETE = 6, /* SAC_file/SAC_add_discrete.py:137-348 (is_continue=False): softmax actor, twin critics with one
                                   value per action; one agent, actions stored as one float index, act_dim[0] = number of actions */
+    FRL_ALGO_REINFORCE = 7     /* REINFORCE_file/REINFORCE.py:32-127: one net (index 0) obs -> hidden (ReLU) -> n_actions, softmax in the
+                                  kernels; one agent, actions stored as one float index, act_dim[0] = number of actions (<= 64), hidden
+                                  <= 256.  capacity = the most steps stored between two frl_reinforce_learn calls, and batch_max follows
+                                  it.  The engine has NO target net: FRL_PARAM_TARGET addresses a block that frl_params_set / _get store and
+                                  return but that no kernel of this algorithm reads or writes (frl_act with use_target = 1 runs on it) */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2 };
@@ -273,6 +278,29 @@ typedef struct frl_ppo_args {
     double gae_gamma, gae_lmbda; /* gae_mode 1: the scan's gamma / lambda as the caller's doubles (0: use gamma / lmbda) */
 } frl_ppo_args;
 int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args);
+/* ---------------------------------------------------------------- REINFORCE (REINFORCE_file/REINFORCE.py)
+ * `REINFORCE.learn(gamma)` (:104-127) for every learner in one launch chain: the returns of the stored steps scanned backwards
+ * (G = r + gamma G (1 - done), several episodes per call allowed, a truncated one carries G into the one before it), normalised
+ * with the unbiased std, loss = sum_t -log pi(a_t|s_t) g_t with Categorical(probs)'s clamp at float32 eps, one Adam step, no
+ * gradient clipping.  The stored steps are ring rows 0..n-1 in time order (frl_buffer_add* from an empty ring); a record's
+ * next_obs columns are not read.  Afterwards the ring cursor of every learner that took part is (0, 0): the reference clearing its
+ * lists.  FRL_STAT_ACTOR_LOSS is the loss, FRL_STAT_ACTOR_GNORM the gradient norm.
+ * Refused before any launch: FRL_ERR_INVALID when a participating learner has exactly one step (torch.std of one element is NaN
+ * and the reference turns every parameter into NaN) or more than `capacity`; FRL_ERR_STATE when its ring holds fewer rows than
+ * asked for or was not filled from an empty cursor (index != size mod capacity: a wrapped ring is not in time order), and on
+ * engines of any other algorithm.  frl_act serves this engine with FRL_ACT_RAW, FRL_ACT_ARGMAX and
+ * FRL_ACT_CAT_SAMPLE; frl_learn, frl_ppo_learn, frl_rollout and frl_act_explore return FRL_ERR_STATE for it. */
+struct frl_reinforce_args {
+    const int* n_steps;   /* host [P]: learner p trains on ring rows 0..n_steps[p]-1, in time order; NULL: every learner's cursor size.
+                             0: this learner sits the call out (nothing of its state changes) */
+    double gamma;         /* the scan runs in float64, as the reference's Python floats do */
+    float lr, adam_eps;
+    float* loss_out;      /* host [P] or NULL (NULL: the call is asynchronous); entries of learners that sit out are left as they are */
+    float* returns_out;   /* host [P][capacity] normalised returns or NULL; only rows 0..n_steps[p]-1 are written */
+};
+typedef struct frl_reinforce_args frl_reinforce_args;
+int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args);
+
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */
 int frl_gae(frl_engine* e, const float* td_delta_dev, const float* adv_done_dev, int n_seq, int horizon,

@@ -21,13 +21,26 @@ CTYPE = {"int": "C.c_int", "float": "C.c_float", "double": "C.c_double", "uint64
          "long long": "C.c_longlong", "uint8_t": "C.c_uint8"}
 
 
-def parse_structs(src=None):
+STRUCT_RE = r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;"
+# a struct declared in two steps, `struct frl_x { ... }; typedef struct frl_x frl_x;` (frl_reinforce_args): the same C type,
+# listed by parse_later_structs() and rendered behind the others
+LATER_RE = r"(?<!typedef\s)\bstruct\s+(\w+)\s*\{(.*?)\}\s*;\s*typedef\s+struct\s+\1\s+\1\s*;"
+
+
+def parse_later_structs(src=None):
+    """The two-step declarations, in the format of parse_structs (which lists the one-step typedefs only)."""
+    src = open(HEADER).read() if src is None else src
+    plain = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return parse_structs(src, [(body, name) for name, body in re.findall(LATER_RE, plain, flags=re.S)])[0]
+
+
+def parse_structs(src=None, blocks=None):
     """[(name, [(field, ctypes expression)])] in header order; nested structs refer to earlier ones by name."""
     src = open(HEADER).read() if src is None else src
     defines = {k: int(v) for k, v in re.findall(r"#define\s+(FRL_[A-Z_]+)\s+(\d+)", src)}
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     out = []
-    for body, name in re.findall(r"typedef\s+struct\s+\w+\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+    for body, name in (re.findall(STRUCT_RE, src, flags=re.S) if blocks is None else blocks):
         fields = []
         known = {n for n, _ in out}
         for decl in body.split(";"):
@@ -61,7 +74,7 @@ def render():
     for k in ("FRL_MAX_AGENTS", "FRL_STAT_COUNT", "FRL_COMM_ID_BYTES", "FRL_COMM_MAX_VALUES"):
         if k in defines:
             lines.append("%s = %d" % (k, defines[k]))
-    for name, fields in structs:
+    for name, fields in structs + parse_later_structs():
         lines += ["", "", "class %s(C.Structure):" % name, "    _fields_ = ["]
         row = "        "
         for i, (f, t) in enumerate(fields):

@@ -21,7 +21,10 @@ md = s[s.index("amdhsa.kernels:"):]
 # (round 6: the lane constants re-derived per phase took the K-sliced kernels from 97-397 spilled VGPRs to 0-51, PPO's from 135-140 to 0)
 BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8), ("solo_", 0), ("solow_", 0), ("dqn_fused_", 0), ("c51_grad_", 0), ("ac_critic_kernel", 0),
           ("ac_critic_wide_", 60), ("ac_actor_wide_", 16), ("ac_critic_x_", 700), ("ac_actor_x_", 460), ("ppo_update_v2_", 0),
-          ("sacd_critic_", 9), ("sacd_actor_", 0), ("", 20)]
+          ("sacd_critic_", 9), ("sacd_actor_", 0),
+          # kernels_reinforce.hip: reinforce_returns_kernel 48 VGPRs, reinforce_grad_kernel 254 VGPRs; no spilled VGPR in either (the grad
+          # kernel keeps 56 bytes of its row lambda's captures in scratch: stored at entry, three loads per row chunk, none in an MFMA loop)
+          ("reinforce_returns_", 0), ("reinforce_grad_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
