@@ -326,3 +326,44 @@ class N_Step_PER_Buffer(PER_Buffer):
         self.n_step_deque.append((obs, action, reward, next_obs, done))
         if len(self.n_step_deque) == self.n_step:
             super().add(*_n_step_info(list(self.n_step_deque), self.gamma))
+
+
+class MO_Buffer(_RingView):
+    """Multi-objective replay buffer (ENVELOPE_MORL_file/Buffer.py:12-62): `Buffer` with a reward VECTOR of `preference_dim`
+    entries per transition.  Inside an envelope-DQN engine the record's reward block is that vector; a stand-alone buffer (a
+    replay-only engine, whose records have one reward column) keeps it in the record's extra columns."""
+
+    def __init__(self, capacity, obs_dim, act_dim, preference_dim, device, *, batch_max=1024, _engine=None, _learner=0):
+        self.capacity = capacity = int(capacity)
+        R = int(preference_dim)
+        if _engine is None:
+            hip_id, dev = resolve_device(device)
+            eng = Engine(N.ALGO_REPLAY_ONLY, int(obs_dim), int(act_dim), max(capacity, 1), device_id=hip_id,
+                         batch_max=batch_max, extra_cols=R)
+            self._attach(eng, 0, 0, dev)
+            self._own = True
+            self._rew = (eng.layout.extra_off, R)
+        else:
+            self._attach(_engine, _learner, 0, device)
+            if _engine.reward_dim != R:
+                raise ValueError("the engine stores %d reward columns, preference_dim is %d" % (_engine.reward_dim, R))
+            self._rew = (_engine.layout.rew_off, R)
+        self._rec = np.zeros(self._e.width, dtype=F32)
+
+    @property
+    def rewards(self):
+        return self._column(self._rew)
+
+    def add(self, obs, action, reward, next_obs, done):
+        """add an experience to the memory (Buffer.py:29-39); `reward` is the preference_dim-vector."""
+        r = self._rec
+        r[self._obs[0]:self._obs[0] + self._obs[1]] = np.asarray(obs, dtype=F32).reshape(-1)
+        r[self._act[0]:self._act[0] + self._act[1]] = np.asarray(action, dtype=F32).reshape(-1)
+        r[self._rew[0]:self._rew[0] + self._rew[1]] = np.asarray(reward, dtype=F32).reshape(-1)
+        r[self._nobs[0]:self._nobs[0] + self._nobs[1]] = np.asarray(next_obs, dtype=F32).reshape(-1)
+        r[self._done[0]] = float(done)
+        self._e.add(self._learner, r)
+
+    def sample(self, indices):
+        """(obs[B,O], actions[B,A'], rewards[B,R], next_obs[B,O], dones[B,1]) float32 on `device` (Buffer.py:41-58)."""
+        return tuple(self._gather(indices, [self._obs, self._act, self._rew, self._nobs, self._done]))

@@ -24,7 +24,7 @@ FRL_COMM_ID_BYTES = 128
 FRL_COMM_MAX_VALUES = 64
 
 # enum frl_algo
-ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE, ALGO_REINFORCE = -1, 0, 1, 2, 3, 4, 5, 6, 7
+ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE, ALGO_REINFORCE, ALGO_ENVELOPE_DQN = -1, 0, 1, 2, 3, 4, 5, 6, 7, 8
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
 ACT_RAW, ACT_ARGMAX, ACT_TANHHEAD, ACT_SAC_SAMPLE, ACT_PPO_SAMPLE, ACT_CAT_SAMPLE = 0, 1, 2, 3, 4, 5
@@ -43,7 +43,7 @@ class Config(C.Structure):
                 ("capacity", C.c_int), ("batch_max", C.c_int), ("extra_cols", C.c_int), ("actor_dist", C.c_int), ("dueling", C.c_int), ("noisy", C.c_int),
                 ("c51_atoms", C.c_int), ("c51_vmin", C.c_float), ("c51_vmax", C.c_float),
                 ("device_id", C.c_int),
-                ("seed", C.c_uint64)]
+                ("seed", C.c_uint64), ("reward_dim", C.c_int)]
 
 
 class RecordLayout(C.Structure):
@@ -77,6 +77,12 @@ class PpoArgs(C.Structure):
 class ReinforceArgs(C.Structure):
     _fields_ = [("n_steps", C.POINTER(C.c_int)), ("gamma", C.c_double), ("lr", C.c_float), ("adam_eps", C.c_float),
                 ("loss_out", C.POINTER(C.c_float)), ("returns_out", C.POINTER(C.c_float))]
+
+
+class EnvelopeArgs(C.Structure):
+    _fields_ = [("batch", C.c_int), ("weight_num", C.c_int), ("gamma", C.c_float), ("tau", C.c_float), ("lr", C.c_float),
+                ("beta", C.c_float), ("idx", C.POINTER(C.c_int64)), ("weights", C.POINTER(C.c_float)),
+                ("loss_out", C.POINTER(C.c_float)), ("weights_out", C.POINTER(C.c_float))]
 
 
 class ExploreArgs(C.Structure):
@@ -162,6 +168,7 @@ SIGNATURES = {
     "frl_learn_work_executed": (_i, [_vp, _i, _i, _P(C.c_double)]),
     "frl_ppo_learn": (_i, [_vp, _P(PpoArgs)]),
     "frl_reinforce_learn": (_i, [_vp, _P(ReinforceArgs)]),
+    "frl_envelope_learn": (_i, [_vp, _P(EnvelopeArgs)]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

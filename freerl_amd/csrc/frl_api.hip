@@ -38,6 +38,7 @@
 #include "kernels_solow.hip"
 #include "kernels_sacd.hip"
 #include "kernels_reinforce.hip"
+#include "kernels_envelope.hip"
 #endif
 
 using namespace frl;
@@ -141,6 +142,7 @@ struct frl_engine {
     int* h_ep_n = nullptr;                // [2][P] pinned
     hipEvent_t ev_ep[2] = {nullptr, nullptr};
     unsigned ep_seq = 0;
+    float* h_env_w = nullptr;             // frl_envelope_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
     int lds_per_cu = 160 * 1024;          // LDS bytes of one compute unit
@@ -233,11 +235,11 @@ static void build_record(RecordDesc& R, const frl_config& c) {
     R.obs_total = off;
     for (int j = 0; j < c.n_agents; ++j) {
         R.act_off[j] = off;
-        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE) ? 1 : c.act_dim[j];     // (discrete SAC, REINFORCE: always the index)
+        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || c.algo == FRL_ALGO_ENVELOPE_DQN) ? 1 : c.act_dim[j];     // (discrete SAC, REINFORCE, envelope DQN: always the index)
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
-    R.rew_off = off; off += c.n_agents;
+    R.rew_off = off; off += (c.algo == FRL_ALGO_ENVELOPE_DQN) ? std::max(1, c.reward_dim) : c.n_agents;      // (envelope DQN: the reward vector)
     R.done_off = off; off += c.n_agents;
     for (int j = 0; j < c.n_agents; ++j) { R.nobs_off[j] = off; off += c.obs_dim[j]; }
     R.extra_off = off;
@@ -255,7 +257,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 102; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed
+extern "C" int frl_version(void) { return 103; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -285,6 +287,8 @@ extern "C" int frl_destroy(frl_engine* e) {
     if (e->d_solow_bar2) hipFree(e->d_solow_bar2);
     if (e->h_solo_err) hipHostFree(e->h_solo_err);
     if (e->h_ep_n) hipHostFree(e->h_ep_n);
+    if (e->h_env_w) hipHostFree(e->h_env_w);
+    if (e->h.env_w) hipFree(e->h.env_w);
     if (e->h.ep_n) hipFree(e->h.ep_n);
     for (hipEvent_t ev : e->ev_ep) if (ev) hipEventDestroy(ev);
     float* dev[] = {e->h.act_spill, e->h.theta_eff, e->h.noisy_eps, e->h.isw, e->h.td_err, e->h.theta, e->h.target, e->h.m, e->h.v, e->h.grad, e->h.replay, e->h.noise, e->h.stats, e->h.alpha,
@@ -335,7 +339,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_REINFORCE) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_ENVELOPE_DQN) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -366,7 +370,18 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
     if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;
-    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || c.algo == FRL_ALGO_ENVELOPE_DQN ||
+                    (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    h.reward_dim = 1;
+    if (c.algo == FRL_ALGO_ENVELOPE_DQN) {      // what kernels_envelope.hip handles: one thread per row walks the head's A x R columns, as for discrete SAC
+        if (c.reward_dim < 0) { delete e; return fail(FRL_ERR_INVALID, "envelope DQN: reward_dim %d must be >= 1 (0 means 1)", c.reward_dim); }
+        h.reward_dim = std::max(1, c.reward_dim);
+        if ((long long)c.act_dim[0] * h.reward_dim > kSacdMaxActions) {
+            delete e;
+            return fail(FRL_ERR_INVALID, "envelope DQN: %d actions x %d objectives > %d head columns (kernels_envelope.hip)", c.act_dim[0], h.reward_dim, kSacdMaxActions);
+        }
+        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "envelope DQN: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
+    }
     if (c.algo == FRL_ALGO_REINFORCE) {         // what kernels_reinforce.hip handles: discrete SAC's limits, for the same reasons
         if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: %d actions > %d (kernels_reinforce.hip)", c.act_dim[0], kSacdMaxActions); }
         if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
@@ -398,6 +413,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         const int O = c.obs_dim[0], A = c.act_dim[0];
         build_net(h.net[0], {{H, O}, {H, H}, {A, H}}, 1, ACT_RELU, ACT_NONE, 0);
         build_net(h.net[1], {{H, O}, {H, H}, {A, H}, {H, O}, {H, H}, {A, H}}, 2, ACT_RELU, ACT_NONE, 0);
+    } else if (c.algo == FRL_ALGO_ENVELOPE_DQN) {
+        h.n_nets = 1;                                                   // MLP (ENVELOPE_DQN.py:36-59): [obs | w] -> H -> H -> A x R, with a target
+        build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0] * h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
     } else if (c.algo == FRL_ALGO_REINFORCE) {
         h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
         build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
@@ -509,6 +527,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_PPO && c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
     if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
+    if (c.algo == FRL_ALGO_ENVELOPE_DQN) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);   // the target vector T per row
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -516,7 +535,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
     // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
     // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE) h.rc = 32;
+    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN) h.rc = 32;
     // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
@@ -533,6 +552,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_REINFORCE && lds_bytes_for(h, h.rc) > 80 * 1024) {
         delete e;
         return fail(FRL_ERR_INVALID, "REINFORCE: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
+    }
+    if (c.algo == FRL_ALGO_ENVELOPE_DQN && lds_bytes_for(h, h.rc) > 80 * 1024) {
+        delete e;
+        return fail(FRL_ERR_INVALID, "envelope DQN: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
     }
     e->lds_bytes = lds_bytes_for(h, h.rc);
     // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
@@ -588,7 +611,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(dalloc_zero(&h.grad, P * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
-        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE)
+        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN)
             CREATE_TRY(dalloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
         h.Gmax = 1;
         for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
@@ -615,6 +638,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             CREATE_TRY(dalloc_zero(&h.ep_n, P, e->stream));
             CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
+        if (c.algo == FRL_ALGO_ENVELOPE_DQN) {
+            CREATE_TRY(dalloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
+            CREATE_TRY(hipHostMalloc((void**)&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim * sizeof(float)));
         }
         if (h.solo || h.solow) {
             e->solo_stride = 0;
@@ -675,7 +702,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     { const char* cw = getenv("FRL_CHAIN_WAVES"); e->chain_waves = (cw && atoi(cw) == 4) ? 4 : 8; }
     if (h.algo == ALGO_DQN)
         CREATE_TRY(hipFuncSetAttribute((const void*)dqn_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dqn2_lds_floats() * (int)sizeof(float)));
-    if (h.batch_max > 256 && 4 * h.batch_max <= kDrawTableHost)     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
+    // (envelope DQN: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
+    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || h.algo == ALGO_ENVELOPE_DQN))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
     if (h.wide == 2) {
         const int lb = wide16_lds_floats_host() * (int)sizeof(float);
@@ -712,6 +740,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(hipFuncSetAttribute((const void*)sacd_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)sacd_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)reinforce_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+        CREATE_TRY(hipFuncSetAttribute((const void*)envelope_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) {
@@ -780,6 +809,7 @@ extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, 
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     if (e->h.algo == ALGO_PPO) return fail(FRL_ERR_INVALID, "frl_learn_path describes frl_learn(); PPO updates go through frl_ppo_learn");
     if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_path describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
+    if (e->h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_path describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
     if (batch <= 0 || batch > e->h.batch_max) return fail(FRL_ERR_INVALID, "batch out of range");
     if (dqn_fused_path(e->h, batch, e->per_on)) {           // kernels_dqn2.hip
         if (chained_out) *chained_out = 1;
@@ -1267,6 +1297,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     const EngineDesc& h = e->h;
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_act_explore: discrete SAC acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
+    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_act_explore: envelope DQN acts through frl_act (FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives)");
     if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_act_explore: REINFORCE acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
@@ -1712,6 +1743,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn: envelope DQN updates go through frl_envelope_learn");
     if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
           h.algo == ALGO_SAC_DISCRETE))
         return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn, REINFORCE: frl_reinforce_learn)", h.algo);
@@ -1808,6 +1840,7 @@ extern "C" int frl_learn(frl_engine* e, const frl_learn_args* args) { return lea
 extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, double* flops_out, double* bytes_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_work describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
     if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
     auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
     double fl = 0, by = 0;
@@ -1864,6 +1897,7 @@ extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, doub
 extern "C" int frl_learn_work_executed(const frl_engine* e, int batch, int do_actor, double* flops_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_work_executed describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
     if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work_executed describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
     auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
     auto first = [](const NetDesc& N) {            // the first layers of all heads
@@ -2118,5 +2152,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #endif
 #include "frl_api_ppo.inc"
 #include "frl_api_reinforce.inc"
+#include "frl_api_envelope.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

@@ -223,6 +223,7 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     ENG(e);
     if (e->h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for discrete SAC engines");
     if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for REINFORCE engines");
+    if (e->h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for envelope DQN engines (updates: frl_envelope_learn)");
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;

@@ -147,6 +147,17 @@ __global__ void sacd_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a
 __global__ void reinforce_returns_kernel(const EngineDesc* __restrict__ Dp, double gamma);
 __global__ void reinforce_grad_kernel(const EngineDesc* __restrict__ Dp, int p0, int p_count, int ns);
 
+// kernels_envelope.hip: envelope multi-objective DQN (ENVELOPE_MORL_file/ENVELOPE_DQN.py), row-chunk gradient kernel over batch x weight_num rows
+struct EnvelopeArgs {
+    int batch, weight_num;            // B sampled ring rows x W preference vectors = B W rows
+    int draw_w;                       // 1: envelope_weights_kernel draws the preferences (Philox); 0: EngineDesc::env_w as uploaded
+    float gamma, beta;
+    unsigned long long rng_counter;
+    int p0, p_count;
+};
+__global__ void envelope_weights_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a);
+__global__ void envelope_grad_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

@@ -15,9 +15,9 @@ namespace frl {
 // ------------------------------------------------------------------------------------ returns
 // G_t = r_t + gamma G_{t+1} (1 - done_t) is the affine map G -> b + a G with a = gamma (1 - done_t), b = r_t; a run of steps is the
 // composition of its maps.
-struct Affine { double a, b; };
+struct RetMap { double a, b; };
 // f after g: g belongs to the LATER steps (the scan runs backwards in time)
-__device__ __forceinline__ Affine affine_after(const Affine f, const Affine g) { return Affine{f.a * g.a, f.b + f.a * g.b}; }
+__device__ __forceinline__ RetMap affine_after(const RetMap f, const RetMap g) { return RetMap{f.a * g.a, f.b + f.a * g.b}; }
 
 template <int OFF>
 __device__ __forceinline__ double lane_xor_d(double v) {
@@ -28,8 +28,8 @@ __device__ __forceinline__ double lane_xor_d(double v) {
 // lanes and `tot` the whole block; afterwards the same for blocks of 2 OFF lanes.  Both halves form `tot` from the same two operands
 // in the same order, so every lane of a block holds the same bits.
 template <int OFF>
-__device__ __forceinline__ void rscan_step(Affine& scan, Affine& tot) {
-    const Affine o{lane_xor_d<OFF>(tot.a), lane_xor_d<OFF>(tot.b)};
+__device__ __forceinline__ void rscan_step(RetMap& scan, RetMap& tot) {
+    const RetMap o{lane_xor_d<OFF>(tot.a), lane_xor_d<OFF>(tot.b)};
     if (threadIdx.x & OFF) {
         tot = affine_after(o, tot);
     } else {
@@ -70,18 +70,18 @@ __global__ __launch_bounds__(256) void reinforce_returns_kernel(const EngineDesc
     const int tid = threadIdx.x, seg = (n + kWG - 1) / kWG;
     const int t0 = min(tid * seg, n), t1 = min(t0 + seg, n);
 
-    Affine f{1.0, 0.0};
+    RetMap f{1.0, 0.0};
     for (int t = t1 - 1; t >= t0; --t) {
         const float* rec = ring + (size_t)t * R.stride;
         const double a = gamma * (1.0 - (double)rec[R.done_off]);
-        f = Affine{a * f.a, (double)rec[R.rew_off] + a * f.b};
+        f = RetMap{a * f.a, (double)rec[R.rew_off] + a * f.b};
     }
-    Affine scan = f, tot = f;
+    RetMap scan = f, tot = f;
     rscan_step<1>(scan, tot); rscan_step<2>(scan, tot); rscan_step<4>(scan, tot);
     rscan_step<8>(scan, tot); rscan_step<16>(scan, tot); rscan_step<32>(scan, tot);
     if ((tid & 63) == 0) { wave_a[tid >> 6] = tot.a; wave_b[tid >> 6] = tot.b; }
     __syncthreads();
-    for (int wv = (tid >> 6) + 1; wv < kWG / 64; ++wv) scan = affine_after(scan, Affine{wave_a[wv], wave_b[wv]});
+    for (int wv = (tid >> 6) + 1; wv < kWG / 64; ++wv) scan = affine_after(scan, RetMap{wave_a[wv], wave_b[wv]});
     g_in[tid] = scan.b;                            // the return at the lane's first step: nothing follows the last step (G = 0)
     if (tid == 0) g_in[kWG] = 0.0;
     __syncthreads();

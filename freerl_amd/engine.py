@@ -18,7 +18,7 @@ def _fp(a):
 
 class Engine:
     def __init__(self, algo, obs_dim, act_dim, capacity, *, n_learners=1, discrete=False, hidden=128,
-                 hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None):
+                 hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0):
         obs_dim = list(obs_dim) if isinstance(obs_dim, (list, tuple)) else [int(obs_dim)]
         act_dim = list(act_dim) if isinstance(act_dim, (list, tuple)) else [int(act_dim)]
         assert len(obs_dim) == len(act_dim)
@@ -30,6 +30,7 @@ class Engine:
         cfg.twin_critic, cfg.capacity, cfg.batch_max = int(bool(twin_critic)), int(capacity), int(batch_max)
         cfg.extra_cols, cfg.device_id, cfg.seed = int(extra_cols), int(device_id), int(seed) & (2 ** 64 - 1)
         cfg.actor_dist, cfg.dueling, cfg.noisy = int(actor_dist), int(bool(dueling)), int(bool(noisy))
+        cfg.reward_dim = int(reward_dim)          # envelope DQN: objectives (0 = 1; ignored by the other algorithms)
         if c51 is not None:                     # (atoms, v_min, v_max)
             cfg.c51_atoms, cfg.c51_vmin, cfg.c51_vmax = int(c51[0]), float(c51[1]), float(c51[2])
         self._L = N.lib()
@@ -47,6 +48,7 @@ class Engine:
         self.layout = lay
         self.width = lay.width
         self.act_max = max(lay.act_dim[j] for j in range(self.n_agents))
+        self.reward_dim = lay.done_off - lay.rew_off if self.n_agents == 1 else 1      # (envelope DQN: the reward vector's columns)
         n = C.c_int(0)
         N.check(self._L.frl_net_count(self._h, C.byref(n)))
         self.n_nets = n.value
@@ -360,6 +362,33 @@ class Engine:
             out["returns"] = np.full((self.P, self.capacity), np.nan, dtype=F32)
             a.returns_out = _fp(out["returns"])
         N.check(self._L.frl_reinforce_learn(self._h, C.byref(a)))
+        return out
+
+    def envelope_learn(self, batch, weight_num, *, gamma, tau, lr, beta, idx=None, weights=None, want_loss=False, want_weights=False):
+        """ENVELOPE.learn for every learner (frl_envelope_learn) on batch x weight_num rows: row j is ring row idx[j % batch] under
+        preference weights[j // batch].  idx [P][batch] / weights [P][weight_num][reward_dim], or None: drawn on the device.
+        -> dict with `loss` [P] and / or `weights` [P][weight_num][reward_dim] (the preferences used); empty and asynchronous
+        when neither is asked for."""
+        a = N.EnvelopeArgs()
+        a.batch, a.weight_num = int(batch), int(weight_num)
+        a.gamma, a.tau, a.lr, a.beta = float(gamma), float(tau), float(lr), float(beta)
+        keep = []
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, int(batch))
+            keep.append(ix)
+            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=F32).reshape(self.P, int(weight_num), self.reward_dim)
+            keep.append(w)
+            a.weights = _fp(w)
+        out = {}
+        if want_loss:
+            out["loss"] = np.full(self.P, np.nan, dtype=F32)
+            a.loss_out = _fp(out["loss"])
+        if want_weights:
+            out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
+            a.weights_out = _fp(out["weights"])
+        N.check(self._L.frl_envelope_learn(self._h, C.byref(a)))
         return out
 
     # ------------------------------------------------------------------ timing

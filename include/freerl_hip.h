@@ -41,11 +41,16 @@ enum frl_algo {
     FRL_ALGO_PPO = 5,          /* PPO_file/PPO_with_tricks.py:211-374, PPO.py */
     FRL_ALGO_SAC_DISCRETE = 6, /* SAC_file/SAC_add_discrete.py:137-348 (is_continue=False): softmax actor, twin critics with one
                                   value per action; one agent, actions stored as one float index, act_dim[0] = number of actions */
-    FRL_ALGO_REINFORCE = 7     /* REINFORCE_file/REINFORCE.py:32-127: one net (index 0) obs -> hidden (ReLU) -> n_actions, softmax in the
+    FRL_ALGO_REINFORCE = 7,    /* REINFORCE_file/REINFORCE.py:32-127: one net (index 0) obs -> hidden (ReLU) -> n_actions, softmax in the
                                   kernels; one agent, actions stored as one float index, act_dim[0] = number of actions (<= 64), hidden
                                   <= 256.  capacity = the most steps stored between two frl_reinforce_learn calls, and batch_max follows
                                   it.  The engine has NO target net: FRL_PARAM_TARGET addresses a block that frl_params_set / _get store and
                                   return but that no kernel of this algorithm reads or writes (frl_act with use_target = 1 runs on it) */
+    FRL_ALGO_ENVELOPE_DQN = 8  /* ENVELOPE_MORL_file/ENVELOPE_DQN.py:36-266: one Q-net (index 0) [obs | preference] -> hidden (ReLU) -> hidden
+                                  (ReLU) -> n_actions x reward_dim (column a * reward_dim + k = objective k of action a) with a target net;
+                                  one agent, actions stored as one float index, act_dim[0] = number of actions, frl_config.reward_dim
+                                  objectives: a record carries reward_dim reward columns (done_off = rew_off + reward_dim).  n_actions x
+                                  reward_dim <= 64, hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_learn */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2 };
@@ -105,10 +110,13 @@ typedef struct frl_config {
     float c51_vmin, c51_vmax;     /* its support [v_min, v_max] (-100, 100) */
     int device_id;
     uint64_t seed;                /* device Philox key (fast path only) */
+    int reward_dim;               /* FRL_ALGO_ENVELOPE_DQN: objectives (reward columns per record, preference columns of the Q-net's input);
+                                     0 means 1, and every other algorithm ignores it */
 } frl_config;
 
 /* Column layout of one replay record (all agents of one transition, fp32):
- * [obs_0..|act_0..|rew_0..|done_0..|next_obs_0..|extra] — see DESIGN.md "Data layout". */
+ * [obs_0..|act_0..|rew_0..|done_0..|next_obs_0..|extra] — see DESIGN.md "Data layout".  The reward block is one column per agent,
+ * except on FRL_ALGO_ENVELOPE_DQN engines, where it is the reward VECTOR: done_off - rew_off = reward_dim columns. */
 typedef struct frl_record_layout {
     int n_agents, width, stride;
     int obs_off[FRL_MAX_AGENTS], obs_dim[FRL_MAX_AGENTS];
@@ -300,6 +308,29 @@ struct frl_reinforce_args {
 };
 typedef struct frl_reinforce_args frl_reinforce_args;
 int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args);
+
+/* ---------------------------------------------------------------- envelope multi-objective DQN (ENVELOPE_MORL_file/ENVELOPE_DQN.py)
+ * `ENVELOPE.learn(batch_size, gamma, tau, weight_num, update_freq)` (:204-255) for every learner in one launch chain.  It trains on
+ * N = batch x weight_num rows: row j is sampled ring row idx[j % batch] under preference weights[j / batch].  a' = argmax_a w . Q(s', w)[a]
+ * of the ONLINE net (first maximum), T = r + gamma Q_target(s', w)[a'] (1 - done), Q = Q(s, w)[stored action], and
+ *     loss = beta mean_j (w.Q - w.T)^2 + (1 - beta) mean_{j,k} (Q_k - T_k)^2
+ * then one Adam step (torch defaults) WITHOUT gradient clipping (the reference's clip_grad_norm_ runs before backward() and clips
+ * nothing) and the soft target update with `tau` on every call.  FRL_STAT_ACTOR_LOSS is the loss, FRL_STAT_ACTOR_GNORM the gradient
+ * norm.  Refused before any launch with FRL_ERR_INVALID: batch < 1, weight_num < 1, batch x weight_num > batch_max, NaN scalars,
+ * beta outside [0, 1]; with FRL_ERR_STATE: batch > a learner's stored rows, idx = NULL with fewer than 2 x batch stored rows, and
+ * engines of any other algorithm.  frl_act serves this engine with FRL_ACT_RAW on in_dim = obs_dim + reward_dim; frl_learn,
+ * frl_learn_path, frl_learn_work*, frl_rollout and frl_act_explore return FRL_ERR_STATE for it. */
+struct frl_envelope_args {
+    int batch;              /* B: sampled ring rows */
+    int weight_num;         /* W: preference vectors; B x W <= batch_max */
+    float gamma, tau, lr, beta;
+    const int64_t* idx;     /* host [P][batch] rows drawn by the caller (ENVELOPE.sample, :191-200), or NULL: drawn uniformly on the device */
+    const float* weights;   /* host [P][weight_num][reward_dim] preferences, used as given (:221-223), or NULL: |N(0,1)| / L1 norm on the device */
+    float* loss_out;        /* host [P] or NULL (both outputs NULL: the call is asynchronous) */
+    float* weights_out;     /* host [P][weight_num][reward_dim] or NULL: the preferences the call used */
+};
+typedef struct frl_envelope_args frl_envelope_args;
+int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */

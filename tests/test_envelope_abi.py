@@ -1,0 +1,68 @@
+"""CPU: the C ABI of envelope multi-objective DQN — include/freerl_hip.h declares frl_envelope_learn, frl_envelope_args,
+FRL_ALGO_ENVELOPE_DQN = 8 and frl_config.reward_dim (the struct's LAST field, so a zeroed struct of an earlier caller is
+unchanged), freerl_amd/_native.py binds them, and the struct mirrors (_native.EnvelopeArgs, _native.Config, INTEGRATION.md's
+generated block) have the C compiler's sizes and field offsets."""
+import ctypes as C
+import os
+import re
+
+from tests.test_abi_and_host import HEADER, _gcc_layout, _load_stub_tool
+
+FIELDS = ["batch", "weight_num", "gamma", "tau", "lr", "beta", "idx", "weights", "loss_out", "weights_out"]
+
+
+def _header():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+def test_header_declares_the_entry_point():
+    src = _header()
+    assert re.search(r"\bFRL_ALGO_ENVELOPE_DQN\s*=\s*8\b", src)
+    assert re.search(r"\bint\s+frl_envelope_learn\s*\(\s*frl_engine\s*\*\s*e\s*,\s*const\s+frl_envelope_args\s*\*\s*args\s*\)\s*;", src)
+    # declared in two steps (struct, then typedef), as frl_reinforce_args is
+    assert re.search(r"(?<!typedef )\bstruct\s+frl_envelope_args\s*\{", src)
+    assert re.search(r"\btypedef\s+struct\s+frl_envelope_args\s+frl_envelope_args\s*;", src)
+    cfg = re.search(r"typedef\s+struct\s+frl_config\s*\{(.*?)\}\s*frl_config\s*;", src, flags=re.S).group(1)
+    assert [d.split()[-1] for d in cfg.split(";") if d.strip()][-1] == "reward_dim"
+
+
+def test_native_binds_it():
+    from freerl_amd import _native as N
+    assert N.ALGO_ENVELOPE_DQN == 8
+    res, args = N.SIGNATURES["frl_envelope_learn"]
+    assert res is C.c_int and args == [C.c_void_p, C.POINTER(N.EnvelopeArgs)]
+    assert [f for f, _ in N.EnvelopeArgs._fields_] == FIELDS
+    assert N.Config._fields_[-1][0] == "reward_dim" and N.Config().reward_dim == 0
+    from freerl_amd.engine import Engine
+    assert callable(Engine.envelope_learn)
+    from freerl_amd import Buffer, ENVELOPE_DQN
+    assert callable(ENVELOPE_DQN.ENVELOPE) and callable(Buffer.MO_Buffer)
+
+
+def test_struct_layout_matches_the_c_compiler(tmp_path):
+    from freerl_amd import _native as N
+    cfg_fields = [f for f, _ in N.Config._fields_]
+    want = _gcc_layout(tmp_path, [("frl_envelope_args", [(f, None) for f in FIELDS]), ("frl_config", [(f, None) for f in cfg_fields])])
+    tool = _load_stub_tool()
+    later = dict(tool.parse_later_structs())
+    assert [f for f, _ in later["frl_envelope_args"]] == FIELDS           # the generator sees the struct ...
+    ns = {}
+    exec(tool.extract(), ns)                                              # ... and INTEGRATION.md's block carries it
+    for cls in (N.EnvelopeArgs, ns["frl_envelope_args"]):
+        assert C.sizeof(cls) == want["frl_envelope_args"][0]
+        for f in FIELDS:
+            assert getattr(cls, f).offset == want["frl_envelope_args"][1][f], f
+    for cls in (N.Config, ns["frl_config"]):
+        assert C.sizeof(cls) == want["frl_config"][0]
+        for f in cfg_fields:
+            assert getattr(cls, f).offset == want["frl_config"][1][f], f
+    assert want["frl_config"][1]["reward_dim"] == want["frl_config"][1]["seed"] + 8      # appended behind the last earlier field
+
+
+def test_kernel_unit_and_register_table():
+    """The new translation unit is part of the library's build, and tools/kernel_regs.py lists its two kernels."""
+    from freerl_amd import _native as N
+    assert any(os.path.basename(u) == "kernels_envelope.hip" for u in N.units())
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    table = open(os.path.join(root, "tools", "kernel_regs.py")).read()
+    assert "envelope_weights_" in table and "envelope_grad_" in table

@@ -24,7 +24,10 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           ("sacd_critic_", 9), ("sacd_actor_", 0),
           # kernels_reinforce.hip: reinforce_returns_kernel 48 VGPRs, reinforce_grad_kernel 254 VGPRs; no spilled VGPR in either (the grad
           # kernel keeps 56 bytes of its row lambda's captures in scratch: stored at entry, three loads per row chunk, none in an MFMA loop)
-          ("reinforce_returns_", 0), ("reinforce_grad_", 0), ("", 20)]
+          ("reinforce_returns_", 0), ("reinforce_grad_", 0),
+          # kernels_envelope.hip: envelope_weights_kernel 38 VGPRs, none spilled; envelope_grad_kernel 256 VGPRs with 8 spilled and 88 bytes of
+          # scratch (the Lds carve and the chunk loop's bounds, as in sacd_critic_kernel: reloaded per pass or per row chunk, none in an MFMA loop)
+          ("envelope_weights_", 0), ("envelope_grad_", 8), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
