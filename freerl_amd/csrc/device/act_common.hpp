@@ -98,7 +98,7 @@ __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs&
         const size_t o = ((size_t)p * a.n_rows + r0 + r) * nout + c;
         float v = outb[r * op + c];
         if (a.mode == ACTM_SAC_SAMPLE || a.mode == ACTM_PPO_SAMPLE) {
-            const float ls = fminf(fmaxf(theta[N.extra_off + c], -20.f), 2.f);
+            const float ls = clamp_log_std(theta[N.extra_off + c]);
             const float sd = expf(ls);
             const float eps = a.eps ? a.eps[o] : (a.device_eps ? normal_at(0x9200u, (unsigned)((r0 + r) * nout + c)) : 0.f);
             const float u = v + sd * eps;
@@ -106,7 +106,7 @@ __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs&
                 v = tanhf(u);
             } else {
                 const float du = u - v;
-                if (a.out_logp) a.out_logp[o] = -(du * du) / (2.f * sd * sd) - ls - 0.91893853320467274178f;
+                if (a.out_logp) a.out_logp[o] = normal_logp(du, sd, ls);
                 v = u;
             }
         }

@@ -20,7 +20,6 @@
 //     (the accumulators of two wide heads do not fit next to each other, and the clip coefficient needs all of them).
 #pragma once
 #include "chain_net.hpp"
-#include "update_common.hpp"
 
 namespace frl {
 

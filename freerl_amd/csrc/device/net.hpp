@@ -11,6 +11,7 @@
 #pragma once
 #include "../frl_desc.h"
 #include "adam.hpp"
+#include "policy.hpp"
 #include "rng.hpp"
 #include "tile.hpp"
 

@@ -22,7 +22,6 @@
 // (all their workgroups must be resident at once: the grid barrier spins).
 #pragma once
 #include "chain_net.hpp"
-#include "update_common.hpp"
 
 namespace frl {
 

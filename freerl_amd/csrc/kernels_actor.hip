@@ -71,14 +71,8 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
         for (int c = 0; c < Aa; ++c) {
             float av = S.outb[r * S.op + c];
             if (sac) {
-                const float ls = fminf(fmaxf(thA[NA.extra_off + c], -20.f), 2.f);
-                const float sd = expf(ls);
                 const float eps = (r < nv) ? noise1[(size_t)r * am + c] : 0.f;
-                const float u = av + sd * eps;
-                const float du = u - av;
-                lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                av = tanhf(u);
+                av = sac_sample(av, thA[NA.extra_off + c], eps, lp);
             }
             S.abuf[r * S.ap + c] = av;
             S.dabuf[r * S.ap + c] = 0.f;
@@ -136,12 +130,11 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
         if (r < nv && c < Aa) {
             if (sac) {
                 const float av = S.abuf[r * S.ap + c];
-                d = S.dabuf[r * S.ap + c] * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                const float ls = fminf(fmaxf(thA[NA.extra_off + c], -20.f), 2.f);
-                S.dabuf[r * S.ap + c] = d * expf(ls) * noise1[(size_t)r * am + c] - alpha * invB;   // d/d log_std
+                d = sac_mean_delta(S.dabuf[r * S.ap + c], av, alpha, invB);
+                S.dabuf[r * S.ap + c] = sac_log_std_grad(d, thA[NA.extra_off + c], noise1[(size_t)r * am + c], alpha, invB);
             } else {
                 const float av = S.abuf[r * S.ap + c];      // the actor's tanh output (kept from the forward)
-                d = S.dabuf[r * S.ap + c] * (1.f - av * av);
+                d = tanh_delta(S.dabuf[r * S.ap + c], av);
             }
         } else if (sac && c < Aa) {
             S.dabuf[r * S.ap + c] = 0.f;
@@ -153,7 +146,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
         float gls = 0.f;
         for (int r = 0; r < rc; ++r) gls += S.dabuf[r * S.ap + threadIdx.x];
         const float raw = thA[NA.extra_off + threadIdx.x];
-        const float gl = (raw >= -20.f && raw <= 2.f) ? gls : 0.f;
+        const float gl = log_std_grad_open(raw) ? gls : 0.f;
         slab[NA.extra_off + threadIdx.x] = first ? gl : slab[NA.extra_off + threadIdx.x] + gl;
     }
     mlp_bwd(NA, 0, NA.n_layers, thA, slab, S, gs, false, 0, 0);

@@ -15,7 +15,6 @@
 
 #include "kernels.h"
 #include "device/chain_net.hpp"
-#include "device/update_common.hpp"
 #include "device/ppo_timing.hpp"
 
 namespace frl {
@@ -118,11 +117,7 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
                 for (int r = 0; r < 4; ++r) {
                     if (r < A && row < B) {
                         if (sac) {                                     // SAC.py:70-97
-                            const float ls = fminf(fmaxf(S.ls[r], -20.f), 2.f), sd = expf(ls);
-                            const float u = z[t][r] + sd * noise1[(size_t)row * am + r], du = u - z[t][r];
-                            lpsum += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                            lpsum -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                            an[r] = tanhf(u);
+                            an[r] = sac_sample(z[t][r], S.ls[r], noise1[(size_t)row * am + r], lpsum);
                         } else {
                             an[r] = tanhf(z[t][r]);
                         }
@@ -218,16 +213,15 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
                 for (int r = 0; r < 4; ++r) {
                     if (r < A) {
                         const float av = av4[r];
-                        const float d = dq[r] * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                        const float ls = fminf(fmaxf(S.ls[r], -20.f), 2.f);
+                        const float d = sac_mean_delta(dq[r], av, alpha, invB);
                         dz[r] = d;
-                        gls[r] += d * expf(ls) * ep[r] - alpha * invB;
+                        gls[r] += sac_log_std_grad(d, S.ls[r], ep[r], alpha, invB);
                     }
                 }
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
-                    if (r < A) { const float av = tanhf(z[0][r]); dz[r] = dq[r] * (1.f - av * av); }
+                    if (r < A) dz[r] = tanh_delta(dq[r], tanhf(z[0][r]));
             }
         }
         C.backward(g, xb[0], h1[0], h2[0], dz, A);
@@ -261,7 +255,7 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
         for (int r = 0; r < 4; ++r) {
             if (r < A) {
                 const float raw = S.ls[r];
-                const float gr = (raw >= -20.f && raw <= 2.f) ? red_sum(24 + 8 * r) : 0.f;
+                const float gr = log_std_grad_open(raw) ? red_sum(24 + 8 * r) : 0.f;
                 ss_extra += gr * gr;
                 if (i16 == r) g_extra = gr;
             }

@@ -107,11 +107,7 @@ __device__ __forceinline__ void ac_actor_wide_body(const EngineDesc& D, const Le
                                 const float zr = z[t][o3][r];
                                 float av;
                                 if (sac) {                             // SAC.py:70-97
-                                    const float ls = fminf(fmaxf(S.ls[c], -20.f), 2.f), sd = expf(ls);
-                                    const float u = zr + sd * noise1[(size_t)row * am + c], du = u - zr;
-                                    lpsum += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                                    lpsum -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                                    av = tanhf(u);
+                                    av = sac_sample(zr, S.ls[c], noise1[(size_t)row * am + c], lpsum);
                                 } else {
                                     av = tanhf(zr);
                                 }
@@ -227,13 +223,11 @@ __device__ __forceinline__ void ac_actor_wide_body(const EngineDesc& D, const Le
                     const float dq = X.dqa[(size_t)row * kWideApitch + c];
                     if (sac) {                                         // through a = tanh(u), u = mean + exp(log_std) eps, and alpha log pi
                         const float av = X.xrow[(size_t)row * X.xp + OT + aoff + c];
-                        const float d = dq * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                        const float ls = fminf(fmaxf(S.ls[c], -20.f), 2.f);
+                        const float d = sac_mean_delta(dq, av, alpha, invB);
                         dz[o3][r] = d;
-                        gls[o3][r] += d * expf(ls) * noise1[(size_t)row * am + c] - alpha * invB;
+                        gls[o3][r] += sac_log_std_grad(d, S.ls[c], noise1[(size_t)row * am + c], alpha, invB);
                     } else {
-                        const float av = tanhf(z[0][o3][r]);
-                        dz[o3][r] = dq * (1.f - av * av);
+                        dz[o3][r] = tanh_delta(dq, tanhf(z[0][o3][r]));
                     }
                 }
             }
@@ -272,7 +266,7 @@ __device__ __forceinline__ void ac_actor_wide_body(const EngineDesc& D, const Le
     float ss_extra = 0.f;
     if (sac && tid < Ai) {                                             // outside the clamp [-20, 2] the gradient is zero (SAC.py:77)
         const float raw = S.ls[tid];
-        const float gr = (raw >= -20.f && raw <= 2.f) ? ((lsred[tid] + lsred[32 + tid]) + lsred[64 + tid]) + lsred[96 + tid] : 0.f;
+        const float gr = log_std_grad_open(raw) ? ((lsred[tid] + lsred[32 + tid]) + lsred[64 + tid]) + lsred[96 + tid] : 0.f;
         grA[NA.extra_off + tid] = gr;
         ss_extra = gr * gr;
     }

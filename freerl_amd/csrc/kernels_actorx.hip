@@ -100,10 +100,11 @@ __device__ __forceinline__ void ac_actor_x_body(const EngineDesc& D, const Learn
                             const float zr = z[t][o3][r];
                             float av;
                             if (sac) {                                 // SAC.py:70-97
-                                const float lsc = fminf(fmaxf(N.ls[c], -20.f), 2.f), sd = expf(lsc);
+                                // (sac_sample written out: as its argument, eps is read ahead of expf — a2's spilled VGPRs 437 -> 435, scratch 800 -> 792)
+                                const float lsc = clamp_log_std(N.ls[c]), sd = expf(lsc);
                                 const float u = zr + sd * noise1[(size_t)row * am + c], du = u - zr;
-                                lpsum += -(du * du) / (2.f * sd * sd) - lsc - kLogSqrt2Pi;
-                                lpsum -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
+                                lpsum += normal_logp(du, sd, lsc);
+                                lpsum -= tanh_logp_correction(u);
                                 av = tanhf(u);
                             } else {
                                 av = tanhf(zr);
@@ -233,12 +234,13 @@ __device__ __forceinline__ void ac_actor_x_body(const EngineDesc& D, const Learn
                         const float dq = X.dqa[(size_t)row * kWideApitch + c];
                         const float av = X.xrow[(size_t)row * X.xp + OT + aoff + c];      // a_i (pass A)
                         if (sac) {                                     // through a = tanh(u), u = mean + exp(log_std) eps, and alpha log pi
-                            const float d = dq * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                            const float lsc = fminf(fmaxf(N.ls[c], -20.f), 2.f);
+                            const float d = sac_mean_delta(dq, av, alpha, invB);
+                            // (sac_log_std_grad written out, for the same read: a2's spilled VGPRs 437 -> 440, scratch 800 -> 808)
+                            const float lsc = clamp_log_std(N.ls[c]);
                             dz[t][o3][r] = d;
                             gls[o3][r] += d * expf(lsc) * noise1[(size_t)row * am + c] - alpha * invB;
                         } else {
-                            dz[t][o3][r] = dq * (1.f - av * av);
+                            dz[t][o3][r] = tanh_delta(dq, av);
                         }
                     }
                 }
@@ -281,7 +283,7 @@ __device__ __forceinline__ void ac_actor_x_body(const EngineDesc& D, const Learn
     float ss_extra = 0.f;
     if (sac && tid < Ai) {                                             // outside the clamp [-20, 2] the gradient is zero (SAC.py:77)
         const float raw = N.ls[tid];
-        const float gr = (raw >= -20.f && raw <= 2.f) ? ((lsred[tid] + lsred[32 + tid]) + lsred[64 + tid]) + lsred[96 + tid] : 0.f;
+        const float gr = log_std_grad_open(raw) ? ((lsred[tid] + lsred[32 + tid]) + lsred[64 + tid]) + lsred[96 + tid] : 0.f;
         grA[NA.extra_off + tid] = gr;
         ss_extra = gr * gr;
     }

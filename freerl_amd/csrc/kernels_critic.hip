@@ -77,25 +77,14 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const Engi
             if (sac) {                              // SAC.py:70-97 on actor_target (SAC.py:227)
                 float lp = 0.f;
                 for (int c = 0; c < Aj; ++c) {
-                    const float mean = S.outb[r * S.op + c];
-                    const float ls = fminf(fmaxf(tgJ[NJ.extra_off + c], -20.f), 2.f);
-                    const float sd = expf(ls);
                     const float eps = (r < nv) ? noise0[(size_t)r * am + c] : 0.f;
-                    const float u = mean + sd * eps;
-                    const float du = u - mean;
-                    lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                    lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                    S.abuf[r * S.ap + cj + c] = tanhf(u);
+                    S.abuf[r * S.ap + cj + c] = sac_sample(S.outb[r * S.op + c], tgJ[NJ.extra_off + c], eps, lp);
                 }
                 lp_next = lp;
             } else {
                 for (int c = 0; c < Aj; ++c) {
                     float v = S.outb[r * S.op + c];
-                    if (a.use_policy_noise && r < nv) {   // TD3.py:196-198
-                        float nz = a.policy_noise_scale * (noise0[(size_t)r * am + c] * a.policy_noise);
-                        nz = fminf(fmaxf(nz, -a.noise_clip), a.noise_clip);
-                        v = fminf(fmaxf(v * a.max_action + nz, -a.max_action), a.max_action) / a.max_action;
-                    }
+                    if (a.use_policy_noise && r < nv) v = td3_smooth(a, v, noise0[(size_t)r * am + c]);
                     S.abuf[r * S.ap + cj + c] = v;
                 }
             }
@@ -131,8 +120,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const Engi
     if (threadIdx.x < nv) {
         g_cf rec = ring + (size_t)idx[threadIdx.x] * R.stride;
         const float rew = rec[R.rew_off + ag], done = rec[R.done_off + ag];
-        S.y[threadIdx.x] = sac ? rew + a.gamma * (1.f - done) * (q + alpha * (-lp_next))
-                               : rew + a.gamma * q * (1.f - done);
+        S.y[threadIdx.x] = sac ? td_target_sac(rew, done, a.gamma, q, alpha, lp_next) : td_target(rew, done, a.gamma, q);
     }
     FRL_PHASE(S);
 

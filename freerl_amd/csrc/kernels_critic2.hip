@@ -16,7 +16,6 @@
 
 #include "kernels.h"
 #include "device/chain_net.hpp"
-#include "device/update_common.hpp"
 #include "device/ppo_timing.hpp"
 
 #if defined(FRL_BWD_TIMING)
@@ -201,24 +200,14 @@ __device__ __forceinline__ void ac_critic_v2_body(const EngineDesc& D, const Lea
                     if (sac) {                                         // SAC.py:70-97 on actor_target (SAC.py:227)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            if (r < A) {
-                                const float ls = fminf(fmaxf(S.ls[r], -20.f), 2.f), sd = expf(ls);
-                                const float u = z[t][r] + sd * nr[r], du = u - z[t][r];
-                                lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                                lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                                an[r] = tanhf(u);
-                            }
+                            if (r < A) an[r] = sac_sample(z[t][r], S.ls[r], nr[r], lp);
                         }
                     } else {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             if (r < A) {
                                 float v = tanhf(z[t][r]);
-                                if (a.use_policy_noise) {              // TD3.py:196-198
-                                    float nz = a.policy_noise_scale * (nr[r] * a.policy_noise);
-                                    nz = fminf(fmaxf(nz, -a.noise_clip), a.noise_clip);
-                                    v = fminf(fmaxf(v * a.max_action + nz, -a.max_action), a.max_action) / a.max_action;
-                                }
+                                if (a.use_policy_noise) v = td3_smooth(a, v, nr[r]);
                                 an[r] = v;
                             }
                         }
@@ -270,7 +259,7 @@ __device__ __forceinline__ void ac_critic_v2_body(const EngineDesc& D, const Lea
                     if (hd == 1) qv = fminf(S.q1[row], qv);
                     if (hd == NH - 1) {
                         const float rew = cur.rew[t], done = cur.done[t];
-                        S.yb[row] = sac ? rew + a.gamma * (1.f - done) * (qv + alpha * (-S.lpn[row])) : rew + a.gamma * qv * (1.f - done);
+                        S.yb[row] = sac ? td_target_sac(rew, done, a.gamma, qv, alpha, S.lpn[row]) : td_target(rew, done, a.gamma, qv);
                     } else {
                         S.q1[row] = qv;
                     }

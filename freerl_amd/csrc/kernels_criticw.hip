@@ -97,18 +97,15 @@ __device__ __forceinline__ void ac_critic_wide_body(const EngineDesc& D, const L
                             if (valid && c < Aj) {
                                 const float zr = z[t][o3][r];
                                 if (sac) {                             // SAC.py:70-97 on actor_target (SAC.py:227)
-                                    const float ls = fminf(fmaxf(S.ls[c], -20.f), 2.f), sd = expf(ls);
+                                    // (sac_sample written out: as its argument, eps is read ahead of expf — h2a2's SGPR spills 267 -> 269)
+                                    const float ls = clamp_log_std(S.ls[c]), sd = expf(ls);
                                     const float u = zr + sd * nz[(size_t)row * am + c], du = u - zr;
-                                    lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                                    lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
+                                    lp += normal_logp(du, sd, ls);
+                                    lp -= tanh_logp_correction(u);
                                     an[o3][r] = tanhf(u);
                                 } else {
                                     float v = tanhf(zr);
-                                    if (a.use_policy_noise) {          // TD3.py:196-198
-                                        float n1 = a.policy_noise_scale * (nz[(size_t)row * am + c] * a.policy_noise);
-                                        n1 = fminf(fmaxf(n1, -a.noise_clip), a.noise_clip);
-                                        v = fminf(fmaxf(v * a.max_action + n1, -a.max_action), a.max_action) / a.max_action;
-                                    }
+                                    if (a.use_policy_noise) v = td3_smooth(a, v, nz[(size_t)row * am + c]);
                                     an[o3][r] = v;
                                 }
                             }
@@ -164,7 +161,7 @@ __device__ __forceinline__ void ac_critic_wide_body(const EngineDesc& D, const L
                         if (hd == NH - 1) {
                             g_cf rec = recp[2 * half + t];
                             const float rew = rec[R.rew_off + ag], done = rec[R.done_off + ag];
-                            X.yb[row] = sac ? rew + a.gamma * (1.f - done) * (qv + alpha * (-X.lpn[row])) : rew + a.gamma * qv * (1.f - done);
+                            X.yb[row] = sac ? td_target_sac(rew, done, a.gamma, qv, alpha, X.lpn[row]) : td_target(rew, done, a.gamma, qv);
                         } else {
                             X.q1[row] = qv;
                         }

@@ -96,18 +96,15 @@ __device__ __forceinline__ void ac_critic_x_body(const EngineDesc& D, const Lear
                             const float zr = z[t][o3][r];
                             float av;
                             if (sac) {                                 // SAC.py:70-97 on actor_target (SAC.py:227)
-                                const float lsc = fminf(fmaxf(N.ls[c], -20.f), 2.f), sd = expf(lsc);
+                                // (sac_sample written out: as its argument, eps is read ahead of expf — SGPR spills of h1a2 / h2a1 / h2a2 248 / 477 / 485 -> 236 / 479 / 486)
+                                const float lsc = clamp_log_std(N.ls[c]), sd = expf(lsc);
                                 const float u = zr + sd * nz[(size_t)row * am + c], du = u - zr;
-                                lp += -(du * du) / (2.f * sd * sd) - lsc - kLogSqrt2Pi;
-                                lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
+                                lp += normal_logp(du, sd, lsc);
+                                lp -= tanh_logp_correction(u);
                                 av = tanhf(u);
                             } else {
                                 av = tanhf(zr);
-                                if (a.use_policy_noise) {              // TD3.py:196-198
-                                    float n1 = a.policy_noise_scale * (nz[(size_t)row * am + c] * a.policy_noise);
-                                    n1 = fminf(fmaxf(n1, -a.noise_clip), a.noise_clip);
-                                    av = fminf(fmaxf(av * a.max_action + n1, -a.max_action), a.max_action) / a.max_action;
-                                }
+                                if (a.use_policy_noise) av = td3_smooth(a, av, nz[(size_t)row * am + c]);
                             }
                             X.xrow[(size_t)row * X.xp + OT + aoff + c] = av;
                         }
@@ -155,7 +152,7 @@ __device__ __forceinline__ void ac_critic_x_body(const EngineDesc& D, const Lear
                     if (hd == 1) qv = fminf(X.q1[row], qv);
                     if (hd == NH - 1) {
                         const float rew = recp[t][R.rew_off + ag], done = recp[t][R.done_off + ag];
-                        X.yb[row] = sac ? rew + a.gamma * (1.f - done) * (qv + alpha * (-X.lpn[row])) : rew + a.gamma * qv * (1.f - done);
+                        X.yb[row] = sac ? td_target_sac(rew, done, a.gamma, qv, alpha, X.lpn[row]) : td_target(rew, done, a.gamma, qv);
                     } else {
                         X.q1[row] = qv;
                     }

@@ -16,7 +16,6 @@
 
 #include "kernels.h"
 #include "device/chain.hpp"
-#include "device/update_common.hpp"
 #include "device/ppo_timing.hpp"
 
 namespace frl {

@@ -268,7 +268,6 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)p * a.k_epochs * n_mb * 2;
     constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;   // 0.5 + 0.5*log(2*pi)
-    constexpr float kLogSqrt2Pi = 0.91893853320467274178f;
     PPO_T0();
 
     for (int k = 0; k < a.k_epochs; ++k) {
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
             // ---------------- actor: clipped surrogate + entropy bonus (:324-346)
             float lossp = 0.f, gls = 0.f, ent = 0.f;
             if (!discrete && !beta && threadIdx.x < A) {
-                const float ls = fminf(fmaxf(thA[NA.extra_off + threadIdx.x], -20.f), 2.f);
+                const float ls = clamp_log_std(thA[NA.extra_off + threadIdx.x]);
                 ent = kHalfLog2PiPlusHalf + ls;
             }
             const float ent_sum = block_sum(ent, S.red);          // same for every row
@@ -399,10 +398,10 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                         float lp_now = 0.f, lp_old = 0.f;
                         for (int c = 0; c < A; ++c) {
                             const float mean = S.outb[r * S.op + c];
-                            const float ls = fminf(fmaxf(thA[NA.extra_off + c], -20.f), 2.f);
+                            const float ls = clamp_log_std(thA[NA.extra_off + c]);
                             const float sd = expf(ls);
                             const float d = rec[R.act_off[0] + c] - mean;
-                            lp_now += -(d * d) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
+                            lp_now += normal_logp(d, sd, ls);
                             lp_old += rec[logp_col + c];
                         }
                         const float ratio = expf(lp_now - lp_old);
@@ -421,7 +420,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                     if (r < nv && c < A) {
                         const float coef = S.dabuf[r * S.ap];
                         const float mean = S.outb[r * S.op + c];
-                        const float ls = fminf(fmaxf(thA[NA.extra_off + c], -20.f), 2.f);
+                        const float ls = clamp_log_std(thA[NA.extra_off + c]);
                         const float var = expf(2.f * ls);
                         const float dm = ring[(size_t)idx[r0 + r] * R.stride + R.act_off[0] + c] - mean;
                         d = coef * dm / var * (1.f - mean * mean);        // through mean = tanh(z)
@@ -442,7 +441,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
             }
             if (!discrete && !beta && threadIdx.x < A) {
                 const float raw = thA[NA.extra_off + threadIdx.x];
-                gA[NA.extra_off + threadIdx.x] = (raw >= -20.f && raw <= 2.f) ? (gls - a.ent_coef) : 0.f;
+                gA[NA.extra_off + threadIdx.x] = log_std_grad_open(raw) ? (gls - a.ent_coef) : 0.f;
             }
             const float aloss = block_sum(lossp, S.red) * invm - ((discrete || beta) ? 0.f : a.ent_coef * ent_sum);
             __syncthreads();

@@ -90,7 +90,7 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
     int t_step = steps[critic ? 1 : 0];
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)p * a.k_epochs * n_mb * 2;
-    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f, kLogSqrt2Pi_ = 0.91893853320467274178f;
+    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;
     const float lr = critic ? a.critic_lr : a.actor_lr;
 
     // ---- parameters -> LDS (fragment order); engine layout: Wk[k][n] (n contiguous) then b[n_pad]
@@ -261,7 +261,7 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int c = 4 * q + r;
-                        const float lsr = fminf(fmaxf(S.ls[c & 15], -20.f), 2.f);
+                        const float lsr = clamp_log_std(S.ls[c & 15]);
                         mean[r] = tanhf(z[r]);
                         var[r] = expf(2.f * lsr);
                         dm[r] = (valid && c < A) ? cur.act[r] - mean[r] : 0.f;
@@ -275,8 +275,8 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
                             for (int r = 0; r < 4; ++r) {
                                 const int c = 4 * g + r;
                                 if (c < A) {
-                                    const float lsr = fminf(fmaxf(S.ls[c], -20.f), 2.f), sd = expf(lsr);
-                                    lp_now += -(dm[r] * dm[r]) / (2.f * sd * sd) - lsr - kLogSqrt2Pi_;
+                                    const float lsr = clamp_log_std(S.ls[c]), sd = expf(lsr);
+                                    lp_now += normal_logp(dm[r], sd, lsr);
                                     lp_old += cur.lpo[r];
                                 }
                             }
@@ -491,14 +491,14 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
             if (gauss && w == 0 && i16 < A) {
                 gls_tot = ((S.red[32 + i16] + S.red[48 + i16]) + S.red[64 + i16]) + S.red[80 + i16];
                 const float raw = S.ls[i16];
-                gls_tot = (raw >= -20.f && raw <= 2.f) ? (gls_tot - a.ent_coef) : 0.f;
+                gls_tot = log_std_grad_open(raw) ? (gls_tot - a.ent_coef) : 0.f;
             }
             float ss_ls = (gauss && w == 0 && q == 0 && i16 < A) ? gls_tot * gls_tot : 0.f;
             ss_ls = wave_sum(ss_ls);                               // wave 0 only holds non-zero values
             if (w == 0 && l == 0) S.red[16] = ss_ls;
             float ent_sum = 0.f;
             if (gauss) {
-                for (int c = 0; c < A; ++c) ent_sum += kHalfLog2PiPlusHalf + fminf(fmaxf(S.ls[c], -20.f), 2.f);
+                for (int c = 0; c < A; ++c) ent_sum += kHalfLog2PiPlusHalf + clamp_log_std(S.ls[c]);
             }
             lds_barrier();
             const float total = sqrtf((((S.red[0] + S.red[1]) + S.red[2]) + S.red[3]) + S.red[16]);

@@ -275,18 +275,10 @@ __device__ __forceinline__ void solo_critic_body(const EngineDesc& D, const Lear
         for (int r = 0; r < 4; ++r) {
             if (r < A) {
                 if (sac) {
-                    const float ls = fminf(fmaxf(C.S.ls[r], -20.f), 2.f), sd = expf(ls);
-                    const float u = z[r] + sd * nz[r], du = u - z[r];
-                    lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                    lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                    an[r] = tanhf(u);
+                    an[r] = sac_sample(z[r], C.S.ls[r], nz[r], lp);
                 } else {
                     float v = tanhf(z[r]);
-                    if (a.use_policy_noise) {
-                        float n1 = a.policy_noise_scale * (nz[r] * a.policy_noise);
-                        n1 = fminf(fmaxf(n1, -a.noise_clip), a.noise_clip);
-                        v = fminf(fmaxf(v * a.max_action + n1, -a.max_action), a.max_action) / a.max_action;
-                    }
+                    if (a.use_policy_noise) v = td3_smooth(a, v, nz[r]);
                     an[r] = v;
                 }
             }
@@ -309,7 +301,7 @@ __device__ __forceinline__ void solo_critic_body(const EngineDesc& D, const Lear
             if constexpr (NH == 2) qmin = fminf(qmin, zc[1][0]);
         }
         SOLO_T(2);
-        const float y = sac ? rew + a.gamma * (1.f - done) * (qmin + alpha * (-lp)) : rew + a.gamma * qmin * (1.f - done);
+        const float y = sac ? td_target_sac(rew, done, a.gamma, qmin, alpha, lp) : td_target(rew, done, a.gamma, qmin);
         // ---- the critic's heads: forward, TD delta, backward -> this workgroup's slab
         const f32x4 xin = critic_input(N, so, ac, O, A);
 #pragma unroll
@@ -444,11 +436,7 @@ __device__ __forceinline__ void solo_actor_body(const EngineDesc& D, const Learn
             if (r < A) {
                 if (sac) {
                     lsv[r] = C.S.ls[r];
-                    const float ls = fminf(fmaxf(lsv[r], -20.f), 2.f), sd = expf(ls);
-                    const float u = za[r] + sd * ep[r], du = u - za[r];
-                    lpr += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                    lpr -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                    an[r] = tanhf(u);
+                    an[r] = sac_sample(za[r], lsv[r], ep[r], lpr);
                 } else {
                     an[r] = tanhf(za[r]);
                 }
@@ -488,12 +476,11 @@ __device__ __forceinline__ void solo_actor_body(const EngineDesc& D, const Learn
                 if (r < A) {
                     const float av = an[r];
                     if (sac) {                                             // through u = mean + exp(log_std) eps, and alpha log pi
-                        const float d = dq[r] * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                        const float ls = fminf(fmaxf(lsv[r], -20.f), 2.f);
+                        const float d = sac_mean_delta(dq[r], av, alpha, invB);
                         dz[r] = d;
-                        gls[r] = d * expf(ls) * ep[r] - alpha * invB;
+                        gls[r] = sac_log_std_grad(d, lsv[r], ep[r], alpha, invB);
                     } else {
-                        dz[r] = dq[r] * (1.f - av * av);
+                        dz[r] = tanh_delta(dq[r], av);
                     }
                 }
             }
@@ -507,7 +494,7 @@ __device__ __forceinline__ void solo_actor_body(const EngineDesc& D, const Learn
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float sgl = SoloNet::rows_sum(gls[r]);
-            if (i16 == r) gl = (sac && r < A && lsv[r] >= -20.f && lsv[r] <= 2.f) ? sgl : 0.f;
+            if (i16 == r) gl = (sac && r < A && log_std_grad_open(lsv[r])) ? sgl : 0.f;
         }
         if (w == 0 && q == 0) slab[kHeadFloats + i16] = gl;
         lp += valid ? lpr : 0.f;

@@ -40,18 +40,10 @@ __device__ __forceinline__ float policy_rows(const SoloWNet& N, const LearnArgs&
                 const float zr = z[t][r];
                 if (sac) {
                     lsv[t][r] = N.C.S.ls[c];
-                    const float ls = fminf(fmaxf(lsv[t][r], -20.f), 2.f), sd = expf(ls);
-                    const float u = zr + sd * nz[t][r], du = u - zr;
-                    lp += -(du * du) / (2.f * sd * sd) - ls - kLogSqrt2Pi;
-                    lp -= 2.f * (kLog2 - u - softplus_t(-2.f * u));
-                    an[t][r] = tanhf(u);
+                    an[t][r] = sac_sample(zr, lsv[t][r], nz[t][r], lp);
                 } else {
                     float v = tanhf(zr);
-                    if (TARGET && a.use_policy_noise) {
-                        float n1 = a.policy_noise_scale * (nz[t][r] * a.policy_noise);
-                        n1 = fminf(fmaxf(n1, -a.noise_clip), a.noise_clip);
-                        v = fminf(fmaxf(v * a.max_action + n1, -a.max_action), a.max_action) / a.max_action;
-                    }
+                    if (TARGET && a.use_policy_noise) v = td3_smooth(a, v, nz[t][r]);
                     an[t][r] = v;
                 }
             }
@@ -249,7 +241,7 @@ __device__ __forceinline__ void solow_critic_body(const EngineDesc& D, const Lea
             }
         }
         SOLO_T(2);
-        const float y = sac ? rew + a.gamma * (1.f - done) * (qmin + alpha * (-lp)) : rew + a.gamma * qmin * (1.f - done);
+        const float y = sac ? td_target_sac(rew, done, a.gamma, qmin, alpha, lp) : td_target(rew, done, a.gamma, qmin);
         // ---- the critic's heads: forward, TD delta, backward -> this workgroup's slab, on [s | a] (every wave is behind the
         // first-layer reads of the last target pass: its two barriers)
         N.x_commit(xr, KB1c);
@@ -485,12 +477,11 @@ __device__ __forceinline__ void solow_actor_body(const EngineDesc& D, const Lear
                 if (valid && c < Ai) {
                     const float av = an[t][r];
                     if (sac) {                                             // through u = mean + exp(log_std) eps, and alpha log pi
-                        const float d = dq[t][r] * (1.f - av * av) + (alpha * invB) * (2.f * av);
-                        const float ls = fminf(fmaxf(lsv[t][r], -20.f), 2.f);
+                        const float d = sac_mean_delta(dq[t][r], av, alpha, invB);
                         dz[t][r] = d;
-                        gls[t][r] = d * expf(ls) * ep[t][r] - alpha * invB;
+                        gls[t][r] = sac_log_std_grad(d, lsv[t][r], ep[t][r], alpha, invB);
                     } else {
-                        dz[t][r] = dq[t][r] * (1.f - av * av);
+                        dz[t][r] = tanh_delta(dq[t][r], av);
                     }
                 }
             }
@@ -506,7 +497,7 @@ __device__ __forceinline__ void solow_actor_body(const EngineDesc& D, const Lear
                 for (int r = 0; r < 4; ++r) {
                     const int c = 16 * t + 4 * q + r;
                     const float sgl = SoloNet::rows_sum(gls[t][r]);
-                    if (w == 0 && i16 == 0 && c < Ai) slab[NA.extra_off + c] = (lsv[t][r] >= -20.f && lsv[t][r] <= 2.f) ? sgl : 0.f;
+                    if (w == 0 && i16 == 0 && c < Ai) slab[NA.extra_off + c] = log_std_grad_open(lsv[t][r]) ? sgl : 0.f;
                 }
         }
         lp = valid ? lpr : 0.f;

@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 
 #include "device/net.hpp"
-#include "device/update_common.hpp"
 #include "kernels.h"
 #include "device/noisy.hpp"
 
