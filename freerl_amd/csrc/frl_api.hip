@@ -64,6 +64,36 @@ static int fail(int code, const char* fmt, ...) {
 static inline int pad16(int x) { return (x + 15) / 16 * 16; }
 static inline int pad32(int x) { return (x + 31) / 32 * 32; }
 
+// developer / test knobs from the environment, read where they are used (most of them per call).  Three meanings, kept apart:
+// env_set: the variable is set at all; env_flag(name, false): set and nonzero; env_flag(name, true): a default-on path that "=0" switches off
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
+static bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
+
+// The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels and LDS bytes).
+// frl_create fixes the engine's chained family — or none: FAM_ROWCHUNK — with its parameter layout; learn_family() says what one call takes.
+enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16 };
+using LearnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs);
+using SolowKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs);
+using SoloKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs, frl::SoloStepArgs);
+using DqnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::DqnStepArgs);
+struct KernelPtr {                // one typed member per kernel signature; a family uses the one its kernels have
+    LearnKernel k = nullptr;
+    SolowKernel kw = nullptr;
+    SoloKernel ks = nullptr;
+    DqnKernel kd = nullptr;
+    KernelPtr() = default;
+    KernelPtr(LearnKernel f) : k(f) {}
+    KernelPtr(SolowKernel f) : kw(f) {}
+    KernelPtr(SoloKernel f) : ks(f) {}
+    KernelPtr(DqnKernel f) : kd(f) {}
+    const void* address() const { return k ? (const void*)k : kw ? (const void*)kw : ks ? (const void*)ks : (const void*)kd; }
+};
+struct LearnKernels {             // a family's kernels for one engine's shape (resolve_learn_kernels)
+    KernelPtr critic, critic_nv, actor, step;
+    int lds_bytes = 0, block = 256;
+};
+
 struct frl_engine {
     frl_config cfg;
     EngineDesc h;                 // host mirror of the device descriptor
@@ -71,6 +101,8 @@ struct frl_engine {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_stage = nullptr;
     int lds_bytes = 0;
+    LearnFamily family = FAM_ROWCHUNK;    // the chained kernel family the engine was created for (host only; frl_obsnorm_enable moves it to the row-chunk kernels for good)
+    LearnKernels kern;                    // ... its kernels (a DQN engine: the one-launch update's)
     // replay cursors (host authoritative, reference semantics Buffer.py:23-24,36-38)
     std::vector<int> index, size;
     // pinned staging of not-yet-flushed adds
@@ -146,7 +178,6 @@ struct frl_engine {
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
     int lds_per_cu = 160 * 1024;          // LDS bytes of one compute unit
-    int chain_waves = 8;                  // waves per workgroup of the register-chained actor-critic kernels (FRL_CHAIN_WAVES=4: round 5's)
     int* stage_bucket = nullptr;          // PER, pinned: [off[P + 1] | size_before[P] | leaf[stage_cap]] of the flush being applied
     int* d_stage_bucket = nullptr;
     float* d_per_prio = nullptr;          // [P][batch_max] float32 priorities of the last sample
@@ -328,8 +359,9 @@ static hipError_t dalloc_zero(T** p, size_t count, hipStream_t s) {
     return hipMemsetAsync(*p, 0, count * sizeof(T), s);
 }
 
-static bool chained_shape(const EngineDesc& h);
-static bool wide_shape(const EngineDesc& h);
+static LearnFamily choose_engine_family(frl_engine* e);       // frl_api_learn.inc
+static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, const EngineDesc& h);
+static hipError_t set_family_lds_attributes(LearnFamily fam);
 
 extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (!cfg || !out) return fail(FRL_ERR_INVALID, "cfg/out is NULL");
@@ -356,8 +388,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             e->n_cus = std::max(1, prop.multiProcessorCount);
             e->lds_per_cu = (int)std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock);
         }
-        const char* fc = getenv("FRL_ASSUME_CUS");                      // (tests: a smaller / partitioned device)
-        if (fc && atoi(fc) > 0) e->n_cus = atoi(fc);
+        const int fc = env_int("FRL_ASSUME_CUS", 0);                    // (tests: a smaller / partitioned device)
+        if (fc > 0) e->n_cus = fc;
     }
     EngineDesc& h = e->h;
     memset(&h, 0, sizeof h);
@@ -454,64 +486,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         }
     }
     h.learner_stride = pad32(off);
-    if (e->has_nets && chained_shape(h) && !(getenv("FRL_SOLOW_NARROW") && atoi(getenv("FRL_SOLOW_NARROW")) != 0)) {       // kernel family (and with it the parameter layout in HBM), fixed for the engine's life
-        // (FRL_SOLOW_NARROW=1, developer knob: the narrow standard shape on kernels_solow.hip — one first-layer k-tile — for A/Bs against kernels_solo.hip)
-        const char* force = getenv("FRL_CRITIC_V2");
-        // measured (bench workload, updates/s): 128 learners are exactly one round of the row-chunk kernels' 512 resident
-        // workgroups — 484 k against 373 k for 128 one-learner workgroups on half the CUs; from 129 up the chained kernels win
-        // (160: 459 k / 393 k, 256: 694 k / 566 k) or tie (320: 472 k / 480 k)
-        // up to kSoloMaxP learners: one learner on sixteen workgroups (kernels_solo.hip; FRL_SOLO=0/1 overrides, FRL_CRITIC_V2 set
-        // means the caller asked for one of the other two families by name)
-        const char* solo = getenv("FRL_SOLO");
-        // (every one of its P x 16 workgroups — 156 KB of LDS each: one per CU — has to be RESIDENT: they wait for each other's flags.
-        //  On a device with fewer CUs, a CU-masked or partitioned one, the row-chunk kernels take the engine instead)
-        // h.solo = workgroups per learner: 16 (one 16-row tile each) up to 16 learners; 8 (two tiles each, a slab per tile) up to 32
-        // learners — populations the row-chunk kernels used to take at 150-160 us per learn() (kernels_solo.hip has the numbers;
-        // FRL_SOLO_MAXP: the largest population on this family, default 32)
-        const char* smp = getenv("FRL_SOLO_MAXP");
-        const int solo_maxp = smp ? std::min(atoi(smp), 2 * kSoloMaxP) : 2 * kSoloMaxP;
-        int wgs = 0;
-        for (int cand : {16, 8})
-            if (wgs == 0 && (long long)h.P * cand <= e->n_cus && h.P * cand <= kSoloMaxP * kSoloWG) wgs = cand;
-        const bool solo_fits = wgs > 0 && h.P <= solo_maxp && e->lds_per_cu >= (int)(std::max(solo_lds_floats(), critic2_lds_floats()) * sizeof(float));
-        h.solo = (solo ? atoi(solo) != 0 : !force) && solo_fits ? wgs : 0;
-        if (h.solo || (force ? atoi(force) != 0 : h.P > 128)) h.net[0].frag = h.net[1].frag = 1;
-    } else if (e->has_nets && wide_shape(h)) {   // the K-sliced chained family (kernels_criticw.hip / kernels_actorw.hip): one workgroup per (learner, agent)
-        const char* force = getenv("FRL_CRITIC_V2");
-        // a handful of single-agent learners at hidden 128: sixteen workgroups per learner, W1 streamed from the block (kernels_solow.hip;
-        // FRL_SOLOW=0/1 overrides, FRL_CRITIC_V2 set means the caller asked for one of the other two families by name).  Every one of
-        // the P x 16 workgroups has to be resident, as for kernels_solo.hip.  [s | a] must be the record's first columns, 16-byte aligned
-        const char* sw = getenv("FRL_SOLOW");
-        // ... MADDPG / MATD3 (config 5: three agents, batches of 1024): a unit = (learner, agent), 64 row tiles = 64 workgroups per unit; the
-        // updating agent's own observation rows sit behind the joint rows in LDS, so both first layers have at most kSoloWActorBase k-tiles
-        bool solow_shape = h.hidden == 128 && h.batch_max <= (h.n_agents == 1 ? 256 : 1024) && h.rec.stride % 4 == 0 && h.rec.obs_off[0] % 4 == 0 &&
-                           h.rec.act_off[0] == h.rec.obs_off[0] + h.rec.obs_total;
-        for (int i = 0; i < h.n_nets; ++i) solow_shape = solow_shape && h.net[i].L[0].k_pad <= 16 * (h.n_agents == 1 ? kSoloWMaxKB : kSoloWActorBase);
-        const int solow_tiles = h.batch_max <= 256 ? kSoloWG : 4 * kSoloWG;
-        const long long solow_units = (long long)h.P * h.n_agents;
-        // (two row tiles per workgroup for 17 .. 32 units: measured level with the row-chunk chain — kernels_solow.hip — and not built)
-        const int solow_rw = solow_tiles;
-        const bool solow_fits = solow_units <= kSoloMaxP && solow_units * solow_rw <= e->n_cus && e->lds_per_cu >= (int)(solow_lds_floats() * sizeof(float) + 256);
-        if ((sw ? atoi(sw) != 0 : !force) && solow_shape && solow_fits) {
-            for (int i = 0; i < h.n_nets; ++i) h.net[i].frag = 1;
-            h.solow = solow_tiles;
-            e->solow_row_wgs = solow_rw;
-        } else
-        // from 129 (learner, agent) units up: hidden 128 (chain_wide.hpp) SAC at Humanoid dims 85.5 TFLOP/s against the row-chunk
-        // kernels' 46.2, MADDPG simple_spread 77.2 / 55.5; hidden 256 (chain_wide16.hpp: x-stationary sweeps) 71.1 / 56.9
-        // (profiles/r04)
-        // (profiles/r04/family_crossover.txt: hidden 128 ties at ~110-129 units; hidden 256 at 128 units 38.9 against 53.1, at 192
-        // 55.3 / 51.5, at 256 68.0 / 55.7 — its workgroups are twice as long, so the half-empty chip costs more: from 177 up)
-        if (force ? atoi(force) != 0 : (long long)h.P * h.n_agents > (h.hidden == 256 ? 176 : 128)) {
-            for (int i = 0; i < h.n_nets; ++i) h.net[i].frag = 1;
-            h.wide = h.hidden == 256 ? 2 : 1;
-            h.wide_bm = h.wide == 2 ? (h.batch_max + 255) / 256 * 256 : (h.batch_max + 63) / 64 * 64;      // (hidden 256 works in super-chunks of 256 rows)
-            h.wide_xp = h.net[1].L[0].k_pad;
-            h.wide_op = 16;
-            for (int j = 0; j < h.n_agents; ++j) h.wide_op = std::max(h.wide_op, h.net[2 * j].L[0].k_pad);
-            h.wide_unit = ((h.wide_xp + h.n_agents * h.wide_op + (h.wide == 2 ? kWide16ScratchPerRowHost : kWideScratchPerRow)) * h.wide_bm + 128 + 63) / 64 * 64;
-        }
-    }
+    e->family = choose_engine_family(e);
     h.act_max = 1;
     for (int j = 0; j < c.n_agents; ++j) h.act_max = std::max(h.act_max, R.act_dim[j]);
     h.lds_kin_pad = kin;
@@ -540,8 +515,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
     if (c.algo != FRL_ALGO_PPO && h.rc == 64 && (long long)h.P * ((h.batch_max + 63) / 64) < 512) h.rc = 32;
-    if (const char* force = getenv("FRL_RC")) {             // developer knob: rows per workgroup (16 / 32 / 64 / 128)
-        const int v = atoi(force);
+    {   // developer knob: rows per workgroup (16 / 32 / 64 / 128)
+        const int v = env_int("FRL_RC", 0);
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
     if (lds_bytes_for(h, h.rc) > 160 * 1024) { delete e; return fail(FRL_ERR_INVALID, "network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc)); }
@@ -579,8 +554,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; h.cps = cps; }
         }
         if (c.algo == FRL_ALGO_PPO) h.cps = 1;
-        if (const char* force = getenv("FRL_CPS")) {        // developer knob
-            const int v = atoi(force);
+        {   // developer knob
+            const int v = env_int("FRL_CPS", 0);
             if (v >= 1 && n_chunks % v == 0) h.cps = v;
         }
         h.S = n_chunks / h.cps;
@@ -652,10 +627,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             //  FRL_SOLOW_HELPERS=0 switches them off; every workgroup of a launch must be resident)
             e->solow_wgs = (int)NT;
             if (h.solow) {
-                const char* hp = getenv("FRL_SOLOW_HELPERS");
                 const int rw = e->solow_row_wgs;
                 const int per = std::min(64 / rw > 0 ? 64 / rw : 1, std::max(1, e->n_cus / (rw * (int)U)));      // (at most 64 workgroups per unit: the mailboxes are polled by one wave)
-                e->solow_wgs = (hp && atoi(hp) == 0) ? rw : rw * per;
+                e->solow_wgs = env_flag("FRL_SOLOW_HELPERS", true) ? rw * per : rw;
             }
             CREATE_TRY(dalloc_zero(&e->d_solo_part, U * (size_t)std::max((int)NT, e->solow_wgs) * kSoloPartHost, e->stream));
             { float* z = nullptr; CREATE_TRY(dalloc_zero(&z, 2 * U * (size_t)std::max(kSoloPre, 8 + h.batch_max), e->stream)); e->d_solo_pre = (int*)z; }
@@ -699,64 +673,23 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     e->index.assign(P, 0);
     e->size.assign(P, 0);
     e->staged_per_learner.assign(P, 0);
-    { const char* cw = getenv("FRL_CHAIN_WAVES"); e->chain_waves = (cw && atoi(cw) == 4) ? 4 : 8; }
-    if (h.algo == ALGO_DQN)
-        CREATE_TRY(hipFuncSetAttribute((const void*)dqn_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dqn2_lds_floats() * (int)sizeof(float)));
+    const int chain_waves = env_int("FRL_CHAIN_WAVES", 8) == 4 ? 4 : 8;      // waves per workgroup of the register-chained actor-critic kernels (4: round 5's)
+    if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
+    if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, chain_waves, h);
     // (envelope DQN: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
     if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || h.algo == ALGO_ENVELOPE_DQN))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
-    if (h.wide == 2) {
-        const int lb = wide16_lds_floats_host() * (int)sizeof(float);
-        for (auto k : {ac_critic_x_h1a1_kernel, ac_critic_x_h1a2_kernel, ac_critic_x_h2a1_kernel, ac_critic_x_h2a2_kernel, ac_actor_x_a1_kernel, ac_actor_x_a2_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    } else if (h.wide) {
-        const int lb = wide_lds_floats() * (int)sizeof(float);
-        for (auto k : {ac_critic_wide_h1a1_kernel, ac_critic_wide_h1a2_kernel, ac_critic_wide_h2a1_kernel, ac_critic_wide_h2a2_kernel,
-                       ac_actor_wide_a1_kernel, ac_actor_wide_a2_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    } else if (h.solow) {
-        const int lb = solow_lds_floats() * (int)sizeof(float);
-        for (auto k : {solow_critic_h1a1_kernel, solow_critic_h1a2_kernel, solow_critic_h2a1_kernel, solow_critic_h2a2_kernel, solow_actor_a1_kernel, solow_actor_a2_kernel,
-                       solow_critic_ma_h1a1_kernel, solow_critic_ma_h1a2_kernel, solow_critic_ma_h2a1_kernel, solow_critic_ma_h2a2_kernel, solow_actor_ma_a1_kernel, solow_actor_ma_a2_kernel,
-                       solow_step_h1a1_kernel, solow_step_h1a2_kernel, solow_step_h2a1_kernel, solow_step_h2a2_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    } else if (h.solo) {
-        const int lb = std::max(solo_lds_floats(), critic2_lds_floats()) * (int)sizeof(float);      // (critic2: the rollout tail's act_frag_body)
-        for (auto k : {solo_critic_twin_kernel, solo_critic_single_kernel, solo_actor_kernel, solo_critic_twin_w8_kernel, solo_critic_single_w8_kernel, solo_actor_w8_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
+    if (e->family != FAM_ROWCHUNK) CREATE_TRY(set_family_lds_attributes(e->family));
+    if (e->family == FAM_SOLO || e->family == FAM_CHAINED)         // select_action on fragment-image nets, the solo rollout tail's act_frag_body
         CREATE_TRY(hipFuncSetAttribute((const void*)act_frag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, critic2_lds_floats() * (int)sizeof(float)));
-    } else if (h.net[0].frag) {        // the register-chained family: one workgroup per learner with the nets as LDS images (156 KB)
-        const int lb = critic2_lds_floats() * (int)sizeof(float), lb8 = critic8_lds_floats() * (int)sizeof(float);
-        for (auto k : {ac_critic_v2_twin_kernel, ac_critic_v2_single_kernel, ac_critic_v2_twin_nv_kernel, ac_critic_v2_single_nv_kernel, ac_actor_v2_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb8));
-        for (auto k : {ac_critic_v2w4_twin_kernel, ac_critic_v2w4_single_kernel, ac_actor_v2w4_kernel})
-            CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-        CREATE_TRY(hipFuncSetAttribute((const void*)act_frag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-    }
     if (e->lds_bytes > 64 * 1024) {
-        CREATE_TRY(hipFuncSetAttribute((const void*)dqn_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)ac_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)ac_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)sacd_critic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)sacd_actor_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)reinforce_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)envelope_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)act_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
-        if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) {
-            const int lb = critic2_lds_floats() * (int)sizeof(float), lb8 = critic8_lds_floats() * (int)sizeof(float);
-            for (auto k : {ac_critic_v2_twin_kernel, ac_critic_v2_single_kernel, ac_critic_v2_twin_nv_kernel, ac_critic_v2_single_nv_kernel, ac_actor_v2_kernel})
-                CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb8));
-            for (auto k : {ac_critic_v2w4_twin_kernel, ac_critic_v2w4_single_kernel, ac_actor_v2w4_kernel})
-                CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-        }
-        if (h.algo == ALGO_PPO) {
-            const int lb = ppo2_lds_floats(2) * (int)sizeof(float);
-            CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_v2_k1_relu, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-            CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_v2_k2_relu, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-            CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_v2_k1_tanh, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-            CREATE_TRY(hipFuncSetAttribute((const void*)ppo_update_v2_k2_tanh, hipFuncAttributeMaxDynamicSharedMemorySize, lb));
-        }
+        for (const void* k : {(const void*)dqn_grad_kernel, (const void*)ac_critic_kernel, (const void*)ac_actor_kernel, (const void*)sacd_critic_kernel, (const void*)sacd_actor_kernel,
+                              (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)act_kernel, (const void*)ppo_update_kernel})
+            CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
+        if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
+        if (h.algo == ALGO_PPO)
+            for (auto k : {ppo_update_v2_k1_relu, ppo_update_v2_k2_relu, ppo_update_v2_k1_tanh, ppo_update_v2_k2_tanh})
+                CREATE_TRY(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, ppo2_lds_floats(2) * (int)sizeof(float)));
     }
     CREATE_TRY(hipStreamSynchronize(e->stream));
     *out = e;
@@ -791,48 +724,6 @@ extern "C" int frl_lds_bytes(const frl_engine* e, int* bytes_out, int* rc_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     if (bytes_out) *bytes_out = e->lds_bytes;
     if (rc_out) *rc_out = e->h.rc;
-    return FRL_OK;
-}
-
-static bool chained_path(const EngineDesc& h, int batch, int pc);
-static bool dqn_fused_path(const EngineDesc& h, int batch, bool per_weights);
-// workgroups per learner of the one-launch DQN update (kernels_dqn2.hip).  A few learners: one 64-row chunk per workgroup (the
-// last to arrive reduces and steps); populations: one workgroup each (measured: P = 64 x 4 workgroups 74 us, x 1 45 us).
-static int dqn_split_for(const EngineDesc& h, int batch, int pc) {
-    const int nchunks = (batch + 63) / 64;
-    int split = (pc <= 16) ? std::min(std::min(4, nchunks), h.S) : 1;
-    if (const char* sp = getenv("FRL_DQN_SPLIT")) split = std::max(1, std::min(std::min(atoi(sp), nchunks), h.S));
-    return split;
-}
-
-extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, int* bytes_out, int* rows_out) {
-    if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
-    if (e->h.algo == ALGO_PPO) return fail(FRL_ERR_INVALID, "frl_learn_path describes frl_learn(); PPO updates go through frl_ppo_learn");
-    if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_path describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
-    if (e->h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_path describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
-    if (batch <= 0 || batch > e->h.batch_max) return fail(FRL_ERR_INVALID, "batch out of range");
-    if (dqn_fused_path(e->h, batch, e->per_on)) {           // kernels_dqn2.hip
-        if (chained_out) *chained_out = 1;
-        if (bytes_out) *bytes_out = dqn2_lds_floats() * (int)sizeof(float);
-        if (rows_out) { const int sp = dqn_split_for(e->h, batch, e->h.P); *rows_out = ((batch + 63) / 64 + sp - 1) / sp * 64 < batch ? ((batch + 63) / 64 + sp - 1) / sp * 64 : batch; }
-        return FRL_OK;
-    }
-    const bool v2 = chained_path(e->h, batch, e->h.P);
-    if (v2 && e->h.solo) {                                  // kernels_solo.hip: 16-row tiles, 16 / h.solo of them per workgroup
-        if (chained_out) *chained_out = 1;
-        if (bytes_out) *bytes_out = solo_lds_floats() * (int)sizeof(float);
-        if (rows_out) *rows_out = 16 * (kSoloWG / e->h.solo);
-        return FRL_OK;
-    }
-    if (v2 && e->h.solow) {                                 // kernels_solow.hip: one 16-row tile per workgroup
-        if (chained_out) *chained_out = 1;
-        if (bytes_out) *bytes_out = solow_lds_floats() * (int)sizeof(float);
-        if (rows_out) *rows_out = 16 * (e->h.solow / std::max(1, e->solow_row_wgs));
-        return FRL_OK;
-    }
-    if (chained_out) *chained_out = v2 ? 1 : 0;
-    if (bytes_out) *bytes_out = v2 ? (e->h.wide == 2 ? wide16_lds_floats_host() : (e->h.wide ? wide_lds_floats() : (e->chain_waves == 8 && !e->h.solo ? critic8_lds_floats() : critic2_lds_floats()))) * (int)sizeof(float) : e->lds_bytes;
-    if (rows_out) *rows_out = v2 ? batch : e->h.rc;
     return FRL_OK;
 }
 
@@ -1444,502 +1335,7 @@ extern "C" int frl_noisy_resample(frl_engine* e, const float* eps_host) {
     return FRL_OK;
 }
 
-// One stage of learn() for learners [p0, p0 + pc) on `st`: stage 0 = [draw, obsnorm,] grad(critic | Q) + reduce + adam;
-// stage 1 = grad(actor) + reduce + adam; stage 2 = MADDPG's soft update.
-// reduce + clip + Adam (+ soft update) of every unit's net `ad.which`: one fused launch when each net's gradient fits the
-// registers of one workgroup, else the two streaming passes
-static void launch_adam(frl_engine* e, hipStream_t st, const AdamArgs& ad, int units, dim3 grid_adam) {
-    const EngineDesc& h = e->h;
-    int max_n4 = 0;
-    for (int ag = 0; ag < h.n_agents; ++ag) {
-        const int net = (h.algo == ALGO_DQN) ? 0 : (ad.which == 0 ? 2 * ag + 1 : 2 * ag);
-        max_n4 = std::max(max_n4, h.net[net].size / 4);
-    }
-    const bool two_pass = getenv("FRL_ADAM_TWO_PASS") != nullptr;
-    if (max_n4 <= kFusedThreads * kFusedVec && !h.noisy && !two_pass) {
-        hipLaunchKernelGGL(adam_fused_kernel, dim3(units), dim3(kFusedThreads), 0, st, e->d, ad);
-    } else if (max_n4 <= kFusedThreads * kFusedVecWide && !two_pass) {       // (also every NoisyLinear head: the sigma gradients)
-        hipLaunchKernelGGL(adam_fused_wide_kernel, dim3(units), dim3(kFusedThreads), 0, st, e->d, ad);
-    } else {
-        hipLaunchKernelGGL(reduce_kernel, grid_adam, dim3(256), 0, st, e->d, ad);
-        hipLaunchKernelGGL(adam_kernel, grid_adam, dim3(256), 0, st, e->d, ad);
-    }
-}
-
-// One learner per workgroup, register-chained, Adam fused (kernels_critic2.hip / kernels_actor2.hip): the reference's standard
-// narrow shape at populations that give every CU a learner; everything else takes the row-chunk kernels + reduce / Adam
-// launches.  The family is chosen ONCE, at frl_create (chained_shape + population, FRL_CRITIC_V2=0/1 overrides the population
-// threshold — the tests run both families on the same inputs): the chained kernels keep the nets in fragment-image order in
-// HBM (NetDesc::frag), which the row-chunk kernels do not read.
-static bool chained_shape(const EngineDesc& h) {
-    const NetDesc &NA0 = h.net[0], &NC0 = h.net[1];
-    auto packed = [](const NetDesc& N) {          // every head block at the offsets the kernels hard-code (frl_desc.h: kL1w ...)
-        for (int hd = 0; hd < N.heads; ++hd) {
-            const LayerDesc* L = N.L + 3 * hd;
-            const int b = hd * kHeadFloats;
-            if (L[0].w_off != b + kL1w || L[0].b_off != b + kL1b || L[1].w_off != b + kL2w || L[1].b_off != b + kL2b ||
-                L[2].w_off != b + kL3w || L[2].b_off != b + kL3b) return false;
-        }
-        return N.extra_n == 0 || (N.heads == 1 && N.extra_off == kHeadFloats);
-    };
-    if (NA0.n_layers != 3 || NC0.n_layers != 3 * NC0.heads || h.hidden != 128 || !packed(NA0) || !packed(NC0)) return false;
-    // ([s | a] as one aligned slice of the record: the chained kernels read a lane's four columns of it as one dwordx4)
-    if (h.rec.obs_off[0] % 4 != 0 || h.rec.act_off[0] != h.rec.obs_off[0] + h.rec.obs_dim[0] || h.rec.obs_off[0] + 16 > h.rec.stride) return false;
-    return (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) && h.n_agents == 1 && h.hidden == 128 &&
-           NA0.L[0].k_pad == 16 && NC0.L[0].k_pad == 16 && h.rec.act_dim[0] <= 4 && NA0.L[2].n_pad == 16 &&
-           h.batch_max <= 256 && NA0.hidden_act == ACT_RELU && NC0.hidden_act == ACT_RELU &&
-           NA0.n_layers == 3 && NC0.n_layers == 3 * NC0.heads;
-}
-static bool chained_path(const EngineDesc& h, int batch, int pc) {
-    (void)pc;
-    if (h.wide) return !h.obs_norm_on;          // any batch <= batch_max: super-chunks of 256 rows
-    if (h.solow) return !h.obs_norm_on;         // any batch <= batch_max: a 16-row tile per workgroup, h.solow of them per unit
-    return h.net[0].frag && h.net[1].frag && batch <= 256 && !h.obs_norm_on;
-}
-// The K-sliced chained family (device/chain_wide.hpp): the reference's hidden-128 ReLU actor-critic nets with first layers of up
-// to 416 input columns and actor heads of up to 32 outputs that chained_shape() does not admit — SAC / TD3 / DDPG on wide
-// observations (config 4: Humanoid's 376 + 17), MADDPG_simple's per-agent actors and centralised critics (config 5).
-// MATD3 (MATD3_simple.py:195-262) is the same launch pair with twin critics, set j of the unit's noise on agent j's target action
-// and the host's delayed actor / soft-update stages.
-static bool wide_shape(const EngineDesc& h) {
-    const bool single = (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) && h.n_agents == 1;
-    const bool multi = h.algo == ALGO_MADDPG && h.n_agents >= 1;
-    const int H = h.hidden;                    // 128: chain_wide.hpp; 256: chain_wide16.hpp
-    if (!(single || multi) || (H != 128 && H != 256) || h.rec.act_total > kWideApitch) return false;
-    // WideNet::stage_idx (chain_wide.hpp; also the hidden-256 kernels') copies the batch's ring indices into the 64 KB LDS union:
-    // 2 * kWideSlice = 16384 ints.  Larger batches stay with the row-chunk family.
-    if (h.batch_max > 2 * kWideSlice) return false;
-    const int nt3 = h.net[0].L[2].n_pad;
-    for (int j = 0; j < h.n_agents; ++j) {
-        const NetDesc &NA0 = h.net[2 * j], &NC0 = h.net[2 * j + 1];
-        if (NA0.n_layers != 3 || NA0.heads != 1 || NC0.n_layers != 3 * NC0.heads || NC0.heads != h.net[1].heads) return false;
-        if (NA0.hidden_act != ACT_RELU || NC0.hidden_act != ACT_RELU) return false;
-        if (NA0.L[0].k_pad > 16 * kWideMaxKB1 || NC0.L[0].k_pad > 16 * kWideMaxKB1) return false;
-        if (NA0.L[2].n_pad != nt3 || nt3 > 32) return false;                 // one head-tile count for every agent's actor
-        for (int hd = 0; hd < NC0.heads; ++hd)
-            if (NC0.L[3 * hd].n_pad != H || NC0.L[3 * hd + 1].n_pad != H || NC0.L[3 * hd + 1].k_pad != H || NC0.L[3 * hd + 2].n_pad != 16) return false;
-        if (NA0.L[0].n_pad != H || NA0.L[1].n_pad != H || NA0.L[1].k_pad != H) return false;
-    }
-    return true;
-}
-
-// kernels_dqn2.hip: the reference's Q-net (obs -> 128 -> n_actions, or the Dueling [V ; A] head) with the TD update of DQN.py and
-// DQN_with_tricks.py's Double / PER-weighted variants; Noisy and Categorical heads take the row-chunk chain.  FRL_DQN_FUSED=0/1 overrides.
-static bool dqn_fused_path(const EngineDesc& h, int batch, bool per_weights) {
-    const NetDesc& N = h.net[0];
-    (void)per_weights;          // PER's importance weights (mean or per-row) are applied in the launch
-    const bool shape = h.algo == ALGO_DQN && !h.noisy && !h.c51_atoms && h.hidden == 128 && N.n_layers == 2 &&
-                       N.L[0].k_pad == 16 && N.L[1].n_pad == 16 && batch <= kDqn2Batch && !h.obs_norm_on && N.hidden_act == ACT_RELU;
-    const char* force = getenv("FRL_DQN_FUSED");
-    return shape && (force ? atoi(force) != 0 : true);
-}
-
-static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnArgs a, int stage, int p0, int pc, bool dev_rng, bool needs_noise,
-                               const DqnStepArgs* step = nullptr, const SoloStepArgs* sstep = nullptr) {
-    const EngineDesc& h = e->h;
-    a.p0 = p0; a.p_count = pc;
-    const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
-    const int units = pc * h.n_agents;
-    const dim3 grid_chunks(((units + 7) / 8) * 8 * ns), grid_units(units), blk(256), grid_adam(units * h.Gmax);
-    const bool sac = h.algo == ALGO_SAC || h.algo == ALGO_SAC_DISCRETE, maddpg = h.algo == ALGO_MADDPG;
-    AdamArgs ad;
-    memset(&ad, 0, sizeof ad);
-    ad.ns = ns; ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm;
-    ad.tau = a.tau; ad.alpha_lr = a.alpha_lr; ad.target_entropy = a.target_entropy; ad.p0 = p0; ad.G = h.Gmax;
-    const bool v2 = chained_path(h, a.batch, pc);
-    if (stage == 0 && dqn_fused_path(h, a.batch, a.use_isw != 0)) {
-        a.dqn_split = dqn_split_for(h, a.batch, pc);
-        prof_begin(e, PK_GRAD_CRITIC);
-        DqnStepArgs sa;
-        memset(&sa, 0, sizeof sa);
-        if (step) sa = *step;
-        hipLaunchKernelGGL(dqn_fused_kernel, dim3(pc * a.dqn_split), blk, (size_t)dqn2_lds_floats() * sizeof(float), st, e->d, a, sa);
-        prof_end(e);
-        return;
-    }
-    // kernels_solow.hip, MADDPG without smoothing noise: the rows may have been drawn by the previous launch's spare workgroups (one per
-    // unit, the duplicate table in their own LDS) — for exactly this counter, ring size and batch, or draw_kernel runs as ever
-    const int ma_pre_stride = 8 + h.batch_max;
-    const bool ma_solow = v2 && h.solow && h.n_agents > 1 && stage == 0 && dev_rng && !needs_noise && pc == h.P;
-    const bool ma_use_pre = ma_solow && e->ma_pre_valid && e->ma_pre_counter == a.rng_counter && e->ma_pre_size == a.size && e->ma_pre_batch == a.batch;
-    if (stage == 0) {
-        if (dev_rng && !ma_use_pre && !(v2 && (h.solo || (h.solow && h.n_agents == 1)))) {    // (kernels_solo.hip / single-agent kernels_solow.hip draw inside their critic stages)
-            prof_begin(e, PK_DRAW);
-            const char* scan = getenv("FRL_DRAW_SCAN");                        // developer / test knob: no duplicate table
-            const bool table = a.batch > 256 && 4 * a.batch <= kDrawTableHost && !(scan && atoi(scan) != 0);
-            const size_t draw_lds = ((size_t)2 * ((a.batch + 3) & ~3) + (table ? 2 * kDrawTableHost : 0)) * sizeof(int);
-            hipLaunchKernelGGL(draw_kernel, grid_units, blk, draw_lds, st, e->d, a, (needs_noise ? 1 : 0) | (table ? 0 : 2));
-            prof_end(e);
-        }
-        if (h.obs_norm_on && h.algo != ALGO_DQN)                         // sample(): norm(obs) updates the statistics first
-            hipLaunchKernelGGL(obsnorm_kernel, dim3(pc), blk, 0, st, e->d, a.batch, 0, p0);
-        if (h.noisy)      // sets: 0 online on s' (Double only), 1 target on s', 2 online on s
-            hipLaunchKernelGGL(noisy_materialise_kernel, dim3(h.P), blk, 0, st, e->d, 0, 3, 0x2);
-        if (v2 && h.wide) {                               // kernels_criticw.hip: one workgroup per (learner, agent)
-            prof_begin(e, PK_GRAD_CRITIC);
-            const bool x = h.wide == 2;
-            const size_t lb = (size_t)(x ? wide16_lds_floats_host() : wide_lds_floats()) * sizeof(float);
-            const bool twin = h.net[1].heads == 2, a2 = h.net[0].L[2].n_pad > 16;
-            auto k = x ? (twin ? (a2 ? ac_critic_x_h2a2_kernel : ac_critic_x_h2a1_kernel) : (a2 ? ac_critic_x_h1a2_kernel : ac_critic_x_h1a1_kernel))
-                       : (twin ? (a2 ? ac_critic_wide_h2a2_kernel : ac_critic_wide_h2a1_kernel) : (a2 ? ac_critic_wide_h1a2_kernel : ac_critic_wide_h1a1_kernel));
-            hipLaunchKernelGGL(k, dim3(units), blk, lb, st, e->d, a);
-            prof_end(e);
-            return;
-        }
-        if (v2 && h.solow) {                              // kernels_solow.hip: sixteen workgroups per learner, W1 streamed from the block
-            prof_begin(e, PK_GRAD_CRITIC);
-            SoloArgs sa{e->d_solo_slab, e->d_solo_part, e->d_solo_bar, e->d_solo_err, e->solo_bar_base, e->solo_stride, nullptr, nullptr, 0ull, h.solow, e->d_solow_bar2, e->solow_row_wgs, e->solow_wgs};
-            e->solo_bar_base += kSoloWG;
-            // the next call's rows drawn by the learners' first helper workgroups (kernels_solo.hip's spare-workgroup scheme: two
-            // alternating slots, a tag the reader checks; FRL_SOLO_PREDRAW=0 switches it off)
-            if (dev_rng && e->d_solo_pre && pc == h.P && h.n_agents == 1) {
-                const char* pdf = getenv("FRL_SOLO_PREDRAW");
-                sa.pre_read = e->d_solo_pre + (size_t)(e->solo_pre_seq & 1) * h.P * kSoloPre;      // (stale or foreign tags fail the kernel's check)
-                if (e->solow_wgs > e->solow_row_wgs && !(pdf && atoi(pdf) == 0)) {
-                    sa.pre_write = e->d_solo_pre + (size_t)((e->solo_pre_seq + 1) & 1) * h.P * kSoloPre;
-                    sa.pre_counter = e->rng_counter;              // what the next frl_learn takes, unless something else draws first
-                }
-                ++e->solo_pre_seq;
-            }
-            const bool twin = h.net[1].heads == 2, a2 = h.net[0].L[2].n_pad > 16;
-            auto k = h.n_agents > 1 ? (twin ? (a2 ? solow_critic_ma_h2a2_kernel : solow_critic_ma_h2a1_kernel) : (a2 ? solow_critic_ma_h1a2_kernel : solow_critic_ma_h1a1_kernel))
-                                    : (twin ? (a2 ? solow_critic_h2a2_kernel : solow_critic_h2a1_kernel) : (a2 ? solow_critic_h1a2_kernel : solow_critic_h1a1_kernel));
-            if (a.fuse_actor) k = twin ? (a2 ? solow_step_h2a2_kernel : solow_step_h2a1_kernel) : (a2 ? solow_step_h1a2_kernel : solow_step_h1a1_kernel);
-            int extra = 0;
-            if (h.n_agents > 1) {
-                const char* pdf = getenv("FRL_SOLO_PREDRAW");
-                if (ma_use_pre) sa.pre_read = e->d_solo_pre + (size_t)(e->solo_pre_seq & 1) * h.P * h.n_agents * ma_pre_stride;
-                e->ma_pre_valid = false;
-                if (ma_solow && units * (e->solow_wgs + 1) <= e->n_cus && !(pdf && atoi(pdf) == 0)) {
-                    sa.pre_write = e->d_solo_pre + (size_t)((e->solo_pre_seq + 1) & 1) * h.P * h.n_agents * ma_pre_stride;
-                    sa.pre_counter = e->rng_counter;              // what the next frl_learn takes, unless something else draws first
-                    extra = units;
-                    e->ma_pre_valid = true; e->ma_pre_counter = e->rng_counter; e->ma_pre_size = a.size; e->ma_pre_batch = a.batch;
-                }
-                ++e->solo_pre_seq;
-            }
-            hipLaunchKernelGGL(k, dim3(units * e->solow_wgs + extra), blk, (size_t)solow_lds_floats() * sizeof(float), st, e->d, a, sa);
-            prof_end(e);
-            return;
-        }
-        if (v2 && h.solo) {                               // kernels_solo.hip: sixteen workgroups per learner, reduce + Adam behind grid barriers
-            prof_begin(e, PK_GRAD_CRITIC);
-            SoloArgs sa{e->d_solo_slab, e->d_solo_part, e->d_solo_bar, e->d_solo_err, e->solo_bar_base, e->solo_stride, nullptr, nullptr, 0ull};
-            e->solo_bar_base += kSoloWG;
-            SoloStepArgs ss;
-            memset(&ss, 0, sizeof ss);
-            if (sstep) ss = *sstep;
-            const size_t lb = (size_t)std::max(solo_lds_floats(), critic2_lds_floats()) * sizeof(float);
-            // the next call's rows drawn by pc spare workgroups of this launch (plain frl_learn calls with device draws; the spare ones
-            // need a CU of their own — 117 KB of LDS — next to the learners' pc x 16: FRL_SOLO_PREDRAW=0/1 overrides)
-            const char* pdf = getenv("FRL_SOLO_PREDRAW");
-            const int W = h.solo;
-            const bool predraw = dev_rng && !sstep && e->d_solo_pre && pc == h.P && pc * (W + 1) <= e->n_cus && !(pdf && atoi(pdf) == 0);
-            int extra = 0;
-            if (dev_rng && !sstep && e->d_solo_pre && pc == h.P) {
-                sa.pre_read = e->d_solo_pre + (size_t)(e->solo_pre_seq & 1) * h.P * kSoloPre;      // (stale or foreign tags fail the kernel's check)
-                if (predraw) {
-                    sa.pre_write = e->d_solo_pre + (size_t)((e->solo_pre_seq + 1) & 1) * h.P * kSoloPre;
-                    sa.pre_counter = e->rng_counter;              // what the next frl_learn takes, unless something else draws first
-                    extra = pc;
-                }
-                ++e->solo_pre_seq;
-            }
-            const bool twin = h.net[1].heads == 2;
-            auto k = W == 16 ? (twin ? solo_critic_twin_kernel : solo_critic_single_kernel) : (twin ? solo_critic_twin_w8_kernel : solo_critic_single_w8_kernel);
-            hipLaunchKernelGGL(k, dim3(pc * W + extra), blk, lb, st, e->d, a, sa, ss);
-            prof_end(e);
-            return;
-        }
-        if (v2) {
-            { const char* sg = getenv("FRL_STAGGER"); a.stagger = sg ? atoi(sg) : 0;         // developer knob: spread the Adam bursts of the first round
-              const char* gg = getenv("FRL_STAGGER_GROUPS"); a.stagger_groups = gg ? atoi(gg) : 4; a.stagger_wgs = e->n_cus; }
-            prof_begin(e, PK_GRAD_CRITIC);
-            const bool w8 = e->chain_waves == 8, twin = h.net[1].heads == 2;
-            const size_t lb = (size_t)(w8 ? critic8_lds_floats() : critic2_lds_floats()) * sizeof(float);
-            // (_nv: next_obs 16-byte aligned with its 16 columns inside the row, (reward, done) an aligned pair)
-            const RecordDesc& R = h.rec;
-            const bool nv = R.nobs_off[0] % 4 == 0 && R.nobs_off[0] + 16 <= R.stride && R.rew_off % 2 == 0 && R.done_off == R.rew_off + 1 && !getenv("FRL_CRITIC2_NOVEC");
-            auto k = w8 ? (nv ? (twin ? ac_critic_v2_twin_nv_kernel : ac_critic_v2_single_nv_kernel) : (twin ? ac_critic_v2_twin_kernel : ac_critic_v2_single_kernel))
-                        : (twin ? ac_critic_v2w4_twin_kernel : ac_critic_v2w4_single_kernel);
-            hipLaunchKernelGGL(k, dim3(pc), dim3(w8 ? 512 : 256), lb, st, e->d, a);
-            prof_end(e);
-            return;
-        }
-        prof_begin(e, PK_GRAD_CRITIC);
-        if (h.algo == ALGO_DQN && h.c51_atoms) hipLaunchKernelGGL(c51_grad_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        else if (h.algo == ALGO_DQN) hipLaunchKernelGGL(dqn_grad_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        else if (h.algo == ALGO_SAC_DISCRETE) hipLaunchKernelGGL(sacd_critic_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        else hipLaunchKernelGGL(ac_critic_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        prof_end(e);
-        ad.which = 0; ad.lr = a.critic_lr; ad.wd = a.critic_wd;
-        ad.soft = (h.algo == ALGO_DQN) ? 1 : ((!maddpg && a.do_actor) ? 1 : 0);
-        prof_begin(e, PK_ADAM_CRITIC);
-        launch_adam(e, st, ad, units, grid_adam);      // (a NoisyLinear head's sigma gradients are derived in its slab sums)
-        prof_end(e);
-    } else if (stage == 1) {
-        if (v2 && h.wide) {                               // kernels_actorw.hip
-            prof_begin(e, PK_GRAD_ACTOR);
-            const bool x = h.wide == 2, a2 = h.net[0].L[2].n_pad > 16;
-            auto k = x ? (a2 ? ac_actor_x_a2_kernel : ac_actor_x_a1_kernel) : (a2 ? ac_actor_wide_a2_kernel : ac_actor_wide_a1_kernel);
-            hipLaunchKernelGGL(k, dim3(units), blk, (size_t)(x ? wide16_lds_floats_host() : wide_lds_floats()) * sizeof(float), st, e->d, a);
-            prof_end(e);
-            return;
-        }
-        if (v2 && h.solow) {
-            prof_begin(e, PK_GRAD_ACTOR);
-            SoloArgs sa{e->d_solo_slab, e->d_solo_part, e->d_solo_bar, e->d_solo_err, e->solo_bar_base, e->solo_stride, nullptr, nullptr, 0ull, h.solow, e->d_solow_bar2, e->solow_row_wgs, e->solow_wgs};
-            e->solo_bar_base += kSoloWG;
-            const bool a2 = h.net[0].L[2].n_pad > 16;
-            hipLaunchKernelGGL(h.n_agents > 1 ? (a2 ? solow_actor_ma_a2_kernel : solow_actor_ma_a1_kernel) : (a2 ? solow_actor_a2_kernel : solow_actor_a1_kernel), dim3(units * e->solow_wgs), blk,
-                               (size_t)solow_lds_floats() * sizeof(float), st, e->d, a, sa);
-            prof_end(e);
-            return;
-        }
-        if (v2 && h.solo) {
-            prof_begin(e, PK_GRAD_ACTOR);
-            SoloArgs sa{e->d_solo_slab, e->d_solo_part, e->d_solo_bar, e->d_solo_err, e->solo_bar_base, e->solo_stride, nullptr, nullptr, 0ull};
-            e->solo_bar_base += kSoloWG;
-            SoloStepArgs ss;
-            memset(&ss, 0, sizeof ss);
-            if (sstep) ss = *sstep;
-            const int W = h.solo;
-            hipLaunchKernelGGL(W == 16 ? solo_actor_kernel : solo_actor_w8_kernel, dim3(pc * W), blk,
-                               (size_t)std::max(solo_lds_floats(), critic2_lds_floats()) * sizeof(float), st, e->d, a, sa, ss);
-            prof_end(e);
-            return;
-        }
-        if (v2) {        // kernels_actor2.hip: the whole actor stage of DDPG / TD3 / SAC in one launch
-            prof_begin(e, PK_GRAD_ACTOR);
-            const bool w8 = e->chain_waves == 8;
-            hipLaunchKernelGGL(w8 ? ac_actor_v2_kernel : ac_actor_v2w4_kernel, dim3(pc), dim3(w8 ? 512 : 256),
-                               (size_t)(w8 ? critic8_lds_floats() : critic2_lds_floats()) * sizeof(float), st, e->d, a);
-            prof_end(e);
-            return;
-        }
-        prof_begin(e, PK_GRAD_ACTOR);
-        if (h.algo == ALGO_SAC_DISCRETE) hipLaunchKernelGGL(sacd_actor_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        else hipLaunchKernelGGL(ac_actor_kernel, grid_chunks, blk, e->lds_bytes, st, e->d, a, ns);
-        prof_end(e);
-        ad.which = 1; ad.lr = a.actor_lr; ad.wd = 0.f; ad.soft = maddpg ? 0 : 1; ad.sac_alpha = sac ? 1 : 0;
-        prof_begin(e, PK_ADAM_ACTOR);
-        launch_adam(e, st, ad, units, grid_adam);
-        prof_end(e);
-    } else {                                          // MATD3_simple.py:245-246: targets move with the delayed policy step
-        prof_begin(e, PK_SOFT);
-        int biggest = 0;
-        for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);
-        const int per = std::max(1, std::min((biggest + 4095) / 4096, 4 * e->n_cus / std::max(1, pc * h.n_nets)));
-        hipLaunchKernelGGL(soft_update_kernel, dim3(pc * h.n_nets, per), blk, 0, st, e->d, a.tau, p0);
-        prof_end(e);
-    }
-}
-
-// `step` (frl_rollout only, DQN engines on the fused path): the vector step's add() and the next select_action in the same launch
-// size_override >= 0: the rings' common size WHEN THE LAUNCH RUNS (a pre-armed launch of frl_rollout is enqueued before the step's rows
-// are counted in e->size)
-static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepArgs* step, const SoloStepArgs* sstep = nullptr, int size_override = -1,
-                      hipStream_t stream_override = nullptr) {
-    ENG(e);
-    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
-    const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn: envelope DQN updates go through frl_envelope_learn");
-    if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
-          h.algo == ALGO_SAC_DISCRETE))
-        return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn, REINFORCE: frl_reinforce_learn)", h.algo);
-    if (args->batch < 1 || args->batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d outside [1,%d]", args->batch, h.batch_max);
-    int min_size = h.capacity;
-    for (int p = 0; p < h.P; ++p) min_size = std::min(min_size, e->size[p]);
-    if (size_override >= 0) min_size = size_override;
-    if (min_size < args->batch) return fail(FRL_ERR_STATE, "a ring holds %d rows < batch %d", min_size, args->batch);
-    if (args->per && (h.algo != ALGO_DQN || !e->per_on)) return fail(FRL_ERR_STATE, "per = 1 needs a DQN engine with frl_per_enable");
-    if (args->per && args->idx) return fail(FRL_ERR_INVALID, "per = 1 uses the rows of the last frl_per_sample; idx must be NULL");
-    const bool dev_rng = (args->idx == nullptr) && !args->per;
-    if (dev_rng && min_size < 2 * args->batch)
-        return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
-    const bool td3_like = (h.algo == ALGO_TD3 || h.algo == ALGO_MADDPG);       // MADDPG + noise/delay = MATD3_simple.py
-    const bool needs_noise = (h.algo == ALGO_SAC) || (td3_like && args->use_policy_noise);
-    if (!dev_rng && needs_noise && !args->noise) return fail(FRL_ERR_INVALID, "idx given without noise: both or neither");
-    int rc = flush_stage(e);
-    if (rc) return rc;
-    rc = upload_idx_noise(e, args->idx, needs_noise ? args->noise : nullptr, args->batch, h.n_agents);
-    if (rc) return rc;
-    LearnArgs a;
-    memset(&a, 0, sizeof a);
-    a.batch = args->batch;
-    a.size = min_size;
-    a.device_rng = dev_rng ? 1 : 0;
-    a.do_actor = td3_like ? (args->do_actor ? 1 : 0) : 1;
-    a.gamma = args->gamma; a.tau = args->tau;
-    a.actor_lr = args->actor_lr; a.critic_lr = args->critic_lr; a.alpha_lr = args->alpha_lr;
-    a.adam_eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f;
-    a.beta1 = 0.9f; a.beta2 = 0.999f;
-    a.critic_wd = args->critic_weight_decay;
-    a.clip_norm = args->clip_norm;
-    a.policy_noise = args->policy_noise; a.noise_clip = args->noise_clip;
-    a.max_action = args->max_action != 0.f ? args->max_action : 1.f;
-    a.policy_noise_scale = args->policy_noise_scale;
-    a.use_policy_noise = (td3_like && args->use_policy_noise) ? 1 : 0;
-    a.target_entropy = args->target_entropy;
-    a.double_dqn = (h.algo == ALGO_DQN && args->double_dqn) ? 1 : 0;
-    a.use_isw = (h.algo == ALGO_DQN && args->per) ? (args->per == 2 ? 2 : 1) : 0;
-    if (args->loss_kind != FRL_LOSS_MSE && args->loss_kind != FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "unknown loss_kind %d", args->loss_kind);
-    if (args->loss_kind == FRL_LOSS_HUBER) {
-        if (!(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "Huber loss needs huber_delta > 0");
-        if (h.c51_atoms) return fail(FRL_ERR_STATE, "the Categorical head's loss is a cross-entropy: no Huber variant");
-        if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_INVALID, "discrete SAC's critic loss is F.mse_loss (SAC_add_discrete.py:313-314): no Huber variant");
-        a.huber = 1; a.huber_delta = args->huber_delta;
-    }
-    a.rng_counter = e->rng_counter++;
-    ++e->param_version;                       // (select_action's re-laid-out copies of the nets are stale from here on)
-    // One chain for the whole population.  Measured and rejected (profiles/README.md): two halves of the population on two
-    // streams so that one half's HBM-bound reduce/Adam runs under the other half's MFMA-bound gradient kernel — unchained
-    // +2.7 %, with the gradient kernels chained across the streams -8 %: the Adam workgroups do not get co-resident with
-    // the gradient kernel's (2 x 80 KB of LDS and 448 of 512 VGPRs per SIMD are taken).
-    // (kernels_solow.hip moves MADDPG's targets at the end of its actor launch)
-    const bool actor_stage = (h.algo != ALGO_DQN && a.do_actor), soft_stage = (h.algo == ALGO_MADDPG && a.do_actor && !(h.solow && chained_path(h, a.batch, h.P)));
-    if (h.noisy) {
-        // the reference draws noise per forward in program order: [online(s') if Double,] target(s'), online(s)
-        const int first = a.double_dqn ? 0 : 1;
-        if (args->noisy_eps) { rc = noisy_upload(e, args->noisy_eps, first, 3 - first); if (rc) return rc; }
-        else hipLaunchKernelGGL(noisy_draw_kernel, dim3(h.P, 3), dim3(256), 0, e->stream, e->d, 0, 3, e->rng_counter++);
-    }
-    // kernels_solow.hip, single agent, helper workgroups present: a policy step is ONE launch — the critic's update runs on the helpers
-    // under the policy's forward (FRL_SOLOW_FUSE=0: two launches)
-    if (actor_stage && h.solow && h.n_agents == 1 && e->solow_wgs > e->solow_row_wgs && chained_path(h, a.batch, h.P)) {
-        const char* fz = getenv("FRL_SOLOW_FUSE");
-        a.fuse_actor = (fz && atoi(fz) == 0) ? 0 : 1;
-    }
-    hipStream_t lst = stream_override ? stream_override : e->stream;      // (frl_rollout's pre-armed launches: the pool's second stream)
-    if (sstep) {
-        // frl_rollout on a solo engine: the step's add() rides at the head of the critic launch, its tail (obs advance + the next
-        // select_action + hand-over) at the end of the step's LAST launch
-        if (!(h.solo && chained_path(h, a.batch, h.P)) || !dev_rng) return fail(FRL_ERR_STATE, "step fusion needs a solo engine with device draws");
-        SoloStepArgs s0 = *sstep, s1 = *sstep;
-        s0.head = 1; s0.tail = actor_stage ? 0 : 1;
-        s1.head = 0; s1.tail = 1;
-        launch_learn_stage(e, lst, a, 0, 0, h.P, dev_rng, needs_noise, nullptr, &s0);
-        if (actor_stage) launch_learn_stage(e, lst, a, 1, 0, h.P, dev_rng, needs_noise, nullptr, &s1);
-        HIP_TRY(hipGetLastError());
-        return FRL_OK;
-    }
-    launch_learn_stage(e, lst, a, 0, 0, h.P, dev_rng, needs_noise, step);
-    if (actor_stage && !a.fuse_actor) launch_learn_stage(e, lst, a, 1, 0, h.P, dev_rng, needs_noise);
-    if (soft_stage) launch_learn_stage(e, lst, a, 2, 0, h.P, dev_rng, needs_noise);
-    HIP_TRY(hipGetLastError());
-    if (args->stats_out) return frl_stats_get(e, args->stats_out);
-    return FRL_OK;
-}
-
-extern "C" int frl_learn(frl_engine* e, const frl_learn_args* args) { return learn_impl(e, args, nullptr); }
-
-// Algorithmic work of one launch (DESIGN.md "Roofline"): flops = 2*B*sum(in*out) per forward
-// pass, x2 more per backward pass that needs both dX and dW, x1 for dX-only passes; bytes =
-// gathered records + 24 B per trained parameter (theta, m, v read+write) + 8 B per
-// soft-updated target parameter.
-extern "C" int frl_learn_work(const frl_engine* e, int batch, int do_actor, double* flops_out, double* bytes_out) {
-    if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
-    const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_work describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
-    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
-    auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
-    double fl = 0, by = 0;
-    const double B = batch;
-    const RecordDesc& R = h.rec;
-    if (h.algo == ALGO_DQN) {
-        const NetDesc& N = h.net[0];
-        const double m = macs(N, 0, N.n_layers);
-        fl = 2 * B * m * (1 + 1 + 2);                  // target fwd, online fwd, bwd (dX+dW)
-        by = 4 * B * (2 * R.obs_total + R.act_total + 2) + 24.0 * N.n_params + 8.0 * N.n_params;
-    } else if (h.algo == ALGO_SAC_DISCRETE) {
-        // kernels_sacd.hip: online actor fwd on s', target critic fwd (both heads) on s', critic fwd + bwd (dX + dW);
-        // actor stage: critic fwd (both heads, no backward), actor fwd + bwd.  No target-actor pass, no dX through the critic
-        const NetDesc &NA = h.net[0], &NC = h.net[1];
-        const double ma = macs(NA, 0, NA.n_layers), mc = macs(NC, 0, NC.n_layers);
-        double f = ma + mc + 3 * mc;
-        by = 4 * B * (2 * R.obs_total + R.act_total + 2) + 24.0 * NC.n_params;
-        if (do_actor) {
-            f += mc + 3 * ma;
-            by += 4 * B * R.obs_total + 24.0 * NA.n_params + 8.0 * (NA.n_params + NC.n_params);
-        }
-        fl = 2 * B * f;
-    } else if (h.algo == ALGO_PPO) {
-        fl = 0; by = 0;
-    } else {
-        const int n = h.n_agents;
-        for (int ag = 0; ag < n; ++ag) {
-            const NetDesc& NC = h.net[2 * ag + 1];
-            const NetDesc& NA = h.net[2 * ag];
-            const int ql = NC.n_layers / NC.heads;
-            double f = 0;
-            for (int j = 0; j < n; ++j) f += macs(h.net[2 * j], 0, h.net[2 * j].n_layers);   // target actors fwd
-            f += macs(NC, 0, NC.n_layers);                      // target critic heads fwd
-            f += 3 * macs(NC, 0, NC.n_layers);                  // critic fwd + bwd
-            double bytes = 4 * B * n * (2.0 * R.obs_total / n + R.act_total / (double)n + 2) + 24.0 * NC.n_params;
-            if (do_actor) {
-                const int nq = (h.algo == ALGO_SAC) ? NC.heads : 1;
-                f += macs(NA, 0, NA.n_layers) * 3;              // actor fwd + bwd
-                f += nq * 2 * macs(NC, 0, ql);                  // Q(s, pi(s)) fwd + dX-only bwd
-                bytes += 24.0 * NA.n_params + 8.0 * (NA.n_params + NC.n_params);
-            }
-            fl += 2 * B * f;
-            by += bytes;
-        }
-    }
-    if (flops_out) *flops_out = fl * h.P;
-    if (bytes_out) *bytes_out = by * h.P;
-    return FRL_OK;
-}
-
-// Executed flops of the same launch (include/freerl_hip.h): no first-layer dX for trained nets, the agent's action columns only
-// for dQ/da.  Per (learner, agent): target actors fwd + target critic fwd + critic fwd + dW (all layers) + dX (layers 2..);
-// actor stage: actor fwd + dW + dX (layers 2..) + per Q head used by the policy loss fwd + dX (layers 2.. whole, layer 1 x act_dim).
-extern "C" int frl_learn_work_executed(const frl_engine* e, int batch, int do_actor, double* flops_out) {
-    if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
-    const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn_work_executed describes frl_learn(); envelope DQN updates go through frl_envelope_learn");
-    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_learn_work_executed describes frl_learn(); REINFORCE updates go through frl_reinforce_learn");
-    auto macs = [](const NetDesc& N, int l0, int nl) { double s = 0; for (int i = l0; i < l0 + nl; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
-    auto first = [](const NetDesc& N) {            // the first layers of all heads
-        const int nl = N.n_layers / std::max(1, N.heads);
-        double s = 0;
-        for (int hd = 0; hd < N.heads; ++hd) s += (double)N.L[hd * nl].n * N.L[hd * nl].k;
-        return s;
-    };
-    double fl = 0;
-    const double B = batch;
-    if (h.algo == ALGO_DQN) {
-        const NetDesc& N = h.net[0];
-        const double m = macs(N, 0, N.n_layers);
-        fl = 2 * B * (m + m + m + (m - first(N)));     // target fwd, online fwd, dW, dX from the second layer up
-    } else if (h.algo == ALGO_SAC_DISCRETE) {
-        // actor fwd (s') + target critic fwd + critic fwd + dW + dX (layers 2..); actor stage: critic fwd + actor fwd + dW + dX (layers 2..)
-        const NetDesc &NA = h.net[0], &NC = h.net[1];
-        const double ma = macs(NA, 0, NA.n_layers), mc = macs(NC, 0, NC.n_layers);
-        double f = ma + mc + mc + mc + (mc - first(NC));
-        if (do_actor) f += mc + ma + ma + (ma - first(NA));
-        fl = 2 * B * f;
-    } else if (h.algo != ALGO_PPO) {
-        const int n = h.n_agents;
-        for (int ag = 0; ag < n; ++ag) {
-            const NetDesc &NC = h.net[2 * ag + 1], &NA = h.net[2 * ag];
-            const int ql = NC.n_layers / NC.heads;
-            double f = 0;
-            for (int j = 0; j < n; ++j) f += macs(h.net[2 * j], 0, h.net[2 * j].n_layers);
-            const double mc = macs(NC, 0, NC.n_layers);
-            f += mc + mc + mc + (mc - first(NC));
-            if (do_actor) {
-                const int nq = (h.algo == ALGO_SAC) ? NC.heads : 1;
-                const double ma = macs(NA, 0, NA.n_layers);
-                f += ma + ma + (ma - first(NA));
-                f += nq * (macs(NC, 0, ql) + macs(NC, 1, ql - 1) + (double)NC.L[0].n * h.rec.act_dim[ag]);
-            }
-            fl += 2 * B * f;
-        }
-    }
-    if (flops_out) *flops_out = fl * h.P;
-    return FRL_OK;
-}
+#include "frl_api_learn.inc"
 
 // developer read-back (tools/solo_timing.py): the single-learner kernels' per-workgroup partial sums and, in a -DFRL_SOLO_TIMING build of
 // kernels_solo.hip, their section stamps — [kSoloWG][32] floats of learner 0
@@ -1982,6 +1378,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
         if (he != hipSuccess) return fail(FRL_ERR_HIP, "relayout: %s", hipGetErrorString(he));
         for (int i = 0; i < e->h.n_nets; ++i) e->h.net[i].frag = 0;
         ++e->param_version;
+        e->family = FAM_ROWCHUNK;
         e->h.wide = 0;
         e->h.solo = 0;
         e->h.solow = 0;

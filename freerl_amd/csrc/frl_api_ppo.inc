@@ -106,7 +106,7 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
     const NetDesc &NA = h.net[0], &NC = h.net[1];
     const bool v2 = h.hidden == 128 && NA.n_layers == 3 && NC.n_layers == 3 && NA.L[0].k_pad <= 32 && NA.L[2].n_pad == 16 &&
                     NC.L[2].n_pad == 16 && !h.beta_actor && args->optimizer == 0 && NA.hidden_act == NC.hidden_act &&
-                    (NA.hidden_act == ACT_RELU || NA.hidden_act == ACT_TANH) && !getenv("FRL_PPO_STREAMING");
+                    (NA.hidden_act == ACT_RELU || NA.hidden_act == ACT_TANH) && !env_set("FRL_PPO_STREAMING");
     if (v2) {
         const int k0b = NA.L[0].k_pad / 16;
         const size_t lb = (size_t)ppo2_lds_floats(k0b) * sizeof(float);

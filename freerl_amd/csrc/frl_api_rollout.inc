@@ -288,7 +288,7 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     const auto t0 = std::chrono::steady_clock::now();
     // FRL_ROLLOUT_TIMING=1: host wall time of the loop's sections on stderr (act + action readback incl. the wait for the
     // previous learn, env step, block fill + commit launches, learn launches)
-    const bool timing = getenv("FRL_ROLLOUT_TIMING") != nullptr;
+    const bool timing = env_set("FRL_ROLLOUT_TIMING");
     double t_sec[4] = {0, 0, 0, 0};
     auto tick = std::chrono::steady_clock::now();
     auto lap = [&](int k) {
@@ -299,18 +299,15 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     };
     // DQN on the one-launch update (kernels_dqn2.hip): add(), learn() and the next step's select_action + epsilon-greedy are
     // ONE launch per vector step (FRL_DQN_STEP_FUSE=0: the separate commit / learn / act launches, same draws)
-    const char* sf = getenv("FRL_DQN_STEP_FUSE");
-    const bool can_fuse = dev && !host_commit && dqn && dqn_fused_path(h, ra->learn.batch, false) && !(sf && atoi(sf) == 0);
+    const bool can_fuse = env_flag("FRL_DQN_STEP_FUSE", true) && dev && !host_commit && dqn && learn_family(e, ra->learn.batch) == FAM_DQN_FUSED;
     // DDPG / TD3 / SAC on the single-learner kernels (kernels_solo.hip): the same fold — add() at the head of the critic launch, the
     // next select_action + exploration at the tail of the step's last launch (FRL_SOLO_STEP_FUSE=0: the separate launches, same draws)
-    const char* ssf = getenv("FRL_SOLO_STEP_FUSE");
-    const bool can_fuse_solo = dev && !host_commit && !dqn && h.solo && chained_path(h, ra->learn.batch, h.P) && E <= 1024 && !(ssf && atoi(ssf) == 0);
+    const bool can_fuse_solo = env_flag("FRL_SOLO_STEP_FUSE", true) && dev && !host_commit && !dqn && learn_family(e, ra->learn.batch) == FAM_SOLO && E <= 1024;
     bool have_action = false;                   // the previous step's launch already produced this step's actions
     // small vector steps: the launch reads the pinned block and writes the env actions in host memory directly (hipHostMalloc
     // memory is device-visible and coherent at kernel boundaries) — a hipMemcpyAsync each way costs more than the launch itself
     // (measured at one env: 58 us from enqueue to the actions on the host for a 28 us launch).  FRL_ROLLOUT_ZEROCOPY=0/1 overrides.
-    const char* zcf = getenv("FRL_ROLLOUT_ZEROCOPY");
-    const bool zero_copy = dev && !host_commit && (zcf ? atoi(zcf) != 0 : p->blk_bytes <= 64 * 1024);
+    const bool zero_copy = dev && !host_commit && env_flag("FRL_ROLLOUT_ZEROCOPY", p->blk_bytes <= 64 * 1024);
     unsigned char* blk_dev = nullptr;
     float* env_act_dev = nullptr;
     int* flag_dev = nullptr;
@@ -323,8 +320,7 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     }
     // ... and the host picks the actions up as soon as the launch has flagged them (a release store to a pinned word after
     // the action stores) instead of waiting for the launch to retire and the runtime to notice.  FRL_ROLLOUT_POLL=0: stream sync.
-    const char* pollf = getenv("FRL_ROLLOUT_POLL");
-    const bool poll = zero_copy && (can_fuse || can_fuse_solo) && !(pollf && atoi(pollf) == 0);
+    const bool poll = zero_copy && (can_fuse || can_fuse_solo) && env_flag("FRL_ROLLOUT_POLL", true);
     bool action_on_host = false, action_flagged = false;
     int expect_done = 0;                        // the flag value of the launch whose actions the next step waits for
     // PRE-ARMED launches (small populations on the folded step with the flagged hand-over): the launch of step t + 1 is enqueued as
@@ -333,15 +329,15 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     // launches to have left, stages its nets and spins on a doorbell word; the host, back from env.step with the block filled, only
     // writes that word.  Launch latency, the gap between two launches of one stream, the index draw and the weight staging then run
     // under step t and the host's turn (kernels.h: DqnStepArgs::go_flag).  FRL_ROLLOUT_PREARM=0/1 overrides.
-    const char* paf = getenv("FRL_ROLLOUT_PREARM");
+    const bool prearm_forced = env_flag("FRL_ROLLOUT_PREARM", false), prearm_allowed = env_flag("FRL_ROLLOUT_PREARM", true);
     // (a solo engine's launches need every workgroup resident — the flag hand-overs spin — so an armed launch must fit NEXT to the running
     // one whatever the switch says: 2 x 16 workgroups per learner on the device's CUs (frl_engine::n_cus); past that the armed workgroups would hold the CUs the
     // running step's actor launch is waiting for, until their 2 s bound)
     const bool prearm_fits = can_fuse || (long long)h.P * 2 * std::max(h.solo, 1) <= e->n_cus;
     // (defaults from tools/prearm_soak.py, us per vector step armed / plain: DQN with 8 / 16 / 32 learners 23.8 / 33.1, 27.3 / 34.4, 33.6 / 36.3;
     // TD3 on the solo kernels with 4 / 8 learners 80.9 / 78.4, 100.6 / 89.2 — their armed workgroups' polling costs more than it hides)
-    const bool prearm_ok = ((can_fuse && h.P <= 32) || (can_fuse_solo && h.P <= 2) || (paf && atoi(paf) != 0)) && (can_fuse || can_fuse_solo) && prearm_fits && poll && go_dev &&
-                           !e->profile && !(paf && atoi(paf) == 0);
+    const bool prearm_ok = ((can_fuse && h.P <= 32) || (can_fuse_solo && h.P <= 2) || prearm_forced) && (can_fuse || can_fuse_solo) && prearm_fits && poll && go_dev &&
+                           !e->profile && prearm_allowed;
     bool prearmed = false, prearmed_act = false;
     int prearmed_done = 0;
     bool on_alt = false;                        // the last folded launch went to stream2 (the next pre-armed one takes the other stream)
