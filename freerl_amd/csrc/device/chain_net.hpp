@@ -67,12 +67,17 @@ using HeadGrad = HeadGradT<4>;
 // whole update instead of a 64-bit pointer per array and tile (which the register allocator spilled inside the MFMA chains).
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 struct AdamBuf { __amdgpu_buffer_rsrc_t th, mm, vv, tg; };
-__device__ __forceinline__ AdamBuf adam_buf(g_f th, g_f mA, g_f vA, g_f tg) {
+// `bytes` = the extent the update may touch (the net's blocks up to the end of the head it steps): the descriptors' range check
+// drops every lane-access at or beyond it — a load returns zeros, a store writes nothing.  The update uses that to leave the
+// padding of the 16-wide tiles out of the stream without a branch: a padding lane's offset is kAdamDrop (see ChainNetT::unit_voff).
+// kAdamDrop + any tile offset of a net block stays far below 2^31, so the sum the hardware compares never wraps.
+constexpr int kAdamDrop = 0x40000000;
+__device__ __forceinline__ AdamBuf adam_buf(g_f th, g_f mA, g_f vA, g_f tg, int bytes) {
     AdamBuf B;
-    B.th = __builtin_amdgcn_make_buffer_rsrc((float*)th, 0, 0x7fffffff, 0x00020000);
-    B.mm = __builtin_amdgcn_make_buffer_rsrc((float*)mA, 0, 0x7fffffff, 0x00020000);
-    B.vv = __builtin_amdgcn_make_buffer_rsrc((float*)vA, 0, 0x7fffffff, 0x00020000);
-    B.tg = __builtin_amdgcn_make_buffer_rsrc((float*)tg, 0, 0x7fffffff, 0x00020000);
+    B.th = __builtin_amdgcn_make_buffer_rsrc((float*)th, 0, bytes, 0x00020000);
+    B.mm = __builtin_amdgcn_make_buffer_rsrc((float*)mA, 0, bytes, 0x00020000);
+    B.vv = __builtin_amdgcn_make_buffer_rsrc((float*)vA, 0, bytes, 0x00020000);
+    B.tg = __builtin_amdgcn_make_buffer_rsrc((float*)tg, 0, bytes, 0x00020000);
     return B;
 }
 // cache-policy bits of the update's loads / stores and of the staging loads (developer knobs: 2 = slc / non-temporal)
@@ -617,6 +622,19 @@ struct ChainNetT {
         if constexpr (NW == 8) { const int fs = lanes().fslot; return 4 * (w * OT * (J < 8 * OT ? kHT : 1) * 256 + fs); }
         else return J < 8 * OT ? lane2 : lane1;
     }
+    // ... with the lanes whose slot is ALL padding sent to kAdamDrop.  Read off forward / head_valu: the slot of lane (q, i16) of a
+    // first-layer tile holds input columns 4q .. 4q + 3 (padding when 4q >= in_cols; a partly real slot stays whole), the slot of
+    // a head tile belongs to output i16 (padding when i16 >= hn).  Padded slots hold exact zeros in theta / target / m / v and
+    // have exactly zero gradient, and Adam maps zeros to zeros: nothing needs to read or write them.
+    template <int J> __device__ __forceinline__ int unit_voff(int in_cols, int hn) const {
+        const int vo = unit_voff<J>();
+        if constexpr (J < 8 * OT) return vo;
+        else {
+            const LaneK K = lanes();
+            if constexpr (J < 9 * OT) return 4 * K.q >= in_cols ? kAdamDrop : vo;
+            else return K.i16 >= hn ? kAdamDrop : vo;
+        }
+    }
     template <int J> static constexpr int unit_soff() { return 4 * (J < 8 * OT ? kL2w + J * 256 : (J < 9 * OT ? kL1w + (J - 8 * OT) * 256 : kL3w + (J - 9 * OT) * 256)); }
     template <int J>
     __device__ __forceinline__ static const f32x4& unit_grad(const Grad& g) {
@@ -628,10 +646,10 @@ struct ChainNetT {
     // last head staged is still there, in the same slot order — instead of a second trip to HBM (the update phase is the one
     // that streams HBM with every CU at once)
     template <bool SOFT, int J, int HB, bool THL>
-    __device__ __forceinline__ AdamIn adam_load(const AdamBuf& B) const {
+    __device__ __forceinline__ AdamIn adam_load(const AdamBuf& B, int in_cols, int hn) const {
         AdamIn X;
         constexpr int so = HB + unit_soff<J>();
-        const int vo = unit_voff<J>();
+        const int vo = unit_voff<J>(in_cols, hn);
         if constexpr (THL) X.th = ld4((lds_cf)((J < 8 * OT ? S.w2 + (w * OT * kHT + J) * 256 : (J < 9 * OT ? S.w1 + (w * OT + J - 8 * OT) * 256 : S.w3 + (w * OT + J - 9 * OT) * 256)) + (NW == 8 ? lanes().fslot : fslot)));
         else X.th = buf_ld4(B.th, vo, so);
         X.mm = buf_ld4(B.mm, vo, so); X.vv = buf_ld4(B.vv, vo, so);
@@ -653,9 +671,9 @@ struct ChainNetT {
         return R;
     }
     template <bool SOFT, int J, int HB>
-    __device__ __forceinline__ void adam_store(const AdamBuf& B, const AdamIn& R) const {
+    __device__ __forceinline__ void adam_store(const AdamBuf& B, const AdamIn& R, int in_cols, int hn) const {
         constexpr int so = HB + unit_soff<J>();
-        const int vo = unit_voff<J>();
+        const int vo = unit_voff<J>(in_cols, hn);
         buf_st4(B.th, vo, so, R.th); buf_st4(B.mm, vo, so, R.mm); buf_st4(B.vv, vo, so, R.vv);
         if constexpr (SOFT) buf_st4(B.tg, vo, so, R.tg);
     }
@@ -684,16 +702,18 @@ struct ChainNetT {
     }
     // the whole update of head HD of a net, in the open: the units in batches of up to 8 (loads of a batch before its stores),
     // the 128 x 128 layer's tiles first, then first layer + head layer, then the biases.  th / mA / vA / tg = the NET's blocks.
+    // in_cols = real input columns of the head's first layer, hn = real outputs of its head layer: the lanes whose slot is
+    // padding (unit_voff) neither load nor store — 2 x 2 048 of a head block's 20 752 floats at 8 / 10 columns and 1 / 2 outputs.
     template <bool SOFT, int HD, bool THL = false>
-    __device__ __forceinline__ void adam_head(const Grad& g, g_f th, g_f mA, g_f vA, g_f tg, const AdamCoef& c, float g_extra = 0.f,
-                                              int extra_n = 0) const {
-        const AdamBuf B = adam_buf(th, mA, vA, tg);
+    __device__ __forceinline__ void adam_head(const Grad& g, g_f th, g_f mA, g_f vA, g_f tg, const AdamCoef& c, int in_cols, int hn,
+                                              float g_extra = 0.f, int extra_n = 0) const {
         constexpr int HB = HD * kHeadFloats * 4;
+        const AdamBuf B = adam_buf(th, mA, vA, tg, HB + kHeadFloats * 4);
         constexpr int kBatch = NW == 4 ? 8 : 5;                        // (NW = 8: ten units in two batches of five — 80 registers of state)
         static_for<0, (kUnits + kBatch - 1) / kBatch>([&](auto bc) {
             constexpr int b0 = decltype(bc)::value * kBatch, nb = b0 + kBatch <= kUnits ? kBatch : kUnits - b0;
             AdamIn in[nb];
-            static_for<0, nb>([&](auto j) { in[decltype(j)::value] = adam_load<SOFT, b0 + decltype(j)::value, HB, THL>(B); });
+            static_for<0, nb>([&](auto j) { in[decltype(j)::value] = adam_load<SOFT, b0 + decltype(j)::value, HB, THL>(B, in_cols, hn); });
             // Every load of the batch has landed before its first store is issued: gfx9 counts loads and stores in one counter,
             // and with both kinds in flight hipcc's "all but the N youngest" waits rest on their retiring strictly in issue
             // order.  Nothing measured says they do not (the corruption first blamed on it was the store-data hazard, see
@@ -701,7 +721,7 @@ struct ChainNetT {
             __builtin_amdgcn_s_waitcnt(0x0F70);                        // vmcnt(0)
             static_for<0, nb>([&](auto j) {
                 constexpr int J = b0 + decltype(j)::value;
-                adam_store<SOFT, J, HB>(B, adam_compute<SOFT>(c, unit_grad<J>(g), in[decltype(j)::value]));
+                adam_store<SOFT, J, HB>(B, adam_compute<SOFT>(c, unit_grad<J>(g), in[decltype(j)::value]), in_cols, hn);
             });
         });
         adam_biases<SOFT>(g, th + HD * kHeadFloats, mA + HD * kHeadFloats, vA + HD * kHeadFloats, tg + HD * kHeadFloats, c, g_extra, extra_n);

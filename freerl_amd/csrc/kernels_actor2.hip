@@ -10,7 +10,8 @@
 //      (SAC: once per twin head, each staged in turn, the two dQ/da added)
 //   C  actor forward AGAIN (its activations are registers of pass A, long gone) + backward with the weight-gradient exchanges
 // Recomputing the forward costs 320 of the pass's 928 MFMAs per wave and chunk; keeping both nets' images resident instead
-// would leave no LDS for the exchange buffers.  Shape: as kernels_critic2.hip.
+// would leave no LDS for the exchange buffers.  Shape: as kernels_critic2.hip.  The update (adam_head) leaves the padded slots
+// of the first-layer tiles (input columns past obs_dim) and of the head tiles (outputs past act_dim) out of its stream.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -274,7 +275,7 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
     co.w1 = 1.f - a.beta1; co.w2 = 1.f - a.beta2; co.beta2 = a.beta2; co.eps = a.adam_eps; co.wd = 0.f;
     co.tk = 1.f - a.tau; co.tau = a.tau;
     PPO_T(5);
-    C.template adam_head<true, 0, true>(g, thA, mA, vA, tgA, co, g_extra, sac ? NA.extra_n : 0);      // (theta from the actor's image, still staged from pass C)
+    C.template adam_head<true, 0, true>(g, thA, mA, vA, tgA, co, O, A, g_extra, sac ? NA.extra_n : 0);      // (theta from the actor's image, still staged from pass C)
     PPO_T(6);
     PPO_TDUMP();
     if (tid == 0) {

@@ -8,7 +8,9 @@
 // whole batch: each net's weights are staged once into a fragment-ordered LDS image and used for all its rows (four 64-row
 // chunks at batch 256, every wave carrying 16 rows through the MLP in registers), the weight gradients of BOTH heads stay in
 // the owner lanes' accumulators across the chunks, and clip + Adam + soft update run from those registers against
-// theta / m / v / target in global memory — read and written exactly once per update.
+// theta / m / v / target in global memory — read and written exactly once per update, and without the padding of the 16-wide
+// first-layer and head tiles (the lanes whose slot is padding are dropped by the buffer descriptors' range check, adam_head:
+// 13 % of the stream at obs 8 / act 2, 0.829 -> 0.770 GB per launch).
 //
 // Shape: single agent, hidden 128 (ReLU), obs_dim + act_dim <= 16, act_dim <= 4, batch <= 256, no Batch_ObsNorm; populations
 // of >= 128 learners (one workgroup per CU needs that many to fill the chip).  Everything else runs ac_critic_kernel.
@@ -336,9 +338,9 @@ __device__ __forceinline__ void ac_critic_v2_body(const EngineDesc& D, const Lea
     const AdamCoef co = adam_coef(total, a.clip_norm, t, a.critic_lr, a.beta1, a.beta2, a.adam_eps, a.critic_wd, a.tau);
 #if !(FRL_ABL & 1)
     if (a.do_actor != 0) {                                             // TD3: targets move with the delayed policy step (TD3.py:224-233)
-        static_for<0, NH>([&](auto hd) { C.template adam_head<true, decltype(hd)::value, decltype(hd)::value == NH - 1>(G[decltype(hd)::value], thC, mC, vC, tgCw, co); });
+        static_for<0, NH>([&](auto hd) { C.template adam_head<true, decltype(hd)::value, decltype(hd)::value == NH - 1>(G[decltype(hd)::value], thC, mC, vC, tgCw, co, O + A, 1); });
     } else {
-        static_for<0, NH>([&](auto hd) { C.template adam_head<false, decltype(hd)::value, decltype(hd)::value == NH - 1>(G[decltype(hd)::value], thC, mC, vC, tgCw, co); });
+        static_for<0, NH>([&](auto hd) { C.template adam_head<false, decltype(hd)::value, decltype(hd)::value == NH - 1>(G[decltype(hd)::value], thC, mC, vC, tgCw, co, O + A, 1); });
     }
 #else
     if (co.coef == 123.f) static_for<0, NH>([&](auto hd) { S.red[40 + decltype(hd)::value] = C.grad_sumsq(G[decltype(hd)::value]) * co.step; });
