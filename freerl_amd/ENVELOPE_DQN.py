@@ -67,6 +67,13 @@ def _random_preference(reward_dim):
     return torch.abs(preference) / torch.norm(preference, p=1)
 
 
+def _prioritised_draw(total_size, priority_mem, batch_size):
+    """np.random.choice without replacement, p proportional to the priorities (ENVELOPE_DQN.py:191-195, ENVELOPE_DDPG.py:241-245)."""
+    batch_size = min(total_size, batch_size)
+    priority_mem = np.array(priority_mem)
+    return np.random.choice(range(total_size), batch_size, replace=False, p=priority_mem / priority_mem.sum())
+
+
 class ENVELOPE:
     def __init__(self, dim_info, is_continue, Qnet_lr, buffer_size, device, beta, max_episodes, trick=None, *, hidden=HIDDEN,
                  max_rows=256 * 128, seed=0):
@@ -138,10 +145,7 @@ class ENVELOPE:
         self.priority_mem.append(p.numpy())
 
     def _draw(self, batch_size):
-        total_size = len(self.buffer)
-        batch_size = min(total_size, batch_size)
-        priority_mem = np.array(self.priority_mem)
-        return np.random.choice(range(total_size), batch_size, replace=False, p=priority_mem / priority_mem.sum())
+        return _prioritised_draw(len(self.buffer), self.priority_mem, batch_size)
 
     def sample(self, batch_size):
         """Rows drawn without replacement with probability proportional to `priority_mem` (:191-200)."""

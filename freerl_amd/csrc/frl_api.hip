@@ -39,6 +39,7 @@
 #include "kernels_sacd.hip"
 #include "kernels_reinforce.hip"
 #include "kernels_envelope.hip"
+#include "kernels_envelope_ddpg.hip"
 #endif
 
 using namespace frl;
@@ -174,7 +175,7 @@ struct frl_engine {
     int* h_ep_n = nullptr;                // [2][P] pinned
     hipEvent_t ev_ep[2] = {nullptr, nullptr};
     unsigned ep_seq = 0;
-    float* h_env_w = nullptr;             // frl_envelope_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
+    float* h_env_w = nullptr;             // frl_envelope_learn / frl_envelope_ddpg_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
     int lds_per_cu = 160 * 1024;          // LDS bytes of one compute unit
@@ -270,7 +271,7 @@ static void build_record(RecordDesc& R, const frl_config& c) {
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
-    R.rew_off = off; off += (c.algo == FRL_ALGO_ENVELOPE_DQN) ? std::max(1, c.reward_dim) : c.n_agents;      // (envelope DQN: the reward vector)
+    R.rew_off = off; off += (c.algo == FRL_ALGO_ENVELOPE_DQN || c.algo == FRL_ALGO_ENVELOPE_DDPG) ? std::max(1, c.reward_dim) : c.n_agents;      // (envelope DQN / DDPG: the reward vector)
     R.done_off = off; off += c.n_agents;
     for (int j = 0; j < c.n_agents; ++j) { R.nobs_off[j] = off; off += c.obs_dim[j]; }
     R.extra_off = off;
@@ -288,7 +289,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 103; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn
+extern "C" int frl_version(void) { return 104; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -371,7 +372,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_ENVELOPE_DQN) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -414,6 +415,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         }
         if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "envelope DQN: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
     }
+    if (c.algo == FRL_ALGO_ENVELOPE_DDPG) {     // what kernels_envelope_ddpg.hip handles: the row-chunk layout at two workgroups per CU, as envelope DQN
+        if (c.reward_dim < 0) { delete e; return fail(FRL_ERR_INVALID, "envelope DDPG: reward_dim %d must be >= 1 (0 means 1)", c.reward_dim); }
+        h.reward_dim = std::max(1, c.reward_dim);
+        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "envelope DDPG: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
+    }
     if (c.algo == FRL_ALGO_REINFORCE) {         // what kernels_reinforce.hip handles: discrete SAC's limits, for the same reasons
         if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: %d actions > %d (kernels_reinforce.hip)", c.act_dim[0], kSacdMaxActions); }
         if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
@@ -448,6 +454,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     } else if (c.algo == FRL_ALGO_ENVELOPE_DQN) {
         h.n_nets = 1;                                                   // MLP (ENVELOPE_DQN.py:36-59): [obs | w] -> H -> H -> A x R, with a target
         build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0] * h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
+    } else if (c.algo == FRL_ALGO_ENVELOPE_DDPG) {
+        // Actor (ENVELOPE_DDPG.py:40-63): [obs | w] -> H -> H -> A, tanh; Critic (:65-91): [obs | act | w] -> H -> H -> R; each with a target
+        h.n_nets = 2;
+        build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_TANH, 0);
+        build_net(h.net[1], {{H, c.obs_dim[0] + c.act_dim[0] + h.reward_dim}, {H, H}, {h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
     } else if (c.algo == FRL_ALGO_REINFORCE) {
         h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
         build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
@@ -503,6 +514,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     if (c.algo == FRL_ALGO_ENVELOPE_DQN) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);   // the target vector T per row
+    if (c.algo == FRL_ALGO_ENVELOPE_DDPG) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);  // ... and here the action too: max(A, R)
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -510,7 +522,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
     // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
     // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN) h.rc = 32;
+    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN &&
+        c.algo != FRL_ALGO_ENVELOPE_DDPG) h.rc = 32;
     // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
@@ -531,6 +544,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_ENVELOPE_DQN && lds_bytes_for(h, h.rc) > 80 * 1024) {
         delete e;
         return fail(FRL_ERR_INVALID, "envelope DQN: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
+    }
+    if (c.algo == FRL_ALGO_ENVELOPE_DDPG && lds_bytes_for(h, h.rc) > 80 * 1024) {
+        delete e;
+        return fail(FRL_ERR_INVALID, "envelope DDPG: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
     }
     e->lds_bytes = lds_bytes_for(h, h.rc);
     // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
@@ -614,7 +631,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
-        if (c.algo == FRL_ALGO_ENVELOPE_DQN) {
+        if (c.algo == FRL_ALGO_ENVELOPE_DQN || c.algo == FRL_ALGO_ENVELOPE_DDPG) {
             CREATE_TRY(dalloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
             CREATE_TRY(hipHostMalloc((void**)&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim * sizeof(float)));
         }
@@ -676,15 +693,16 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     const int chain_waves = env_int("FRL_CHAIN_WAVES", 8) == 4 ? 4 : 8;      // waves per workgroup of the register-chained actor-critic kernels (4: round 5's)
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
     if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, chain_waves, h);
-    // (envelope DQN: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
-    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || h.algo == ALGO_ENVELOPE_DQN))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
+    // (envelope DQN / DDPG: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
+    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || h.algo == ALGO_ENVELOPE_DQN || h.algo == ALGO_ENVELOPE_DDPG))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
     if (e->family != FAM_ROWCHUNK) CREATE_TRY(set_family_lds_attributes(e->family));
     if (e->family == FAM_SOLO || e->family == FAM_CHAINED)         // select_action on fragment-image nets, the solo rollout tail's act_frag_body
         CREATE_TRY(hipFuncSetAttribute((const void*)act_frag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, critic2_lds_floats() * (int)sizeof(float)));
     if (e->lds_bytes > 64 * 1024) {
         for (const void* k : {(const void*)dqn_grad_kernel, (const void*)ac_critic_kernel, (const void*)ac_actor_kernel, (const void*)sacd_critic_kernel, (const void*)sacd_actor_kernel,
-                              (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)act_kernel, (const void*)ppo_update_kernel})
+                              (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
+                              (const void*)envelope_ddpg_actor_kernel, (const void*)act_kernel, (const void*)ppo_update_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -1189,6 +1207,8 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_act_explore: discrete SAC acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
     if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_act_explore: envelope DQN acts through frl_act (FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives)");
+    if (h.algo == ALGO_ENVELOPE_DDPG)
+        return fail(FRL_ERR_STATE, "frl_act_explore: envelope DDPG acts through frl_act (FRL_ACT_TANHHEAD on net 0 with [obs | preference]) and learns through frl_envelope_ddpg_learn");
     if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_act_explore: REINFORCE acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
@@ -1550,5 +1570,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_ppo.inc"
 #include "frl_api_reinforce.inc"
 #include "frl_api_envelope.inc"
+#include "frl_api_envelope_ddpg.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

@@ -209,6 +209,7 @@ static int describes_learn_guard(const EngineDesc& h, const char* who, bool ppo_
     if (ppo_too && h.algo == ALGO_PPO) return fail(FRL_ERR_INVALID, "%s describes frl_learn(); PPO updates go through frl_ppo_learn", who);
     if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "%s describes frl_learn(); REINFORCE updates go through frl_reinforce_learn", who);
     if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "%s describes frl_learn(); envelope DQN updates go through frl_envelope_learn", who);
+    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "%s describes frl_learn(); envelope DDPG updates go through frl_envelope_ddpg_learn", who);
     return FRL_OK;
 }
 
@@ -444,6 +445,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
     if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn: envelope DQN updates go through frl_envelope_learn");
+    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_learn: envelope DDPG updates go through frl_envelope_ddpg_learn");
     if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
           h.algo == ALGO_SAC_DISCRETE))
         return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn, REINFORCE: frl_reinforce_learn)", h.algo);

@@ -30,6 +30,7 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_ppo_learn on a non-PPO engine (envelope DDPG updates: frl_envelope_ddpg_learn)");
     if (h.algo != ALGO_PPO) return fail(FRL_ERR_STATE, "frl_ppo_learn on a non-PPO engine");
     const int T = args->horizon, mb = args->minibatch, K = args->k_epochs;
     if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);

@@ -9,6 +9,7 @@ extern "C" int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
+    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_reinforce_learn on an envelope DDPG engine (updates: frl_envelope_ddpg_learn)");
     if (h.algo != ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_reinforce_learn on an engine of algo %d", h.algo);
     if (!(args->gamma == args->gamma) || !(args->lr == args->lr)) return fail(FRL_ERR_INVALID, "gamma / lr is NaN");
     const int P = h.P;

@@ -224,6 +224,7 @@ extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args
     if (e->h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for discrete SAC engines");
     if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for REINFORCE engines");
     if (e->h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for envelope DQN engines (updates: frl_envelope_learn)");
+    if (e->h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for envelope DDPG engines (updates: frl_envelope_ddpg_learn)");
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;
@@ -700,6 +701,7 @@ extern "C" int frl_ppo_rollout(frl_engine* e, frl_envpool* p, const frl_ppo_roll
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;
+    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_ppo_rollout needs a PPO engine (envelope DDPG updates: frl_envelope_ddpg_learn)");
     if (h.algo != ALGO_PPO) return fail(FRL_ERR_STATE, "frl_ppo_rollout needs a PPO engine");
     if (h.beta_actor) return fail(FRL_ERR_STATE, "frl_ppo_rollout: Gaussian and Categorical actors only");
     const int E = ra->envs_per_learner, Tseg = ra->steps_per_env, n = p->pool->n, T = E * Tseg;

@@ -10,7 +10,7 @@ constexpr int kMaxNets = 2 * kMaxAgents;
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
-                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8 };
+                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -90,7 +90,7 @@ struct RecordDesc {
     int obs_total, act_total, extra;
     int obs_off[kMaxAgents], obs_dim[kMaxAgents];
     int act_off[kMaxAgents], act_dim[kMaxAgents];    // act_dim = A' (1 for discrete)
-    int rew_off, done_off;                           // envelope DQN: reward_dim reward columns, so done_off = rew_off + reward_dim
+    int rew_off, done_off;                           // envelope DQN / DDPG: reward_dim reward columns, so done_off = rew_off + reward_dim
     int nobs_off[kMaxAgents];
     int extra_off;
 };
@@ -180,8 +180,8 @@ struct EngineDesc {
                           // shape, sixteen workgroups per learner); parameters in fragment-image order like the chained family's
     int* ep_n;            // [P] REINFORCE: ring rows 0..ep_n[p]-1 are learner p's batch of the current frl_reinforce_learn call (0: it sits
                           // the call out); the normalised returns of those rows are in isw
-    int reward_dim;       // envelope DQN: objectives R (reward columns of a record, preference columns of the net's input); 1 otherwise
-    float* env_w;         // envelope DQN: [P][batch_max][reward_dim], the first weight_num rows = the preference vectors of the current
+    int reward_dim;       // envelope DQN / DDPG: objectives R (reward columns of a record, preference columns of the net's input); 1 otherwise
+    float* env_w;         // envelope DQN / DDPG: [P][batch_max][reward_dim], the first weight_num rows = the preference vectors of the current
                           // frl_envelope_learn call (uploaded, or drawn by envelope_weights_kernel)
 };
 

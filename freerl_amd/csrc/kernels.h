@@ -158,6 +158,11 @@ struct EnvelopeArgs {
 __global__ void envelope_weights_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a);
 __global__ void envelope_grad_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
 
+// kernels_envelope_ddpg.hip: envelope multi-objective DDPG (ENVELOPE_MORL_file/ENVELOPE_DDPG.py), the critic and actor gradient kernels
+// over the same batch x weight_num rows (EnvelopeArgs; envelope_weights_kernel expands the rows and draws the preferences)
+__global__ void envelope_ddpg_critic_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
+__global__ void envelope_ddpg_actor_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

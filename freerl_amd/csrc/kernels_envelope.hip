@@ -9,6 +9,7 @@
 // Same grid, slabs and part[] as sacd_critic_kernel, so reduce / Adam / adam_publish serve the update unchanged.
 #include <hip/hip_runtime.h>
 
+#include "device/envelope.hpp"
 #include "device/net.hpp"
 #include "device/rng.hpp"
 #include "device/update_common.hpp"
@@ -46,14 +47,6 @@ __global__ __launch_bounds__(256) void envelope_weights_kernel(const EngineDesc*
 }
 
 // --------------------------------------------------------------------------------------- grad
-// X[r][dst0 + k] = w[(r0 + r) / B][k] for r < nvalid, 0 for the rows past them
-__device__ __forceinline__ void put_weights(lds_f X, int ldx, int rc, int nvalid, g_cf wts, int r0, int B, int RD, int dst0) {
-    for (int e = threadIdx.x; e < rc * RD; e += kWG) {
-        const int r = e / RD, k = e - r * RD;
-        X[r * ldx + dst0 + k] = r < nvalid ? wts[(size_t)((r0 + r) / B) * RD + k] : 0.f;
-    }
-}
-
 // a' = argmax_a w . Q_online(s', w)[a, :] (the first maximum, as torch.max, :232-234); T = r + gamma Q_target(s', w)[a', :] (1 - done)
 // (:235-240), an R-vector parked per row in abuf; Q = Q_online(s, w)[a, :] (:242);
 //     loss = beta mean_j (w.Q - w.T)^2 + (1 - beta) mean_{j,k} (Q_k - T_k)^2 (:245-249)

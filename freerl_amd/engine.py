@@ -30,7 +30,7 @@ class Engine:
         cfg.twin_critic, cfg.capacity, cfg.batch_max = int(bool(twin_critic)), int(capacity), int(batch_max)
         cfg.extra_cols, cfg.device_id, cfg.seed = int(extra_cols), int(device_id), int(seed) & (2 ** 64 - 1)
         cfg.actor_dist, cfg.dueling, cfg.noisy = int(actor_dist), int(bool(dueling)), int(bool(noisy))
-        cfg.reward_dim = int(reward_dim)          # envelope DQN: objectives (0 = 1; ignored by the other algorithms)
+        cfg.reward_dim = int(reward_dim)          # envelope DQN / DDPG: objectives (0 = 1; ignored by the other algorithms)
         if c51 is not None:                     # (atoms, v_min, v_max)
             cfg.c51_atoms, cfg.c51_vmin, cfg.c51_vmax = int(c51[0]), float(c51[1]), float(c51[2])
         self._L = N.lib()
@@ -48,7 +48,7 @@ class Engine:
         self.layout = lay
         self.width = lay.width
         self.act_max = max(lay.act_dim[j] for j in range(self.n_agents))
-        self.reward_dim = lay.done_off - lay.rew_off if self.n_agents == 1 else 1      # (envelope DQN: the reward vector's columns)
+        self.reward_dim = lay.done_off - lay.rew_off if self.n_agents == 1 else 1      # (envelope DQN / DDPG: the reward vector's columns)
         n = C.c_int(0)
         N.check(self._L.frl_net_count(self._h, C.byref(n)))
         self.n_nets = n.value
@@ -389,6 +389,36 @@ class Engine:
             out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
             a.weights_out = _fp(out["weights"])
         N.check(self._L.frl_envelope_learn(self._h, C.byref(a)))
+        return out
+
+    def envelope_ddpg_learn(self, batch, weight_num, *, gamma, tau, actor_lr, critic_lr, beta, idx=None, weights=None, want_loss=False,
+                            want_weights=False):
+        """ENVELOPE_DDPG.learn for every learner (frl_envelope_ddpg_learn) on batch x weight_num rows: row j is ring row idx[j % batch]
+        under preference weights[j // batch]; the critic step, then the actor step through the updated critic, both clipped at 0.5,
+        then both soft updates.  idx [P][batch] / weights [P][weight_num][reward_dim], or None: drawn on the device.
+        -> dict with `critic_loss` [P] and `actor_loss` [P] and / or `weights` [P][weight_num][reward_dim] (the preferences used);
+        empty and asynchronous when neither is asked for."""
+        a = N.EnvelopeDdpgArgs()
+        a.batch, a.weight_num = int(batch), int(weight_num)
+        a.gamma, a.tau, a.actor_lr, a.critic_lr, a.beta = float(gamma), float(tau), float(actor_lr), float(critic_lr), float(beta)
+        keep = []
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, int(batch))
+            keep.append(ix)
+            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=F32).reshape(self.P, int(weight_num), self.reward_dim)
+            keep.append(w)
+            a.weights = _fp(w)
+        out = {}
+        if want_loss:
+            out["critic_loss"] = np.full(self.P, np.nan, dtype=F32)
+            out["actor_loss"] = np.full(self.P, np.nan, dtype=F32)
+            a.critic_loss_out, a.actor_loss_out = _fp(out["critic_loss"]), _fp(out["actor_loss"])
+        if want_weights:
+            out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
+            a.weights_out = _fp(out["weights"])
+        N.check(self._L.frl_envelope_ddpg_learn(self._h, C.byref(a)))
         return out
 
     # ------------------------------------------------------------------ timing

@@ -46,11 +46,16 @@ enum frl_algo {
                                   <= 256.  capacity = the most steps stored between two frl_reinforce_learn calls, and batch_max follows
                                   it.  The engine has NO target net: FRL_PARAM_TARGET addresses a block that frl_params_set / _get store and
                                   return but that no kernel of this algorithm reads or writes (frl_act with use_target = 1 runs on it) */
-    FRL_ALGO_ENVELOPE_DQN = 8  /* ENVELOPE_MORL_file/ENVELOPE_DQN.py:36-266: one Q-net (index 0) [obs | preference] -> hidden (ReLU) -> hidden
+    FRL_ALGO_ENVELOPE_DQN = 8, /* ENVELOPE_MORL_file/ENVELOPE_DQN.py:36-266: one Q-net (index 0) [obs | preference] -> hidden (ReLU) -> hidden
                                   (ReLU) -> n_actions x reward_dim (column a * reward_dim + k = objective k of action a) with a target net;
                                   one agent, actions stored as one float index, act_dim[0] = number of actions, frl_config.reward_dim
                                   objectives: a record carries reward_dim reward columns (done_off = rew_off + reward_dim).  n_actions x
                                   reward_dim <= 64, hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_learn */
+    FRL_ALGO_ENVELOPE_DDPG = 9 /* ENVELOPE_MORL_file/ENVELOPE_DDPG.py:40-320: net 0 the actor [obs | preference] -> hidden (ReLU) -> hidden
+                                  (ReLU) -> act_dim[0] (tanh), net 1 the critic [obs | action | preference] -> hidden (ReLU) -> hidden
+                                  (ReLU) -> reward_dim (linear), each with a target net; one agent, continuous actions stored as
+                                  act_dim[0] floats, frl_config.reward_dim objectives and reward columns as on envelope-DQN engines.
+                                  hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_ddpg_learn */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2 };
@@ -110,13 +115,13 @@ typedef struct frl_config {
     float c51_vmin, c51_vmax;     /* its support [v_min, v_max] (-100, 100) */
     int device_id;
     uint64_t seed;                /* device Philox key (fast path only) */
-    int reward_dim;               /* FRL_ALGO_ENVELOPE_DQN: objectives (reward columns per record, preference columns of the Q-net's input);
+    int reward_dim;               /* FRL_ALGO_ENVELOPE_DQN / _DDPG: objectives (reward columns per record, preference columns of the Q-net's input);
                                      0 means 1, and every other algorithm ignores it */
 } frl_config;
 
 /* Column layout of one replay record (all agents of one transition, fp32):
  * [obs_0..|act_0..|rew_0..|done_0..|next_obs_0..|extra] — see DESIGN.md "Data layout".  The reward block is one column per agent,
- * except on FRL_ALGO_ENVELOPE_DQN engines, where it is the reward VECTOR: done_off - rew_off = reward_dim columns. */
+ * except on FRL_ALGO_ENVELOPE_DQN / _DDPG engines, where it is the reward VECTOR: done_off - rew_off = reward_dim columns. */
 typedef struct frl_record_layout {
     int n_agents, width, stride;
     int obs_off[FRL_MAX_AGENTS], obs_dim[FRL_MAX_AGENTS];
@@ -331,6 +336,32 @@ struct frl_envelope_args {
 };
 typedef struct frl_envelope_args frl_envelope_args;
 int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args);
+
+/* ---------------------------------------------------------------- envelope multi-objective DDPG (ENVELOPE_MORL_file/ENVELOPE_DDPG.py)
+ * `ENVELOPE_DDPG.learn(batch_size, gamma, tau, weight_num, update_freq)` (:254-320) for every learner in one launch chain, on the
+ * same N = batch x weight_num rows as frl_envelope_learn (row j: ring row idx[j % batch] under preference weights[j / batch]).
+ * Critic step: a' = actor(s', w) of the ONLINE actor (:284), T = r + gamma critic_target(s', a', w) (1 - done), Q = critic(s, a, w),
+ *     loss = beta mean_j (w.Q - w.T)^2 + (1 - beta) mean_{j,k} (Q_k - T_k)^2
+ * clip_grad_norm_ at 0.5 (it runs after backward() here and clips), Adam with critic_lr.  Actor step through the updated critic:
+ * loss = -mean_{j,k} critic(s, actor(s, w), w)_k (the objectives are NOT weighted by w), clip at 0.5, Adam with actor_lr.  Both
+ * target nets then move by `tau`.  FRL_STAT_CRITIC_LOSS / _GNORM and FRL_STAT_ACTOR_LOSS / _GNORM hold the losses and the pre-clip
+ * gradient norms.  Refusals are frl_envelope_learn's: FRL_ERR_INVALID for batch < 1, weight_num < 1, batch x weight_num > batch_max,
+ * NaN scalars, beta outside [0, 1]; FRL_ERR_STATE for batch > a learner's stored rows, idx = NULL with fewer than 2 x batch stored
+ * rows, and engines of any other algorithm.  frl_act serves this engine with FRL_ACT_TANHHEAD on net 0 (in_dim = obs_dim +
+ * reward_dim) and FRL_ACT_RAW on net 1 (in_dim = obs_dim + act_dim + reward_dim); every other learn, rollout or explore entry
+ * point returns FRL_ERR_STATE for it. */
+struct frl_envelope_ddpg_args {
+    int batch;              /* B: sampled ring rows */
+    int weight_num;         /* W: preference vectors; B x W <= batch_max */
+    float gamma, tau, actor_lr, critic_lr, beta;
+    const int64_t* idx;     /* host [P][batch] rows drawn by the caller (ENVELOPE_DDPG.sample, :241-250), or NULL: drawn uniformly on the device */
+    const float* weights;   /* host [P][weight_num][reward_dim] preferences, used as given (:269-271), or NULL: |N(0,1)| / L1 norm on the device */
+    float* critic_loss_out; /* host [P] or NULL (all three outputs NULL: the call is asynchronous) */
+    float* actor_loss_out;  /* host [P] or NULL */
+    float* weights_out;     /* host [P][weight_num][reward_dim] or NULL: the preferences the call used */
+};
+typedef struct frl_envelope_ddpg_args frl_envelope_ddpg_args;
+int frl_envelope_ddpg_learn(frl_engine* e, const frl_envelope_ddpg_args* args);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */

@@ -27,7 +27,10 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           ("reinforce_returns_", 0), ("reinforce_grad_", 0),
           # kernels_envelope.hip: envelope_weights_kernel 38 VGPRs, none spilled; envelope_grad_kernel 256 VGPRs with 8 spilled and 88 bytes of
           # scratch (the Lds carve and the chunk loop's bounds, as in sacd_critic_kernel: reloaded per pass or per row chunk, none in an MFMA loop)
-          ("envelope_weights_", 0), ("envelope_grad_", 8), ("", 20)]
+          ("envelope_weights_", 0), ("envelope_grad_", 8),
+          # kernels_envelope_ddpg.hip: both kernels 256 VGPRs with 18 spilled and 128 bytes of scratch (two NetDescs' layer offsets, the Lds carve
+          # and the chunk loop's bounds: stored at entry, reloaded per pass or per row chunk, none in an MFMA loop)
+          ("envelope_ddpg_critic_", 18), ("envelope_ddpg_actor_", 18), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
