@@ -95,6 +95,45 @@ struct LearnKernels {             // a family's kernels for one engine's shape (
     int lds_bytes = 0, block = 256;
 };
 
+// What the host API needs to know about an algorithm beyond its nets: one row per frl_algo, read through algo_traits().  A new algorithm
+// is a row here, a net-building branch in frl_create and its own learn entry point (DESIGN.md "Where an algorithm is registered on the host").
+static const char kFrlLearn[] = "frl_learn";
+struct AlgoTraits {
+    const char* name;          // in messages
+    const char* learn;         // the entry point that updates such an engine ("": none)
+    const char* act_hint;      // how to act when frl_act_explore (and with it frl_rollout's collection) does not serve the engine; "": it does
+    bool index_action;         // the record holds the action as one index column whatever frl_config.discrete says
+    bool discrete_head;        // n_discrete = act_dim[0]
+    bool vector_reward;        // reward_dim reward columns, the preference buffers (env_w), batch_max counting batch x weight_num rows
+    bool two_wg;               // row chunks at two workgroups per CU: hidden <= 256, <= 80 KB of LDS per chunk, no bump from 16 to 32 rows
+    bool row_walks_head;       // one thread per row walks the head's act_dim x reward_dim columns: at most kSacdMaxActions of them
+    bool act_spill;            // the actor stage parks activations in act_spill
+    bool rollout;              // frl_rollout collects for it
+};
+static const AlgoTraits kAlgo[] = {
+    // name            learn                      act_hint                                                                        index  disc   vecrew two_wg walks  spill  rollout
+    {"replay-only",    "",                        "",                                                                             false, false, false, false, false, false, false},
+    {"DQN",            kFrlLearn,                 "",                                                                             false, true,  false, false, false, false, true},
+    {"DDPG",           kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
+    {"TD3",            kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
+    {"SAC",            kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
+    {"MADDPG",         kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
+    {"PPO",            "frl_ppo_learn",           "",                                                                             false, false, false, false, false, false, false},
+    {"discrete SAC",   kFrlLearn,                 "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX",                                          true,  true,  false, true,  true,  false, false},
+    {"REINFORCE",      "frl_reinforce_learn",     "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX",                                          true,  true,  false, true,  true,  false, false},
+    {"envelope DQN",   "frl_envelope_learn",      "FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives",          true,  true,  true,  true,  true,  false, false},
+    {"envelope DDPG",  "frl_envelope_ddpg_learn", "FRL_ACT_TANHHEAD on net 0 with [obs | preference]",                            false, false, true,  true,  false, true,  false},
+};
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_ENVELOPE_DDPG - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
+
+// An entry point called on an engine of an algorithm it does not serve: the call, the algorithm and the entry point that updates it
+static int wrong_engine(const EngineDesc& h, const char* who, int code = FRL_ERR_STATE) {
+    const AlgoTraits& T = algo_traits(h.algo);
+    return fail(code, "%s does not serve %s engines (updates: %s)%s%s%s", who, T.name, *T.learn ? T.learn : "none",
+                *T.act_hint ? "; such an engine acts through frl_act (" : "", T.act_hint, *T.act_hint ? ")" : "");
+}
+
 struct frl_engine {
     frl_config cfg;
     EngineDesc h;                 // host mirror of the device descriptor
@@ -262,16 +301,17 @@ static int build_net(NetDesc& N, const std::vector<std::pair<int, int>>& layers_
 static void build_record(RecordDesc& R, const frl_config& c) {
     memset(&R, 0, sizeof R);
     R.n_agents = c.n_agents;
+    const AlgoTraits& T = algo_traits(c.algo);
     int off = 0;
     for (int j = 0; j < c.n_agents; ++j) { R.obs_off[j] = off; R.obs_dim[j] = c.obs_dim[j]; off += c.obs_dim[j]; }
     R.obs_total = off;
     for (int j = 0; j < c.n_agents; ++j) {
         R.act_off[j] = off;
-        R.act_dim[j] = (c.discrete || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || c.algo == FRL_ALGO_ENVELOPE_DQN) ? 1 : c.act_dim[j];     // (discrete SAC, REINFORCE, envelope DQN: always the index)
+        R.act_dim[j] = (c.discrete || T.index_action) ? 1 : c.act_dim[j];
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
-    R.rew_off = off; off += (c.algo == FRL_ALGO_ENVELOPE_DQN || c.algo == FRL_ALGO_ENVELOPE_DDPG) ? std::max(1, c.reward_dim) : c.n_agents;      // (envelope DQN / DDPG: the reward vector)
+    R.rew_off = off; off += T.vector_reward ? std::max(1, c.reward_dim) : c.n_agents;
     R.done_off = off; off += c.n_agents;
     for (int j = 0; j < c.n_agents; ++j) { R.nobs_off[j] = off; off += c.obs_dim[j]; }
     R.extra_off = off;
@@ -398,36 +438,23 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     h.P = c.n_learners;
     h.n_agents = c.n_agents;
     h.hidden = c.hidden > 0 ? c.hidden : 128;
-    if (h.hidden % 16) { delete e; return fail(FRL_ERR_INVALID, "hidden must be a multiple of 16"); }
+    const AlgoTraits& T = algo_traits(c.algo);
+    auto refuse = [&](const char* fmt, auto... a) { delete e; return fail(FRL_ERR_INVALID, fmt, a...); };      // (before anything is allocated)
+    if (h.hidden % 16) return refuse("hidden must be a multiple of 16");
     h.capacity = c.capacity;
     h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
     if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;
-    h.n_discrete = (c.algo == FRL_ALGO_DQN || c.algo == FRL_ALGO_SAC_DISCRETE || c.algo == FRL_ALGO_REINFORCE || c.algo == FRL_ALGO_ENVELOPE_DQN ||
-                    (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    h.n_discrete = (T.discrete_head || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
     h.reward_dim = 1;
-    if (c.algo == FRL_ALGO_ENVELOPE_DQN) {      // what kernels_envelope.hip handles: one thread per row walks the head's A x R columns, as for discrete SAC
-        if (c.reward_dim < 0) { delete e; return fail(FRL_ERR_INVALID, "envelope DQN: reward_dim %d must be >= 1 (0 means 1)", c.reward_dim); }
+    if (T.vector_reward) {
+        if (c.reward_dim < 0) return refuse("%s: reward_dim %d must be >= 1 (0 means 1)", T.name, c.reward_dim);
         h.reward_dim = std::max(1, c.reward_dim);
-        if ((long long)c.act_dim[0] * h.reward_dim > kSacdMaxActions) {
-            delete e;
-            return fail(FRL_ERR_INVALID, "envelope DQN: %d actions x %d objectives > %d head columns (kernels_envelope.hip)", c.act_dim[0], h.reward_dim, kSacdMaxActions);
-        }
-        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "envelope DQN: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
     }
-    if (c.algo == FRL_ALGO_ENVELOPE_DDPG) {     // what kernels_envelope_ddpg.hip handles: the row-chunk layout at two workgroups per CU, as envelope DQN
-        if (c.reward_dim < 0) { delete e; return fail(FRL_ERR_INVALID, "envelope DDPG: reward_dim %d must be >= 1 (0 means 1)", c.reward_dim); }
-        h.reward_dim = std::max(1, c.reward_dim);
-        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "envelope DDPG: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
-    }
-    if (c.algo == FRL_ALGO_REINFORCE) {         // what kernels_reinforce.hip handles: discrete SAC's limits, for the same reasons
-        if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: %d actions > %d (kernels_reinforce.hip)", c.act_dim[0], kSacdMaxActions); }
-        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "REINFORCE: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
-    }
-    if (c.algo == FRL_ALGO_SAC_DISCRETE) {      // what kernels_sacd.hip handles: one thread per row walks the action columns
-        if (c.act_dim[0] > kSacdMaxActions) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: %d actions > %d (kernels_sacd.hip)", c.act_dim[0], kSacdMaxActions); }
-        if (h.hidden > 256) { delete e; return fail(FRL_ERR_INVALID, "discrete SAC: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", h.hidden); }
-    }
+    // what the kernels of these algorithms handle: one thread per row walks the head's columns; the row-chunk layout at two workgroups per CU
+    if (T.row_walks_head && (long long)c.act_dim[0] * h.reward_dim > kSacdMaxActions)
+        return refuse("%s: %d actions x %d reward columns > %d head columns", T.name, c.act_dim[0], h.reward_dim, kSacdMaxActions);
+    if (T.two_wg && h.hidden > 256) return refuse("%s: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", T.name, h.hidden);
     build_record(h.rec, c);
     const RecordDesc& R = h.rec;
     const int H = h.hidden;
@@ -438,7 +465,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         h.dueling = c.dueling ? 1 : 0;
         h.noisy = c.noisy ? 1 : 0;
         h.c51_atoms = c.c51_atoms > 1 ? c.c51_atoms : 0;
-        if (h.c51_atoms > 64) { delete e; return fail(FRL_ERR_INVALID, "c51_atoms %d: the distribution arithmetic runs one wave lane per atom (<= 64; the reference uses 51)", h.c51_atoms); }
+        if (h.c51_atoms > 64) return refuse("c51_atoms %d: the distribution arithmetic runs one wave lane per atom (<= 64; the reference uses 51)", h.c51_atoms);
         h.c51_vmin = c.c51_vmin; h.c51_vmax = c.c51_vmax;
         const int per_out = h.c51_atoms ? h.c51_atoms : 1;        // head rows: [V (per_out) ;] A (act_dim x per_out)
         build_net(h.net[0], {{H, c.obs_dim[0]}, {(c.act_dim[0] + (c.dueling ? 1 : 0)) * per_out, H}}, 1, ACT_RELU, ACT_NONE, 0,
@@ -513,8 +540,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_PPO && c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
     if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
-    if (c.algo == FRL_ALGO_ENVELOPE_DQN) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);   // the target vector T per row
-    if (c.algo == FRL_ALGO_ENVELOPE_DDPG) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);  // ... and here the action too: max(A, R)
+    if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -522,8 +548,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
     // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
     // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN &&
-        c.algo != FRL_ALGO_ENVELOPE_DDPG) h.rc = 32;
+    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && !T.two_wg) h.rc = 32;
     // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
@@ -532,23 +557,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         const int v = env_int("FRL_RC", 0);
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
-    if (lds_bytes_for(h, h.rc) > 160 * 1024) { delete e; return fail(FRL_ERR_INVALID, "network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc)); }
-    if (c.algo == FRL_ALGO_SAC_DISCRETE && lds_bytes_for(h, h.rc) > 80 * 1024) {
-        delete e;
-        return fail(FRL_ERR_INVALID, "discrete SAC: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
-    }
-    if (c.algo == FRL_ALGO_REINFORCE && lds_bytes_for(h, h.rc) > 80 * 1024) {
-        delete e;
-        return fail(FRL_ERR_INVALID, "REINFORCE: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
-    }
-    if (c.algo == FRL_ALGO_ENVELOPE_DQN && lds_bytes_for(h, h.rc) > 80 * 1024) {
-        delete e;
-        return fail(FRL_ERR_INVALID, "envelope DQN: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
-    }
-    if (c.algo == FRL_ALGO_ENVELOPE_DDPG && lds_bytes_for(h, h.rc) > 80 * 1024) {
-        delete e;
-        return fail(FRL_ERR_INVALID, "envelope DDPG: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", lds_bytes_for(h, h.rc));
-    }
+    if (lds_bytes_for(h, h.rc) > 160 * 1024) return refuse("network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc));
+    if (T.two_wg && lds_bytes_for(h, h.rc) > 80 * 1024)
+        return refuse("%s: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", T.name, lds_bytes_for(h, h.rc));
     e->lds_bytes = lds_bytes_for(h, h.rc);
     // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
     // ceil(units * s / slots) rounds of n_chunks / s chunk-times on the chip's resident-workgroup slots, and the reduce
@@ -603,7 +614,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         CREATE_TRY(dalloc_zero(&h.grad, P * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
         CREATE_TRY(dalloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
-        if (c.algo != FRL_ALGO_DQN && c.algo != FRL_ALGO_PPO && c.algo != FRL_ALGO_SAC_DISCRETE && c.algo != FRL_ALGO_REINFORCE && c.algo != FRL_ALGO_ENVELOPE_DQN)
+        if (T.act_spill)
             CREATE_TRY(dalloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
         h.Gmax = 1;
         for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
@@ -631,7 +642,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
-        if (c.algo == FRL_ALGO_ENVELOPE_DQN || c.algo == FRL_ALGO_ENVELOPE_DDPG) {
+        if (T.vector_reward) {
             CREATE_TRY(dalloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
             CREATE_TRY(hipHostMalloc((void**)&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim * sizeof(float)));
         }
@@ -693,8 +704,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     const int chain_waves = env_int("FRL_CHAIN_WAVES", 8) == 4 ? 4 : 8;      // waves per workgroup of the register-chained actor-critic kernels (4: round 5's)
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
     if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, chain_waves, h);
-    // (envelope DQN / DDPG: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
-    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || h.algo == ALGO_ENVELOPE_DQN || h.algo == ALGO_ENVELOPE_DDPG))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
+    // (a vector reward: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
+    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || T.vector_reward))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
     if (e->family != FAM_ROWCHUNK) CREATE_TRY(set_family_lds_attributes(e->family));
     if (e->family == FAM_SOLO || e->family == FAM_CHAINED)         // select_action on fragment-image nets, the solo rollout tail's act_frag_body
@@ -1205,11 +1216,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
-    if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_act_explore: discrete SAC acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_act_explore: envelope DQN acts through frl_act (FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives)");
-    if (h.algo == ALGO_ENVELOPE_DDPG)
-        return fail(FRL_ERR_STATE, "frl_act_explore: envelope DDPG acts through frl_act (FRL_ACT_TANHHEAD on net 0 with [obs | preference]) and learns through frl_envelope_ddpg_learn");
-    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_act_explore: REINFORCE acts through frl_act (FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX)");
+    if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * O, out_n = rows * nout;
@@ -1291,6 +1298,27 @@ extern "C" int frl_stats_get(frl_engine* e, float* out_host) {
     HIP_TRY(hipMemcpyAsync(out_host, e->h.stats, (size_t)e->h.P * e->h.n_agents * ST_COUNT * sizeof(float), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return solo_err_check(e);
+}
+
+// What a learn entry point of its own hands back once its launches are enqueued: [the preference vectors used, weight_num per learner,]
+// and up to two statistics per learner out of one copy of h.stats, after one synchronise (which also lands what the caller enqueued).
+// written: per learner, > 0 = write its statistics (nullptr: everybody's)
+struct StatOut { int slot; float* out; };
+static int read_back(frl_engine* e, float* weights_out, int weight_num, StatOut s0, StatOut s1 = {0, nullptr}, const int* written = nullptr) {
+    const EngineDesc& h = e->h;
+    const size_t wpitch = (size_t)h.batch_max * h.reward_dim, wn = (size_t)weight_num * h.reward_dim;
+    for (int p = 0; weights_out && p < h.P; ++p)
+        HIP_TRY(hipMemcpyAsync(weights_out + p * wn, h.env_w + p * wpitch, wn * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    std::vector<float> st;
+    if (s0.out || s1.out) {
+        st.resize((size_t)h.P * ST_COUNT);
+        HIP_TRY(hipMemcpyAsync(st.data(), h.stats, st.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (const StatOut& s : {s0, s1})
+        for (int p = 0; s.out && p < h.P; ++p)
+            if (!written || written[p] > 0) s.out[p] = st[(size_t)p * ST_COUNT + s.slot];
+    return FRL_OK;
 }
 
 extern "C" int frl_last_indices(frl_engine* e, int batch, int64_t* out_host) {

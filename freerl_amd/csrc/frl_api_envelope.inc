@@ -1,28 +1,36 @@
-// frl_envelope_learn (include/freerl_hip.h): ENVELOPE.learn (ENVELOPE_MORL_file/ENVELOPE_DQN.py:204-255) for a population.
-// Included by frl_api.hip.
+// frl_envelope_learn (include/freerl_hip.h): ENVELOPE.learn (ENVELOPE_MORL_file/ENVELOPE_DQN.py:204-255) for a population, and the part
+// of it that frl_envelope_ddpg_learn (frl_api_envelope_ddpg.inc) shares.  Included by frl_api.hip.
 //
 // Launch chain: [draw_kernel: `batch` distinct ring rows per learner when idx is NULL] -> envelope_weights_kernel (one workgroup per
 // learner: the batch's rows expanded to batch x weight_num index entries, the preference vectors drawn when weights is NULL) ->
 // envelope_grad_kernel (row chunks over the batch x weight_num rows) -> reduce + Adam + soft update (launch_adam: net 0, statistics
 // in the actor slots, no clipping — the reference's clip_grad_norm_ runs between zero_grad() and backward(), on gradients that are None).
 
-extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) {
-    ENG(e);
-    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+// Both envelope entry points up to and including envelope_weights_kernel: validation, the staged rows, idx and the preference vectors
+// on the device, the draw.  `scalars` (named in `scalar_names`) are refused when NaN.
+struct EnvelopeCall {
+    int batch, weight_num;
+    float gamma, beta;
+    const int64_t* idx;
+    const float* weights;
+};
+struct EnvelopeLaunch {
+    EnvelopeArgs a;
+    int rows, ns;                   // batch x weight_num; workgroups (= slabs) per learner
+};
+static int envelope_prelude(frl_engine* e, const EnvelopeCall& c, std::initializer_list<float> scalars, const char* scalar_names, EnvelopeLaunch* out) {
     const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_envelope_learn on an envelope DDPG engine (updates: frl_envelope_ddpg_learn)");
-    if (h.algo != ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_envelope_learn on an engine of algo %d", h.algo);
-    const int B = args->batch, W = args->weight_num, RD = h.reward_dim, P = h.P;
+    const int B = c.batch, W = c.weight_num, RD = h.reward_dim, P = h.P;
     if (B < 1) return fail(FRL_ERR_INVALID, "batch %d must be >= 1", B);
     if (W < 1) return fail(FRL_ERR_INVALID, "weight_num %d must be >= 1", W);
     if ((long long)B * W > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d x weight_num %d = %lld rows > batch_max %d", B, W, (long long)B * W, h.batch_max);
-    if (!(args->gamma == args->gamma) || !(args->tau == args->tau) || !(args->lr == args->lr) || !(args->beta == args->beta))
-        return fail(FRL_ERR_INVALID, "gamma / tau / lr / beta is NaN");
-    if (args->beta < 0.f || args->beta > 1.f) return fail(FRL_ERR_INVALID, "beta %g outside [0, 1]", (double)args->beta);
+    for (const float v : scalars)
+        if (!(v == v)) return fail(FRL_ERR_INVALID, "%s is NaN", scalar_names);
+    if (c.beta < 0.f || c.beta > 1.f) return fail(FRL_ERR_INVALID, "beta %g outside [0, 1]", (double)c.beta);
     int min_size = h.capacity;
     for (int p = 0; p < P; ++p) min_size = std::min(min_size, e->size[p]);
     if (min_size < B) return fail(FRL_ERR_STATE, "a ring holds %d rows < batch %d", min_size, B);
-    const bool dev_idx = args->idx == nullptr;
+    const bool dev_idx = c.idx == nullptr;
     const bool table = B > 256 && 4 * B <= kDrawTableHost;
     const size_t draw_lds = ((size_t)2 * ((B + 3) & ~3) + (table ? 2 * kDrawTableHost : 0)) * sizeof(int);
     if (dev_idx && min_size < 2 * B) return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
@@ -30,24 +38,24 @@ extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) 
         return fail(FRL_ERR_INVALID, "device index draw of %d rows does not fit the draw kernel's LDS; pass idx", B);
     int rc = flush_stage(e);
     if (rc) return rc;
-    rc = upload_idx_noise(e, args->idx, nullptr, B, 1);
+    rc = upload_idx_noise(e, c.idx, nullptr, B, 1);
     if (rc) return rc;
     const size_t wpitch = (size_t)h.batch_max * RD, wn = (size_t)W * RD;
-    if (args->weights) {
+    if (c.weights) {
         HIP_TRY(hipStreamSynchronize(e->stream));                       // pinned staging reuse
         for (int p = 0; p < P; ++p) {
-            memcpy(e->h_env_w + p * wpitch, args->weights + p * wn, wn * sizeof(float));
+            memcpy(e->h_env_w + p * wpitch, c.weights + p * wn, wn * sizeof(float));
             HIP_TRY(hipMemcpyAsync(h.env_w + p * wpitch, e->h_env_w + p * wpitch, wn * sizeof(float), hipMemcpyHostToDevice, e->stream));
         }
     }
-    EnvelopeArgs a;
+    EnvelopeArgs& a = out->a;
     memset(&a, 0, sizeof a);
-    a.batch = B; a.weight_num = W; a.draw_w = args->weights ? 0 : 1;
-    a.gamma = args->gamma; a.beta = args->beta;
+    a.batch = B; a.weight_num = W; a.draw_w = c.weights ? 0 : 1;
+    a.gamma = c.gamma; a.beta = c.beta;
     a.p0 = 0; a.p_count = P;
     ++e->param_version;
-    const int rows = B * W;
-    const int ns = ((rows + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per learner
+    out->rows = B * W;
+    out->ns = ((out->rows + h.rc - 1) / h.rc + h.cps - 1) / h.cps;
     if (dev_idx) {
         LearnArgs la;
         memset(&la, 0, sizeof la);
@@ -58,13 +66,25 @@ extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) 
     }
     a.rng_counter = e->rng_counter++;
     hipLaunchKernelGGL(envelope_weights_kernel, dim3(P), dim3(256), 0, e->stream, e->d, a);
+    return FRL_OK;
+}
+
+extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) {
+    ENG(e);
+    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+    const EngineDesc& h = e->h;
+    if (h.algo != ALGO_ENVELOPE_DQN) return wrong_engine(h, "frl_envelope_learn");
+    EnvelopeLaunch L;
+    if (const int rc = envelope_prelude(e, {args->batch, args->weight_num, args->gamma, args->beta, args->idx, args->weights},
+                                        {args->gamma, args->tau, args->lr, args->beta}, "gamma / tau / lr / beta", &L)) return rc;
+    const int P = h.P;
     prof_begin(e, PK_GRAD_ACTOR);
-    hipLaunchKernelGGL(envelope_grad_kernel, dim3(((P + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, e->stream, e->d, a, ns);
+    hipLaunchKernelGGL(envelope_grad_kernel, dim3(((P + 7) / 8) * 8 * L.ns), dim3(256), e->lds_bytes, e->stream, e->d, L.a, L.ns);
     prof_end(e);
     AdamArgs ad;
     memset(&ad, 0, sizeof ad);
     ad.which = 1;                                  // net 0, statistics in the actor slots
-    ad.ns = ns; ad.batch = rows;                   // the loss partials are per row: beta d^2 + (1 - beta) / R sum_k e_k^2
+    ad.ns = L.ns; ad.batch = L.rows;               // the loss partials are per row: beta d^2 + (1 - beta) / R sum_k e_k^2
     ad.lr = args->lr; ad.eps = 1e-8f; ad.beta1 = 0.9f; ad.beta2 = 0.999f;
     ad.clip = 0.f; ad.soft = 1; ad.tau = args->tau; ad.p0 = 0; ad.G = h.Gmax;
     prof_begin(e, PK_ADAM_ACTOR);
@@ -72,16 +92,5 @@ extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) 
     prof_end(e);
     HIP_TRY(hipGetLastError());
     if (!args->loss_out && !args->weights_out) return FRL_OK;
-    if (args->weights_out)
-        for (int p = 0; p < P; ++p)
-            HIP_TRY(hipMemcpyAsync(args->weights_out + p * wn, h.env_w + p * wpitch, wn * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    std::vector<float> st;
-    if (args->loss_out) {
-        st.resize((size_t)P * ST_COUNT);
-        HIP_TRY(hipMemcpyAsync(st.data(), h.stats, st.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (args->loss_out)
-        for (int p = 0; p < P; ++p) args->loss_out[p] = st[(size_t)p * ST_COUNT + ST_ACTOR_LOSS];
-    return FRL_OK;
+    return read_back(e, args->weights_out, args->weight_num, {ST_ACTOR_LOSS, args->loss_out});
 }

@@ -205,12 +205,11 @@ static int dqn_split_for(const EngineDesc& h, int batch, int pc) {
 }
 
 // frl_learn_path / frl_learn_work / frl_learn_work_executed describe frl_learn(): not the engines that learn through another entry point
+// (a PPO engine: frl_learn_path has always said FRL_ERR_INVALID, the work models report no work; a replay-only engine is let through)
 static int describes_learn_guard(const EngineDesc& h, const char* who, bool ppo_too) {
-    if (ppo_too && h.algo == ALGO_PPO) return fail(FRL_ERR_INVALID, "%s describes frl_learn(); PPO updates go through frl_ppo_learn", who);
-    if (h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "%s describes frl_learn(); REINFORCE updates go through frl_reinforce_learn", who);
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "%s describes frl_learn(); envelope DQN updates go through frl_envelope_learn", who);
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "%s describes frl_learn(); envelope DDPG updates go through frl_envelope_ddpg_learn", who);
-    return FRL_OK;
+    if (h.algo == ALGO_PPO) return ppo_too ? wrong_engine(h, who, FRL_ERR_INVALID) : FRL_OK;
+    const char* learn = algo_traits(h.algo).learn;
+    return (learn == kFrlLearn || !*learn) ? FRL_OK : wrong_engine(h, who);
 }
 
 extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, int* bytes_out, int* rows_out) {
@@ -444,11 +443,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_learn: envelope DQN updates go through frl_envelope_learn");
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_learn: envelope DDPG updates go through frl_envelope_ddpg_learn");
-    if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC || h.algo == ALGO_MADDPG ||
-          h.algo == ALGO_SAC_DISCRETE))
-        return fail(FRL_ERR_STATE, "frl_learn: engine algo %d has no off-policy learn (PPO: frl_ppo_learn, REINFORCE: frl_reinforce_learn)", h.algo);
+    if (algo_traits(h.algo).learn != kFrlLearn) return wrong_engine(h, "frl_learn");
     if (args->batch < 1 || args->batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d outside [1,%d]", args->batch, h.batch_max);
     int min_size = h.capacity;
     for (int p = 0; p < h.P; ++p) min_size = std::min(min_size, e->size[p]);

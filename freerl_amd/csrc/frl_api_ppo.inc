@@ -30,8 +30,7 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_ppo_learn on a non-PPO engine (envelope DDPG updates: frl_envelope_ddpg_learn)");
-    if (h.algo != ALGO_PPO) return fail(FRL_ERR_STATE, "frl_ppo_learn on a non-PPO engine");
+    if (h.algo != ALGO_PPO) return wrong_engine(h, "frl_ppo_learn");
     const int T = args->horizon, mb = args->minibatch, K = args->k_epochs;
     if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
     if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
@@ -137,7 +136,7 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
 extern "C" int frl_ppo_work(const frl_engine* e, int horizon, int k_epochs, double* flops_out, double* bytes_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     const EngineDesc& h = e->h;
-    if (h.algo != ALGO_PPO) return fail(FRL_ERR_STATE, "frl_ppo_work on a non-PPO engine");
+    if (h.algo != ALGO_PPO) return wrong_engine(h, "frl_ppo_work");
     auto macs = [](const NetDesc& N) { double s = 0; for (int i = 0; i < N.n_layers; ++i) s += (double)N.L[i].n * N.L[i].k; return s; };
     const double T = horizon, K = k_epochs, ma = macs(h.net[0]), mc = macs(h.net[1]);
     const RecordDesc& R = h.rec;

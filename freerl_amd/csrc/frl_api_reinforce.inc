@@ -9,8 +9,7 @@ extern "C" int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_reinforce_learn on an envelope DDPG engine (updates: frl_envelope_ddpg_learn)");
-    if (h.algo != ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_reinforce_learn on an engine of algo %d", h.algo);
+    if (h.algo != ALGO_REINFORCE) return wrong_engine(h, "frl_reinforce_learn");
     if (!(args->gamma == args->gamma) || !(args->lr == args->lr)) return fail(FRL_ERR_INVALID, "gamma / lr is NaN");
     const int P = h.P;
     int n_max = 0;
@@ -63,14 +62,5 @@ extern "C" int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args
             if (hn[p] > 0)
                 HIP_TRY(hipMemcpyAsync(args->returns_out + (size_t)p * h.capacity, h.isw + (size_t)p * h.batch_max, (size_t)hn[p] * sizeof(float),
                                        hipMemcpyDeviceToHost, e->stream));
-    std::vector<float> st;
-    if (args->loss_out) {
-        st.resize((size_t)P * ST_COUNT);
-        HIP_TRY(hipMemcpyAsync(st.data(), h.stats, st.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (args->loss_out)
-        for (int p = 0; p < P; ++p)
-            if (hn[p] > 0) args->loss_out[p] = st[(size_t)p * ST_COUNT + ST_ACTOR_LOSS];
-    return FRL_OK;
+    return read_back(e, nullptr, 0, {ST_ACTOR_LOSS, args->loss_out}, {0, nullptr}, hn);
 }

@@ -221,16 +221,13 @@ static float decayed_scale(const frl_rollout_args* ra, const frl::EnvPool* pool,
 // host_explore = 1 is round 1's loop: obs H2D, action D2H, exploration by a host generator, records staged from the host.
 extern "C" int frl_rollout(frl_engine* e, frl_envpool* p, const frl_rollout_args* ra, frl_rollout_stats* out) {
     ENG(e);
-    if (e->h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for discrete SAC engines");
-    if (e->h.algo == ALGO_REINFORCE) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for REINFORCE engines");
-    if (e->h.algo == ALGO_ENVELOPE_DQN) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for envelope DQN engines (updates: frl_envelope_learn)");
-    if (e->h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_rollout: no fused collection for envelope DDPG engines (updates: frl_envelope_ddpg_learn)");
+    const AlgoTraits& T = algo_traits(e->h.algo);
+    if (*T.act_hint) return wrong_engine(e->h, "frl_rollout");      // (no fused collection where the explore launch does not serve; said before the arguments are looked at, as ever)
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;
     const int E = ra->envs_per_learner, n = p->pool->n;
-    if (!(h.algo == ALGO_DQN || h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC))
-        return fail(FRL_ERR_STATE, "frl_rollout supports DQN / DDPG / TD3 / SAC engines");
+    if (!T.rollout) return wrong_engine(h, "frl_rollout");
     if (E < 1 || n != h.P * E) return fail(FRL_ERR_INVALID, "pool has %d envs, engine needs P*E = %d*%d", n, h.P, E);
     if (E > h.capacity) return fail(FRL_ERR_INVALID, "a vector step adds E = %d rows to a ring of %d", E, h.capacity);
     if (es.obs_dim != h.rec.obs_dim[0]) return fail(FRL_ERR_INVALID, "obs_dim mismatch (%d vs %d)", es.obs_dim, h.rec.obs_dim[0]);
@@ -701,8 +698,7 @@ extern "C" int frl_ppo_rollout(frl_engine* e, frl_envpool* p, const frl_ppo_roll
     if (!p || !ra) return fail(FRL_ERR_INVALID, "NULL argument");
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;
-    if (h.algo == ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_STATE, "frl_ppo_rollout needs a PPO engine (envelope DDPG updates: frl_envelope_ddpg_learn)");
-    if (h.algo != ALGO_PPO) return fail(FRL_ERR_STATE, "frl_ppo_rollout needs a PPO engine");
+    if (h.algo != ALGO_PPO) return wrong_engine(h, "frl_ppo_rollout");
     if (h.beta_actor) return fail(FRL_ERR_STATE, "frl_ppo_rollout: Gaussian and Categorical actors only");
     const int E = ra->envs_per_learner, Tseg = ra->steps_per_env, n = p->pool->n, T = E * Tseg;
     if (E < 1 || Tseg < 1 || n != h.P * E) return fail(FRL_ERR_INVALID, "pool has %d envs, engine needs P*E = %d*%d", n, h.P, E);

@@ -364,14 +364,9 @@ class Engine:
         N.check(self._L.frl_reinforce_learn(self._h, C.byref(a)))
         return out
 
-    def envelope_learn(self, batch, weight_num, *, gamma, tau, lr, beta, idx=None, weights=None, want_loss=False, want_weights=False):
-        """ENVELOPE.learn for every learner (frl_envelope_learn) on batch x weight_num rows: row j is ring row idx[j % batch] under
-        preference weights[j // batch].  idx [P][batch] / weights [P][weight_num][reward_dim], or None: drawn on the device.
-        -> dict with `loss` [P] and / or `weights` [P][weight_num][reward_dim] (the preferences used); empty and asynchronous
-        when neither is asked for."""
-        a = N.EnvelopeArgs()
+    def _envelope_call(self, fn, a, batch, weight_num, idx, weights, want_weights, out):
+        """What envelope_learn and envelope_ddpg_learn share: batch / weight_num / idx / weights into `a`, the `weights` output, the call."""
         a.batch, a.weight_num = int(batch), int(weight_num)
-        a.gamma, a.tau, a.lr, a.beta = float(gamma), float(tau), float(lr), float(beta)
         keep = []
         if idx is not None:
             ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, int(batch))
@@ -381,15 +376,24 @@ class Engine:
             w = np.ascontiguousarray(weights, dtype=F32).reshape(self.P, int(weight_num), self.reward_dim)
             keep.append(w)
             a.weights = _fp(w)
+        if want_weights:
+            out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
+            a.weights_out = _fp(out["weights"])
+        N.check(fn(self._h, C.byref(a)))
+        return out
+
+    def envelope_learn(self, batch, weight_num, *, gamma, tau, lr, beta, idx=None, weights=None, want_loss=False, want_weights=False):
+        """ENVELOPE.learn for every learner (frl_envelope_learn) on batch x weight_num rows: row j is ring row idx[j % batch] under
+        preference weights[j // batch].  idx [P][batch] / weights [P][weight_num][reward_dim], or None: drawn on the device.
+        -> dict with `loss` [P] and / or `weights` [P][weight_num][reward_dim] (the preferences used); empty and asynchronous
+        when neither is asked for."""
+        a = N.EnvelopeArgs()
+        a.gamma, a.tau, a.lr, a.beta = float(gamma), float(tau), float(lr), float(beta)
         out = {}
         if want_loss:
             out["loss"] = np.full(self.P, np.nan, dtype=F32)
             a.loss_out = _fp(out["loss"])
-        if want_weights:
-            out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
-            a.weights_out = _fp(out["weights"])
-        N.check(self._L.frl_envelope_learn(self._h, C.byref(a)))
-        return out
+        return self._envelope_call(self._L.frl_envelope_learn, a, batch, weight_num, idx, weights, want_weights, out)
 
     def envelope_ddpg_learn(self, batch, weight_num, *, gamma, tau, actor_lr, critic_lr, beta, idx=None, weights=None, want_loss=False,
                             want_weights=False):
@@ -399,27 +403,13 @@ class Engine:
         -> dict with `critic_loss` [P] and `actor_loss` [P] and / or `weights` [P][weight_num][reward_dim] (the preferences used);
         empty and asynchronous when neither is asked for."""
         a = N.EnvelopeDdpgArgs()
-        a.batch, a.weight_num = int(batch), int(weight_num)
         a.gamma, a.tau, a.actor_lr, a.critic_lr, a.beta = float(gamma), float(tau), float(actor_lr), float(critic_lr), float(beta)
-        keep = []
-        if idx is not None:
-            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, int(batch))
-            keep.append(ix)
-            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
-        if weights is not None:
-            w = np.ascontiguousarray(weights, dtype=F32).reshape(self.P, int(weight_num), self.reward_dim)
-            keep.append(w)
-            a.weights = _fp(w)
         out = {}
         if want_loss:
             out["critic_loss"] = np.full(self.P, np.nan, dtype=F32)
             out["actor_loss"] = np.full(self.P, np.nan, dtype=F32)
             a.critic_loss_out, a.actor_loss_out = _fp(out["critic_loss"]), _fp(out["actor_loss"])
-        if want_weights:
-            out["weights"] = np.full((self.P, max(int(weight_num), 0), self.reward_dim), np.nan, dtype=F32)
-            a.weights_out = _fp(out["weights"])
-        N.check(self._L.frl_envelope_ddpg_learn(self._h, C.byref(a)))
-        return out
+        return self._envelope_call(self._L.frl_envelope_ddpg_learn, a, batch, weight_num, idx, weights, want_weights, out)
 
     # ------------------------------------------------------------------ timing
     def ppo_work(self, horizon, k_epochs):
