@@ -26,7 +26,9 @@ FRL_COMM_MAX_VALUES = 64
 # enum frl_algo
 ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE, ALGO_REINFORCE, ALGO_ENVELOPE_DQN = -1, 0, 1, 2, 3, 4, 5, 6, 7, 8
 ALGO_ENVELOPE_DDPG = 9
+ALGO_GAIL = 10
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
+ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
 ACT_RAW, ACT_ARGMAX, ACT_TANHHEAD, ACT_SAC_SAMPLE, ACT_PPO_SAMPLE, ACT_CAT_SAMPLE = 0, 1, 2, 3, 4, 5
 ACT_NO_OBSNORM = 0x100
@@ -91,6 +93,12 @@ class EnvelopeDdpgArgs(C.Structure):
                 ("critic_lr", C.c_float), ("beta", C.c_float), ("idx", C.POINTER(C.c_int64)), ("weights", C.POINTER(C.c_float)),
                 ("critic_loss_out", C.POINTER(C.c_float)), ("actor_loss_out", C.POINTER(C.c_float)),
                 ("weights_out", C.POINTER(C.c_float))]
+
+
+class GailArgs(C.Structure):
+    _fields_ = [("n_expert", C.c_int), ("n_policy", C.c_int), ("gp", C.c_int), ("gp_weight", C.c_float), ("lr", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("idx", C.POINTER(C.c_int64)),
+                ("policy_rows", C.POINTER(C.c_float)), ("out", C.POINTER(C.c_float)), ("idx_out", C.POINTER(C.c_int64))]
 
 
 class ExploreArgs(C.Structure):
@@ -178,6 +186,8 @@ SIGNATURES = {
     "frl_reinforce_learn": (_i, [_vp, _P(ReinforceArgs)]),
     "frl_envelope_learn": (_i, [_vp, _P(EnvelopeArgs)]),
     "frl_envelope_ddpg_learn": (_i, [_vp, _P(EnvelopeDdpgArgs)]),
+    "frl_gail_learn": (_i, [_vp, _P(GailArgs)]),
+    "frl_gail_reward": (_i, [_vp, _i, _i, _fp, _fp]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

@@ -105,34 +105,53 @@ template <int ACT>
 __device__ __forceinline__ f32x4 act_apply4(f32x4 v) {
     if constexpr (ACT == ACT_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
     if constexpr (ACT == ACT_TANH) { v.x = tanhf(v.x); v.y = tanhf(v.y); v.z = tanhf(v.z); v.w = tanhf(v.w); }
+    if constexpr (ACT == ACT_LEAKY_RELU) {
+        v.x = v.x > 0.f ? v.x : kLeakySlope * v.x; v.y = v.y > 0.f ? v.y : kLeakySlope * v.y;
+        v.z = v.z > 0.f ? v.z : kLeakySlope * v.z; v.w = v.w > 0.f ? v.w : kLeakySlope * v.w;
+    }
     return v;
 }
-template <class F>
+// LEAKY: the call site may meet ACT_LEAKY_RELU (the GAIL discriminator's kernels only).  Every other call site keeps its three
+// instantiations: a fourth copy of the MFMA block in each of them costs the 64-row kernels registers (see for_il_blocks).
+template <bool LEAKY = false, class F>
 __device__ __forceinline__ void dispatch_act(int act, F f) {
+    if constexpr (LEAKY) {
+        if (act == ACT_LEAKY_RELU) { f(std::integral_constant<int, ACT_LEAKY_RELU>{}); return; }
+    }
     if (act == ACT_RELU) f(std::integral_constant<int, ACT_RELU>{});
     else if (act == ACT_TANH) f(std::integral_constant<int, ACT_TANH>{});
     else f(std::integral_constant<int, ACT_NONE>{});
 }
 
+// (LEAKY as in dispatch_act: the runtime forms test for ACT_LEAKY_RELU only where the caller asks for it)
+template <bool LEAKY = false>
 __device__ __forceinline__ float act_apply(float v, int act) {
     if (act == ACT_RELU) return fmaxf(v, 0.f);
     if (act == ACT_TANH) return tanhf(v);
+    if constexpr (LEAKY) {
+        if (act == ACT_LEAKY_RELU) return v > 0.f ? v : kLeakySlope * v;
+    }
     return v;
 }
 // derivative from the activation OUTPUT
+template <bool LEAKY = false>
 __device__ __forceinline__ float act_grad(float h, int act) {
     if (act == ACT_RELU) return h > 0.f ? 1.f : 0.f;
     if (act == ACT_TANH) return 1.f - h * h;
+    if constexpr (LEAKY) {
+        if (act == ACT_LEAKY_RELU) return h > 0.f ? 1.f : kLeakySlope;
+    }
     return 1.f;
 }
 
 // Y[rc][n_pad] = act(X[rc][k_pad] * W^T + b);  theta holds Wk[k_pad][n_pad] (contraction-major) then b[n_pad]
+template <bool LEAKY = false>
 __device__ __forceinline__ void linear_fwd(const LayerDesc& L, g_cf theta, lds_cf X, int ldx, lds_f Y, int ldy,
                                            int act, int rc) {
     g_cf W = theta + L.w_off;
     g_cf b = theta + L.b_off;
     const int kpad = L.k_pad, npad = L.n_pad, q4 = (lane_id() >> 4) * 4;
-    dispatch_act(act, [&](auto act_c) {
+    dispatch_act<LEAKY>(act, [&](auto act_c) {
     constexpr int ACT = decltype(act_c)::value;
     auto finish = [&](int r, int c4, f32x4 v, f32x4 bias) { st4(Y + r * ldy + c4, act_apply4<ACT>(v + bias)); };
     if (npad % 64 == 0) {
@@ -161,6 +180,7 @@ __device__ __forceinline__ void linear_fwd(const LayerDesc& L, g_cf theta, lds_c
 
 // dX[rc][k tiles ct0..ct1) = (dY[rc][n_pad] * W) (.) act'(H)   written in place over H (pitch ldh); the contraction
 // runs along the rows of Wk[k_pad][n_pad].  act_prev == ACT_NONE: plain store (used for d/d(first-layer input)).
+template <bool LEAKY = false>
 __device__ __forceinline__ void linear_bwd_dx(const LayerDesc& L, g_cf theta, lds_cf dY, int ldy, lds_f H, int ldh,
                                               int act_prev, int rc, int ct0, int ct1) {
     g_cf W = theta + L.w_off;
@@ -174,8 +194,8 @@ __device__ __forceinline__ void linear_bwd_dx(const LayerDesc& L, g_cf theta, ld
             lds_f h = H + r * ldh + c4;
             if (act_prev != ACT_NONE) {
                 const f32x4 hv = ld4((lds_cf)h);
-                v.x *= act_grad(hv.x, act_prev); v.y *= act_grad(hv.y, act_prev);
-                v.z *= act_grad(hv.z, act_prev); v.w *= act_grad(hv.w, act_prev);
+                v.x *= act_grad<LEAKY>(hv.x, act_prev); v.y *= act_grad<LEAKY>(hv.y, act_prev);
+                v.z *= act_grad<LEAKY>(hv.z, act_prev); v.w *= act_grad<LEAKY>(hv.w, act_prev);
             }
             st4(h, v);
         });
@@ -187,8 +207,9 @@ __device__ __forceinline__ void linear_bwd_dx(const LayerDesc& L, g_cf theta, ld
 // store), GS_STORE first of several row chunks (plain store: the next chunk reads it back), GS_ADD a later chunk.
 enum GradStore : int { GS_STREAM = 0, GS_STORE = 1, GS_ADD = 2 };
 
+// bias = false: the weight block only (an outer product that is no layer's backward: device/gail.hpp)
 __device__ __forceinline__ void linear_bwd_dw(const LayerDesc& L, g_f G, lds_cf dY, int ldy, lds_cf X, int ldx, int rc,
-                                              int gs) {
+                                              int gs, bool bias = true) {
     g_f GW = G + L.w_off;
     const int kpad = L.k_pad, npad = L.n_pad;
     const bool first = gs != GS_ADD;
@@ -243,6 +264,7 @@ __device__ __forceinline__ void linear_bwd_dw(const LayerDesc& L, g_f G, lds_cf 
     // bias gradient = column sums of dY.  The last wave(s) take it (the first ones own the odd tile block when the
     // tile count does not divide by 4); 8 independent partial sums keep 8 LDS reads in flight — as one dependent
     // chain of rc reads this loop was the longest thing in every dW phase.
+    if (!bias) return;
     g_f Gb = G + L.b_off;
     for (int n = kWG - 1 - threadIdx.x; n < L.n_pad; n += kWG) {
         const float oldb = first ? 0.f : Gb[n];             // in flight during the column sum
@@ -272,14 +294,14 @@ __device__ __forceinline__ bool head_fusable(const NetDesc& N, int l0, int nl) {
 // ONE: single-output head (every critic): the 16 head weights a lane needs are scalars fetched with the layer's own
 // weights; otherwise they are float4s (4 outputs) fetched in the epilogue.
 // STORE = false: the hidden activations are not kept (target nets: nothing is differentiated through them).
-template <bool ONE, bool STORE = true>
+template <bool ONE, bool STORE = true, bool LEAKY = false>
 __device__ __forceinline__ void linear_fwd_head_t(const LayerDesc& L, const LayerDesc& LH, g_cf theta, lds_cf X, int ldx, lds_f Y,
                                                   int ldy, int act, int rc, lds_f outb, int op) {
     g_cf W = theta + L.w_off;
     g_cf b = theta + L.b_off;
     g_cf WH = theta + LH.w_off;                       // Wk[L.n_pad][16]
     const int kpad = L.k_pad, npad = L.n_pad, l = lane_id(), q = l >> 4, row = l & 15;
-    dispatch_act(act, [&](auto act_c) {
+    dispatch_act<LEAKY>(act, [&](auto act_c) {
     constexpr int ACT = decltype(act_c)::value;
     for_il_blocks(rc / 16, npad / 64, [&](auto bm, int mt0, int g) {
         constexpr int BM = decltype(bm)::value;
@@ -322,10 +344,11 @@ __device__ __forceinline__ void linear_fwd_head_t(const LayerDesc& L, const Laye
     });
     });
 }
+template <bool LEAKY = false>
 __device__ __forceinline__ void linear_fwd_head(const LayerDesc& L, const LayerDesc& LH, g_cf theta, lds_cf X, int ldx, lds_f Y,
                                                 int ldy, int act, int rc, lds_f outb, int op) {
-    if (LH.n == 1) linear_fwd_head_t<true>(L, LH, theta, X, ldx, Y, ldy, act, rc, outb, op);
-    else linear_fwd_head_t<false>(L, LH, theta, X, ldx, Y, ldy, act, rc, outb, op);
+    if (LH.n == 1) linear_fwd_head_t<true, true, LEAKY>(L, LH, theta, X, ldx, Y, ldy, act, rc, outb, op);
+    else linear_fwd_head_t<false, true, LEAKY>(L, LH, theta, X, ldx, Y, ldy, act, rc, outb, op);
 }
 
 // outb[r][0..16) = out_act(b + sum of the `groups` partials), zero beyond the head's n outputs; one thread per row
@@ -348,6 +371,7 @@ __device__ __forceinline__ void head_finalize(const LayerDesc& LH, g_cf theta, l
 // halves 0-31 / 32-63), each taking half of the rows: dWk[k][:] = sum_r h[r][k] d[r] (halves combined by a shuffle),
 // and h[r][k] <- (d[r] . WH[k]) * act'(h[r][k]) in place (the delta of the hidden layer).  The last 16 threads also
 // sum the bias gradient.  G == nullptr: input gradient only.  k_pad <= 128 (32 units per wave).
+template <bool LEAKY = false>
 __device__ __forceinline__ void head_bwd(const LayerDesc& LH, g_cf theta, g_f G, lds_cf outb, int op, lds_f H, int ldh,
                                          int act_prev, int rc, int gs) {
     const bool first = gs != GS_ADD;
@@ -366,7 +390,7 @@ __device__ __forceinline__ void head_bwd(const LayerDesc& LH, g_cf theta, g_f G,
             for (int j = 0; j < 4; ++j) {
                 gw += h[j] * d[j];
                 const float dx = d[j].x * w.x + d[j].y * w.y + d[j].z * w.z + d[j].w * w.w;
-                H[(r + j) * ldh + k] = dx * act_grad(h[j], act_prev);
+                H[(r + j) * ldh + k] = dx * act_grad<LEAKY>(h[j], act_prev);
             }
         }
 #pragma unroll
@@ -404,9 +428,10 @@ struct NoRowConsumer {
     __device__ __forceinline__ void operator()() const {}
 };
 // allf() runs on every thread in that same last phase (the hidden activations in h1 / h2 are final by then).
-template <class RowF, class AllF = NoRowConsumer>
+// A trailing std::true_type lets the net's hidden activation be ACT_LEAKY_RELU (dispatch_act).
+template <class RowF, class AllF = NoRowConsumer, bool LEAKY = false>
 __device__ __forceinline__ void mlp_fwd_rows(const NetDesc& N, int l0, int nl, g_cf theta, const Lds& S, int out_act, RowF rowf,
-                                             AllF allf = AllF{}) {
+                                             AllF allf = AllF{}, std::integral_constant<bool, LEAKY> = {}) {
     lds_cf in = S.xin;
     int ldin = S.xp;
     const bool fuse = head_fusable(N, l0, nl);
@@ -416,7 +441,7 @@ __device__ __forceinline__ void mlp_fwd_rows(const NetDesc& N, int l0, int nl, g
         const int ldo = last ? S.op : S.hp;
         if (fuse && i == nl - 2) {
             const LayerDesc& LH = N.L[l0 + nl - 1];
-            linear_fwd_head(N.L[l0 + i], LH, theta, in, ldin, out, ldo, N.hidden_act, S.rc, S.outb, S.op);
+            linear_fwd_head<LEAKY>(N.L[l0 + i], LH, theta, in, ldin, out, ldo, N.hidden_act, S.rc, S.outb, S.op);
             FRL_PHASE(S);
             head_finalize(LH, theta, S.outb, S.op, S.rc, N.L[l0 + i].n_pad / 64, out_act);
             if (threadIdx.x < S.rc) rowf((int)threadIdx.x);
@@ -424,7 +449,7 @@ __device__ __forceinline__ void mlp_fwd_rows(const NetDesc& N, int l0, int nl, g
             FRL_PHASE(S);
             return;
         }
-        linear_fwd(N.L[l0 + i], theta, in, ldin, out, ldo, last ? out_act : N.hidden_act, S.rc);
+        linear_fwd<LEAKY>(N.L[l0 + i], theta, in, ldin, out, ldo, last ? out_act : N.hidden_act, S.rc);
         FRL_PHASE(S);
         in = out;
         ldin = ldo;
@@ -462,9 +487,10 @@ __device__ __forceinline__ float twin_target_q(const NetDesc& N, g_cf theta, con
 
 // Backward of layers [l0, l0+nl): head delta in outb (zero in padded columns and invalid rows).
 // G != nullptr: weight/bias gradients go to G the way `gs` (GradStore) says.  want_dx0 leaves
-// d loss / d xin in xin for column tiles [ct0, ct1).  Ends with a barrier.
+// d loss / d xin in xin for column tiles [ct0, ct1).  Ends with a barrier.  A trailing std::true_type: as for mlp_fwd_rows.
+template <bool LEAKY = false>
 __device__ __forceinline__ void mlp_bwd(const NetDesc& N, int l0, int nl, g_cf theta, g_f G, const Lds& S, int gs,
-                                        bool want_dx0, int ct0, int ct1) {
+                                        bool want_dx0, int ct0, int ct1, std::integral_constant<bool, LEAKY> = {}) {
     const bool fuse = head_fusable(N, l0, nl);
     for (int i = nl - 1; i >= 0; --i) {
         const bool last = (i == nl - 1);
@@ -474,7 +500,7 @@ __device__ __forceinline__ void mlp_bwd(const NetDesc& N, int l0, int nl, g_cf t
         const int ldx = (i == 0) ? S.xp : S.hp;
         const LayerDesc& L = N.L[l0 + i];
         if (last && fuse) {
-            head_bwd(L, theta, G, D, ldd, X, ldx, N.hidden_act, S.rc, gs);
+            head_bwd<LEAKY>(L, theta, G, D, ldd, X, ldx, N.hidden_act, S.rc, gs);
             FRL_PHASE(S);
             continue;
         }
@@ -483,7 +509,7 @@ __device__ __forceinline__ void mlp_bwd(const NetDesc& N, int l0, int nl, g_cf t
             FRL_PHASE(S);
         }
         if (i > 0) {
-            linear_bwd_dx(L, theta, D, ldd, X, ldx, N.hidden_act, S.rc, 0, L.k_pad / 16);
+            linear_bwd_dx<LEAKY>(L, theta, D, ldd, X, ldx, N.hidden_act, S.rc, 0, L.k_pad / 16);
             FRL_PHASE(S);
         } else if (want_dx0) {
             linear_bwd_dx(L, theta, D, ldd, X, ldx, ACT_NONE, S.rc, ct0, ct1);

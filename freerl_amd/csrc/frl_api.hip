@@ -40,6 +40,7 @@
 #include "kernels_reinforce.hip"
 #include "kernels_envelope.hip"
 #include "kernels_envelope_ddpg.hip"
+#include "kernels_gail.hip"
 #endif
 
 using namespace frl;
@@ -123,8 +124,9 @@ static const AlgoTraits kAlgo[] = {
     {"REINFORCE",      "frl_reinforce_learn",     "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX",                                          true,  true,  false, true,  true,  false, false},
     {"envelope DQN",   "frl_envelope_learn",      "FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives",          true,  true,  true,  true,  true,  false, false},
     {"envelope DDPG",  "frl_envelope_ddpg_learn", "FRL_ACT_TANHHEAD on net 0 with [obs | preference]",                            false, false, true,  true,  false, true,  false},
+    {"GAIL",           "frl_gail_learn",          "FRL_ACT_RAW on [obs | act]: the discriminator's logits; rewards: frl_gail_reward",   false, false, false, true,  false, false, false},
 };
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_ENVELOPE_DDPG - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_GAIL - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 static const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // An entry point called on an engine of an algorithm it does not serve: the call, the algorithm and the entry point that updates it
@@ -214,6 +216,7 @@ struct frl_engine {
     int* h_ep_n = nullptr;                // [2][P] pinned
     hipEvent_t ev_ep[2] = {nullptr, nullptr};
     unsigned ep_seq = 0;
+    float* h_gail_rows = nullptr;         // frl_gail_learn: pinned staging of the uploaded policy rows [P][batch_max][obs_dim + act_dim]
     float* h_env_w = nullptr;             // frl_envelope_learn / frl_envelope_ddpg_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
@@ -329,7 +332,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 104; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn
+extern "C" int frl_version(void) { return 105; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -360,10 +363,11 @@ extern "C" int frl_destroy(frl_engine* e) {
     if (e->h_solo_err) hipHostFree(e->h_solo_err);
     if (e->h_ep_n) hipHostFree(e->h_ep_n);
     if (e->h_env_w) hipHostFree(e->h_env_w);
+    if (e->h_gail_rows) hipHostFree(e->h_gail_rows);
     if (e->h.env_w) hipFree(e->h.env_w);
     if (e->h.ep_n) hipFree(e->h.ep_n);
     for (hipEvent_t ev : e->ev_ep) if (ev) hipEventDestroy(ev);
-    float* dev[] = {e->h.act_spill, e->h.theta_eff, e->h.noisy_eps, e->h.isw, e->h.td_err, e->h.theta, e->h.target, e->h.m, e->h.v, e->h.grad, e->h.replay, e->h.noise, e->h.stats, e->h.alpha,
+    float* dev[] = {e->h.gail_rows, e->h.gail_part, e->h.gail_out, e->h.act_spill, e->h.theta_eff, e->h.noisy_eps, e->h.isw, e->h.td_err, e->h.theta, e->h.target, e->h.m, e->h.v, e->h.grad, e->h.replay, e->h.noise, e->h.stats, e->h.alpha,
                     e->d_stage_rows, e->d_act_in, e->d_act_eps, e->d_act_out, e->d_act_logp, e->d_ppo, e->d_act_wk, e->h.wide_scr};
     for (float* p : dev) if (p) hipFree(p);
     if (e->h.idx) hipFree(e->h.idx);
@@ -412,7 +416,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_ENVELOPE_DDPG) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_GAIL) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -459,6 +463,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     const RecordDesc& R = h.rec;
     const int H = h.hidden;
     const int hact = c.hidden_act == FRL_ACT_TANH ? ACT_TANH : ACT_RELU;
+    if (c.hidden_act == FRL_ACT_LEAKY_RELU && c.algo != FRL_ALGO_GAIL) return refuse("FRL_ACT_LEAKY_RELU is the GAIL discriminator's hidden activation; %s engines do not take it", T.name);
+    // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
+    if (c.algo == FRL_ALGO_GAIL && c.hidden_act == FRL_ACT_TANH) return refuse("GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
     e->has_nets = c.algo != FRL_ALGO_REPLAY_ONLY;
     if (c.algo == FRL_ALGO_DQN) {
         h.n_nets = 1;
@@ -486,6 +493,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         h.n_nets = 2;
         build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_TANH, 0);
         build_net(h.net[1], {{H, c.obs_dim[0] + c.act_dim[0] + h.reward_dim}, {H, H}, {h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
+    } else if (c.algo == FRL_ALGO_GAIL) {
+        h.n_nets = 1;                                                   // Discriminator (GAIL.py:17-28): mlp(s_dim + a_dim, [H, H], 1), no target
+        build_net(h.net[0], {{H, c.obs_dim[0] + c.act_dim[0]}, {H, H}, {1, H}}, 1, c.hidden_act == FRL_ACT_LEAKY_RELU ? ACT_LEAKY_RELU : ACT_RELU, ACT_NONE, 0);
     } else if (c.algo == FRL_ALGO_REINFORCE) {
         h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
         build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
@@ -541,6 +551,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
+    if (c.algo == FRL_ALGO_GAIL) h.lds_act_pad = std::max(h.lds_act_pad, ((H + 31) / 32 + 3) / 4 * 4);             // abuf / dabuf: a row's slope bits of h1 / h2
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -566,7 +577,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     // pass streams s slabs: take the fewest slabs (but two) among the cheapest schedules.  512 learners x 4 chunks of 64
     // rows on 512 slots: two workgroups per learner walk 2 chunks each (2 slabs) instead of 4 workgroups writing 4 slabs.
     {
-        const int n_chunks = (h.batch_max + h.rc - 1) / h.rc;
+        // (GAIL: a call has up to batch_max expert rows AND up to batch_max policy rows)
+        const int n_chunks = ((c.algo == FRL_ALGO_GAIL ? 2 : 1) * h.batch_max + h.rc - 1) / h.rc;
         // resident gradient workgroups: 256 CUs x (2 by registers — the kernels are built for FRL_GRAD_WGS = 2 — or 1 by LDS)
         const long long slots = 256LL * std::max(1, std::min(2, (160 * 1024) / std::max(1, e->lds_bytes)));
         const long long units = (long long)h.P * h.n_agents;
@@ -642,6 +654,13 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
+        if (c.algo == FRL_ALGO_GAIL) {
+            const size_t rows_n = P * (size_t)h.batch_max * (c.obs_dim[0] + c.act_dim[0]);
+            CREATE_TRY(dalloc_zero(&h.gail_rows, rows_n, e->stream));
+            CREATE_TRY(dalloc_zero(&h.gail_part, P * (size_t)h.S * 8, e->stream));
+            CREATE_TRY(dalloc_zero(&h.gail_out, P * 8, e->stream));
+            CREATE_TRY(hipHostMalloc((void**)&e->h_gail_rows, rows_n * sizeof(float)));
+        }
         if (T.vector_reward) {
             CREATE_TRY(dalloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
             CREATE_TRY(hipHostMalloc((void**)&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim * sizeof(float)));
@@ -713,7 +732,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (e->lds_bytes > 64 * 1024) {
         for (const void* k : {(const void*)dqn_grad_kernel, (const void*)ac_critic_kernel, (const void*)ac_actor_kernel, (const void*)sacd_critic_kernel, (const void*)sacd_actor_kernel,
                               (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
-                              (const void*)envelope_ddpg_actor_kernel, (const void*)act_kernel, (const void*)ppo_update_kernel})
+                              (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
+                              (const void*)ppo_update_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -1132,6 +1152,12 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     a.normalize = (!no_norm && e->h.obs_norm_on && (e->h.n_agents == 1 || net % 2 == 0) && in_dim == e->h.rec.obs_dim[agent]) ? 1 : 0;
     a.in = in_dev; a.eps = eps_dev; a.out = out_dev; a.out_logp = logp_dev;
     if (build_only) { *build_only = a; return FRL_OK; }
+    if (e->h.algo == ALGO_GAIL) {      // LeakyReLU hidden layers: the discriminator's own forward kernel (kernels_gail.hip), logits of the online net
+        if (mode != FRL_ACT_RAW || use_target || ex) return fail(FRL_ERR_INVALID, "a GAIL engine acts through FRL_ACT_RAW on its online net (the logits)");
+        hipLaunchKernelGGL(gail_forward_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, 0, n_rows, in_dev, out_dev);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
     if (N.frag && (e->h.wide || e->h.solow)) {
         // fragment-image parameters of a shape act_frag_kernel does not take: the net is re-laid out to Wk in a scratch copy (one
         // small launch: the actor of config 4 is 67 k floats per learner) and act_kernel reads that
@@ -1599,5 +1625,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_reinforce.inc"
 #include "frl_api_envelope.inc"
 #include "frl_api_envelope_ddpg.inc"
+#include "frl_api_gail.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

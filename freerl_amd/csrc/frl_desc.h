@@ -8,9 +8,10 @@ constexpr int kMaxLayers = 6;     // twin critic = 2 x 3 layers in ONE net (one 
 constexpr int kMaxAgents = 8;
 constexpr int kMaxNets = 2 * kMaxAgents;
 
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: the GAIL discriminator's hidden layers only)
+constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
-                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9 };
+                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -183,6 +184,10 @@ struct EngineDesc {
     int reward_dim;       // envelope DQN / DDPG: objectives R (reward columns of a record, preference columns of the net's input); 1 otherwise
     float* env_w;         // envelope DQN / DDPG: [P][batch_max][reward_dim], the first weight_num rows = the preference vectors of the current
                           // frl_envelope_learn call (uploaded, or drawn by envelope_weights_kernel)
+    // GAIL's discriminator (kernels_gail.hip): the ring holds the expert rows, batch_max bounds the rows of EITHER kind in a call
+    float* gail_rows;     // [P][batch_max][obs_dim + act_dim] the policy rows of the current frl_gail_learn call
+    float* gail_part;     // [P][S][8] per-workgroup partial sums (device/gail.hpp: GailPart)
+    float* gail_out;      // [P][8] what frl_gail_args::out returns, written by gail_stats_kernel
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -163,6 +163,20 @@ __global__ void envelope_grad_kernel(const EngineDesc* __restrict__ Dp, Envelope
 __global__ void envelope_ddpg_critic_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
 __global__ void envelope_ddpg_actor_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns);
 
+// kernels_gail.hip: GAIL's discriminator (GAIL_file/GAIL.py): E expert ring rows + N staged policy rows per call
+struct GailArgs {
+    int n_expert, n_policy;           // E, N
+    int gp;                           // 0: sigmoid + BCE; 1: logits, 0.5 x BCE-with-logits + gp_weight x gradient penalty on the expert rows
+    int size;                         // gail_draw_kernel: rows valid in every ring
+    float gp_weight;
+    unsigned long long rng_counter;
+    int p0, p_count;
+};
+__global__ void gail_draw_kernel(const EngineDesc* __restrict__ Dp, GailArgs a);
+__global__ void gail_disc_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, int ns);
+__global__ void gail_stats_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, int ns);
+__global__ void gail_forward_kernel(const EngineDesc* __restrict__ Dp, int mode, int n_rows, const float* __restrict__ in, float* __restrict__ out);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

@@ -411,6 +411,43 @@ class Engine:
             a.critic_loss_out, a.actor_loss_out = _fp(out["critic_loss"]), _fp(out["actor_loss"])
         return self._envelope_call(self._L.frl_envelope_ddpg_learn, a, batch, weight_num, idx, weights, want_weights, out)
 
+    def gail_learn(self, policy_rows, *, gp, lr, beta1, beta2, n_expert=None, gp_weight=5.0, adam_eps=1e-8, idx=None, want_out=True,
+                   want_idx=False):
+        """GAIL.trian_D for every learner (frl_gail_learn): policy_rows [P][n_policy][obs_dim + act_dim] against expert ring rows
+        idx [P][n_expert] (None: n_expert rows drawn with replacement on the device).  gp False: sigmoid + BCE; True: logits,
+        0.5 x BCE-with-logits + gp_weight x the gradient penalty on the expert rows.
+        -> dict with `out` [P][6] = d_loss, expert_prob, policy_prob, w_dis, penalty mean, gradient norm and / or `idx`
+        [P][n_expert] (the rows used); empty and asynchronous when neither is asked for."""
+        rows = np.ascontiguousarray(policy_rows, dtype=F32)
+        cols = self.layout.obs_dim[0] + self.layout.act_dim[0]
+        rows = rows.reshape(self.P, rows.size // (self.P * cols), cols)
+        a = N.GailArgs()
+        keep = [rows]
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, -1)
+            keep.append(ix)
+            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
+            n_expert = ix.shape[1] if n_expert is None else n_expert
+        a.n_expert, a.n_policy, a.gp, a.gp_weight = int(n_expert), rows.shape[1], int(gp), float(gp_weight)
+        a.lr, a.beta1, a.beta2, a.adam_eps = float(lr), float(beta1), float(beta2), float(adam_eps)
+        a.policy_rows = _fp(rows)
+        out = {}
+        if want_out:
+            out["out"] = np.full((self.P, 6), np.nan, dtype=F32)
+            a.out = _fp(out["out"])
+        if want_idx:
+            out["idx"] = np.full((self.P, max(int(n_expert), 0)), -1, dtype=np.int64)
+            a.idx_out = out["idx"].ctypes.data_as(C.POINTER(C.c_int64))
+        N.check(self._L.frl_gail_learn(self._h, C.byref(a)))
+        return out
+
+    def gail_reward(self, rows, *, gp):
+        """GAIL.compute_reward (frl_gail_reward): rows [P][n][obs_dim + act_dim] -> float32 [P][n]."""
+        x = np.ascontiguousarray(rows, dtype=F32).reshape(self.P, -1, self.layout.obs_dim[0] + self.layout.act_dim[0])
+        out = np.empty((self.P, x.shape[1]), dtype=F32)
+        N.check(self._L.frl_gail_reward(self._h, int(gp), x.shape[1], _fp(x), _fp(out)))
+        return out
+
     # ------------------------------------------------------------------ timing
     def ppo_work(self, horizon, k_epochs):
         fl, by = C.c_double(0), C.c_double(0)

@@ -51,14 +51,21 @@ enum frl_algo {
                                   one agent, actions stored as one float index, act_dim[0] = number of actions, frl_config.reward_dim
                                   objectives: a record carries reward_dim reward columns (done_off = rew_off + reward_dim).  n_actions x
                                   reward_dim <= 64, hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_learn */
-    FRL_ALGO_ENVELOPE_DDPG = 9 /* ENVELOPE_MORL_file/ENVELOPE_DDPG.py:40-320: net 0 the actor [obs | preference] -> hidden (ReLU) -> hidden
+    FRL_ALGO_ENVELOPE_DDPG = 9,/* ENVELOPE_MORL_file/ENVELOPE_DDPG.py:40-320: net 0 the actor [obs | preference] -> hidden (ReLU) -> hidden
                                   (ReLU) -> act_dim[0] (tanh), net 1 the critic [obs | action | preference] -> hidden (ReLU) -> hidden
                                   (ReLU) -> reward_dim (linear), each with a target net; one agent, continuous actions stored as
                                   act_dim[0] floats, frl_config.reward_dim objectives and reward columns as on envelope-DQN engines.
                                   hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_ddpg_learn */
+    FRL_ALGO_GAIL = 10         /* GAIL_file/GAIL.py:17-120, the discriminator: one net (index 0) [obs | act] -> hidden -> hidden -> 1 with
+                                  frl_config.hidden_act = FRL_ACT_LEAKY_RELU (slope 0.01, the reference's) or FRL_ACT_RELU, a linear head and
+                                  NO target net (FRL_PARAM_TARGET as on REINFORCE engines).  One agent, continuous actions.  The ring holds
+                                  the EXPERT rows in the standard record layout, of which only the obs and act columns are read: capacity
+                                  = the number of expert rows, batch_max = the most rows of EITHER kind (expert, policy) one
+                                  frl_gail_learn call may use.  hidden <= 256 */
 };
 
-enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2 };
+enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
+                      FRL_ACT_LEAKY_RELU = 3 /* slope 0.01; FRL_ALGO_GAIL engines only (frl_create refuses it elsewhere) */ };
 
 /* which copy of a net's parameters frl_params_get/set addresses.  FRL_PARAM_GRAD is a debugging view of the reduced
  * gradient block: PPO engines, noisy DQN engines and nets wider than the fused Adam kernel materialise it; the other
@@ -98,7 +105,7 @@ typedef struct frl_config {
     int act_dim[FRL_MAX_AGENTS];  /* continuous: action width; discrete (DQN): number of actions */
     int discrete;                 /* 1: actions are stored as ONE float index (Buffer.py:3-9 act_dim vs action_dim) */
     int hidden;                   /* 128 = the reference's hard-coded width (DQN.py:38, TD3.py:53 ...) */
-    int hidden_act;               /* FRL_ACT_RELU, or FRL_ACT_TANH for PPO trick['tanh'] */
+    int hidden_act;               /* FRL_ACT_RELU, or FRL_ACT_TANH for PPO trick['tanh']; FRL_ALGO_GAIL: FRL_ACT_LEAKY_RELU or FRL_ACT_RELU */
     int twin_critic;              /* Critic_TD3 / SAC Critic: l1..l6 in one module */
     int capacity;                 /* replay rows per learner (PPO: horizon) */
     int batch_max;                /* largest batch / minibatch a learn call will use */
@@ -362,6 +369,40 @@ struct frl_envelope_ddpg_args {
 };
 typedef struct frl_envelope_ddpg_args frl_envelope_ddpg_args;
 int frl_envelope_ddpg_learn(frl_engine* e, const frl_envelope_ddpg_args* args);
+
+/* ---------------------------------------------------------------- GAIL's discriminator (GAIL_file/GAIL.py)
+ * `GAIL.trian_D(expert_states, expert_actions, policy_states, policy_actions)` (:75-120) for every learner in one launch chain, on
+ * E = n_expert expert rows (ring rows idx[j]: drawn WITH replacement, as InfiniteUniformSampler's torch.randint does) and
+ * N = n_policy policy rows (uploaded).  With x = [s | a] and l the net's logit:
+ *     gp = 0:  p = sigmoid(l);  d_loss = BCE(p_expert, 1) + BCE(p_policy, 0), each a mean over its own rows, with torch's clamps (both
+ *              logs at -100, the backward's divisor max(p (1 - p), 1e-12)); the reference's Adam betas are (0.9, 0.999)
+ *     gp = 1:  d_loss = 0.5 (mean_e softplus(-l) + mean_p softplus(l)) + gp_weight mean_e ||dl/dx||^2, the penalty on the EXPERT rows
+ *              only and its weight the reference's literal 5 (NOT config gp_coef); the reference's betas are (0.5, 0.9)
+ * then one Adam step with `lr`, the betas and eps given, no gradient clip, no target.  The penalty's gradient is second order; the
+ * kernel takes it in closed form (csrc/device/gail.hpp), which needs a piecewise-linear hidden activation: frl_create refuses
+ * FRL_ACT_TANH for this algorithm.  out[p] = { d_loss, mean p_expert (gp: mean sigmoid(l_expert)), mean p_policy, w_dis = mean l_expert -
+ * mean l_policy (0 without gp), penalty mean (0 without gp), gradient norm }; FRL_STAT_ACTOR_LOSS / _GNORM hold d_loss and the norm.
+ * Refused before any launch with FRL_ERR_INVALID: n_expert or n_policy < 1 or > batch_max, NaN scalars, betas outside [0, 1),
+ * policy_rows NULL, gp outside {0, 1}, gp_weight < 0; with FRL_ERR_STATE: an idx entry at or past a learner's stored rows (negative
+ * entries included), an empty ring, and engines of any other algorithm.  idx = NULL draws from the engine's Philox stream over the rows
+ * EVERY learner's ring holds (the smallest ring's count).
+ * frl_gail_reward is `GAIL.compute_reward` (:62-73) on n_rows uploaded rows per learner, fp32 in the reference's order of operations:
+ *     gp = 1:  2 x -log(max(1 - 1 / (1 + exp(-l)), 1e-4));      gp = 0:  -log(1 - sigmoid(l) + 1e-8)
+ * frl_act serves this engine with FRL_ACT_RAW on in_dim = obs_dim + act_dim (the logits, online net only); every other learn, rollout
+ * or explore entry point returns FRL_ERR_STATE for it. */
+struct frl_gail_args {
+    int n_expert, n_policy;        /* E, N >= 1, each <= batch_max */
+    int gp;                        /* 0: sigmoid + BCE; 1: logits, 0.5 x BCE-with-logits + gp_weight x penalty */
+    float gp_weight;               /* the reference's literal 5 */
+    float lr, beta1, beta2, adam_eps;
+    const int64_t* idx;            /* host [P][n_expert] expert ring rows (torch.randint draws), or NULL: device draw with replacement */
+    const float* policy_rows;      /* host [P][n_policy][obs_dim + act_dim] */
+    float* out;                    /* host [P][6]: d_loss, expert_prob, policy_prob, w_dis (0 without gp), penalty mean (0 without gp), gradient norm; NULL: asynchronous */
+    int64_t* idx_out;              /* host [P][n_expert] or NULL: the rows the call used */
+};
+typedef struct frl_gail_args frl_gail_args;
+int frl_gail_learn(frl_engine* e, const frl_gail_args* args);
+int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* rows_host /* [P][n_rows][obs_dim + act_dim] */, float* reward_out /* [P][n_rows] */);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */

@@ -30,7 +30,12 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           ("envelope_weights_", 0), ("envelope_grad_", 8),
           # kernels_envelope_ddpg.hip: both kernels 256 VGPRs with 18 spilled and 128 bytes of scratch (two NetDescs' layer offsets, the Lds carve
           # and the chunk loop's bounds: stored at entry, reloaded per pass or per row chunk, none in an MFMA loop)
-          ("envelope_ddpg_critic_", 18), ("envelope_ddpg_actor_", 18), ("", 20)]
+          ("envelope_ddpg_critic_", 18), ("envelope_ddpg_actor_", 18),
+          # kernels_gail.hip: gail_disc_kernel 256 VGPRs with 70 spilled and 288 bytes of scratch: values that live across the whole chunk loop
+          # (the per-row partial sums, the layers' offsets, the Lds carve, the row counts) are stored at entry (55 of the 62 scratch stores) and
+          # reloaded at the start of a barrier phase or between two tile blocks of a dW phase (tools/asm_spills.py), none inside an MFMA k-loop;
+          # gail_forward_kernel 188 VGPRs, gail_draw_kernel 28, gail_stats_kernel 19, none spilled
+          ("gail_disc_", 70), ("gail_forward_", 0), ("gail_draw_", 0), ("gail_stats_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
