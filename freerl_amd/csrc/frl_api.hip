@@ -548,7 +548,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     h.lds_act_pad = (std::max(R.act_total, 1) + 3) / 4 * 4; // abuf / dabuf are scalar-accessed: no tile padding
     if (c.algo == FRL_ALGO_PPO && c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, pad16(c.act_dim[0]));   // logits' delta staging
     if (c.algo == FRL_ALGO_PPO && c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
-    if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (h.c51_atoms + 3) / 4 * 4);      // projected distribution / probabilities per row
+    // projected distribution / probabilities per row, and the row's q value per action (more actions than atoms: 7 on 3 atoms)
+    if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (std::max(h.c51_atoms, c.act_dim[0]) + 3) / 4 * 4);
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
     if (c.algo == FRL_ALGO_GAIL) h.lds_act_pad = std::max(h.lds_act_pad, ((H + 31) / 32 + 3) / 4 * 4);             // abuf / dabuf: a row's slope bits of h1 / h2

@@ -121,7 +121,8 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void c51_grad_kernel(const Engin
             for (int i = 0; i < atoms; ++i) {
                 const float z = vmin + dz * (float)i;
                 const float tz = fminf(fmaxf(rew + a.gamma * z * (1.f - done), vmin), vmax);
-                const float b = (tz - vmin) / dz;
+                // (vmax - vmin) / dz can round to atoms - 1 plus an ulp (16 atoms on [-500, 500]): ceilf would index mr[atoms]
+                const float b = fminf((tz - vmin) / dz, (float)(atoms - 1));
                 const float lf = floorf(b), uf = ceilf(b);
                 const int l = (int)lf, u = (int)uf;
                 if (pass == 0) mr[l] += (uf + (l == u ? 1.f : 0.f) - b) * ndl[i];

@@ -170,6 +170,26 @@ class C51DQN:
     def select_action(self, obs, eps=None):
         return int(np.argmax(self.net.forward(self.q, nn.f32(obs).reshape(1, -1), eps)[1], axis=1)[0])
 
+    def project(self, next_dist, rew, done, gamma):
+        """projection_dist (:147-158) in float32: next_dist [B, atoms], rew / done [B, 1] -> m [B, atoms]."""
+        net = self.net
+        B, atoms = next_dist.shape
+        t_z = np.clip(rew + F32(gamma) * net.z * (F32(1) - done), net.vmin, net.vmax).astype(F32)
+        b = ((t_z - F32(net.vmin)) / F32(net.delta_z)).astype(F32)
+        # not in the reference: (vmax - vmin) / delta_z can round to atoms - 1 plus an ulp (16 atoms on [-500, 500]), ceil(b) is
+        # then `atoms` and index_add_ raises IndexError (:155-156); clamped, l == u == atoms - 1 and the mass is on the top atom
+        b = np.minimum(b, F32(atoms - 1))
+        l, u = np.floor(b).astype(np.int64), np.ceil(b).astype(np.int64)
+        dl = ((u + (l == u) - b) * next_dist).astype(F32)
+        du = ((b - l) * next_dist).astype(F32)
+        m = np.zeros((B, atoms), dtype=F32)
+        for r in range(B):                               # index_add_: sequential in source order, lower bins first
+            for i in range(atoms):
+                m[r, l[r, i]] += dl[r, i]
+            for i in range(atoms):
+                m[r, u[r, i]] += du[r, i]
+        return m
+
     def learn_with(self, idx, gamma, tau, double=False, is_weight=None, noisy_eps=(None, None, None)):
         net = self.net
         obs, act, rew, nobs, done = self.buffer.sample(idx)
@@ -181,17 +201,7 @@ class C51DQN:
             dist_t, q_t, _ = net.forward(self.q_t, nobs, noisy_eps[1])
             next_a = np.argmax(q_t, axis=1)
         next_dist = dist_t[np.arange(B), next_a]                                     # [B, atoms]
-        t_z = np.clip(rew + F32(gamma) * net.z * (F32(1) - done), net.vmin, net.vmax).astype(F32)
-        b = ((t_z - F32(net.vmin)) / F32(net.delta_z)).astype(F32)
-        l, u = np.floor(b).astype(np.int64), np.ceil(b).astype(np.int64)
-        dl = ((u + (l == u) - b) * next_dist).astype(F32)
-        du = ((b - l) * next_dist).astype(F32)
-        m = np.zeros((B, atoms), dtype=F32)
-        for r in range(B):                               # index_add_: sequential in source order, lower bins first
-            for i in range(atoms):
-                m[r, l[r, i]] += dl[r, i]
-            for i in range(atoms):
-                m[r, u[r, i]] += du[r, i]
+        m = self.project(next_dist, rew, done, gamma)
         dist, _, acts = net.forward(self.q, obs, noisy_eps[2])
         a = act.astype(np.int64).reshape(-1)
         p = dist[np.arange(B), a]
