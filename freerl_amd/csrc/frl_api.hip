@@ -13,6 +13,7 @@
 
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
+#include "host_mem.hpp"
 
 #include "kernels.h"
 #ifdef FRL_UNITY      // developer variants (tools/phase_timing.py): one translation unit, so that the phase-timing symbols exist once
@@ -62,6 +63,18 @@ static int fail(int code, const char* fmt, ...) {
         hipError_t _e = (expr);                                                                    \
         if (_e != hipSuccess) return fail(FRL_ERR_HIP, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
+
+struct HipMem {                   // host_mem.hpp's backend.  hipFree synchronises the device: what makes regrowing a buffer under a busy stream safe
+    using error_t = hipError_t;
+    using stream_t = hipStream_t;
+    static constexpr hipError_t ok = hipSuccess;
+    static hipError_t device_alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t device_free(void* p) { return hipFree(p); }
+    static hipError_t pinned_alloc(void** p, size_t bytes, unsigned flags) { return hipHostMalloc(p, bytes, flags); }
+    static hipError_t pinned_free(void* p) { return hipHostFree(p); }
+    static hipError_t memset_async(void* p, int value, size_t bytes, hipStream_t s) { return hipMemsetAsync(p, value, bytes, s); }
+};
+using HostMem = frl::MemOwner<HipMem>;
 
 static inline int pad16(int x) { return (x + 15) / 16 * 16; }
 static inline int pad32(int x) { return (x + 31) / 32 * 32; }
@@ -137,6 +150,7 @@ static int wrong_engine(const EngineDesc& h, const char* who, int code = FRL_ERR
 }
 
 struct frl_engine {
+    HostMem mem;                  // owns every device and pinned buffer below and in h: allocate through it and frl_destroy needs no line
     frl_config cfg;
     EngineDesc h;                 // host mirror of the device descriptor
     EngineDesc* d = nullptr;      // device copy
@@ -192,7 +206,7 @@ struct frl_engine {
     float* d_act_eps = nullptr;
     float* d_act_out = nullptr;
     float* d_act_logp = nullptr;
-    size_t act_in_cap = 0, act_out_cap = 0;
+    size_t act_in_cap = 0, act_eps_cap = 0, act_out_cap = 0, act_logp_cap = 0;      // floats each holds (act_scratch)
     float* d_ou = nullptr;                // frl_act_explore's Ornstein-Uhlenbeck state [P][n_rows][A]
     unsigned char* d_ou_flags = nullptr;
     size_t ou_n = 0;
@@ -347,61 +361,13 @@ extern "C" int frl_destroy(frl_engine* e) {
     if (!e) return FRL_OK;
     hipSetDevice(e->cfg.device_id);
     if (e->stream) hipStreamSynchronize(e->stream);
-    if (e->d_per_sum) hipFree(e->d_per_sum);
-    if (e->d_per_max) hipFree(e->d_per_max);
-    if (e->d_size) hipFree(e->d_size);
-    if (e->d_stage_bucket) hipFree(e->d_stage_bucket);
-    if (e->stage_bucket) hipHostFree(e->stage_bucket);
-    if (e->d_per_prio) hipFree(e->d_per_prio);
-    if (e->d_uniforms) hipFree(e->d_uniforms);
-    if (e->h_noisy) hipHostFree(e->h_noisy);
-    if (e->d_solo_slab) hipFree(e->d_solo_slab);
-    if (e->d_solo_part) hipFree(e->d_solo_part);
-    if (e->d_solo_pre) hipFree(e->d_solo_pre);
-    if (e->d_solo_bar) hipFree(e->d_solo_bar);
-    if (e->d_solow_bar2) hipFree(e->d_solow_bar2);
-    if (e->h_solo_err) hipHostFree(e->h_solo_err);
-    if (e->h_ep_n) hipHostFree(e->h_ep_n);
-    if (e->h_env_w) hipHostFree(e->h_env_w);
-    if (e->h_gail_rows) hipHostFree(e->h_gail_rows);
-    if (e->h.env_w) hipFree(e->h.env_w);
-    if (e->h.ep_n) hipFree(e->h.ep_n);
+    e->mem.release_all();
     for (hipEvent_t ev : e->ev_ep) if (ev) hipEventDestroy(ev);
-    float* dev[] = {e->h.gail_rows, e->h.gail_part, e->h.gail_out, e->h.act_spill, e->h.theta_eff, e->h.noisy_eps, e->h.isw, e->h.td_err, e->h.theta, e->h.target, e->h.m, e->h.v, e->h.grad, e->h.replay, e->h.noise, e->h.stats, e->h.alpha,
-                    e->d_stage_rows, e->d_act_in, e->d_act_eps, e->d_act_out, e->d_act_logp, e->d_ppo, e->d_act_wk, e->h.wide_scr};
-    for (float* p : dev) if (p) hipFree(p);
-    if (e->h.idx) hipFree(e->h.idx);
-    if (e->h.steps) hipFree(e->h.steps);
-    if (e->h.ticket) hipFree(e->h.ticket);
-    if (e->d_stage_slots) hipFree(e->d_stage_slots);
-    if (e->d_ou) hipFree(e->d_ou);
-    if (e->d_ou_flags) hipFree(e->d_ou_flags);
-    if (e->d_idx64) hipFree(e->d_idx64);
-    if (e->d_perm) hipFree(e->d_perm);
-    if (e->d) hipFree(e->d);
-    if (e->stage_rows) hipHostFree(e->stage_rows);
-    if (e->stage_slots) hipHostFree(e->stage_slots);
-    if (e->h_idx) hipHostFree(e->h_idx);
-    if (e->h_idx64) hipHostFree(e->h_idx64);
-    if (e->h_noise) hipHostFree(e->h_noise);
-    if (e->ev0) hipEventDestroy(e->ev0);
-    if (e->ev1) hipEventDestroy(e->ev1);
-    if (e->ev_stage) hipEventDestroy(e->ev_stage);
+    for (hipEvent_t ev : {e->ev0, e->ev1, e->ev_stage}) if (ev) hipEventDestroy(ev);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
-    if (e->h.slab) hipFree(e->h.slab);
-    if (e->h.part) hipFree(e->h.part);
-    if (e->h.gsq) hipFree(e->h.gsq);
-    if (e->h.obsnorm) hipFree(e->h.obsnorm);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
     return FRL_OK;
-}
-
-template <class T>
-static hipError_t dalloc_zero(T** p, size_t count, hipStream_t s) {
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemsetAsync(*p, 0, count * sizeof(T), s);
 }
 
 static LearnFamily choose_engine_family(frl_engine* e);       // frl_api_learn.inc
@@ -617,60 +583,60 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     CREATE_TRY(hipEventCreate(&e->ev1));
     CREATE_TRY(hipEventCreateWithFlags(&e->ev_stage, hipEventDisableTiming));
     const size_t P = h.P;
-    CREATE_TRY(dalloc_zero(&h.replay, P * (size_t)h.capacity * R.stride, e->stream));
+    CREATE_TRY(e->mem.alloc_zero(&h.replay, P * (size_t)h.capacity * R.stride, e->stream));
     if (e->has_nets) {
         const size_t ls = h.learner_stride;
-        CREATE_TRY(dalloc_zero(&h.theta, P * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.target, P * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.m, P * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.v, P * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.grad, P * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
-        CREATE_TRY(dalloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.theta, P * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.target, P * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.m, P * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.v, P * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.grad, P * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
         if (T.act_spill)
-            CREATE_TRY(dalloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
         h.Gmax = 1;
         for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
-        CREATE_TRY(dalloc_zero(&h.gsq, P * (size_t)h.n_agents * h.Gmax, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.gsq, P * (size_t)h.n_agents * h.Gmax, e->stream));
         e->idx_count = P * h.n_agents * h.batch_max;
         if (h.noisy) {
             const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];
             e->noisy_per_set = 2 * (HL.k_pad + HL.n_pad);
-            CREATE_TRY(dalloc_zero(&h.theta_eff, P * 3 * ls, e->stream));
-            CREATE_TRY(dalloc_zero(&h.noisy_eps, P * 3 * (size_t)e->noisy_per_set, e->stream));
-            CREATE_TRY(hipHostMalloc((void**)&e->h_noisy, P * 3 * (size_t)e->noisy_per_set * sizeof(float)));
+            CREATE_TRY(e->mem.alloc_zero(&h.theta_eff, P * 3 * ls, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.noisy_eps, P * 3 * (size_t)e->noisy_per_set, e->stream));
+            CREATE_TRY(e->mem.alloc(&e->h_noisy, P * 3 * (size_t)e->noisy_per_set, MEM_PINNED));
         }
-        CREATE_TRY(dalloc_zero(&h.isw, P * (size_t)h.batch_max, e->stream));
-        CREATE_TRY(dalloc_zero(&h.td_err, P * (size_t)h.batch_max, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.isw, P * (size_t)h.batch_max, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.td_err, P * (size_t)h.batch_max, e->stream));
         h.noise_sets = std::max(2, h.n_agents);
         e->noise_count = P * h.n_agents * h.noise_sets * (size_t)h.batch_max * h.act_max;
-        CREATE_TRY(dalloc_zero(&h.idx, e->idx_count, e->stream));
-        CREATE_TRY(dalloc_zero(&h.noise, e->noise_count, e->stream));
-        CREATE_TRY(dalloc_zero(&h.stats, P * h.n_agents * ST_COUNT, e->stream));
-        CREATE_TRY(dalloc_zero(&h.steps, P * (kMaxNets + 1), e->stream));
-        CREATE_TRY(dalloc_zero(&h.ticket, P + 1, e->stream));
-        CREATE_TRY(dalloc_zero(&h.alpha, P * 4, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.idx, e->idx_count, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.noise, e->noise_count, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.stats, P * h.n_agents * ST_COUNT, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.steps, P * (kMaxNets + 1), e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.ticket, P + 1, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.alpha, P * 4, e->stream));
         if (c.algo == FRL_ALGO_REINFORCE) {
-            CREATE_TRY(dalloc_zero(&h.ep_n, P, e->stream));
-            CREATE_TRY(hipHostMalloc((void**)&e->h_ep_n, 2 * P * sizeof(int)));
+            CREATE_TRY(e->mem.alloc_zero(&h.ep_n, P, e->stream));
+            CREATE_TRY(e->mem.alloc(&e->h_ep_n, 2 * P, MEM_PINNED));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
         if (c.algo == FRL_ALGO_GAIL) {
             const size_t rows_n = P * (size_t)h.batch_max * (c.obs_dim[0] + c.act_dim[0]);
-            CREATE_TRY(dalloc_zero(&h.gail_rows, rows_n, e->stream));
-            CREATE_TRY(dalloc_zero(&h.gail_part, P * (size_t)h.S * 8, e->stream));
-            CREATE_TRY(dalloc_zero(&h.gail_out, P * 8, e->stream));
-            CREATE_TRY(hipHostMalloc((void**)&e->h_gail_rows, rows_n * sizeof(float)));
+            CREATE_TRY(e->mem.alloc_zero(&h.gail_rows, rows_n, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.gail_part, P * (size_t)h.S * 8, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.gail_out, P * 8, e->stream));
+            CREATE_TRY(e->mem.alloc(&e->h_gail_rows, rows_n, MEM_PINNED));
         }
         if (T.vector_reward) {
-            CREATE_TRY(dalloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
-            CREATE_TRY(hipHostMalloc((void**)&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim * sizeof(float)));
+            CREATE_TRY(e->mem.alloc_zero(&h.env_w, P * (size_t)h.batch_max * h.reward_dim, e->stream));
+            CREATE_TRY(e->mem.alloc(&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim, MEM_PINNED));
         }
         if (h.solo || h.solow) {
             e->solo_stride = 0;
             for (int i = 0; i < h.n_nets; ++i) e->solo_stride = std::max(e->solo_stride, h.net[i].size);
             const size_t U = P * (size_t)h.n_agents, NT = h.solow ? (size_t)h.solow : (size_t)kSoloWG;      // (kernels_solow.hip: units, row tiles per unit)
-            CREATE_TRY(dalloc_zero(&e->d_solo_slab, U * NT * e->solo_stride, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&e->d_solo_slab, U * NT * e->solo_stride, e->stream));
             // (kernels_solow.hip: helper workgroups on the CUs a small population leaves idle take a share of the slab sum and of Adam —
             //  FRL_SOLOW_HELPERS=0 switches them off; every workgroup of a launch must be resident)
             e->solow_wgs = (int)NT;
@@ -679,44 +645,42 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
                 const int per = std::min(64 / rw > 0 ? 64 / rw : 1, std::max(1, e->n_cus / (rw * (int)U)));      // (at most 64 workgroups per unit: the mailboxes are polled by one wave)
                 e->solow_wgs = env_flag("FRL_SOLOW_HELPERS", true) ? rw * per : rw;
             }
-            CREATE_TRY(dalloc_zero(&e->d_solo_part, U * (size_t)std::max((int)NT, e->solow_wgs) * kSoloPartHost, e->stream));
-            { float* z = nullptr; CREATE_TRY(dalloc_zero(&z, 2 * U * (size_t)std::max(kSoloPre, 8 + h.batch_max), e->stream)); e->d_solo_pre = (int*)z; }
-            float* z = nullptr;
-            CREATE_TRY(dalloc_zero(&z, 2 * U * NT + 2, e->stream));
-            e->d_solo_bar = (unsigned*)z;                                  // [units][tiles] slab flags, then as many "actor slice stepped" flags (kernels_solo.hip: offset P * 16),
-            e->d_solo_ticket = (int*)(z + 2 * U * NT);                     // ... and the rollout tail's learner ticket
-            if (h.solow) { float* z2 = nullptr; CREATE_TRY(dalloc_zero(&z2, U * 64, e->stream)); e->d_solow_bar2 = (unsigned*)z2; }
+            CREATE_TRY(e->mem.alloc_zero(&e->d_solo_part, U * (size_t)std::max((int)NT, e->solow_wgs) * kSoloPartHost, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&e->d_solo_pre, 2 * U * (size_t)std::max(kSoloPre, 8 + h.batch_max), e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&e->d_solo_bar, 2 * U * NT + 2, e->stream));      // [units][tiles] slab flags, then as many "actor slice stepped" flags (kernels_solo.hip: offset P * 16),
+            e->d_solo_ticket = (int*)(e->d_solo_bar + 2 * U * NT);                         // ... and, in the same block, the rollout tail's learner ticket
+            if (h.solow) CREATE_TRY(e->mem.alloc_zero(&e->d_solow_bar2, U * 64, e->stream));
         }
         if (h.solo || h.solow || h.algo == ALGO_DQN) {                     // the pinned give-up word of the spinning launches (solo hand-overs, pre-armed DQN steps)
-            CREATE_TRY(hipHostMalloc((void**)&e->h_solo_err, 64, hipHostMallocCoherent | hipHostMallocMapped));
+            CREATE_TRY(e->mem.alloc(&e->h_solo_err, 64 / sizeof(int), MEM_PINNED, hipHostMallocCoherent | hipHostMallocMapped));
             *e->h_solo_err = 0;
             CREATE_TRY(hipHostGetDevicePointer((void**)&e->d_solo_err, e->h_solo_err, 0));
         }
-        if (h.wide) CREATE_TRY(dalloc_zero(&h.wide_scr, P * (size_t)h.n_agents * h.wide_unit, e->stream));
+        if (h.wide) CREATE_TRY(e->mem.alloc_zero(&h.wide_scr, P * (size_t)h.n_agents * h.wide_unit, e->stream));
         if (h.wide || h.solow) {                                           // select_action's Wk-layout copies of the nets (launch_act)
             int biggest = 0;
             for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);
             e->act_wk_slot = P * (size_t)biggest;
             e->act_wk_version.assign(2 * (size_t)h.n_nets, 0ULL);
-            CREATE_TRY(hipMalloc((void**)&e->d_act_wk, 2 * (size_t)h.n_nets * e->act_wk_slot * sizeof(float)));
+            CREATE_TRY(e->mem.alloc(&e->d_act_wk, 2 * (size_t)h.n_nets * e->act_wk_slot, MEM_DEVICE));
         }
         {
             int omax = 1;
             for (int j = 0; j < c.n_agents; ++j) omax = std::max(omax, c.obs_dim[j]);
             h.obsnorm_w = 1 + 3 * omax;
-            CREATE_TRY(dalloc_zero(&h.obsnorm, P * (size_t)c.n_agents * c.n_agents * h.obsnorm_w, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.obsnorm, P * (size_t)c.n_agents * c.n_agents * h.obsnorm_w, e->stream));
         }
-        CREATE_TRY(hipHostMalloc((void**)&e->h_idx, e->idx_count * sizeof(int)));
-        CREATE_TRY(hipHostMalloc((void**)&e->h_noise, e->noise_count * sizeof(float)));
+        CREATE_TRY(e->mem.alloc(&e->h_idx, e->idx_count, MEM_PINNED));
+        CREATE_TRY(e->mem.alloc(&e->h_noise, e->noise_count, MEM_PINNED));
     }
     e->stage_cap = 4096;
-    CREATE_TRY(hipHostMalloc((void**)&e->stage_rows, (size_t)e->stage_cap * R.width * sizeof(float)));
-    CREATE_TRY(hipHostMalloc((void**)&e->stage_slots, (size_t)e->stage_cap * sizeof(long long)));
-    CREATE_TRY(hipMalloc((void**)&e->d_stage_rows, (size_t)e->stage_cap * R.width * sizeof(float)));
-    CREATE_TRY(hipMalloc((void**)&e->d_stage_slots, (size_t)e->stage_cap * sizeof(long long)));
-    CREATE_TRY(hipHostMalloc((void**)&e->h_idx64, (size_t)h.batch_max * 16 * sizeof(long long)));
-    CREATE_TRY(hipMalloc((void**)&e->d_idx64, (size_t)h.batch_max * 16 * sizeof(long long)));
-    CREATE_TRY(hipMalloc((void**)&e->d, sizeof(EngineDesc)));
+    CREATE_TRY(e->mem.alloc(&e->stage_rows, (size_t)e->stage_cap * R.width, MEM_PINNED));
+    CREATE_TRY(e->mem.alloc(&e->stage_slots, (size_t)e->stage_cap, MEM_PINNED));
+    CREATE_TRY(e->mem.alloc(&e->d_stage_rows, (size_t)e->stage_cap * R.width, MEM_DEVICE));
+    CREATE_TRY(e->mem.alloc(&e->d_stage_slots, (size_t)e->stage_cap, MEM_DEVICE));
+    CREATE_TRY(e->mem.alloc(&e->h_idx64, (size_t)h.batch_max * 16, MEM_PINNED));
+    CREATE_TRY(e->mem.alloc(&e->d_idx64, (size_t)h.batch_max * 16, MEM_DEVICE));
+    CREATE_TRY(e->mem.alloc(&e->d, 1, MEM_DEVICE));
     CREATE_TRY(hipMemcpyAsync(e->d, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
     e->index.assign(P, 0);
     e->size.assign(P, 0);
@@ -1194,6 +1158,16 @@ extern "C" int frl_act_device(frl_engine* e, int net, int mode, int head, int us
     return launch_act(e, net, mode, head, use_target, n_rows, in_dim, in_dev, eps_dev, out_dev, logp_dev);
 }
 
+// The host-facing act entry points' device scratch (frl_act, frl_act_explore, frl_gail_reward): the input rows, and eps / out / logp
+// of out_n floats each.  Buffers only grow; one that could not holds nothing, and the next call allocates it again
+static int act_scratch(frl_engine* e, size_t in_n, size_t out_n) {
+    HIP_TRY(e->mem.grow(&e->d_act_in, e->act_in_cap, in_n, MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_act_eps, e->act_eps_cap, out_n, MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_act_out, e->act_out_cap, out_n, MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_act_logp, e->act_logp_cap, out_n, MEM_DEVICE));
+    return FRL_OK;
+}
+
 extern "C" int frl_act(frl_engine* e, int net, int mode, int head, int use_target, int n_rows, int in_dim,
                        const float* in_host, const float* eps_host, float* out_host, float* logp_host) {
     ENG(e);
@@ -1206,22 +1180,11 @@ extern "C" int frl_act(frl_engine* e, int net, int mode, int head, int use_targe
     const int nout = N.L[head * nl + nl - 1].n;
     const size_t rows = (size_t)e->h.P * n_rows;
     const size_t in_n = rows * in_dim, out_n = rows * nout;
-    if (in_n > e->act_in_cap) {
-        if (e->d_act_in) hipFree(e->d_act_in);
-        e->d_act_in = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->d_act_in, in_n * sizeof(float)));
-        e->act_in_cap = in_n;
-    }
-    if (out_n > e->act_out_cap) {
-        for (float** p : {&e->d_act_eps, &e->d_act_out, &e->d_act_logp}) { if (*p) hipFree(*p); *p = nullptr; }
-        HIP_TRY(hipMalloc((void**)&e->d_act_eps, out_n * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_out, out_n * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_logp, out_n * sizeof(float)));
-        e->act_out_cap = out_n;
-    }
+    int rc = act_scratch(e, in_n, out_n);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_act_in, in_host, in_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
     if (eps_host) HIP_TRY(hipMemcpyAsync(e->d_act_eps, eps_host, out_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    int rc = launch_act(e, net, mode, head, use_target, n_rows, in_dim, e->d_act_in, eps_host ? e->d_act_eps : nullptr,
+    rc = launch_act(e, net, mode, head, use_target, n_rows, in_dim, e->d_act_in, eps_host ? e->d_act_eps : nullptr,
                         e->d_act_out, logp_host ? e->d_act_logp : nullptr);
     if (rc) return rc;
     const int base_mode = mode & ~FRL_ACT_NO_OBSNORM;
@@ -1247,27 +1210,12 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * O, out_n = rows * nout;
-    if (in_n > e->act_in_cap) {
-        if (e->d_act_in) hipFree(e->d_act_in);
-        e->d_act_in = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->d_act_in, in_n * sizeof(float)));
-        e->act_in_cap = in_n;
-    }
-    if (out_n > e->act_out_cap) {
-        for (float** p : {&e->d_act_eps, &e->d_act_out, &e->d_act_logp}) { if (*p) hipFree(*p); *p = nullptr; }
-        HIP_TRY(hipMalloc((void**)&e->d_act_eps, out_n * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_out, out_n * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_logp, out_n * sizeof(float)));
-        e->act_out_cap = out_n;
-    }
+    int rc = act_scratch(e, in_n, out_n);
+    if (rc) return rc;
     if (out_n != e->ou_n) {                 // OU state of the host-facing entry point: one process per (learner, row, dimension)
-        if (e->d_ou) hipFree(e->d_ou);
-        e->d_ou = nullptr; e->ou_n = 0;
-        if (e->d_ou_flags) hipFree(e->d_ou_flags);
-        e->d_ou_flags = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->d_ou, out_n * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_ou_flags, rows));
-        HIP_TRY(hipMemsetAsync(e->d_ou, 0, out_n * sizeof(float), e->stream));
+        e->ou_n = 0;
+        HIP_TRY(e->mem.alloc_zero(&e->d_ou, out_n, e->stream));
+        HIP_TRY(e->mem.alloc(&e->d_ou_flags, rows, MEM_DEVICE));
         e->ou_n = out_n;
     }
     HIP_TRY(hipMemcpyAsync(e->d_act_in, obs_host, in_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
@@ -1280,7 +1228,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     ex.x = *x; ex.ou_state_dev = e->d_ou; ex.flags_dev = ended_host ? e->d_ou_flags : nullptr;
     ex.env_out_dev = e->d_act_eps;           // scratch of the same size, unused by a device_eps launch
     ex.device_eps = true;
-    int rc = launch_act(e, 0, mode, 0, 0, n_rows, O, e->d_act_in, nullptr, e->d_act_out, nullptr, &ex);
+    rc = launch_act(e, 0, mode, 0, 0, n_rows, O, e->d_act_in, nullptr, e->d_act_out, nullptr, &ex);
     if (rc) return rc;
     const size_t got = disc ? rows : out_n;
     HIP_TRY(hipMemcpyAsync(store_act_out, e->d_act_out, got * sizeof(float), hipMemcpyDeviceToHost, e->stream));
@@ -1508,23 +1456,31 @@ extern "C" int frl_per_enable(frl_engine* e, double alpha, double beta, double b
     for (int p = 0; p < e->h.P; ++p)
         if (e->size[p] != 0) return fail(FRL_ERR_STATE, "enable PER on an empty buffer (priorities are assigned by add)");
     const size_t nn = 2 * (size_t)e->h.capacity - 1, P = e->h.P;
-    HIP_TRY(hipMalloc((void**)&e->d_per_sum, P * nn * sizeof(double)));
-    HIP_TRY(hipMalloc((void**)&e->d_per_max, P * nn * sizeof(double)));
-    HIP_TRY(hipMemsetAsync(e->d_per_sum, 0, P * nn * sizeof(double), e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_per_max, 0, P * nn * sizeof(double), e->stream));
-    HIP_TRY(hipMalloc((void**)&e->d_size, 2 * P * sizeof(int)));
-    HIP_TRY(hipMalloc((void**)&e->d_stage_bucket, (2 * P + 1 + (size_t)e->stage_cap) * sizeof(int)));
-    HIP_TRY(hipHostMalloc((void**)&e->stage_bucket, (2 * P + 1 + (size_t)e->stage_cap) * sizeof(int)));
-    const size_t bm = (size_t)std::max(e->h.batch_max, 1);
-    HIP_TRY(hipMalloc((void**)&e->d_per_prio, P * bm * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&e->d_uniforms, P * bm * sizeof(double)));
-    if (!e->h.isw) {          // replay-only engine (Buffer.py's PER_Buffer on its own): sample rows, weights and TD errors still need a home
-        HIP_TRY(hipMalloc((void**)&e->h.isw, P * bm * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->h.td_err, P * bm * sizeof(float)));
-        e->idx_count = P * e->h.n_agents * bm;
-        HIP_TRY(hipMalloc((void**)&e->h.idx, e->idx_count * sizeof(int)));
-        HIP_TRY(hipHostMalloc((void**)&e->h_idx, e->idx_count * sizeof(int)));
-        HIP_TRY(hipMemcpy(e->d, &e->h, sizeof(EngineDesc), hipMemcpyHostToDevice));
+    const size_t bm = (size_t)std::max(e->h.batch_max, 1), bucket_n = 2 * P + 1 + (size_t)e->stage_cap;
+    const bool replay_only = !e->h.isw;       // Buffer.py's PER_Buffer on its own: sample rows, weights and TD errors still need a home
+    const size_t mark = e->mem.live();
+    auto allocate = [&]() -> int {
+        HIP_TRY(e->mem.alloc_zero(&e->d_per_sum, P * nn, e->stream));
+        HIP_TRY(e->mem.alloc_zero(&e->d_per_max, P * nn, e->stream));
+        HIP_TRY(e->mem.alloc(&e->d_size, 2 * P, MEM_DEVICE));
+        HIP_TRY(e->mem.alloc(&e->d_stage_bucket, bucket_n, MEM_DEVICE));
+        HIP_TRY(e->mem.alloc(&e->stage_bucket, bucket_n, MEM_PINNED));
+        HIP_TRY(e->mem.alloc(&e->d_per_prio, P * bm, MEM_DEVICE));
+        HIP_TRY(e->mem.alloc(&e->d_uniforms, P * bm, MEM_DEVICE));
+        if (replay_only) {
+            HIP_TRY(e->mem.alloc(&e->h.isw, P * bm, MEM_DEVICE));
+            HIP_TRY(e->mem.alloc(&e->h.td_err, P * bm, MEM_DEVICE));
+            e->idx_count = P * e->h.n_agents * bm;
+            HIP_TRY(e->mem.alloc(&e->h.idx, e->idx_count, MEM_DEVICE));
+            HIP_TRY(e->mem.alloc(&e->h_idx, e->idx_count, MEM_PINNED));
+            HIP_TRY(hipMemcpy(e->d, &e->h, sizeof(EngineDesc), hipMemcpyHostToDevice));
+        }
+        return FRL_OK;
+    };
+    rc = allocate();
+    if (rc) {                 // nothing of a failed call stays: a retry starts from empty slots
+        e->mem.release_to(mark);
+        return rc;
     }
     e->per_alpha = (float)alpha; e->per_beta = beta; e->per_beta_inc = beta_increment; e->per_eps = (float)epsilon;
     e->size_flushed.assign(P, 0);

@@ -90,20 +90,8 @@ extern "C" int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* r
     if (n_rows < 1 || !rows_host || !reward_out) return fail(FRL_ERR_INVALID, "bad argument");
     const int IN = h.rec.obs_dim[0] + h.rec.act_dim[0];
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * IN;
-    if (in_n > e->act_in_cap) {
-        if (e->d_act_in) hipFree(e->d_act_in);
-        e->d_act_in = nullptr; e->act_in_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->d_act_in, in_n * sizeof(float)));
-        e->act_in_cap = in_n;
-    }
-    if (rows > e->act_out_cap) {
-        for (float** p : {&e->d_act_eps, &e->d_act_out, &e->d_act_logp}) { if (*p) hipFree(*p); *p = nullptr; }
-        e->act_out_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->d_act_eps, rows * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_out, rows * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&e->d_act_logp, rows * sizeof(float)));
-        e->act_out_cap = rows;
-    }
+    int rc = act_scratch(e, in_n, rows);
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_act_in, rows_host, in_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(gail_forward_kernel, dim3((n_rows + h.rc - 1) / h.rc, h.P), dim3(256), e->lds_bytes, e->stream, e->d, gp ? 2 : 1, n_rows,
                        (const float*)e->d_act_in, e->d_act_out);

@@ -2,20 +2,8 @@
 
 static int ppo_scratch(frl_engine* e, int T, int k_epochs, int n_mb) {
     const size_t P = e->h.P;
-    const size_t need = P * ((size_t)5 * T + (size_t)k_epochs * n_mb * 2);
-    if (need > e->ppo_cap) {
-        if (e->d_ppo) hipFree(e->d_ppo);
-        e->d_ppo = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->d_ppo, need * sizeof(float)));
-        e->ppo_cap = need;
-    }
-    const size_t pneed = P * (size_t)k_epochs * T;
-    if (pneed > e->perm_cap) {
-        if (e->d_perm) hipFree(e->d_perm);
-        e->d_perm = nullptr;
-        HIP_TRY(hipMalloc((void**)&e->d_perm, pneed * sizeof(int)));
-        e->perm_cap = pneed;
-    }
+    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, P * ((size_t)5 * T + (size_t)k_epochs * n_mb * 2), MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, P * (size_t)k_epochs * T, MEM_DEVICE));
     return FRL_OK;
 }
 

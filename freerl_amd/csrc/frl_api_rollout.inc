@@ -2,6 +2,7 @@
 #include "envpool.hpp"
 
 struct frl_envpool {
+    HostMem mem;                // owns the pinned and device buffers below (envpool_bind allocates, envpool_free_buffers releases)
     frl::EnvPool* pool = nullptr;
     // pinned staging (allocated lazily by frl_rollout on the engine's device)
     float* obs = nullptr;       // [n][O] what the policy sees
@@ -68,20 +69,9 @@ extern "C" int frl_envpool_create_callback(int n_envs, int obs_dim, int act_dim,
 }
 
 static void envpool_free_buffers(frl_envpool* p) {
-    if (!p->pinned) return;
-    for (float* q : {p->obs, p->next_obs, p->obs_next, p->act_out, p->eps, p->env_act, p->reward, p->logp}) if (q) hipHostFree(q);
-    if (p->term) hipHostFree(p->term);
-    if (p->trunc) hipHostFree(p->trunc);
-    for (float* q : {p->d_obs, p->d_out, p->d_eps, p->d_logp, p->d_obs_cur, p->d_store, p->d_env, p->d_ou}) if (q) hipFree(q);
-    if (p->blk) hipHostFree(p->blk);
-    if (p->d_blk) hipFree(p->d_blk);
-    if (p->done_flag) hipHostFree(p->done_flag);
-    if (p->go_flag) hipHostFree(p->go_flag);
+    p->mem.release_all();
     if (p->stream2) hipStreamDestroy(p->stream2);
-    if (p->d_dev) hipFree(p->d_dev);
-    p->stream2 = nullptr; p->d_dev = nullptr;
-    p->blk = nullptr; p->d_blk = nullptr;
-    p->d_obs_cur = p->d_store = p->d_env = p->d_ou = nullptr;
+    p->stream2 = nullptr;
     p->pinned = false;
 }
 
@@ -133,26 +123,25 @@ extern "C" int frl_envpool_step(frl_envpool* p, const float* actions, float* nex
     return FRL_OK;
 }
 
-static int envpool_bind(frl_engine* e, frl_envpool* p, int a_out) {
-    if (p->pinned) return FRL_OK;
+static int envpool_alloc(frl_engine* e, frl_envpool* p, int a_out) {
     const size_t n = p->pool->n, O = p->pool->spec.obs_dim,
                  A = std::max(std::max(p->pool->spec.act_dim, a_out), p->pool->spec.discrete ? p->pool->spec.n_actions : 1);
-    HIP_TRY(hipHostMalloc((void**)&p->obs, n * O * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->next_obs, n * O * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->obs_next, n * O * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->act_out, n * A * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->eps, n * A * sizeof(float)));
+    HIP_TRY(p->mem.alloc(&p->obs, n * O, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->next_obs, n * O, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->obs_next, n * O, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->act_out, n * A, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->eps, n * A, MEM_PINNED));
     // env_act, blk and done_flag are also read / written by kernels in place (the folded DQN step): fine-grained coherent whatever
     // HIP_HOST_COHERENT says
-    HIP_TRY(hipHostMalloc((void**)&p->env_act, n * A * sizeof(float), hipHostMallocCoherent | hipHostMallocMapped));
-    HIP_TRY(hipHostMalloc((void**)&p->reward, n * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->term, n));
-    HIP_TRY(hipHostMalloc((void**)&p->trunc, n));
-    HIP_TRY(hipMalloc((void**)&p->d_obs, n * O * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_out, n * A * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_eps, n * A * sizeof(float)));
-    HIP_TRY(hipHostMalloc((void**)&p->logp, n * A * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_logp, n * A * sizeof(float)));
+    HIP_TRY(p->mem.alloc(&p->env_act, n * A, MEM_PINNED, hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(p->mem.alloc(&p->reward, n, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->term, n, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->trunc, n, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->d_obs, n * O, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->d_out, n * A, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->d_eps, n * A, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->logp, n * A, MEM_PINNED));
+    HIP_TRY(p->mem.alloc(&p->d_logp, n * A, MEM_DEVICE));
     // the one block a vector step uploads, sections 16-byte aligned
     const size_t P = e->h.P;
     auto up16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
@@ -162,24 +151,30 @@ static int envpool_bind(frl_engine* e, frl_envpool* p, int a_out) {
     p->off_rew = up16(p->off_onext + n * O * sizeof(float));
     p->off_flags = up16(p->off_rew + n * sizeof(float));
     p->blk_bytes = up16(p->off_flags + n);
-    HIP_TRY(hipHostMalloc((void**)&p->blk, p->blk_bytes, hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(p->mem.alloc(&p->blk, p->blk_bytes, MEM_PINNED, hipHostMallocCoherent | hipHostMallocMapped));
     std::memset(p->blk, 0, p->blk_bytes);
-    HIP_TRY(hipMalloc((void**)&p->d_blk, p->blk_bytes));
-    HIP_TRY(hipHostMalloc((void**)&p->done_flag, 64, hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(p->mem.alloc_zero(&p->d_blk, p->blk_bytes, e->stream));
+    HIP_TRY(p->mem.alloc(&p->done_flag, 64 / sizeof(int), MEM_PINNED, hipHostMallocCoherent | hipHostMallocMapped));
     *p->done_flag = 0;
-    HIP_TRY(hipHostMalloc((void**)&p->go_flag, 64, hipHostMallocCoherent | hipHostMallocMapped));
+    HIP_TRY(p->mem.alloc(&p->go_flag, 64 / sizeof(int), MEM_PINNED, hipHostMallocCoherent | hipHostMallocMapped));
     *p->go_flag = 0;
     HIP_TRY(hipStreamCreateWithFlags(&p->stream2, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void**)&p->d_dev, 64));
-    HIP_TRY(hipMalloc((void**)&p->d_obs_cur, n * O * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_store, n * A * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_env, n * A * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&p->d_ou, n * A * sizeof(float)));
-    HIP_TRY(hipMemsetAsync(p->d_ou, 0, n * A * sizeof(float), e->stream));
-    HIP_TRY(hipMemsetAsync(p->d_blk, 0, p->blk_bytes, e->stream));
+    HIP_TRY(p->mem.alloc(&p->d_dev, 64 / sizeof(int), MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->d_obs_cur, n * O, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->d_store, n * A, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc(&p->d_env, n * A, MEM_DEVICE));
+    HIP_TRY(p->mem.alloc_zero(&p->d_ou, n * A, e->stream));
     p->bound_P = (int)P;
-    p->pinned = true;
     return FRL_OK;
+}
+
+// The pool's staging on the engine's device, allocated by the first rollout; a bind that fails half-way leaves nothing behind
+static int envpool_bind(frl_engine* e, frl_envpool* p, int a_out) {
+    if (p->pinned) return FRL_OK;
+    const int rc = envpool_alloc(e, p, a_out);
+    if (rc) envpool_free_buffers(p);
+    p->pinned = rc == FRL_OK;
+    return rc;
 }
 
 // One vector step's upload + commit on the device path: the host has filled the block (scale, rows, env outputs, flags).
