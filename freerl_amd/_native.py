@@ -27,6 +27,8 @@ FRL_COMM_MAX_VALUES = 64
 ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO, ALGO_SAC_DISCRETE, ALGO_REINFORCE, ALGO_ENVELOPE_DQN = -1, 0, 1, 2, 3, 4, 5, 6, 7, 8
 ALGO_ENVELOPE_DDPG = 9
 ALGO_GAIL = 10
+ALGO_MAPPO, ALGO_IPPO = 11, 12
+LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
@@ -99,6 +101,15 @@ class GailArgs(C.Structure):
     _fields_ = [("n_expert", C.c_int), ("n_policy", C.c_int), ("gp", C.c_int), ("gp_weight", C.c_float), ("lr", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("idx", C.POINTER(C.c_int64)),
                 ("policy_rows", C.POINTER(C.c_float)), ("out", C.POINTER(C.c_float)), ("idx_out", C.POINTER(C.c_int64))]
+
+
+class MappoArgs(C.Structure):
+    _fields_ = [("horizon", C.c_int), ("minibatch", C.c_int), ("k_epochs", C.c_int),
+                ("gamma", C.c_float), ("lmbda", C.c_float), ("clip", C.c_float), ("ent_coef", C.c_float),
+                ("actor_lr", C.c_float), ("critic_lr", C.c_float), ("adam_eps", C.c_float), ("clip_norm", C.c_float),
+                ("adv_norm", C.c_int), ("value_clip", C.c_int), ("loss_kind", C.c_int), ("huber_delta", C.c_float),
+                ("perms", C.POINTER(C.c_int64)), ("adv_out", C.POINTER(C.c_float)), ("vtarget_out", C.POINTER(C.c_float)),
+                ("loss_trace_out", C.POINTER(C.c_float))]
 
 
 class ExploreArgs(C.Structure):
@@ -188,6 +199,8 @@ SIGNATURES = {
     "frl_envelope_ddpg_learn": (_i, [_vp, _P(EnvelopeDdpgArgs)]),
     "frl_gail_learn": (_i, [_vp, _P(GailArgs)]),
     "frl_gail_reward": (_i, [_vp, _i, _i, _fp, _fp]),
+    "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
+    "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

@@ -42,6 +42,7 @@
 #include "kernels_envelope.hip"
 #include "kernels_envelope_ddpg.hip"
 #include "kernels_gail.hip"
+#include "kernels_mappo.hip"
 #endif
 
 using namespace frl;
@@ -138,8 +139,11 @@ static const AlgoTraits kAlgo[] = {
     {"envelope DQN",   "frl_envelope_learn",      "FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives",          true,  true,  true,  true,  true,  false, false},
     {"envelope DDPG",  "frl_envelope_ddpg_learn", "FRL_ACT_TANHHEAD on net 0 with [obs | preference]",                            false, false, true,  true,  false, true,  false},
     {"GAIL",           "frl_gail_learn",          "FRL_ACT_RAW on [obs | act]: the discriminator's logits; rewards: frl_gail_reward",   false, false, false, true,  false, false, false},
+    {"MAPPO",          "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
+    {"IPPO",           "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
 };
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_GAIL - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_IPPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 static const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // An entry point called on an engine of an algorithm it does not serve: the call, the algorithm and the entry point that updates it
@@ -340,13 +344,13 @@ static void build_record(RecordDesc& R, const frl_config& c) {
 
 static int lds_bytes_for(const EngineDesc& h, int rc) {
     const int xp = h.lds_kin_pad + 4, hp = h.hidden + 4, op = h.lds_out_pad + 4, ap = h.lds_act_pad;
-    long long fl = (long long)rc * (xp + h.lds_hbufs * hp + op + 2 * ap) + h.lds_batch_pad + 8;
+    long long fl = (long long)rc * (xp + h.lds_hbufs * hp + op + 2 * ap + h.lds_row_extra) + h.lds_batch_pad + 8;
     return (int)(fl * 4);
 }
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 105; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward
+extern "C" int frl_version(void) { return 106; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -380,9 +384,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     const frl_config& c = *cfg;
     if (c.n_learners < 1) return fail(FRL_ERR_INVALID, "n_learners must be >= 1");
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
-    if (c.algo != FRL_ALGO_MADDPG && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
+    if (c.algo != FRL_ALGO_MADDPG && !is_mappo(c.algo) && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_GAIL) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_IPPO) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -416,6 +420,19 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;
     h.n_discrete = (T.discrete_head || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
+    if (is_mappo(c.algo)) {
+        // what kernels_mappo.hip handles (the LayerNorm mask is 256 bits per row; one thread per row walks a discrete head)
+        int amax = 0, lp_cols = 0;
+        for (int j = 0; j < c.n_agents; ++j) { amax = std::max(amax, c.act_dim[j]); lp_cols += c.discrete ? 1 : c.act_dim[j]; }
+        if (h.hidden > 256) return refuse("%s: hidden %d > 256 does not fit the row-chunk layout with LayerNorm", T.name, h.hidden);
+        if (c.discrete && amax > kSacdMaxActions) return refuse("%s: %d actions > %d head columns", T.name, amax, kSacdMaxActions);
+        if (c.hidden_act != FRL_ACT_RELU) return refuse("%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
+        if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0)
+            return refuse("%s: twin_critic, dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
+        if (c.extra_cols != lp_cols + c.n_agents)
+            return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns", T.name, c.extra_cols, lp_cols, c.n_agents);
+        if (c.discrete) h.n_discrete = amax;      // (a flag to these kernels: an agent's action count is its actor's head width)
+    }
     h.reward_dim = 1;
     if (T.vector_reward) {
         if (c.reward_dim < 0) return refuse("%s: reward_dim %d must be >= 1 (0 means 1)", T.name, c.reward_dim);
@@ -465,6 +482,14 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     } else if (c.algo == FRL_ALGO_REINFORCE) {
         h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
         build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
+    } else if (is_mappo(c.algo)) {
+        // Actor / Actor_discrete (MAPPO.py:123-186 = IPPO.py:57-116) on the agent's own observation; Critic on the global observation
+        // (MAPPO.py:188-218) or on the agent's own (IPPO.py:118-153, with the agent's own index: its class counter is a defect)
+        h.n_nets = 2 * c.n_agents;
+        for (int j = 0; j < c.n_agents; ++j) {
+            build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[j]);
+            build_net(h.net[2 * j + 1], {{H, c.algo == FRL_ALGO_MAPPO ? R.obs_total : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
+        }
     } else if (c.algo == FRL_ALGO_PPO) {
         h.n_nets = 2;
         if (c.discrete && c.actor_dist == 2) h.cat_logits = 1;     // PPO_file/PPO.py:78-90,176,257: raw logits into Categorical(logits=)
@@ -519,6 +544,10 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
     if (c.algo == FRL_ALGO_GAIL) h.lds_act_pad = std::max(h.lds_act_pad, ((H + 31) / 32 + 3) / 4 * 4);             // abuf / dabuf: a row's slope bits of h1 / h2
+    if (is_mappo(c.algo)) {
+        if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, outp);      // logits' delta staging
+        h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
+    }
     // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
     // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
     // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
@@ -531,10 +560,17 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
     if (c.algo != FRL_ALGO_PPO && h.rc == 64 && (long long)h.P * ((h.batch_max + 63) / 64) < 512) h.rc = 32;
+    // MAPPO / IPPO: one persistent workgroup per (learner, agent, net), like PPO's: the largest chunk one workgroup's LDS holds
+    if (is_mappo(c.algo)) {
+        h.rc = 64;
+        while (h.rc > 16 && lds_bytes_for(h, h.rc) > 160 * 1024) h.rc /= 2;
+    }
     {   // developer knob: rows per workgroup (16 / 32 / 64 / 128)
         const int v = env_int("FRL_RC", 0);
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
+    if (is_mappo(c.algo) && lds_bytes_for(h, h.rc) > 160 * 1024)
+        return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns)", T.name, lds_bytes_for(h, h.rc), kin);
     if (lds_bytes_for(h, h.rc) > 160 * 1024) return refuse("network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc));
     if (T.two_wg && lds_bytes_for(h, h.rc) > 80 * 1024)
         return refuse("%s: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", T.name, lds_bytes_for(h, h.rc));
@@ -560,7 +596,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             const long long cost = ((units * s + slots - 1) / slots) * cps;
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; h.cps = cps; }
         }
-        if (c.algo == FRL_ALGO_PPO) h.cps = 1;
+        if (c.algo == FRL_ALGO_PPO || is_mappo(c.algo)) h.cps = 1;
         {   // developer knob
             const int v = env_int("FRL_CPS", 0);
             if (v >= 1 && n_chunks % v == 0) h.cps = v;
@@ -698,7 +734,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         for (const void* k : {(const void*)dqn_grad_kernel, (const void*)ac_critic_kernel, (const void*)ac_actor_kernel, (const void*)sacd_critic_kernel, (const void*)sacd_actor_kernel,
                               (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
                               (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
-                              (const void*)ppo_update_kernel})
+                              (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -1117,6 +1153,12 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     a.normalize = (!no_norm && e->h.obs_norm_on && (e->h.n_agents == 1 || net % 2 == 0) && in_dim == e->h.rec.obs_dim[agent]) ? 1 : 0;
     a.in = in_dev; a.eps = eps_dev; a.out = out_dev; a.out_logp = logp_dev;
     if (build_only) { *build_only = a; return FRL_OK; }
+    if (is_mappo(e->h.algo)) {        // the normalised forward (kernels_mappo.hip) in front of act_kernel's epilogue
+        if (mode == FRL_ACT_SAC_SAMPLE || ex) return fail(FRL_ERR_INVALID, "a %s engine acts through FRL_ACT_RAW, _TANHHEAD, _ARGMAX, _PPO_SAMPLE or _CAT_SAMPLE", algo_traits(e->h.algo).name);
+        hipLaunchKernelGGL(mappo_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
     if (e->h.algo == ALGO_GAIL) {      // LeakyReLU hidden layers: the discriminator's own forward kernel (kernels_gail.hip), logits of the online net
         if (mode != FRL_ACT_RAW || use_target || ex) return fail(FRL_ERR_INVALID, "a GAIL engine acts through FRL_ACT_RAW on its online net (the logits)");
         hipLaunchKernelGGL(gail_forward_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, 0, n_rows, in_dev, out_dev);
@@ -1205,6 +1247,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
+    if (is_mappo(h.algo)) return wrong_engine(h, "frl_act_explore");
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
@@ -1390,6 +1433,7 @@ extern "C" int frl_timer_stop(frl_engine* e, float* ms_out) {
 extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
+    if (is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
     if (on && e->h.net[0].frag) {
         // Batch_ObsNorm belongs to the row-chunk family: an engine created for the register-chained kernels (parameters in
         // fragment-image order) moves over for good — every parameter array back to Wk, through a scratch copy
@@ -1583,5 +1627,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_envelope.inc"
 #include "frl_api_envelope_ddpg.inc"
 #include "frl_api_gail.inc"
+#include "frl_api_mappo.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

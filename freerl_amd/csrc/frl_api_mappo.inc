@@ -1,0 +1,93 @@
+// MAPPO / IPPO entry points (included at the end of frl_api.hip).
+
+extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm) {
+    ENG(e);
+    if (!is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_net_norm_set");
+    e->h.feature_norm = feature_norm ? 1 : 0;
+    e->h.layer_norm = layer_norm ? 1 : 0;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
+    return FRL_OK;
+}
+
+extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
+    ENG(e);
+    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+    const EngineDesc& h = e->h;
+    if (!is_mappo(h.algo)) return wrong_engine(h, "frl_mappo_learn");
+    const int T = args->horizon, mb = args->minibatch, K = args->k_epochs, n = h.n_agents;
+    if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
+    if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
+    if (K < 1) return fail(FRL_ERR_INVALID, "k_epochs must be >= 1");
+    if (args->loss_kind != FRL_LOSS_MSE && args->loss_kind != FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "loss_kind %d (FRL_LOSS_MSE or FRL_LOSS_HUBER)", args->loss_kind);
+    if (args->loss_kind == FRL_LOSS_HUBER && !(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "FRL_LOSS_HUBER needs huber_delta > 0");
+    const int n_mb = (T + mb - 1) / mb;
+    const size_t P = h.P, U = P * n;
+    std::vector<int> perm;
+    if (args->perms) {
+        perm.resize(U * (size_t)K * T);
+        for (size_t i = 0; i < perm.size(); ++i) {
+            const int64_t v = args->perms[i];
+            if (v < 0 || v >= T) return fail(FRL_ERR_INVALID, "permutation entry %lld outside [0,%d)", (long long)v, T);
+            perm[i] = (int)v;
+        }
+    }
+    int rc = flush_stage(e);
+    if (rc) return rc;
+    const size_t trace_n = U * (size_t)K * n_mb * 2;
+    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, 7 * U * T + trace_n, MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, U * (size_t)K * T, MEM_DEVICE));
+    // permutations: the caller's np.random.permutation draws, one per (agent, epoch) in agent-major order (MAPPO.py:391-395,
+    // IPPO.py:254,275-277), else ppo_perm_kernel's with a unit = (learner, agent); horizons beyond 8192 rows: a host Fisher-Yates
+    int Tpad = 2;
+    while (Tpad < T) Tpad <<= 1;
+    const bool dev_perm = !args->perms && Tpad <= 8192;
+    if (dev_perm) {
+        hipLaunchKernelGGL(ppo_perm_kernel, dim3(K, (unsigned)U), dim3(256), (size_t)Tpad * sizeof(unsigned long long), e->stream,
+                           e->d_perm, T, Tpad, (unsigned long long)(++e->rng_counter), (unsigned long long)h.seed);
+    } else {
+        if (!args->perms) {
+            perm.resize(U * (size_t)K * T);
+            unsigned long long s = h.seed ^ (0xD1B54A32D192ED03ull * (++e->rng_counter));
+            for (size_t blk = 0; blk < U * (size_t)K; ++blk) {
+                int* q = perm.data() + blk * T;
+                for (int i = 0; i < T; ++i) q[i] = i;
+                for (int i = T - 1; i > 0; --i) std::swap(q[i], q[(int)(splitmix64(s) % (unsigned long long)(i + 1))]);
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_perm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    }
+    MappoArgs a;
+    memset(&a, 0, sizeof a);
+    a.horizon = T; a.minibatch = mb; a.k_epochs = K; a.adv_norm = args->adv_norm ? 1 : 0;
+    a.huber = args->loss_kind == FRL_LOSS_HUBER ? 1 : 0;
+    a.huber_delta = args->huber_delta;
+    a.gamma = args->gamma; a.lmbda = args->lmbda; a.clip = args->clip; a.ent_coef = args->ent_coef;
+    a.actor_lr = args->actor_lr; a.critic_lr = args->critic_lr;
+    a.adam_eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f;
+    a.beta1 = 0.9f; a.beta2 = 0.999f;
+    a.clip_norm = args->clip_norm;
+    float* q = e->d_ppo;
+    a.td = q; q += U * T;
+    a.advd = q; q += U * T;
+    a.vs = q; q += U * T;
+    a.adv_seq = q; q += U * T;
+    a.adv_raw = q; q += U * T;
+    a.adv = q; q += U * T;
+    a.vtarget = q; q += U * T;
+    a.trace = q;
+    a.perm = e->d_perm;
+    hipLaunchKernelGGL(mappo_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    hipLaunchKernelGGL(gae_dense_kernel, dim3((unsigned)U), dim3(256), 0, e->stream, a.td, a.advd, T, args->gamma * args->lmbda, a.adv_seq);
+    hipLaunchKernelGGL(mappo_adv_kernel, dim3(h.P), dim3(256), 0, e->stream, e->d, a);
+    hipLaunchKernelGGL(mappo_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));      // `perm` (pageable) must outlive the copy
+    ++e->param_version;
+    if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, U * T * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, U * T * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, trace_n * sizeof(float), hipMemcpyDeviceToHost));
+    // Buffer_for_PPO.clear() (MAPPO.py:481-482, IPPO.py:321-322): counters only
+    for (int p = 0; p < h.P; ++p) { e->index[p] = 0; e->size[p] = 0; }
+    return FRL_OK;
+}

@@ -11,7 +11,7 @@ constexpr int kMaxNets = 2 * kMaxAgents;
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: the GAIL discriminator's hidden layers only)
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
-                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10 };
+                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -71,6 +71,10 @@ constexpr int wide_lds_floats() { return 8 * 8 * 256 + 2 * 8 * 256 + 2 * kWideSl
 // ... at hidden 256 (device/chain_wide16.hpp: every layer streamed)
 constexpr int kWide16ScratchPerRowHost = kWideApitch + 4 + 32 + 5 * 256;      // Wide16Scratch + the actor stage's third critic tensor
 constexpr int wide16_lds_floats_host() { return 16384 + 2 * 16 * 256 + 3 * 16 * 256 + 256 + 256 + 32 + 32 + 192; }
+
+// MAPPO / IPPO's LayerNorm case (device/mappo.hpp: carve_mappo): per chunk row a third hidden buffer, two rstd and the two hidden layers' mask words
+constexpr int kMappoMaskWords = 8;       // 32-bit words of ReLU mask bits per row and hidden layer: hidden <= 256
+constexpr int mappo_row_extra(int hidden) { return (hidden + 4) + 2 + 2 * kMappoMaskWords + 2; }
 
 // float index of W[out n][in k] inside a layer's weight block (host and device)
 #if defined(__HIPCC__)
@@ -188,6 +192,11 @@ struct EngineDesc {
     float* gail_rows;     // [P][batch_max][obs_dim + act_dim] the policy rows of the current frl_gail_learn call
     float* gail_part;     // [P][S][8] per-workgroup partial sums (device/gail.hpp: GailPart)
     float* gail_out;      // [P][8] what frl_gail_args::out returns, written by gail_stats_kernel
+    // MAPPO / IPPO (kernels_mappo.hip): F.layer_norm (no affine, biased variance, eps 1e-5) over the input row before l1 and over each
+    // hidden row after its ReLU (MAPPO_file/MAPPO.py:204-216); both off at create, switched by frl_net_norm_set
+    int feature_norm, layer_norm;
+    int lds_row_extra;    // floats per chunk row behind carve_lds()'s region: the LayerNorm backward's third hidden buffer, rstd and the
+                          // ReLU mask bits of both hidden layers (device/mappo.hpp: carve_mappo); 0 on every other engine
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -177,6 +177,27 @@ __global__ void gail_disc_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, 
 __global__ void gail_stats_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, int ns);
 __global__ void gail_forward_kernel(const EngineDesc* __restrict__ Dp, int mode, int n_rows, const float* __restrict__ in, float* __restrict__ out);
 
+// kernels_mappo.hip: MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py): a unit = (learner, agent); nets 2i / 2i+1 = agent i's actor / critic
+struct MappoArgs {
+    int horizon, minibatch, k_epochs, adv_norm;
+    int huber;            // critic loss: 0 F.mse_loss, 1 huber_loss(e, huber_delta).mean()
+    float gamma, lmbda, clip, ent_coef;
+    float actor_lr, critic_lr, adam_eps, beta1, beta2, clip_norm, huber_delta;
+    float* td;            // [P * n][T] td_delta of agent i's critic, reward and done columns
+    float* advd;          // [P * n][T] agent i's adv_done column, dense (gae_dense_kernel reads it)
+    float* vs;            // [P * n][T] V_i(s)
+    float* adv_seq;       // [P * n][T] the scan's output
+    float* adv_raw;       // [P][T][n] advantages before normalisation
+    float* adv;           // [P][T][n] advantages the surrogate uses
+    float* vtarget;       // [P][T][n]
+    float* trace;         // [P][n][k_epochs * n_mb][2] (actor, critic) loss of every step
+    const int* perm;      // [P][n][k_epochs][T]
+};
+__global__ void mappo_values_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_adv_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

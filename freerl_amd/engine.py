@@ -448,6 +448,39 @@ class Engine:
         N.check(self._L.frl_gail_reward(self._h, int(gp), x.shape[1], _fp(x), _fp(out)))
         return out
 
+    def net_norm_set(self, feature_norm, layer_norm):
+        """trick['feature_norm'] / trick['LayerNorm'] of a MAPPO / IPPO engine (frl_net_norm_set); both off at create."""
+        N.check(self._L.frl_net_norm_set(self._h, int(bool(feature_norm)), int(bool(layer_norm))))
+
+    def mappo_learn(self, horizon, minibatch, k_epochs, *, gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8, clip_norm=0.5,
+                    adv_norm=False, value_clip=False, huber_delta=None, perms=None, want_trace=False, want_adv=False):
+        """MAPPO.learn / IPPO.learn for every learner (frl_mappo_learn).  perms [P][n_agents][k_epochs][horizon] (None: drawn on the
+        device); huber_delta None: F.mse_loss.  -> dict with `trace` [P][n_agents][k_epochs * n_mb][2] and / or `adv` (before
+        normalisation) and `v_target`, both [P][horizon][n_agents]."""
+        a = N.MappoArgs()
+        a.horizon, a.minibatch, a.k_epochs = int(horizon), int(minibatch), int(k_epochs)
+        a.gamma, a.lmbda, a.clip, a.ent_coef = gamma, lmbda, clip, ent_coef
+        a.actor_lr, a.critic_lr, a.adam_eps, a.clip_norm = actor_lr, critic_lr, adam_eps, clip_norm
+        a.adv_norm, a.value_clip = int(bool(adv_norm)), int(bool(value_clip))
+        if huber_delta is not None:
+            a.loss_kind, a.huber_delta = N.LOSS_HUBER, float(huber_delta)
+        keep = []
+        if perms is not None:
+            pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, self.n_agents, int(k_epochs), int(horizon))
+            keep.append(pm)
+            a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
+        n_mb = (int(horizon) + int(minibatch) - 1) // int(minibatch)
+        out = {}
+        if want_trace:
+            out["trace"] = np.zeros((self.P, self.n_agents, int(k_epochs) * n_mb, 2), dtype=F32)
+            a.loss_trace_out = _fp(out["trace"])
+        if want_adv:
+            out["adv"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
+            out["v_target"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
+            a.adv_out, a.vtarget_out = _fp(out["adv"]), _fp(out["v_target"])
+        N.check(self._L.frl_mappo_learn(self._h, C.byref(a)))
+        return out
+
     # ------------------------------------------------------------------ timing
     def ppo_work(self, horizon, k_epochs):
         fl, by = C.c_double(0), C.c_double(0)

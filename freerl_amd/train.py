@@ -33,6 +33,11 @@ _REPLAY = [("buffer_size", int, int(1e6)), ("batch_size", int, 256)]
 _GAUSS = [("gauss_sigma", float, 0.1), ("gauss_scale", float, 1), ("gauss_init_scale", float, None),
           ("gauss_final_scale", float, 0.0)]
 
+_MAPPO = [("N", int, None), ("horizon", int, 256), ("clip_param", float, 0.2), ("K_epochs", int, 15), ("entropy_coefficient", float, 0.01),
+          ("minibatch_size", int, 256), ("lmbda", float, 0.95), ("huber_delta", float, 10.0)]
+_MAPPO_TRICK = {"adv_norm": False, "ObsNorm": False, "reward_norm": False, "reward_scaling": False, "orthogonal_init": False,
+                "adam_eps": False, "lr_decay": False, "ValueClip": False, "huber_loss": False, "LayerNorm": False, "feature_norm": False}
+
 FLAGS = {
     "dqn": dict(env_name="BipedalWalker-v3", policy_name="DQN", device="cuda", is_dis_to_con=True,
                 flags=_COMMON + _REPLAY + [("Qnet_lr", float, 1e-3), ("epsilon", float, 0.1)],
@@ -70,6 +75,13 @@ FLAGS = {
                    flags=_COMMON + _AC + _REPLAY + _GAUSS + [("N", int, 5)],
                    overrides=dict(seed=100, max_episodes=600, save_freq=600 // 4, gamma=0.95, gauss_sigma=1,
                                   gauss_init_scale=1), trick=None),
+    # MAPPO_file/MAPPO.py:533-571 and IPPO.py:409-449: the two scripts' own defaults
+    "mappo": dict(env_name="simple_spread_v3", policy_name="MAPPO", device="cuda", is_dis_to_con=False,
+                  flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=200, save_freq=5000 // 4, start_steps=0,
+                                                               learn_steps_interval=0, gamma=0.95), trick=dict(_MAPPO_TRICK)),
+    "ippo": dict(env_name="simple_adversary_v3", policy_name="IPPO", device="cuda", is_dis_to_con=False,
+                 flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=5000, save_freq=5000 // 4, start_steps=0,
+                                                              learn_steps_interval=0), trick=dict(_MAPPO_TRICK)),
 }
 
 
@@ -87,6 +99,8 @@ def build_parser(algo):
         p.add_argument("--realize", type=dict, default={"clip_double": True, "policy_noise": True, "twin_delay": True})
     if algo == "ppo":
         p.add_argument("--beta", type=bool, default=False)
+    if algo in ("mappo", "ippo"):          # (type=bool as in the scripts: any non-empty string is True)
+        p.add_argument("--continuous_actions", type=bool, default=(algo == "mappo"))
     p.add_argument("--device", type=str, default=spec["device"])
     # additions of this build (not in the reference)
     p.add_argument("--results_root", type=str, default=os.path.join(os.getcwd(), "results"))
@@ -511,6 +525,94 @@ def _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log=
     return dict(returns=arr, steps=step, seconds=time.time() - t0)
 
 
+def _mappo_policy_name(args, base):
+    """MAPPO.py:573-588 / IPPO.py:451-465: the policy name decides the tricks — `MAPPO` switches all on but reward_norm and lr_decay,
+    `MAPPO_simple` all off"""
+    t = args.trick
+    if t["reward_norm"] and t["reward_scaling"]:
+        raise ValueError("reward_norm and reward_scaling are mutually exclusive")
+    if args.policy_name == base or (t["lr_decay"] is False and all(v for k, v in t.items() if k not in ("reward_norm", "lr_decay"))):
+        args.policy_name = base
+        for k in t:
+            t[k] = k not in ("reward_norm", "lr_decay")
+    if args.policy_name == base + "_simple" or not any(t.values()):
+        args.policy_name = base + "_simple"
+        for k in t:
+            t[k] = False
+
+
+def _run_mappo(args, env, policy, dim_info, max_action, is_continue, model_dir, writer, log=print):
+    """MAPPO.py:617-700 = IPPO.py:495-579: dict-in/dict-out parallel env, one learn() every `horizon` steps; ObsNorm, reward_norm and
+    reward_scaling live here, per agent"""
+    import pickle
+    agents = list(env.agents)
+    base = "MAPPO" if args.policy_name.startswith("MAPPO") else "IPPO"
+    episode_num, step = 0, 0
+    episode_reward = {a: 0 for a in agents}
+    returns = {a: [] for a in agents}
+    obs, _ = env.reset(seed=args.seed)
+    for a in agents:
+        env.action_space(a).seed(seed=args.seed)
+    t = args.trick
+    if t["ObsNorm"]:
+        obs_norm = {a: _norm.Normalization(shape=dim_info[a][0]) for a in agents}
+        obs = {a: obs_norm[a](obs[a]) for a in agents}
+    if t["reward_norm"]:
+        reward_norm = {a: _norm.Normalization(shape=1) for a in agents}
+    elif t["reward_scaling"]:
+        reward_norm = {a: _norm.RewardScaling(shape=1, gamma=args.gamma) for a in agents}
+    t0 = time.time()
+    while episode_num < args.max_episodes:
+        step += 1
+        action, action_log_pi = policy.select_action(obs)
+        if is_continue:
+            env_action = {a: (np.clip(action[a] * max_action, -max_action, max_action, dtype=np.float32) + 1) / 2 for a in agents}
+        else:
+            env_action = {a: int(action[a]) for a in agents}
+        next_obs, reward, terminated, truncated, _ = env.step(env_action)
+        if t["ObsNorm"]:
+            next_obs = {a: obs_norm[a](next_obs[a]) for a in agents}
+        done = {a: terminated[a] or truncated[a] for a in agents}
+        done_bool = {a: terminated[a] for a in agents}
+        if t["reward_norm"] or t["reward_scaling"]:
+            # (IPPO.py:530 takes element [0] of the (1,) array, MAPPO.py:659 stores the array: the same float either way)
+            reward_ = {a: float(np.asarray(reward_norm[a](reward[a])).reshape(-1)[0]) for a in agents}
+            policy.add(obs, action, reward_, next_obs, done_bool, action_log_pi, done)
+        else:
+            policy.add(obs, action, reward, next_obs, done_bool, action_log_pi, done)
+        episode_reward = {a: episode_reward[a] + reward[a] for a in agents}
+        obs = next_obs
+        if any(done.values()):
+            if (episode_num + 1) % 100 == 0:
+                log("episode: {}, reward: {}".format(episode_num + 1, episode_reward))
+            for a in agents:
+                writer.add_scalar("reward_%s" % a, episode_reward[a], episode_num + 1)
+                returns[a].append(episode_reward[a])
+            episode_num += 1
+            obs, _ = env.reset(seed=args.seed)
+            if t["ObsNorm"]:
+                obs = {a: obs_norm[a](obs[a]) for a in agents}
+            if t["reward_scaling"]:
+                for a in agents:
+                    reward_norm[a].reset()
+            episode_reward = {a: 0 for a in agents}
+        if step % args.horizon == 0:
+            policy.learn(args.minibatch_size, args.gamma, args.lmbda, args.clip_param, args.K_epochs, args.entropy_coefficient, args.huber_delta)
+            if t["lr_decay"]:
+                policy.lr_decay(episode_num, max_episodes=args.max_episodes)
+        if episode_num % args.save_freq == 0:
+            policy.save(model_dir)
+    log("total_time:", time.time() - t0)
+    policy.save(model_dir)
+    arr = np.array([returns[a] for a in agents])
+    suffix = "" if args.N is None else "_N_%d" % len(agents)
+    np.save(os.path.join(model_dir, "%s_seed_%d%s.npy" % (args.policy_name, args.seed, suffix)), arr)
+    if t["ObsNorm"]:
+        with open(os.path.join(model_dir, "obs_norm.pkl"), "wb") as f:
+            pickle.dump({a: [obs_norm[a].running_ms.mean, obs_norm[a].running_ms.std] for a in agents}, f)
+    return dict(returns=arr, steps=step, seconds=time.time() - t0)
+
+
 # ------------------------------------------------------------------------------------ drivers
 def run(algo, argv=None, env=None, log=print):
     """Parse the reference's flags for `algo`, build env + policy, run the loop, return a dict
@@ -524,11 +626,16 @@ def run(algo, argv=None, env=None, log=print):
     log("-" * 50)
     log("Algorithm:", args.policy_name)
     device = torch.device(args.device) if torch.cuda.is_available() else torch.device("cpu")
-    if algo == "maddpg":
+    if algo in ("mappo", "ippo"):
+        _mappo_policy_name(args, algo.upper())
+    if algo in ("maddpg", "mappo", "ippo"):
+        if algo != "maddpg" and not args.continuous_actions and env is None:
+            raise ValueError("the in-repo multi-agent environments have continuous actions: pass --continuous_actions True, or an env of your own")
         env = env if env is not None else _envs.make_parallel(args.env_name, args.N)
         env.reset()
-        dim_info = {a: [env.observation_space(a).shape[0], env.action_space(a).shape[0]] for a in env.agents}
-        max_action, is_continue = 1, True
+        is_continue = algo == "maddpg" or hasattr(env.action_space(env.agents[0]), "low")
+        dim_info = {a: [env.observation_space(a).shape[0], env.action_space(a).shape[0] if is_continue else env.action_space(a).n] for a in env.agents}
+        max_action = 1 if is_continue else None
     else:
         if env is None:
             env, dim_info, max_action, is_continue = get_env(args.env_name, args.is_dis_to_con)
@@ -536,7 +643,8 @@ def run(algo, argv=None, env=None, log=print):
             _, dim_info, max_action, is_continue = _space_info(env, args.is_dis_to_con)
     np.random.seed(args.seed)                       # seeds AFTER env creation, BEFORE the policy (DQN.py:260-266)
     torch.manual_seed(args.seed)
-    model_dir = make_dir(args.results_root, args.env_name, policy_name=args.policy_name, trick=args.trick)
+    # (the two multi-agent PPO scripts' make_dir leaves the trick names out of the folder's name: MAPPO.py:512-518)
+    model_dir = make_dir(args.results_root, args.env_name, policy_name=args.policy_name, trick=None if algo in ("mappo", "ippo") else args.trick)
     log("model_dir:", model_dir)
     writer = ScalarWriter(model_dir)
     # the engine's Philox key follows --seed too: with rng="auto" the index / noise draws move from the seeded NumPy / torch
@@ -586,6 +694,16 @@ def run(algo, argv=None, env=None, log=print):
         from .MADDPG import MADDPG
         policy = MADDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
         out = _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log)
+        writer.close()
+        return dict(out, model_dir=model_dir, policy=policy, args=args)
+    elif algo in ("mappo", "ippo"):
+        from .IPPO import IPPO
+        from .MAPPO import MAPPO
+        cls = MAPPO if algo == "mappo" else IPPO
+        # (these classes draw their permutations from np.random like the scripts unless --rng device is asked for)
+        policy = cls(dim_info, is_continue, args.actor_lr, args.critic_lr, args.horizon, device, args.trick,
+                     rng="device" if args.rng == "device" else "host", seed=args.seed, minibatch_max=max(args.minibatch_size, 1))
+        out = _run_mappo(args, env, policy, dim_info, max_action, is_continue, model_dir, writer, log)
         writer.close()
         return dict(out, model_dir=model_dir, policy=policy, args=args)
     else:

@@ -56,12 +56,21 @@ enum frl_algo {
                                   (ReLU) -> reward_dim (linear), each with a target net; one agent, continuous actions stored as
                                   act_dim[0] floats, frl_config.reward_dim objectives and reward columns as on envelope-DQN engines.
                                   hidden <= 256, and batch_max counts ROWS = batch x weight_num of frl_envelope_ddpg_learn */
-    FRL_ALGO_GAIL = 10         /* GAIL_file/GAIL.py:17-120, the discriminator: one net (index 0) [obs | act] -> hidden -> hidden -> 1 with
+    FRL_ALGO_GAIL = 10,        /* GAIL_file/GAIL.py:17-120, the discriminator: one net (index 0) [obs | act] -> hidden -> hidden -> 1 with
                                   frl_config.hidden_act = FRL_ACT_LEAKY_RELU (slope 0.01, the reference's) or FRL_ACT_RELU, a linear head and
                                   NO target net (FRL_PARAM_TARGET as on REINFORCE engines).  One agent, continuous actions.  The ring holds
                                   the EXPERT rows in the standard record layout, of which only the obs and act columns are read: capacity
                                   = the number of expert rows, batch_max = the most rows of EITHER kind (expert, policy) one
                                   frl_gail_learn call may use.  hidden <= 256 */
+    FRL_ALGO_MAPPO = 11,       /* MAPPO_file/MAPPO.py:123-482: n_agents <= FRL_MAX_AGENTS agents, net 2i the actor of agent i on its own observation
+                                  obs_dim[i] -> hidden (ReLU) -> hidden (ReLU) -> act_dim[i] (tanh mean + a log_std block, or the logits of
+                                  `discrete`, as on PPO engines), net 2i+1 its critic on the CONCATENATION of every agent's observation
+                                  -> hidden -> hidden -> 1.  No target nets (FRL_PARAM_TARGET as on REINFORCE engines).  Records use the
+                                  multi-agent layout (per-agent reward and done columns); extra_cols = sum_i (log-prob columns of agent i:
+                                  act_dim[i], or 1 when discrete) + n_agents: the log-prob blocks in agent order, then one adv_done
+                                  column per agent.  capacity = horizon.  hidden <= 256, ReLU only, <= 64 discrete actions */
+    FRL_ALGO_IPPO = 12         /* MAPPO_file/IPPO.py:57-347: the same, but the critic of agent i takes agent i's OWN observation and every
+                                  agent is an independent PPO learner */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -403,6 +412,51 @@ struct frl_gail_args {
 typedef struct frl_gail_args frl_gail_args;
 int frl_gail_learn(frl_engine* e, const frl_gail_args* args);
 int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* rows_host /* [P][n_rows][obs_dim + act_dim] */, float* reward_out /* [P][n_rows] */);
+
+/* ---------------------------------------------------------------- MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py)
+ * `MAPPO.learn / IPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner in
+ * one launch chain: every critic's V(s), V(s') over the horizon, the GAE scan per agent (float32) from that agent's reward, done and
+ * adv_done columns, v_target = adv + V(s), the optional advantage normalisation, then k_epochs x ceil(horizon / minibatch) steps of
+ * every agent's actor and critic.  What the two engine kinds do differently, as the reference's two files do:
+ *     IPPO   the critic reads the agent's own observation; actor and critic of agent i use column i of adv / v_target; adv_norm is
+ *            per column (std over horizon - 1)
+ *     MAPPO  the critic reads every agent's observation; the surrogate of EVERY actor is the mean over all n_agents advantage columns
+ *            (ratios [m, 1] x adv[index] [m, n]) and EVERY critic regresses V repeated n times on all n target columns; adv_norm is
+ *            over the whole [horizon, n_agents] matrix (std over horizon x n_agents - 1)
+ * MAPPO.py's one Adam over actor + critic parameters (lr = actor_lr, eps 1e-5, no gradient clip) is elementwise, hence two Adams with
+ * equal settings: its caller passes critic_lr = actor_lr, adam_eps = 1e-5, clip_norm = 0.  value_clip is accepted and changes nothing:
+ * the reference clamps the TARGET around V and takes torch.max of the two MEAN losses, which always steps like, and reports, the
+ * unclipped loss (DESIGN.md "MAPPO / IPPO" has the argument).  Afterwards every ring cursor is (0, 0): Buffer_for_PPO.clear.
+ * Refused before any launch with FRL_ERR_INVALID: horizon outside [2, capacity], minibatch outside [1, batch_max], k_epochs < 1, a
+ * loss_kind other than FRL_LOSS_MSE / FRL_LOSS_HUBER, FRL_LOSS_HUBER with huber_delta <= 0, a permutation entry outside [0, horizon);
+ * with FRL_ERR_STATE: engines of any other algorithm.  frl_act serves these engines with FRL_ACT_RAW (the critic's value on nets
+ * 2i+1; a MAPPO critic's input row is [obs_0 | ... | obs_{n-1}]), FRL_ACT_TANHHEAD, FRL_ACT_ARGMAX, FRL_ACT_PPO_SAMPLE and
+ * FRL_ACT_CAT_SAMPLE, through the same normalised forward as the update; every other learn, rollout or explore entry point returns
+ * FRL_ERR_STATE for them. */
+struct frl_mappo_args {
+    int horizon;               /* rows 0..horizon-1 of the ring, in time order */
+    int minibatch, k_epochs;
+    float gamma, lmbda, clip, ent_coef;
+    float actor_lr, critic_lr; /* per call, so that lr_decay is the caller's arithmetic */
+    float adam_eps;            /* IPPO: 1e-5 with trick['adam_eps'], else 1e-8 (0 means 1e-8); MAPPO: 1e-5 */
+    float clip_norm;           /* IPPO: 0.5; <= 0: none (MAPPO) */
+    int adv_norm;              /* trick['adv_norm'] */
+    int value_clip;            /* trick['ValueClip']: accepted, without effect (above) */
+    int loss_kind;             /* FRL_LOSS_MSE, or FRL_LOSS_HUBER with trick['huber_loss'] */
+    float huber_delta;         /* the scripts' 10 */
+    const int64_t* perms;      /* host [P][n_agents][k_epochs][horizon] np.random.permutation draws in the reference's order (agent-major), or
+                                  NULL: drawn on the device */
+    float* adv_out;            /* host [P][horizon][n_agents] advantages before normalisation, or NULL */
+    float* vtarget_out;        /* host [P][horizon][n_agents] or NULL */
+    float* loss_trace_out;     /* host [P][n_agents][k_epochs * n_mb][2] (actor, critic) loss of every step, or NULL */
+};
+typedef struct frl_mappo_args frl_mappo_args;
+int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args);
+/* trick['feature_norm'] / trick['LayerNorm'] of a MAPPO / IPPO engine: F.layer_norm (no affine part, biased variance, eps 1e-5) over the
+ * whole input row before l1, and over the hidden row after each ReLU, in every net of the engine and in every forward (frl_act and
+ * frl_mappo_learn alike).  Both are off at create (MAPPO_simple / IPPO_simple); the LDS of the LayerNorm case is reserved at create,
+ * so the call cannot fail for space.  Engines of any other algorithm return FRL_ERR_STATE. */
+int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */
