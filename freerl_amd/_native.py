@@ -28,6 +28,7 @@ ALGO_REPLAY_ONLY, ALGO_DQN, ALGO_DDPG, ALGO_TD3, ALGO_SAC, ALGO_MADDPG, ALGO_PPO
 ALGO_ENVELOPE_DDPG = 9
 ALGO_GAIL = 10
 ALGO_MAPPO, ALGO_IPPO = 11, 12
+ALGO_HAPPO = 13
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only
@@ -110,6 +111,10 @@ class MappoArgs(C.Structure):
                 ("adv_norm", C.c_int), ("value_clip", C.c_int), ("loss_kind", C.c_int), ("huber_delta", C.c_float),
                 ("perms", C.POINTER(C.c_int64)), ("adv_out", C.POINTER(C.c_float)), ("vtarget_out", C.POINTER(C.c_float)),
                 ("loss_trace_out", C.POINTER(C.c_float))]
+
+
+class HappoArgs(C.Structure):           # frl_mappo_args' fields, then HAPPO's two
+    _fields_ = MappoArgs._fields_ + [("agent_order", C.POINTER(C.c_int32)), ("factor_out", C.POINTER(C.c_float))]
 
 
 class ExploreArgs(C.Structure):
@@ -201,6 +206,7 @@ SIGNATURES = {
     "frl_gail_reward": (_i, [_vp, _i, _i, _fp, _fp]),
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
+    "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

@@ -1,5 +1,6 @@
-// MAPPO / IPPO device code (MAPPO_file/MAPPO.py, IPPO.py): the normalised forward and backward of one row chunk, and the per-row
-// head arithmetic of the clipped surrogate and of the critic's regression over one or n_agents advantage / target columns.
+// MAPPO / IPPO / HAPPO device code (MAPPO_file/MAPPO.py, IPPO.py, HAPPO.py): the normalised forward and backward of one row chunk, the
+// per-row head arithmetic of the clipped surrogate and of the critic's regression over one or n_agents advantage / target columns, the
+// per-row log-probability, and the K_epochs x minibatch steps of one net that kernels_mappo.hip and kernels_happo.hip both run.
 //
 // Forward: [feature_norm] -> l1 -> ReLU -> [LN] -> l2 -> ReLU -> [LN] -> head, both norms F.layer_norm without affine part, biased
 // variance, eps 1e-5.  Without LayerNorm this is device/net.hpp's mlp_fwd / mlp_bwd as they are (feature_norm rewrites xin only and
@@ -10,6 +11,7 @@
 // both means are a fixed butterfly over its 64 lanes: the same bits on every run.
 #pragma once
 #include "net.hpp"
+#include "../kernels.h"
 
 namespace frl {
 
@@ -139,6 +141,218 @@ __device__ __forceinline__ float value_row(const LearnArgs& la, float v, g_cf vt
         dv -= g;
     }
     return dv;
+}
+
+// ---- the per-row log-probability of the stored action under the actor's head row: ONE definition for the update step and for HAPPO's
+// two horizon passes (kernels_happo.hip), so that the ratio of a step and the factor of a later agent cannot drift apart.
+
+// Normal(mean, exp(clamp(log_std))).log_prob(action) summed over the agent's A action columns; `mean` is the head row after tanh
+__device__ __forceinline__ float normal_row_logp(g_cf act, lds_cf mean, g_cf log_std_raw, int A) {
+    float lp = 0.f;
+    for (int c = 0; c < A; ++c) {
+        const float ls = clamp_log_std(log_std_raw[c]);
+        lp += normal_logp(act[c] - mean[c], expf(ls), ls);
+    }
+    return lp;
+}
+
+// Categorical(probs = softmax(z)): torch renormalises the probabilities and clamps them to [eps, 1 - eps] before the logarithm
+struct CatRow {
+    float mx, sum, psum;
+    __device__ __forceinline__ float prob(float z) const { return expf(z - mx) / sum; }
+    __device__ __forceinline__ float logp(float pc) const { return logf(fminf(fmaxf(pc / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f)); }
+};
+__device__ __forceinline__ CatRow cat_row(lds_cf z, int A) {
+    CatRow q;
+    q.mx = z[0];
+    for (int c = 1; c < A; ++c) q.mx = fmaxf(q.mx, z[c]);
+    q.sum = 0.f;
+    for (int c = 0; c < A; ++c) q.sum += expf(z[c] - q.mx);
+    q.psum = 0.f;
+    for (int c = 0; c < A; ++c) q.psum += expf(z[c] - q.mx) / q.sum;
+    return q;
+}
+
+// the critic's input of agent i: its own observation block, or all blocks (they are contiguous in a record, in agent order)
+struct CriticIn { int obs, nobs, width; };
+__device__ __forceinline__ CriticIn critic_in(const EngineDesc& D, int i) {
+    const RecordDesc& R = D.rec;
+    if (mappo_joint(D.algo)) return CriticIn{R.obs_off[0], R.nobs_off[0], R.obs_total};
+    return CriticIn{R.obs_off[i], R.nobs_off[i], R.obs_dim[i]};
+}
+
+// ---- all K_epochs x minibatch steps of one net of (learner p, agent i) by the calling workgroup: the actor (net 2i) or the critic
+// (net 2i+1), each step with its own Adam.  kWeighted (HAPPO.py:415): a row's surrogate and its gradient are multiplied by factor[t]
+// (nullptr: 1, not read); the entropy term is not weighted.  Without it this is MAPPO.py:399-436 / IPPO.py:281-316 as they stand.
+template <bool kWeighted>
+__device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs& a, const Lds& S, const MappoLds& X, int p, int i, bool do_actor,
+                                            g_cf factor) {
+    const int n = D.n_agents, u = p * n + i;
+    const int T = a.horizon, mb = a.minibatch, rc = D.rc;
+    const int net = 2 * i + (do_actor ? 0 : 1);
+    const NetDesc& N = D.net[net];
+    const RecordDesc& R = D.rec;
+    const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
+    g_f th = as_global(D.theta + off);
+    g_f G = as_global(D.grad + off);
+    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf adv = as_global(a.adv + (size_t)p * T * n);
+    g_cf vt = as_global(a.vtarget + (size_t)p * T * n);
+    const bool discrete = D.n_discrete > 0;
+    const int c0 = mappo_joint(D.algo) ? 0 : i, c1 = mappo_joint(D.algo) ? n : i + 1;      // advantage / target columns of a row
+    const int O = R.obs_dim[i], A = D.net[2 * i].L[2].n;
+    const int logp_col = R.extra_off + (R.act_off[i] - R.act_off[0]);                       // the log-prob blocks come first, in agent order
+    const CriticIn ci = critic_in(D, i);
+    const int npad = N.L[2].n_pad;
+    int* steps = D.steps + (size_t)p * (kMaxNets + 1);
+    int t_adam = steps[net];
+    const int n_mb = (T + mb - 1) / mb;
+    float* trace = a.trace + (size_t)u * a.k_epochs * n_mb * 2;
+    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;   // 0.5 + 0.5*log(2*pi)
+    LearnArgs la = {};
+    la.huber = a.huber;
+    la.huber_delta = a.huber_delta;
+    float last = 0.f;
+    // a row's surrogate: into `lossp` and as d / d (sum of log-probs), weighted by the row's factor where the kernel has one
+    auto surrogate = [&](float ratio, int t, float invmn, float& lossp) {
+        if constexpr (kWeighted) {
+            const float f = factor ? factor[t] : 1.f;
+            float row = 0.f;
+            const float g = surrogate_row(ratio, adv + (size_t)t * n, c0, c1, a.clip, row);
+            lossp += f * row;
+            return f * g * invmn;
+        } else {
+            return surrogate_row(ratio, adv + (size_t)t * n, c0, c1, a.clip, lossp) * invmn;
+        }
+    };
+
+    for (int k = 0; k < a.k_epochs; ++k) {
+        g_ci perm = as_global_i(a.perm + ((size_t)u * a.k_epochs + k) * T);
+        for (int s = 0; s < T; s += mb) {
+            const int m = min(mb, T - s);
+            const float invm = 1.f / (float)m, invmn = 1.f / (float)(m * (c1 - c0));
+            g_ci idx = perm + s;
+            const int j_tr = k * n_mb + s / mb;
+            float loss = 0.f;
+            if (do_actor) {
+                // ---------------- clipped surrogate - entropy_coefficient * mean entropy (MAPPO.py:399-412, IPPO.py:281-294)
+                float lossp = 0.f, entp = 0.f, gls = 0.f, ent = 0.f;
+                if (!discrete && threadIdx.x < A) ent = kHalfLog2PiPlusHalf + clamp_log_std(th[N.extra_off + threadIdx.x]);
+                const float ent_sum = block_sum(ent, S.red);          // Normal's entropy: the same for every row
+                for (int r0 = 0; r0 < m; r0 += rc) {
+                    const int nv = min(rc, m - r0);
+                    gather_cols(S.xin, S.xp, rc, nv, idx + r0, ring, R.stride, R.obs_off[i], O, 0);
+                    zero_cols(S.xin, S.xp, rc, O, N.L[0].k_pad);
+                    __syncthreads();
+                    mappo_fwd(D, N, th, S, X, O, discrete ? ACT_NONE : ACT_TANH);          // mean = tanh(mean_layer(.))
+                    if (discrete) {
+                        // one thread per row
+                        if (threadIdx.x < rc) {
+                            const int r = threadIdx.x;
+                            if (r < nv) {
+                                const int t = idx[r0 + r];
+                                g_cf rec = ring + (size_t)t * R.stride;
+                                const CatRow q = cat_row(S.outb + r * S.op, A);
+                                const int ar = (int)rec[R.act_off[i]];
+                                float entr = 0.f, lp_now = 0.f;
+                                for (int c = 0; c < A; ++c) {
+                                    const float pc = q.prob(S.outb[r * S.op + c]);
+                                    const float lg = q.logp(pc);
+                                    entr -= lg * pc;
+                                    if (c == ar) lp_now = lg;
+                                }
+                                const float ratio = expf(lp_now - rec[logp_col]);
+                                const float coef = surrogate(ratio, t, invmn, lossp);
+                                entp += entr;
+                                for (int c = 0; c < npad; ++c) {
+                                    float d = 0.f;
+                                    if (c < A) {
+                                        const float pc = q.prob(S.outb[r * S.op + c]);
+                                        d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_coef * invm) * pc * (q.logp(pc) + entr);
+                                    }
+                                    S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
+                                }
+                            } else {
+                                for (int c = 0; c < npad; ++c) S.abuf[r * S.ap + c] = 0.f;
+                            }
+                            for (int c = 0; c < npad; ++c) S.outb[r * S.op + c] = S.abuf[r * S.ap + c];
+                        }
+                        __syncthreads();
+                    } else {
+                        if (threadIdx.x < rc) {
+                            const int r = threadIdx.x;
+                            float coef = 0.f;
+                            if (r < nv) {
+                                const int t = idx[r0 + r];
+                                g_cf rec = ring + (size_t)t * R.stride;
+                                const float lp_now = normal_row_logp(rec + R.act_off[i], S.outb + r * S.op, th + N.extra_off, A);
+                                float lp_old = 0.f;
+                                for (int c = 0; c < A; ++c) lp_old += rec[logp_col + c];
+                                coef = surrogate(expf(lp_now - lp_old), t, invmn, lossp);
+                            }
+                            S.dabuf[r * S.ap] = coef;      // d loss / d sum_c logp_now
+                        }
+                        __syncthreads();
+                        for (int e = threadIdx.x; e < rc * npad; e += kWG) {
+                            const int r = e / npad, c = e - r * npad;
+                            float d = 0.f, dl = 0.f;
+                            if (r < nv && c < A) {
+                                const float coef = S.dabuf[r * S.ap];
+                                const float mean = S.outb[r * S.op + c];
+                                const float var = expf(2.f * clamp_log_std(th[N.extra_off + c]));
+                                const float dm = ring[(size_t)idx[r0 + r] * R.stride + R.act_off[i] + c] - mean;
+                                d = coef * dm / var * (1.f - mean * mean);        // through mean = tanh(z)
+                                dl = coef * (dm * dm / var - 1.f);
+                            }
+                            S.outb[r * S.op + c] = d;
+                            if (c < A) S.abuf[r * S.ap + c] = dl;
+                        }
+                        __syncthreads();
+                        if (threadIdx.x < A)
+                            for (int r = 0; r < rc; ++r) gls += S.abuf[r * S.ap + threadIdx.x];
+                    }
+                    mappo_bwd(D, N, th, G, S, X, r0 == 0 ? GS_STORE : GS_ADD);
+                }
+                if (!discrete && threadIdx.x < A)
+                    G[N.extra_off + threadIdx.x] = log_std_grad_open(th[N.extra_off + threadIdx.x]) ? (gls - a.ent_coef) : 0.f;
+                const float surr = block_sum(lossp, S.red) * invmn;
+                const float entm = discrete ? block_sum(entp, S.red) * invm : ent_sum;
+                loss = surr - a.ent_coef * entm;
+            } else {
+                // ---------------- critic: the loss of v_target[idx] against V (MAPPO.py:416-436, IPPO.py:300-316)
+                float lossp = 0.f;
+                for (int r0 = 0; r0 < m; r0 += rc) {
+                    const int nv = min(rc, m - r0);
+                    gather_cols(S.xin, S.xp, rc, nv, idx + r0, ring, R.stride, ci.obs, ci.width, 0);
+                    zero_cols(S.xin, S.xp, rc, ci.width, N.L[0].k_pad);
+                    __syncthreads();
+                    mappo_fwd(D, N, th, S, X, ci.width, ACT_NONE);
+                    if (threadIdx.x < rc) {
+                        const int r = threadIdx.x;
+                        float d = 0.f;
+                        if (r < nv) d = value_row(la, S.outb[r * S.op], vt + (size_t)idx[r0 + r] * n, c0, c1, lossp) * invmn;
+                        S.outb[r * S.op] = d;
+                        for (int c = 1; c < npad; ++c) S.outb[r * S.op + c] = 0.f;
+                    }
+                    __syncthreads();
+                    mappo_bwd(D, N, th, G, S, X, r0 == 0 ? GS_STORE : GS_ADD);
+                }
+                loss = block_sum(lossp, S.red) * invmn;
+            }
+            __syncthreads();
+            ++t_adam;
+            adam_net(N.size, th, as_global(D.m + off), as_global(D.v + off), G, nullptr, do_actor ? a.actor_lr : a.critic_lr, a.adam_eps, a.beta1,
+                     a.beta2, 0.f, a.clip_norm, t_adam, 0.f, S.red);
+            __syncthreads();
+            if (threadIdx.x == 0) trace[2 * j_tr + (do_actor ? 0 : 1)] = loss;
+            last = loss;
+        }
+    }
+    if (threadIdx.x == 0) {
+        float* st = D.stats + (size_t)u * ST_COUNT;
+        steps[net] = t_adam;
+        st[do_actor ? ST_ACTOR_LOSS : ST_CRITIC_LOSS] = last;
+    }
 }
 
 }  // namespace frl

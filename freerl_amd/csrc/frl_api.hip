@@ -43,6 +43,7 @@
 #include "kernels_envelope_ddpg.hip"
 #include "kernels_gail.hip"
 #include "kernels_mappo.hip"
+#include "kernels_happo.hip"
 #endif
 
 using namespace frl;
@@ -141,9 +142,11 @@ static const AlgoTraits kAlgo[] = {
     {"GAIL",           "frl_gail_learn",          "FRL_ACT_RAW on [obs | act]: the discriminator's logits; rewards: frl_gail_reward",   false, false, false, true,  false, false, false},
     {"MAPPO",          "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"IPPO",           "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
+    {"HAPPO",          "frl_happo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
 };
-static bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_IPPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
+static bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_HAPPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 static const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // An entry point called on an engine of an algorithm it does not serve: the call, the algorithm and the entry point that updates it
@@ -350,7 +353,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 106; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set
+extern "C" int frl_version(void) { return 107; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -384,9 +387,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     const frl_config& c = *cfg;
     if (c.n_learners < 1) return fail(FRL_ERR_INVALID, "n_learners must be >= 1");
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
-    if (c.algo != FRL_ALGO_MADDPG && !is_mappo(c.algo) && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
+    if (c.algo != FRL_ALGO_MADDPG && !is_mappo_family(c.algo) && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_IPPO) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_HAPPO) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
     int ndev = 0;
@@ -420,7 +423,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;
     h.n_discrete = (T.discrete_head || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
-    if (is_mappo(c.algo)) {
+    if (is_mappo_family(c.algo)) {
         // what kernels_mappo.hip handles (the LayerNorm mask is 256 bits per row; one thread per row walks a discrete head)
         int amax = 0, lp_cols = 0;
         for (int j = 0; j < c.n_agents; ++j) { amax = std::max(amax, c.act_dim[j]); lp_cols += c.discrete ? 1 : c.act_dim[j]; }
@@ -482,13 +485,13 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     } else if (c.algo == FRL_ALGO_REINFORCE) {
         h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
         build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
-    } else if (is_mappo(c.algo)) {
+    } else if (is_mappo_family(c.algo)) {
         // Actor / Actor_discrete (MAPPO.py:123-186 = IPPO.py:57-116) on the agent's own observation; Critic on the global observation
-        // (MAPPO.py:188-218) or on the agent's own (IPPO.py:118-153, with the agent's own index: its class counter is a defect)
+        // (MAPPO.py:188-218 = HAPPO.py:196-226) or on the agent's own (IPPO.py:118-153, with the agent's own index: its class counter is a defect)
         h.n_nets = 2 * c.n_agents;
         for (int j = 0; j < c.n_agents; ++j) {
             build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[j]);
-            build_net(h.net[2 * j + 1], {{H, c.algo == FRL_ALGO_MAPPO ? R.obs_total : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
+            build_net(h.net[2 * j + 1], {{H, mappo_joint(c.algo) ? R.obs_total : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
         }
     } else if (c.algo == FRL_ALGO_PPO) {
         h.n_nets = 2;
@@ -544,7 +547,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
     if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
     if (c.algo == FRL_ALGO_GAIL) h.lds_act_pad = std::max(h.lds_act_pad, ((H + 31) / 32 + 3) / 4 * 4);             // abuf / dabuf: a row's slope bits of h1 / h2
-    if (is_mappo(c.algo)) {
+    if (is_mappo_family(c.algo)) {
         if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, outp);      // logits' delta staging
         h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
     }
@@ -561,7 +564,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     // per net whatever rc is, and prefers the whole minibatch in one chunk.
     if (c.algo != FRL_ALGO_PPO && h.rc == 64 && (long long)h.P * ((h.batch_max + 63) / 64) < 512) h.rc = 32;
     // MAPPO / IPPO: one persistent workgroup per (learner, agent, net), like PPO's: the largest chunk one workgroup's LDS holds
-    if (is_mappo(c.algo)) {
+    if (is_mappo_family(c.algo)) {
         h.rc = 64;
         while (h.rc > 16 && lds_bytes_for(h, h.rc) > 160 * 1024) h.rc /= 2;
     }
@@ -569,7 +572,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         const int v = env_int("FRL_RC", 0);
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
-    if (is_mappo(c.algo) && lds_bytes_for(h, h.rc) > 160 * 1024)
+    if (is_mappo_family(c.algo) && lds_bytes_for(h, h.rc) > 160 * 1024)
         return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns)", T.name, lds_bytes_for(h, h.rc), kin);
     if (lds_bytes_for(h, h.rc) > 160 * 1024) return refuse("network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc));
     if (T.two_wg && lds_bytes_for(h, h.rc) > 80 * 1024)
@@ -596,7 +599,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
             const long long cost = ((units * s + slots - 1) / slots) * cps;
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; h.cps = cps; }
         }
-        if (c.algo == FRL_ALGO_PPO || is_mappo(c.algo)) h.cps = 1;
+        if (c.algo == FRL_ALGO_PPO || is_mappo_family(c.algo)) h.cps = 1;
         {   // developer knob
             const int v = env_int("FRL_CPS", 0);
             if (v >= 1 && n_chunks % v == 0) h.cps = v;
@@ -734,7 +737,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         for (const void* k : {(const void*)dqn_grad_kernel, (const void*)ac_critic_kernel, (const void*)ac_actor_kernel, (const void*)sacd_critic_kernel, (const void*)sacd_actor_kernel,
                               (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
                               (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
-                              (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel})
+                              (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
+                              (const void*)happo_update_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -1153,7 +1157,7 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     a.normalize = (!no_norm && e->h.obs_norm_on && (e->h.n_agents == 1 || net % 2 == 0) && in_dim == e->h.rec.obs_dim[agent]) ? 1 : 0;
     a.in = in_dev; a.eps = eps_dev; a.out = out_dev; a.out_logp = logp_dev;
     if (build_only) { *build_only = a; return FRL_OK; }
-    if (is_mappo(e->h.algo)) {        // the normalised forward (kernels_mappo.hip) in front of act_kernel's epilogue
+    if (is_mappo_family(e->h.algo)) {        // the normalised forward (kernels_mappo.hip) in front of act_kernel's epilogue
         if (mode == FRL_ACT_SAC_SAMPLE || ex) return fail(FRL_ERR_INVALID, "a %s engine acts through FRL_ACT_RAW, _TANHHEAD, _ARGMAX, _PPO_SAMPLE or _CAT_SAMPLE", algo_traits(e->h.algo).name);
         hipLaunchKernelGGL(mappo_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
@@ -1247,7 +1251,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
-    if (is_mappo(h.algo)) return wrong_engine(h, "frl_act_explore");
+    if (is_mappo_family(h.algo)) return wrong_engine(h, "frl_act_explore");
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
@@ -1433,7 +1437,7 @@ extern "C" int frl_timer_stop(frl_engine* e, float* ms_out) {
 extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
-    if (is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
+    if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
     if (on && e->h.net[0].frag) {
         // Batch_ObsNorm belongs to the row-chunk family: an engine created for the register-chained kernels (parameters in
         // fragment-image order) moves over for good — every parameter array back to Wk, through a scratch copy
@@ -1628,5 +1632,6 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_envelope_ddpg.inc"
 #include "frl_api_gail.inc"
 #include "frl_api_mappo.inc"
+#include "frl_api_happo.inc"
 #include "frl_api_rollout.inc"
 #include "frl_api_comm.inc"

@@ -1,8 +1,8 @@
-// MAPPO / IPPO entry points (included at the end of frl_api.hip).
+// MAPPO / IPPO entry points (included at the end of frl_api.hip); mappo_learn_chain is frl_happo_learn's too (frl_api_happo.inc).
 
 extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm) {
     ENG(e);
-    if (!is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_net_norm_set");
+    if (!is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_net_norm_set");
     e->h.feature_norm = feature_norm ? 1 : 0;
     e->h.layer_norm = layer_norm ? 1 : 0;
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -10,11 +10,16 @@ extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm)
     return FRL_OK;
 }
 
-extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
-    ENG(e);
-    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+// HAPPO's part of a call (frl_happo_learn): nullptr for frl_mappo_learn
+struct HappoCall {
+    const int32_t* agent_order;
+    float* factor_out;
+};
+
+// the whole of frl_mappo_learn, and of frl_happo_learn with `hc`: the argument refusals, the permutations, the three advantage launches,
+// then mappo_update_kernel once or happo_update_kernel once per visiting position, all on the engine's one stream
+static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const HappoCall* hc) {
     const EngineDesc& h = e->h;
-    if (!is_mappo(h.algo)) return wrong_engine(h, "frl_mappo_learn");
     const int T = args->horizon, mb = args->minibatch, K = args->k_epochs, n = h.n_agents;
     if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
     if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
@@ -32,11 +37,24 @@ extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
             perm[i] = (int)v;
         }
     }
+    std::vector<int> order;
+    if (hc && hc->agent_order) {
+        order.assign(hc->agent_order, hc->agent_order + U);
+        for (size_t p = 0; p < P; ++p) {
+            unsigned seen = 0;
+            for (int k = 0; k < n; ++k) {
+                const int v = order[p * n + k];
+                if (v < 0 || v >= n || (seen >> v & 1u)) return fail(FRL_ERR_INVALID, "agent_order of learner %d is not a permutation of 0..%d (entry %d: %d)", (int)p, n - 1, k, v);
+                seen |= 1u << v;
+            }
+        }
+    }
     int rc = flush_stage(e);
     if (rc) return rc;
     const size_t trace_n = U * (size_t)K * n_mb * 2;
-    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, 7 * U * T + trace_n, MEM_DEVICE));
-    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, U * (size_t)K * T, MEM_DEVICE));
+    // (HAPPO: old [P][T] and factor [P][n][T] behind the trace, the visiting order [P][n] behind the permutations)
+    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, 7 * U * T + trace_n + (hc ? (P + U) * T : 0), MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, U * (size_t)K * T + (hc ? U : 0), MEM_DEVICE));
     // permutations: the caller's np.random.permutation draws, one per (agent, epoch) in agent-major order (MAPPO.py:391-395,
     // IPPO.py:254,275-277), else ppo_perm_kernel's with a unit = (learner, agent); horizons beyond 8192 rows: a host Fisher-Yates
     int Tpad = 2;
@@ -80,14 +98,43 @@ extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
     hipLaunchKernelGGL(mappo_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
     hipLaunchKernelGGL(gae_dense_kernel, dim3((unsigned)U), dim3(256), 0, e->stream, a.td, a.advd, T, args->gamma * args->lmbda, a.adv_seq);
     hipLaunchKernelGGL(mappo_adv_kernel, dim3(h.P), dim3(256), 0, e->stream, e->d, a);
-    hipLaunchKernelGGL(mappo_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    HappoArgs x = {};
+    if (hc) {
+        // the visiting order (HAPPO.py:375: torch.randperm(n)): the caller's, else a host Fisher-Yates per learner from the seed and counter
+        if (order.empty()) {
+            order.resize(U);
+            unsigned long long s = h.seed ^ (0xD1B54A32D192ED03ull * (++e->rng_counter));
+            for (size_t p = 0; p < P; ++p) {
+                int* q = order.data() + p * n;
+                for (int i = 0; i < n; ++i) q[i] = i;
+                for (int i = n - 1; i > 0; --i) std::swap(q[i], q[(int)(splitmix64(s) % (unsigned long long)(i + 1))]);
+            }
+        }
+        int* d_order = e->d_perm + U * (size_t)K * T;
+        HIP_TRY(hipMemcpyAsync(d_order, order.data(), U * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        x.order = d_order;
+        x.old = a.trace + trace_n;
+        x.factor = x.old + P * T;
+        for (x.k = 0; x.k < n; ++x.k)
+            hipLaunchKernelGGL(happo_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, x);
+    } else {
+        hipLaunchKernelGGL(mappo_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->stream));      // `perm` (pageable) must outlive the copy
+    HIP_TRY(hipStreamSynchronize(e->stream));      // `perm` and `order` (pageable) must outlive their copies
     ++e->param_version;
     if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, U * T * sizeof(float), hipMemcpyDeviceToHost));
     if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, U * T * sizeof(float), hipMemcpyDeviceToHost));
     if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, trace_n * sizeof(float), hipMemcpyDeviceToHost));
-    // Buffer_for_PPO.clear() (MAPPO.py:481-482, IPPO.py:321-322): counters only
+    if (hc && hc->factor_out) HIP_TRY(hipMemcpy(hc->factor_out, x.factor, U * T * sizeof(float), hipMemcpyDeviceToHost));
+    // Buffer_for_PPO.clear() (MAPPO.py:481-482, IPPO.py:321-322, HAPPO.py:456-458): counters only
     for (int p = 0; p < h.P; ++p) { e->index[p] = 0; e->size[p] = 0; }
     return FRL_OK;
+}
+
+extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
+    ENG(e);
+    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+    if (!is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_mappo_learn");
+    return mappo_learn_chain(e, args, nullptr);
 }

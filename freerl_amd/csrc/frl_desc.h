@@ -11,7 +11,7 @@ constexpr int kMaxNets = 2 * kMaxAgents;
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: the GAIL discriminator's hidden layers only)
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
-                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12 };
+                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -75,6 +75,9 @@ constexpr int wide16_lds_floats_host() { return 16384 + 2 * 16 * 256 + 3 * 16 * 
 // MAPPO / IPPO's LayerNorm case (device/mappo.hpp: carve_mappo): per chunk row a third hidden buffer, two rstd and the two hidden layers' mask words
 constexpr int kMappoMaskWords = 8;       // 32-bit words of ReLU mask bits per row and hidden layer: hidden <= 256
 constexpr int mappo_row_extra(int hidden) { return (hidden + 4) + 2 + 2 * kMappoMaskWords + 2; }
+// MAPPO and HAPPO engines (not IPPO): every critic reads the concatenated observation, actor and critic use all n advantage / target
+// columns of a row, adv_norm runs over the whole [T][n] matrix (host and device)
+constexpr bool mappo_joint(int algo) { return algo == ALGO_MAPPO || algo == ALGO_HAPPO; }
 
 // float index of W[out n][in k] inside a layer's weight block (host and device)
 #if defined(__HIPCC__)

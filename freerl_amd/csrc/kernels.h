@@ -198,6 +198,15 @@ __global__ void mappo_adv_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a)
 __global__ void mappo_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
 __global__ void mappo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
+// kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
+struct HappoArgs {
+    const int* order;     // [P][n] the agent visited at each position
+    float* old;           // [P][T] sum_c log pi(a | o) of the visited agent's actor before its steps
+    float* factor;        // [P][n][T] by visiting position: the product of the earlier visited agents' new-over-old policy ratios
+    int k;                // this launch's visiting position
+};
+__global__ void happo_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a, HappoArgs x);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

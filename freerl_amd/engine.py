@@ -452,25 +452,20 @@ class Engine:
         """trick['feature_norm'] / trick['LayerNorm'] of a MAPPO / IPPO engine (frl_net_norm_set); both off at create."""
         N.check(self._L.frl_net_norm_set(self._h, int(bool(feature_norm)), int(bool(layer_norm))))
 
-    def mappo_learn(self, horizon, minibatch, k_epochs, *, gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8, clip_norm=0.5,
-                    adv_norm=False, value_clip=False, huber_delta=None, perms=None, want_trace=False, want_adv=False):
-        """MAPPO.learn / IPPO.learn for every learner (frl_mappo_learn).  perms [P][n_agents][k_epochs][horizon] (None: drawn on the
-        device); huber_delta None: F.mse_loss.  -> dict with `trace` [P][n_agents][k_epochs * n_mb][2] and / or `adv` (before
-        normalisation) and `v_target`, both [P][horizon][n_agents]."""
-        a = N.MappoArgs()
+    def _mappo_args(self, a, keep, out, horizon, minibatch, k_epochs, *, gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8,
+                    clip_norm=0.5, adv_norm=False, value_clip=False, huber_delta=None, perms=None, want_trace=False, want_adv=False):
+        """fills frl_mappo_args' fields of `a` (a MappoArgs, or a HappoArgs, which begins with them)"""
         a.horizon, a.minibatch, a.k_epochs = int(horizon), int(minibatch), int(k_epochs)
         a.gamma, a.lmbda, a.clip, a.ent_coef = gamma, lmbda, clip, ent_coef
         a.actor_lr, a.critic_lr, a.adam_eps, a.clip_norm = actor_lr, critic_lr, adam_eps, clip_norm
         a.adv_norm, a.value_clip = int(bool(adv_norm)), int(bool(value_clip))
         if huber_delta is not None:
             a.loss_kind, a.huber_delta = N.LOSS_HUBER, float(huber_delta)
-        keep = []
         if perms is not None:
             pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, self.n_agents, int(k_epochs), int(horizon))
             keep.append(pm)
             a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
-        n_mb = (int(horizon) + int(minibatch) - 1) // int(minibatch)
-        out = {}
+        n_mb = (int(horizon) + int(minibatch) - 1) // max(int(minibatch), 1)      # (minibatch < 1: the library refuses the call)
         if want_trace:
             out["trace"] = np.zeros((self.P, self.n_agents, int(k_epochs) * n_mb, 2), dtype=F32)
             a.loss_trace_out = _fp(out["trace"])
@@ -478,7 +473,31 @@ class Engine:
             out["adv"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
             out["v_target"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
             a.adv_out, a.vtarget_out = _fp(out["adv"]), _fp(out["v_target"])
+
+    def mappo_learn(self, horizon, minibatch, k_epochs, **kw):
+        """MAPPO.learn / IPPO.learn for every learner (frl_mappo_learn): gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8,
+        clip_norm=0.5, adv_norm, value_clip, huber_delta (None: F.mse_loss), perms [P][n_agents][k_epochs][horizon] (None: drawn on the
+        device).  -> dict with `trace` [P][n_agents][k_epochs * n_mb][2] (want_trace) and / or `adv` (before normalisation) and
+        `v_target`, both [P][horizon][n_agents] (want_adv)."""
+        a, keep, out = N.MappoArgs(), [], {}
+        self._mappo_args(a, keep, out, horizon, minibatch, k_epochs, **kw)
         N.check(self._L.frl_mappo_learn(self._h, C.byref(a)))
+        return out
+
+    def happo_learn(self, horizon, minibatch, k_epochs, *, agent_order=None, want_factor=False, **kw):
+        """HAPPO.learn for every learner (frl_happo_learn): mappo_learn's arguments (perms and `trace` indexed by agent id), and
+        agent_order [P][n_agents], the agent visited at each position (None: drawn on the host from the engine's seed).  want_factor
+        adds `factor` [P][n_agents][horizon] by visiting position: what the k-th visited agent's steps were weighted with."""
+        a, keep, out = N.HappoArgs(), [], {}
+        self._mappo_args(a, keep, out, horizon, minibatch, k_epochs, **kw)
+        if agent_order is not None:
+            od = np.ascontiguousarray(agent_order, dtype=np.int32).reshape(self.P, self.n_agents)
+            keep.append(od)
+            a.agent_order = od.ctypes.data_as(C.POINTER(C.c_int32))
+        if want_factor:
+            out["factor"] = np.zeros((self.P, self.n_agents, int(horizon)), dtype=F32)
+            a.factor_out = _fp(out["factor"])
+        N.check(self._L.frl_happo_learn(self._h, C.byref(a)))
         return out
 
     # ------------------------------------------------------------------ timing

@@ -38,6 +38,8 @@ _MAPPO = [("N", int, None), ("horizon", int, 256), ("clip_param", float, 0.2), (
 _MAPPO_TRICK = {"adv_norm": False, "ObsNorm": False, "reward_norm": False, "reward_scaling": False, "orthogonal_init": False,
                 "adam_eps": False, "lr_decay": False, "ValueClip": False, "huber_loss": False, "LayerNorm": False, "feature_norm": False}
 
+_MA_PPO = ("mappo", "ippo", "happo")      # the multi-agent PPO scripts: one loop (_run_mappo)
+
 FLAGS = {
     "dqn": dict(env_name="BipedalWalker-v3", policy_name="DQN", device="cuda", is_dis_to_con=True,
                 flags=_COMMON + _REPLAY + [("Qnet_lr", float, 1e-3), ("epsilon", float, 0.1)],
@@ -82,6 +84,11 @@ FLAGS = {
     "ippo": dict(env_name="simple_adversary_v3", policy_name="IPPO", device="cuda", is_dis_to_con=False,
                  flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=5000, save_freq=5000 // 4, start_steps=0,
                                                               learn_steps_interval=0), trick=dict(_MAPPO_TRICK)),
+    # MAPPO_file/HAPPO.py:547-583
+    "happo": dict(env_name="simple_spread_v3", policy_name="HAPPO", device="cuda", is_dis_to_con=False,
+                  flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=120000, save_freq=5000 // 4, start_steps=0,
+                                                               learn_steps_interval=0, gamma=0.95, actor_lr=1e-4, critic_lr=1e-4),
+                  trick=dict(_MAPPO_TRICK)),
 }
 
 
@@ -99,7 +106,7 @@ def build_parser(algo):
         p.add_argument("--realize", type=dict, default={"clip_double": True, "policy_noise": True, "twin_delay": True})
     if algo == "ppo":
         p.add_argument("--beta", type=bool, default=False)
-    if algo in ("mappo", "ippo"):          # (type=bool as in the scripts: any non-empty string is True)
+    if algo in _MA_PPO:                    # (type=bool as in the scripts: any non-empty string is True)
         p.add_argument("--continuous_actions", type=bool, default=(algo == "mappo"))
     p.add_argument("--device", type=str, default=spec["device"])
     # additions of this build (not in the reference)
@@ -526,7 +533,7 @@ def _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log=
 
 
 def _mappo_policy_name(args, base):
-    """MAPPO.py:573-588 / IPPO.py:451-465: the policy name decides the tricks — `MAPPO` switches all on but reward_norm and lr_decay,
+    """MAPPO.py:573-588 / IPPO.py:451-465 / HAPPO.py:586-601: the policy name decides the tricks — `MAPPO` switches all on but reward_norm and lr_decay,
     `MAPPO_simple` all off"""
     t = args.trick
     if t["reward_norm"] and t["reward_scaling"]:
@@ -542,11 +549,12 @@ def _mappo_policy_name(args, base):
 
 
 def _run_mappo(args, env, policy, dim_info, max_action, is_continue, model_dir, writer, log=print):
-    """MAPPO.py:617-700 = IPPO.py:495-579: dict-in/dict-out parallel env, one learn() every `horizon` steps; ObsNorm, reward_norm and
-    reward_scaling live here, per agent"""
+    """MAPPO.py:617-700 = IPPO.py:495-579 = HAPPO.py:631-713: dict-in/dict-out parallel env, one learn() every `horizon` steps; ObsNorm,
+    reward_norm and reward_scaling live here, per agent.  HAPPO.py:681-685 writes and keeps an episode's return only where it prints
+    it, every 100th episode"""
     import pickle
     agents = list(env.agents)
-    base = "MAPPO" if args.policy_name.startswith("MAPPO") else "IPPO"
+    sparse_returns = args.policy_name.startswith("HAPPO")
     episode_num, step = 0, 0
     episode_reward = {a: 0 for a in agents}
     returns = {a: [] for a in agents}
@@ -585,9 +593,10 @@ def _run_mappo(args, env, policy, dim_info, max_action, is_continue, model_dir, 
         if any(done.values()):
             if (episode_num + 1) % 100 == 0:
                 log("episode: {}, reward: {}".format(episode_num + 1, episode_reward))
-            for a in agents:
-                writer.add_scalar("reward_%s" % a, episode_reward[a], episode_num + 1)
-                returns[a].append(episode_reward[a])
+            if not sparse_returns or (episode_num + 1) % 100 == 0:
+                for a in agents:
+                    writer.add_scalar("reward_%s" % a, episode_reward[a], episode_num + 1)
+                    returns[a].append(episode_reward[a])
             episode_num += 1
             obs, _ = env.reset(seed=args.seed)
             if t["ObsNorm"]:
@@ -626,9 +635,9 @@ def run(algo, argv=None, env=None, log=print):
     log("-" * 50)
     log("Algorithm:", args.policy_name)
     device = torch.device(args.device) if torch.cuda.is_available() else torch.device("cpu")
-    if algo in ("mappo", "ippo"):
+    if algo in _MA_PPO:
         _mappo_policy_name(args, algo.upper())
-    if algo in ("maddpg", "mappo", "ippo"):
+    if algo == "maddpg" or algo in _MA_PPO:
         if algo != "maddpg" and not args.continuous_actions and env is None:
             raise ValueError("the in-repo multi-agent environments have continuous actions: pass --continuous_actions True, or an env of your own")
         env = env if env is not None else _envs.make_parallel(args.env_name, args.N)
@@ -644,7 +653,7 @@ def run(algo, argv=None, env=None, log=print):
     np.random.seed(args.seed)                       # seeds AFTER env creation, BEFORE the policy (DQN.py:260-266)
     torch.manual_seed(args.seed)
     # (the two multi-agent PPO scripts' make_dir leaves the trick names out of the folder's name: MAPPO.py:512-518)
-    model_dir = make_dir(args.results_root, args.env_name, policy_name=args.policy_name, trick=None if algo in ("mappo", "ippo") else args.trick)
+    model_dir = make_dir(args.results_root, args.env_name, policy_name=args.policy_name, trick=None if algo in _MA_PPO else args.trick)
     log("model_dir:", model_dir)
     writer = ScalarWriter(model_dir)
     # the engine's Philox key follows --seed too: with rng="auto" the index / noise draws move from the seeded NumPy / torch
@@ -696,10 +705,11 @@ def run(algo, argv=None, env=None, log=print):
         out = _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log)
         writer.close()
         return dict(out, model_dir=model_dir, policy=policy, args=args)
-    elif algo in ("mappo", "ippo"):
+    elif algo in _MA_PPO:
+        from .HAPPO import HAPPO
         from .IPPO import IPPO
         from .MAPPO import MAPPO
-        cls = MAPPO if algo == "mappo" else IPPO
+        cls = dict(mappo=MAPPO, ippo=IPPO, happo=HAPPO)[algo]
         # (these classes draw their permutations from np.random like the scripts unless --rng device is asked for)
         policy = cls(dim_info, is_continue, args.actor_lr, args.critic_lr, args.horizon, device, args.trick,
                      rng="device" if args.rng == "device" else "host", seed=args.seed, minibatch_max=max(args.minibatch_size, 1))

@@ -69,8 +69,11 @@ enum frl_algo {
                                   multi-agent layout (per-agent reward and done columns); extra_cols = sum_i (log-prob columns of agent i:
                                   act_dim[i], or 1 when discrete) + n_agents: the log-prob blocks in agent order, then one adv_done
                                   column per agent.  capacity = horizon.  hidden <= 256, ReLU only, <= 64 discrete actions */
-    FRL_ALGO_IPPO = 12         /* MAPPO_file/IPPO.py:57-347: the same, but the critic of agent i takes agent i's OWN observation and every
+    FRL_ALGO_IPPO = 12,        /* MAPPO_file/IPPO.py:57-347: the same, but the critic of agent i takes agent i's OWN observation and every
                                   agent is an independent PPO learner */
+    FRL_ALGO_HAPPO = 13        /* MAPPO_file/HAPPO.py:128-458: a FRL_ALGO_MAPPO engine in every respect at create (nets, the critic on the
+                                  concatenated observation, record layout, limits), for heterogeneous agents updated one after another
+                                  in a random order: updated by frl_happo_learn, not by frl_mappo_learn */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -429,7 +432,7 @@ int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* rows_host /*
  * unclipped loss (DESIGN.md "MAPPO / IPPO" has the argument).  Afterwards every ring cursor is (0, 0): Buffer_for_PPO.clear.
  * Refused before any launch with FRL_ERR_INVALID: horizon outside [2, capacity], minibatch outside [1, batch_max], k_epochs < 1, a
  * loss_kind other than FRL_LOSS_MSE / FRL_LOSS_HUBER, FRL_LOSS_HUBER with huber_delta <= 0, a permutation entry outside [0, horizon);
- * with FRL_ERR_STATE: engines of any other algorithm.  frl_act serves these engines with FRL_ACT_RAW (the critic's value on nets
+ * with FRL_ERR_STATE: engines of any other algorithm (FRL_ALGO_HAPPO among them: frl_happo_learn).  frl_act serves these engines with FRL_ACT_RAW (the critic's value on nets
  * 2i+1; a MAPPO critic's input row is [obs_0 | ... | obs_{n-1}]), FRL_ACT_TANHHEAD, FRL_ACT_ARGMAX, FRL_ACT_PPO_SAMPLE and
  * FRL_ACT_CAT_SAMPLE, through the same normalised forward as the update; every other learn, rollout or explore entry point returns
  * FRL_ERR_STATE for them. */
@@ -457,6 +460,50 @@ int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args);
  * frl_mappo_learn alike).  Both are off at create (MAPPO_simple / IPPO_simple); the LDS of the LayerNorm case is reserved at create,
  * so the call cannot fail for space.  Engines of any other algorithm return FRL_ERR_STATE. */
 int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm);
+
+/* ---------------------------------------------------------------- HAPPO (MAPPO_file/HAPPO.py)
+ * `HAPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner.  Values, the
+ * GAE scan, v_target and adv_norm over the whole [horizon, n_agents] matrix are FRL_ALGO_MAPPO's (HAPPO.py:343-370), and so are the
+ * surrogate's mean over all n_agents advantage columns, the critic's regression of V repeated n times on all n target columns
+ * (:420-440) and the ValueClip that changes nothing.  What HAPPO adds (:373-453): factor = ones [horizon]; the agents are visited in
+ * the order `agent_order`; the visited agent's actor and critic take their k_epochs x ceil(horizon / minibatch) steps, the actor on
+ *     -(factor[idx] * min(surr1, surr2)).mean() - ent_coef * entropy.mean()          (the entropy term is not weighted)
+ * and unless it is the last visited, factor *= exp(new - old) row by row, with old / new = sum_c log pi(a | o) of that actor over the
+ * whole horizon before / after its steps (float32, no clamp).  Each agent has two Adams (:237-254): the caller passes its two learning
+ * rates, adam_eps 1e-5 with trick['adam_eps'] else 1e-8, clip_norm 0.5.  One launch per visiting position follows the three advantage
+ * launches on the engine's one stream; stream order alone carries the dependency between agents.
+ * Deviation from the reference, discrete actions only: HAPPO.py:449-450 takes `new` on `[index]`, the LAST MINIBATCH of the epoch loop,
+ * against `old` over all rows - a RuntimeError unless that minibatch has horizon rows (then in permuted order against time order) or
+ * one row (a silent broadcast).  Here both kinds do what the continuous branch does: all rows, in time order (DESIGN.md "HAPPO").
+ * Refusals are frl_mappo_learn's, and FRL_ERR_INVALID before any launch for an agent_order row that is not a permutation of
+ * 0..n_agents-1; FRL_ERR_STATE on engines of any other algorithm, and frl_mappo_learn returns it for FRL_ALGO_HAPPO engines.  A refused
+ * call changes nothing and does not clear the ring; afterwards every ring cursor is (0, 0).  frl_net_norm_set and frl_act serve these
+ * engines as they serve FRL_ALGO_MAPPO engines; every other learn, rollout or explore entry point returns FRL_ERR_STATE. */
+struct frl_happo_args {
+    /* frl_mappo_args' fields, in its order and with its meaning; perms and loss_trace_out are indexed by AGENT ID, not by visiting position */
+    int horizon;
+    int minibatch, k_epochs;
+    float gamma, lmbda, clip, ent_coef;
+    float actor_lr, critic_lr;
+    float adam_eps;            /* 1e-5 with trick['adam_eps'], else 1e-8 (0 means 1e-8) */
+    float clip_norm;           /* 0.5 */
+    int adv_norm;
+    int value_clip;
+    int loss_kind;
+    float huber_delta;
+    const int64_t* perms;      /* host [P][n_agents][k_epochs][horizon], or NULL: drawn on the device.  The reference draws them while it
+                                  visits: the k_epochs permutations of the first VISITED agent first */
+    float* adv_out;
+    float* vtarget_out;
+    float* loss_trace_out;
+    /* HAPPO's own */
+    const int32_t* agent_order;/* host [P][n_agents]: the agent visited at each position (torch.randperm(n_agents), HAPPO.py:375), or NULL:
+                                  a Fisher-Yates shuffle per learner on the host from the engine's seed and call counter */
+    float* factor_out;         /* host [P][n_agents][horizon] BY VISITING POSITION: the factor the k-th visited agent's steps used; slice 0
+                                  is all ones.  Or NULL */
+};
+typedef struct frl_happo_args frl_happo_args;
+int frl_happo_learn(frl_engine* e, const frl_happo_args* args);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */

@@ -17,7 +17,7 @@ HEADER = os.path.join(ROOT, "include", "freerl_hip.h")
 DOC = os.path.join(ROOT, "INTEGRATION.md")
 BEGIN, END = "<!-- ctypes-structs:begin -->", "<!-- ctypes-structs:end -->"
 
-CTYPE = {"int": "C.c_int", "float": "C.c_float", "double": "C.c_double", "uint64_t": "C.c_uint64", "int64_t": "C.c_int64",
+CTYPE = {"int": "C.c_int", "float": "C.c_float", "double": "C.c_double", "uint64_t": "C.c_uint64", "int64_t": "C.c_int64", "int32_t": "C.c_int32",
          "long long": "C.c_longlong", "uint8_t": "C.c_uint8"}
 
 
