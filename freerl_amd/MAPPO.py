@@ -58,6 +58,7 @@ class MultiAgentPPO:
     """What MAPPO and IPPO share: the engine, the joint ring, select / evaluate / add / save / load"""
     _algo = None
     _file = None
+    _mask_cols = 0                               # mask columns behind a record's adv_done columns (MAPPO_for_mask_action.py)
 
     def __init__(self, dim_info, is_continue, actor_lr, critic_lr, horizon, device, trick=None, *, rng="host", hidden=128,
                  minibatch_max=256, seed=0):
@@ -69,9 +70,9 @@ class MultiAgentPPO:
         self.horizon = int(horizon)
         self.is_continue = is_continue
         self.num_agents = len(self.agent_ids)
-        stored = sum(self._ad) if is_continue else self.num_agents
+        stored = self._stored = sum(self._ad) if is_continue else self.num_agents
         self._e = Engine(self._algo, self._od, self._ad, max(self.horizon, 2), hidden=hidden, batch_max=max(minibatch_max, 1),
-                         extra_cols=stored + self.num_agents, discrete=not is_continue, device_id=hip_id, seed=seed)
+                         extra_cols=stored + self.num_agents + self._mask_cols, discrete=not is_continue, device_id=hip_id, seed=seed)
         self._e.net_norm_set(self.trick["feature_norm"], self.trick["LayerNorm"])
         self.agents, self.buffers = {}, {}
         for j, aid in enumerate(self.agent_ids):
@@ -120,7 +121,7 @@ class MultiAgentPPO:
             r[lay.next_obs_off[j]:lay.next_obs_off[j] + lay.obs_dim[j]] = np.asarray(next_obs[aid], dtype=F32).reshape(-1)
             r[lp:lp + lay.act_dim[j]] = np.asarray(action_log_pi[aid], dtype=F32).reshape(-1)
             lp += lay.act_dim[j]
-            r[lay.extra_off + lay.extra - self.num_agents + j] = float(adv_dones[aid])
+            r[lay.extra_off + self._stored + j] = float(adv_dones[aid])
         self._e.add(0, r)
 
     def _learn(self, minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta, **opt):

@@ -207,6 +207,8 @@ SIGNATURES = {
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),
+    "frl_action_mask_set": (_i, [_vp, _i]),
+    "frl_act_masked": (_i, [_vp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),
     "frl_gae": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp]),
     "frl_envpool_create": (_i, [_i, _i, _i, C.c_uint64, _P(C.c_double), _i, _P(_vp)]),

@@ -1,6 +1,7 @@
 // MAPPO / IPPO / HAPPO device code (MAPPO_file/MAPPO.py, IPPO.py, HAPPO.py): the normalised forward and backward of one row chunk, the
 // per-row head arithmetic of the clipped surrogate and of the critic's regression over one or n_agents advantage / target columns, the
-// per-row log-probability, and the K_epochs x minibatch steps of one net that kernels_mappo.hip and kernels_happo.hip both run.
+// per-row log-probability, and the K_epochs x minibatch steps of one net that kernels_mappo.hip and kernels_happo.hip both run; and
+// the row arithmetic of CategoricalMasked (MAPPO_for_mask_action.py) for kernels_mappo_mask.hip's update and act kernels.
 //
 // Forward: [feature_norm] -> l1 -> ReLU -> [LN] -> l2 -> ReLU -> [LN] -> head, both norms F.layer_norm without affine part, biased
 // variance, eps 1e-5.  Without LayerNorm this is device/net.hpp's mlp_fwd / mlp_bwd as they are (feature_norm rewrites xin only and
@@ -173,6 +174,47 @@ __device__ __forceinline__ CatRow cat_row(lds_cf z, int A) {
     return q;
 }
 
+// CategoricalMasked (MAPPO_for_mask_action.py:191-215) of one row: logits' = where(mask, z, -1e8), Categorical(logits = logits').  The
+// normalised logit is l = logits' - (max + log sum exp(logits' - max)), in torch's order: in a row whose mask is all closed the
+// bracket rounds back to -1e8 and every l is exactly 0 (p = 1 / A, log-prob 0), where (z - max) - log sum would give -log A.
+// p = softmax(l); a closed column has p = 0 exactly next to an open one.  `mask` is the row's block in its ring record: nonzero = open.
+constexpr float kMaskedLogit = -1e8f;
+struct MaskedCatRow {
+    g_cf mask;
+    float lse, lmx, sum;
+    __device__ __forceinline__ bool open(int c) const { return mask[c] != 0.f; }
+    __device__ __forceinline__ float logit(float z, int c) const { return (open(c) ? z : kMaskedLogit) - lse; }      // l_c
+    __device__ __forceinline__ float prob(float l) const { return expf(l - lmx) / sum; }
+};
+__device__ __forceinline__ MaskedCatRow masked_cat_row(lds_cf z, g_cf mask, int A) {
+    MaskedCatRow q;
+    q.mask = mask;
+    auto sub = [&](int c) { return mask[c] != 0.f ? z[c] : kMaskedLogit; };
+    float mx = sub(0);
+    for (int c = 1; c < A; ++c) mx = fmaxf(mx, sub(c));
+    float s = 0.f;
+    for (int c = 0; c < A; ++c) s += expf(sub(c) - mx);
+    q.lse = mx + logf(s);
+    q.lmx = sub(0) - q.lse;
+    for (int c = 1; c < A; ++c) q.lmx = fmaxf(q.lmx, sub(c) - q.lse);
+    q.sum = 0.f;
+    for (int c = 0; c < A; ++c) q.sum += expf((sub(c) - q.lse) - q.lmx);
+    return q;
+}
+// entropy() of the same row: -sum over the open columns of p_c l_c
+__device__ __forceinline__ float masked_entropy(const MaskedCatRow& q, lds_cf z, int A) {
+    float h = 0.f;
+    for (int c = 0; c < A; ++c)
+        if (q.open(c)) { const float l = q.logit(z[c], c); h -= q.prob(l) * l; }
+    return h;
+}
+// the head delta of column c: coef (1[c = a] - p_c) + ent_m p_c (l_c + H) where open, 0 where closed (torch.where passes no gradient)
+__device__ __forceinline__ float masked_delta(const MaskedCatRow& q, float z, int c, int a, float coef, float ent_m, float H) {
+    if (!q.open(c)) return 0.f;
+    const float l = q.logit(z, c), pc = q.prob(l);
+    return coef * ((c == a ? 1.f : 0.f) - pc) + ent_m * pc * (l + H);
+}
+
 // the critic's input of agent i: its own observation block, or all blocks (they are contiguous in a record, in agent order)
 struct CriticIn { int obs, nobs, width; };
 __device__ __forceinline__ CriticIn critic_in(const EngineDesc& D, int i) {
@@ -184,7 +226,9 @@ __device__ __forceinline__ CriticIn critic_in(const EngineDesc& D, int i) {
 // ---- all K_epochs x minibatch steps of one net of (learner p, agent i) by the calling workgroup: the actor (net 2i) or the critic
 // (net 2i+1), each step with its own Adam.  kWeighted (HAPPO.py:415): a row's surrogate and its gradient are multiplied by factor[t]
 // (nullptr: 1, not read); the entropy term is not weighted.  Without it this is MAPPO.py:399-436 / IPPO.py:281-316 as they stand.
-template <bool kWeighted>
+// kMasked (MAPPO_for_mask_action.py:349-352): the discrete actor's row is CategoricalMasked under the mask block of its ring record
+// (D.mask_off: frl_action_mask_set); the critic's steps and the continuous actor's are untouched.
+template <bool kWeighted, bool kMasked = false>
 __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs& a, const Lds& S, const MappoLds& X, int p, int i, bool do_actor,
                                             g_cf factor) {
     const int n = D.n_agents, u = p * n + i;
@@ -204,6 +248,11 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
     const int logp_col = R.extra_off + (R.act_off[i] - R.act_off[0]);                       // the log-prob blocks come first, in agent order
     const CriticIn ci = critic_in(D, i);
     const int npad = N.L[2].n_pad;
+    int mask_col = 0;                                                                       // agent i's mask block: behind the earlier agents'
+    if constexpr (kMasked) {
+        mask_col = D.mask_off;
+        for (int j = 0; j < i; ++j) mask_col += D.net[2 * j].L[2].n;
+    }
     int* steps = D.steps + (size_t)p * (kMaxNets + 1);
     int t_adam = steps[net];
     const int n_mb = (T + mb - 1) / mb;
@@ -252,25 +301,39 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
                             if (r < nv) {
                                 const int t = idx[r0 + r];
                                 g_cf rec = ring + (size_t)t * R.stride;
-                                const CatRow q = cat_row(S.outb + r * S.op, A);
                                 const int ar = (int)rec[R.act_off[i]];
-                                float entr = 0.f, lp_now = 0.f;
-                                for (int c = 0; c < A; ++c) {
-                                    const float pc = q.prob(S.outb[r * S.op + c]);
-                                    const float lg = q.logp(pc);
-                                    entr -= lg * pc;
-                                    if (c == ar) lp_now = lg;
-                                }
-                                const float ratio = expf(lp_now - rec[logp_col]);
-                                const float coef = surrogate(ratio, t, invmn, lossp);
-                                entp += entr;
-                                for (int c = 0; c < npad; ++c) {
-                                    float d = 0.f;
-                                    if (c < A) {
+                                if constexpr (kMasked) {
+                                    lds_cf z = S.outb + r * S.op;
+                                    const MaskedCatRow q = masked_cat_row(z, rec + mask_col, A);
+                                    const float entr = masked_entropy(q, z, A);
+                                    float lp_now = 0.f;
+                                    for (int c = 0; c < A; ++c)
+                                        if (c == ar) lp_now = q.logit(z[c], c);
+                                    const float ratio = expf(lp_now - rec[logp_col]);
+                                    const float coef = surrogate(ratio, t, invmn, lossp);
+                                    entp += entr;
+                                    for (int c = 0; c < npad; ++c)      // staged: outb is still being read by this row
+                                        S.abuf[r * S.ap + c] = c < A ? masked_delta(q, z[c], c, ar, coef, a.ent_coef * invm, entr) : 0.f;
+                                } else {
+                                    const CatRow q = cat_row(S.outb + r * S.op, A);
+                                    float entr = 0.f, lp_now = 0.f;
+                                    for (int c = 0; c < A; ++c) {
                                         const float pc = q.prob(S.outb[r * S.op + c]);
-                                        d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_coef * invm) * pc * (q.logp(pc) + entr);
+                                        const float lg = q.logp(pc);
+                                        entr -= lg * pc;
+                                        if (c == ar) lp_now = lg;
                                     }
-                                    S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
+                                    const float ratio = expf(lp_now - rec[logp_col]);
+                                    const float coef = surrogate(ratio, t, invmn, lossp);
+                                    entp += entr;
+                                    for (int c = 0; c < npad; ++c) {
+                                        float d = 0.f;
+                                        if (c < A) {
+                                            const float pc = q.prob(S.outb[r * S.op + c]);
+                                            d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_coef * invm) * pc * (q.logp(pc) + entr);
+                                        }
+                                        S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
+                                    }
                                 }
                             } else {
                                 for (int c = 0; c < npad; ++c) S.abuf[r * S.ap + c] = 0.f;

@@ -44,6 +44,7 @@
 #include "kernels_gail.hip"
 #include "kernels_mappo.hip"
 #include "kernels_happo.hip"
+#include "kernels_mappo_mask.hip"
 #endif
 
 using namespace frl;
@@ -353,7 +354,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 107; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn
+extern "C" int frl_version(void) { return 108; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -432,7 +433,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         if (c.hidden_act != FRL_ACT_RELU) return refuse("%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
         if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0)
             return refuse("%s: twin_critic, dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
-        if (c.extra_cols != lp_cols + c.n_agents)
+        // (a discrete FRL_ALGO_MAPPO engine may carry one mask block of act_dim[i] columns per agent behind them: frl_action_mask_set)
+        int mask_cols = 0;
+        for (int j = 0; j < c.n_agents; ++j) mask_cols += c.act_dim[j];
+        const bool with_masks = c.algo == FRL_ALGO_MAPPO && c.discrete && c.extra_cols == lp_cols + c.n_agents + mask_cols;
+        if (c.extra_cols != lp_cols + c.n_agents && !with_masks)
             return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns", T.name, c.extra_cols, lp_cols, c.n_agents);
         if (c.discrete) h.n_discrete = amax;      // (a flag to these kernels: an agent's action count is its actor's head width)
     }
@@ -738,7 +743,7 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
                               (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
                               (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
                               (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
-                              (const void*)happo_update_kernel})
+                              (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)

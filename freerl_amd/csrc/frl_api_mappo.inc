@@ -10,6 +10,55 @@ extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm)
     return FRL_OK;
 }
 
+// MAPPO_for_mask_action.py on a FRL_ALGO_MAPPO engine: the record column of the first mask block (behind the log-prob and adv_done
+// columns), copied to the device like frl_net_norm_set's flags
+extern "C" int frl_action_mask_set(frl_engine* e, int on) {
+    ENG(e);
+    if (e->h.algo != FRL_ALGO_MAPPO) return wrong_engine(e->h, "frl_action_mask_set");
+    const RecordDesc& R = e->h.rec;
+    if (!e->h.n_discrete) return fail(FRL_ERR_INVALID, "frl_action_mask_set: the engine's actions are continuous (a mask closes discrete actions)");
+    int blocks = 0;
+    for (int i = 0; i < e->h.n_agents; ++i) blocks += e->h.net[2 * i].L[2].n;
+    const int first = 2 * e->h.n_agents;      // one log-prob and one adv_done column per agent come first
+    if (R.extra < first + blocks)
+        return fail(FRL_ERR_INVALID, "frl_action_mask_set: extra_cols %d < %d log-prob and adv_done columns + %d mask columns", R.extra, first, blocks);
+    e->h.mask_off = on ? R.extra_off + first : 0;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
+    return FRL_OK;
+}
+
+// select_action of a masked engine: one synchronous categorical draw per row of an actor, host in / host out
+extern "C" int frl_act_masked(frl_engine* e, int net, int n_rows, int in_dim, const float* in_host, const float* mask_host, const float* eps_host,
+                              float* out_host, float* logp_host) {
+    ENG(e);
+    if (e->h.algo != FRL_ALGO_MAPPO) return wrong_engine(e->h, "frl_act_masked");
+    if (!e->h.mask_off) return fail(FRL_ERR_STATE, "frl_act_masked: action masking is off for this engine (frl_action_mask_set)");
+    if (net < 0 || net >= e->h.n_nets || net % 2) return fail(FRL_ERR_INVALID, "net %d is not an actor (nets 0, 2, ..)", net);
+    if (!in_host || !mask_host || !out_host || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
+    const NetDesc& N = e->h.net[net];
+    if (in_dim != N.L[0].k) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, N.L[0].k);
+    const size_t rows = (size_t)e->h.P * n_rows, in_n = rows * in_dim, out_n = rows * N.L[2].n;
+    int rc = act_scratch(e, in_n, 2 * out_n);      // the masks ride behind the draws
+    if (rc) return rc;
+    float* d_mask = e->d_act_eps + out_n;
+    HIP_TRY(hipMemcpyAsync(e->d_act_in, in_host, in_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_mask, mask_host, out_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    if (eps_host) HIP_TRY(hipMemcpyAsync(e->d_act_eps, eps_host, out_n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    ActArgs a;
+    memset(&a, 0, sizeof a);
+    a.net = net; a.mode = ACTM_CAT_SAMPLE; a.n_rows = n_rows; a.in_dim = in_dim;
+    a.in = e->d_act_in; a.eps = eps_host ? e->d_act_eps : nullptr; a.out = e->d_act_out; a.out_logp = logp_host ? e->d_act_logp : nullptr;
+    a.device_eps = eps_host ? 0 : 1;
+    if (!eps_host) a.rng_counter = e->rng_counter++;
+    hipLaunchKernelGGL(mappo_mask_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a, (const float*)d_mask);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out_host, e->d_act_out, rows * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    if (logp_host) HIP_TRY(hipMemcpyAsync(logp_host, e->d_act_logp, rows * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return FRL_OK;
+}
+
 // HAPPO's part of a call (frl_happo_learn): nullptr for frl_mappo_learn
 struct HappoCall {
     const int32_t* agent_order;
@@ -117,6 +166,8 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
         x.factor = x.old + P * T;
         for (x.k = 0; x.k < n; ++x.k)
             hipLaunchKernelGGL(happo_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, x);
+    } else if (h.mask_off) {      // the discrete actors' rows under their mask blocks (kernels_mappo_mask.hip)
+        hipLaunchKernelGGL(mappo_mask_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
     } else {
         hipLaunchKernelGGL(mappo_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
     }

@@ -200,6 +200,8 @@ struct EngineDesc {
     int feature_norm, layer_norm;
     int lds_row_extra;    // floats per chunk row behind carve_lds()'s region: the LayerNorm backward's third hidden buffer, rstd and the
                           // ReLU mask bits of both hidden layers (device/mappo.hpp: carve_mappo); 0 on every other engine
+    int mask_off;         // action-masked MAPPO (kernels_mappo_mask.hip, frl_action_mask_set): the record column of agent 0's mask block, the
+                          // other agents' blocks of act_dim[i] floats behind it in agent order (nonzero = available); 0: masking is off
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -198,6 +198,10 @@ __global__ void mappo_adv_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a)
 __global__ void mappo_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
 __global__ void mappo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
+// kernels_mappo_mask.hip: action-masked MAPPO (MAPPO_file/MAPPO_for_mask_action.py) on a FRL_ALGO_MAPPO engine with EngineDesc::mask_off set
+__global__ void mappo_mask_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_mask_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a, const float* __restrict__ mask);
+
 // kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
 struct HappoArgs {
     const int* order;     // [P][n] the agent visited at each position

@@ -452,6 +452,31 @@ class Engine:
         """trick['feature_norm'] / trick['LayerNorm'] of a MAPPO / IPPO engine (frl_net_norm_set); both off at create."""
         N.check(self._L.frl_net_norm_set(self._h, int(bool(feature_norm)), int(bool(layer_norm))))
 
+    def action_mask_set(self, on=True):
+        """invalid-action masking of a discrete FRL_ALGO_MAPPO engine whose extra columns end with one mask block per agent
+        (frl_action_mask_set): mappo_learn then reads the masks, and act_masked serves select_action."""
+        N.check(self._L.frl_action_mask_set(self._h, int(bool(on))))
+
+    def act_masked(self, net, obs, mask, *, eps=None, want_logp=False):
+        """CategoricalMasked(logits = actor(obs), masks = mask).sample() (frl_act_masked): obs [P, n_rows, in_dim], mask [P, n_rows, A]
+        (nonzero = available), eps [P, n_rows, A] Exp(1) draws (None: drawn on the device) -> action index [P, n_rows] (and its
+        log-prob [P, n_rows] with want_logp).  2-D inputs when P == 1."""
+        obs = np.ascontiguousarray(obs, dtype=F32)
+        if obs.ndim == 2:
+            obs = obs[None]
+        P, n_rows, in_dim = obs.shape
+        assert P == self.P
+        mask = np.ascontiguousarray(mask, dtype=F32).reshape(P, n_rows, -1)
+        assert 0 <= int(net) < self.n_nets and mask.shape[2] == self.cfg.act_dim[int(net) // 2], mask.shape
+        ep = None
+        if eps is not None:
+            eps = np.ascontiguousarray(eps, dtype=F32).reshape(mask.shape)
+            ep = _fp(eps)
+        out = np.empty((P, n_rows), dtype=F32)
+        logp = np.empty((P, n_rows), dtype=F32) if want_logp else None
+        N.check(self._L.frl_act_masked(self._h, int(net), n_rows, in_dim, _fp(obs), _fp(mask), ep, _fp(out), _fp(logp) if want_logp else None))
+        return (out, logp) if want_logp else out
+
     def _mappo_args(self, a, keep, out, horizon, minibatch, k_epochs, *, gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8,
                     clip_norm=0.5, adv_norm=False, value_clip=False, huber_delta=None, perms=None, want_trace=False, want_adv=False):
         """fills frl_mappo_args' fields of `a` (a MappoArgs, or a HappoArgs, which begins with them)"""

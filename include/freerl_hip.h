@@ -460,6 +460,27 @@ int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args);
  * frl_mappo_learn alike).  Both are off at create (MAPPO_simple / IPPO_simple); the LDS of the LayerNorm case is reserved at create,
  * so the call cannot fail for space.  Engines of any other algorithm return FRL_ERR_STATE. */
 int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm);
+/* Invalid-action masking (MAPPO_file/MAPPO_for_mask_action.py) on a discrete FRL_ALGO_MAPPO engine created with
+ *     extra_cols = n_agents (log-probs) + n_agents (adv_done) + sum_i act_dim[i]
+ * so that a record's extra columns are [log-probs | adv_done x n | mask block of agent 0 | .. | mask block of agent n-1], block i being
+ * act_dim[i] floats, nonzero = the action is available.  on != 0: frl_mappo_learn reads the masks: the actor's row becomes
+ * CategoricalMasked, i.e. Categorical(logits = where(mask, logits, -1e8)), normalised in torch's order l = logits' - (max + log sum
+ * exp(logits' - max)) (a row whose mask is all closed has l = 0 everywhere: log-prob 0, no entropy, no gradient), entropy = -sum over
+ * the open actions of p l, no gradient into a closed action, the log-prob not clamped.  The critic, GAE, v_target and adv_norm are
+ * FRL_ALGO_MAPPO's; the caller passes the reference's two Adams as for IPPO (two lrs, clip_norm 0.5).  The reference's learn() runs on
+ * the WHOLE capacity in one minibatch whatever the cursor says (Buffer_for_PPO_mask.all()): pass horizon = minibatch = capacity; rows
+ * never written read as zeros (frl_create zeroes the ring) and rows of earlier episodes stay (clear() resets the counters only).
+ * on == 0: masking off, the blocks are ignored.  FRL_ERR_STATE on any engine but FRL_ALGO_MAPPO (IPPO and HAPPO engines too);
+ * FRL_ERR_INVALID when the engine's actions are continuous or its extra_cols hold no mask blocks.  A refused call changes nothing. */
+int frl_action_mask_set(frl_engine* e, int on);
+/* select_action of such an engine: for every learner and row, CategoricalMasked(logits = actor `net`(in), masks = mask).sample() and
+ * its log_prob.  in_host [P][n_rows][in_dim]; mask_host [P][n_rows][act_dim], nonzero = available; eps_host [P][n_rows][act_dim]
+ * Exp(1) draws (torch's `empty_like(p).exponential_(1)`: the sample is argmax(p / q)), or NULL: drawn on the device; out_host
+ * [P][n_rows] the action index; logp_host [P][n_rows] its normalised logit, or NULL.  A closed action has p = 0 and is never drawn
+ * while any is open.  Synchronous.  FRL_ERR_STATE unless masking is on for the engine; FRL_ERR_INVALID for a net that is not an actor
+ * (even index), in_dim other than its input width, NULL in / mask / out or n_rows < 1. */
+int frl_act_masked(frl_engine* e, int net, int n_rows, int in_dim, const float* in_host, const float* mask_host, const float* eps_host,
+                   float* out_host, float* logp_host);
 
 /* ---------------------------------------------------------------- HAPPO (MAPPO_file/HAPPO.py)
  * `HAPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner.  Values, the

@@ -43,7 +43,11 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # kernels_happo.hip: happo_update_kernel = mappo_update_kernel's steps (device/mappo.hpp: mappo_steps) between two forward-only
           # horizon passes, one persistent workgroup per CU as well: 353 VGPRs + 97 AGPRs, no spilled VGPR, 56 bytes of scratch (with the step
           # loop shared, mappo_update_kernel keeps its 366 + 110 and holds 72 bytes of scratch, the lambda's captures again)
-          ("happo_", 0), ("", 20)]
+          ("happo_", 0),
+          # kernels_mappo_mask.hip: mappo_mask_update_kernel = mappo_steps with the masked categorical row in its discrete branch, 365 VGPRs +
+          # 109 AGPRs and 72 bytes of scratch; mappo_mask_act_kernel = mappo_act_kernel's forward with the masked draw behind it, 188 + 40 and
+          # 56 bytes; no spilled VGPR in either (mappo_update_kernel and happo_update_kernel keep their figures)
+          ("mappo_mask_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
