@@ -59,6 +59,7 @@ class MultiAgentPPO:
     _algo = None
     _file = None
     _mask_cols = 0                               # mask columns behind a record's adv_done columns (MAPPO_for_mask_action.py)
+    _state_dim, _state_rows = 0, 0               # state columns behind those, and their pairing (MAPPO_for_mask_action_state.py)
 
     def __init__(self, dim_info, is_continue, actor_lr, critic_lr, horizon, device, trick=None, *, rng="host", hidden=128,
                  minibatch_max=256, seed=0):
@@ -72,7 +73,8 @@ class MultiAgentPPO:
         self.num_agents = len(self.agent_ids)
         stored = self._stored = sum(self._ad) if is_continue else self.num_agents
         self._e = Engine(self._algo, self._od, self._ad, max(self.horizon, 2), hidden=hidden, batch_max=max(minibatch_max, 1),
-                         extra_cols=stored + self.num_agents + self._mask_cols, discrete=not is_continue, device_id=hip_id, seed=seed)
+                         extra_cols=stored + self.num_agents + self._mask_cols + self._state_dim, discrete=not is_continue, device_id=hip_id,
+                         seed=seed, state_dim=self._state_dim, state_rows=self._state_rows)
         self._e.net_norm_set(self.trick["feature_norm"], self.trick["LayerNorm"])
         self.agents, self.buffers = {}, {}
         for j, aid in enumerate(self.agent_ids):

@@ -11,7 +11,7 @@ the capacity, :303-304); rows never written are zeros with an all-closed mask; `
 episodes take part again; two Adams per agent behind clip_grad_norm_(..., 0.5) and a working `lr_decay`, as in IPPO.py;
 `evaluate_action` takes the argmax of the raw logits and ignores the mask; with is_continue=True the masks are stored and never read.
 Critic, GAE, v_target, adv_norm, the n-column surrogate and regression are `freerl_amd.MAPPO`'s.  This class is not re-exported over
-`freerl_amd.MAPPO`; `MAPPO_for_mask_action_state.py` has no port (DESIGN.md says what its buffers do).
+`freerl_amd.MAPPO`; `MAPPO_for_mask_action_state.py` is `freerl_amd.MAPPO_for_mask_action_state`, a subclass of this one.
 """
 import numpy as np
 import torch

@@ -52,6 +52,13 @@ class Config(C.Structure):
                 ("seed", C.c_uint64), ("reward_dim", C.c_int)]
 
 
+class ConfigExt(C.Structure):          # frl_config_ext: what frl_create_ex takes next to a Config (`size` = sizeof, set by Engine)
+    _fields_ = [("size", C.c_int), ("state_dim", C.c_int), ("state_rows", C.c_int)]
+
+
+STATE_ROWS_POSITION, STATE_ROWS_SAMPLE = 0, 1          # enum frl_state_rows
+
+
 class RecordLayout(C.Structure):
     _fields_ = [("n_agents", C.c_int), ("width", C.c_int), ("stride", C.c_int),
                 ("obs_off", C.c_int * FRL_MAX_AGENTS), ("obs_dim", C.c_int * FRL_MAX_AGENTS),
@@ -158,6 +165,8 @@ SIGNATURES = {
     "frl_version": (_i, []),
     "frl_device_count": (_i, [_ip]),
     "frl_create": (_i, [_P(Config), _P(_vp)]),
+    "frl_create_ex": (_i, [_P(Config), _P(ConfigExt), _P(_vp)]),
+    "frl_state_info": (_i, [_vp, _ip, _ip]),
     "frl_destroy": (_i, [_vp]),
     "frl_sync": (_i, [_vp]),
     "frl_lds_bytes": (_i, [_vp, _ip, _ip]),

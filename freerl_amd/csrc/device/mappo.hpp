@@ -1,7 +1,8 @@
 // MAPPO / IPPO / HAPPO device code (MAPPO_file/MAPPO.py, IPPO.py, HAPPO.py): the normalised forward and backward of one row chunk, the
 // per-row head arithmetic of the clipped surrogate and of the critic's regression over one or n_agents advantage / target columns, the
 // per-row log-probability, and the K_epochs x minibatch steps of one net that kernels_mappo.hip and kernels_happo.hip both run; and
-// the row arithmetic of CategoricalMasked (MAPPO_for_mask_action.py) for kernels_mappo_mask.hip's update and act kernels.
+// the row arithmetic of CategoricalMasked (MAPPO_for_mask_action.py) for kernels_mappo_mask.hip's update and act kernels; and the
+// critic's second input segment (MAPPO_for_mask_action_state.py) for kernels_mappo_state.hip.
 //
 // Forward: [feature_norm] -> l1 -> ReLU -> [LN] -> l2 -> ReLU -> [LN] -> head, both norms F.layer_norm without affine part, biased
 // variance, eps 1e-5.  Without LayerNorm this is device/net.hpp's mlp_fwd / mlp_bwd as they are (feature_norm rewrites xin only and
@@ -223,12 +224,24 @@ __device__ __forceinline__ CriticIn critic_in(const EngineDesc& D, int i) {
     return CriticIn{R.obs_off[i], R.nobs_off[i], R.obs_dim[i]};
 }
 
+// the state segment of a critic's chunk (MAPPO_for_mask_action_state.py: kernels_mappo_state.hip): columns [dst0, dst0 + sd) of the nv
+// valid rows = the state block (record columns [src0, src0 + sd)) of ring rows row0 .. row0 + nv - 1, zeros in the rows behind them.  A
+// straight copy: consecutive threads read consecutive floats of a record, no index load
+__device__ __forceinline__ void state_cols(lds_f X, int ldx, int rc, int nv, int row0, g_cf ring, int stride, int src0, int sd, int dst0) {
+    for (int e = threadIdx.x; e < rc * sd; e += kWG) {
+        const int r = e / sd, c = e - r * sd;
+        X[r * ldx + dst0 + c] = r < nv ? ring[(size_t)(row0 + r) * stride + src0 + c] : 0.f;
+    }
+}
+
 // ---- all K_epochs x minibatch steps of one net of (learner p, agent i) by the calling workgroup: the actor (net 2i) or the critic
 // (net 2i+1), each step with its own Adam.  kWeighted (HAPPO.py:415): a row's surrogate and its gradient are multiplied by factor[t]
 // (nullptr: 1, not read); the entropy term is not weighted.  Without it this is MAPPO.py:399-436 / IPPO.py:281-316 as they stand.
 // kMasked (MAPPO_for_mask_action.py:349-352): the discrete actor's row is CategoricalMasked under the mask block of its ring record
 // (D.mask_off: frl_action_mask_set); the critic's steps and the continuous actor's are untouched.
-template <bool kWeighted, bool kMasked = false>
+// kState (MAPPO_for_mask_action_state.py:371-373): the critic's row is [obs blocks of ring row idx[r] | state block], the state block
+// that of ring row s + r (D.state_rows 0: the reference's `state` is not indexed) or of row idx[r] (1); the actor's steps are untouched.
+template <bool kWeighted, bool kMasked = false, bool kState = false>
 __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs& a, const Lds& S, const MappoLds& X, int p, int i, bool do_actor,
                                             g_cf factor) {
     const int n = D.n_agents, u = p * n + i;
@@ -387,9 +400,15 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
                 for (int r0 = 0; r0 < m; r0 += rc) {
                     const int nv = min(rc, m - r0);
                     gather_cols(S.xin, S.xp, rc, nv, idx + r0, ring, R.stride, ci.obs, ci.width, 0);
-                    zero_cols(S.xin, S.xp, rc, ci.width, N.L[0].k_pad);
+                    if constexpr (kState) {
+                        if (D.state_rows) gather_cols(S.xin, S.xp, rc, nv, idx + r0, ring, R.stride, D.state_off, D.state_dim, ci.width);
+                        else state_cols(S.xin, S.xp, rc, nv, s + r0, ring, R.stride, D.state_off, D.state_dim, ci.width);
+                        zero_cols(S.xin, S.xp, rc, ci.width + D.state_dim, N.L[0].k_pad);
+                    } else {
+                        zero_cols(S.xin, S.xp, rc, ci.width, N.L[0].k_pad);
+                    }
                     __syncthreads();
-                    mappo_fwd(D, N, th, S, X, ci.width, ACT_NONE);
+                    mappo_fwd(D, N, th, S, X, kState ? ci.width + D.state_dim : ci.width, ACT_NONE);
                     if (threadIdx.x < rc) {
                         const int r = threadIdx.x;
                         float d = 0.f;

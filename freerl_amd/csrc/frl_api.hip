@@ -45,6 +45,7 @@
 #include "kernels_mappo.hip"
 #include "kernels_happo.hip"
 #include "kernels_mappo_mask.hip"
+#include "kernels_mappo_state.hip"
 #endif
 
 using namespace frl;
@@ -354,7 +355,7 @@ static int lds_bytes_for(const EngineDesc& h, int rc) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 108; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked
+extern "C" int frl_version(void) { return 109; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -382,10 +383,24 @@ static LearnFamily choose_engine_family(frl_engine* e);       // frl_api_learn.i
 static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, const EngineDesc& h);
 static hipError_t set_family_lds_attributes(LearnFamily fam);
 
-extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
+extern "C" int frl_create(const frl_config* cfg, frl_engine** out) { return frl_create_ex(cfg, nullptr, out); }
+
+// ext: what frl_config cannot grow to hold (its last field is pinned).  NULL, or state_dim 0: frl_create's engine exactly
+extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, frl_engine** out) {
     if (!cfg || !out) return fail(FRL_ERR_INVALID, "cfg/out is NULL");
     *out = nullptr;
     const frl_config& c = *cfg;
+    int state_dim = 0, state_rows = FRL_STATE_ROWS_POSITION;
+    if (ext) {
+        if (ext->size != (int)sizeof(frl_config_ext)) return fail(FRL_ERR_INVALID, "frl_config_ext.size %d != sizeof(frl_config_ext) %d", ext->size, (int)sizeof(frl_config_ext));
+        if (ext->state_dim < 0) return fail(FRL_ERR_INVALID, "frl_config_ext.state_dim %d must be >= 0", ext->state_dim);
+        if (ext->state_rows != FRL_STATE_ROWS_POSITION && ext->state_rows != FRL_STATE_ROWS_SAMPLE)
+            return fail(FRL_ERR_INVALID, "frl_config_ext.state_rows %d (FRL_STATE_ROWS_POSITION or FRL_STATE_ROWS_SAMPLE)", ext->state_rows);
+        state_dim = ext->state_dim;
+        if (state_dim > 0) state_rows = ext->state_rows;
+    }
+    if (state_dim > 0 && c.algo != FRL_ALGO_MAPPO)
+        return fail(FRL_ERR_INVALID, "state_dim %d: a global-state critic belongs to FRL_ALGO_MAPPO engines (MAPPO_for_mask_action_state.py); algo %d has none", state_dim, c.algo);
     if (c.n_learners < 1) return fail(FRL_ERR_INVALID, "n_learners must be >= 1");
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
     if (c.algo != FRL_ALGO_MADDPG && !is_mappo_family(c.algo) && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
@@ -436,8 +451,11 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         // (a discrete FRL_ALGO_MAPPO engine may carry one mask block of act_dim[i] columns per agent behind them: frl_action_mask_set)
         int mask_cols = 0;
         for (int j = 0; j < c.n_agents; ++j) mask_cols += c.act_dim[j];
-        const bool with_masks = c.algo == FRL_ALGO_MAPPO && c.discrete && c.extra_cols == lp_cols + c.n_agents + mask_cols;
-        if (c.extra_cols != lp_cols + c.n_agents && !with_masks)
+        const bool with_masks = c.algo == FRL_ALGO_MAPPO && c.discrete && c.extra_cols == lp_cols + c.n_agents + mask_cols + state_dim;
+        if (state_dim > 0 && c.extra_cols != lp_cols + c.n_agents + state_dim && !with_masks)      // (the state block: the last state_dim columns)
+            return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns [+ %d mask columns] + %d state columns", T.name, c.extra_cols,
+                          lp_cols, c.n_agents, mask_cols, state_dim);
+        if (c.extra_cols != lp_cols + c.n_agents + state_dim && !with_masks)
             return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns", T.name, c.extra_cols, lp_cols, c.n_agents);
         if (c.discrete) h.n_discrete = amax;      // (a flag to these kernels: an agent's action count is its actor's head width)
     }
@@ -496,7 +514,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         h.n_nets = 2 * c.n_agents;
         for (int j = 0; j < c.n_agents; ++j) {
             build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[j]);
-            build_net(h.net[2 * j + 1], {{H, mappo_joint(c.algo) ? R.obs_total : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
+            // (+ the global state behind the observations: MAPPO_for_mask_action_state.py:122-127; state_dim > 0 on FRL_ALGO_MAPPO only)
+            build_net(h.net[2 * j + 1], {{H, mappo_joint(c.algo) ? R.obs_total + state_dim : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
         }
     } else if (c.algo == FRL_ALGO_PPO) {
         h.n_nets = 2;
@@ -537,6 +556,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
     h.act_max = 1;
     for (int j = 0; j < c.n_agents; ++j) h.act_max = std::max(h.act_max, R.act_dim[j]);
     h.lds_kin_pad = kin;
+    h.state_dim = state_dim;
+    h.state_off = state_dim > 0 ? R.extra_off + R.extra - state_dim : 0;
+    h.state_rows = state_rows;
     // one hidden-activation buffer is enough when every head is input -> hidden -> output (DQN's Q-net): 17 KB less per 32-row
     // chunk, which puts the Categorical update's 32-row workgroups at two per CU
     h.lds_hbufs = 1;
@@ -577,6 +599,9 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
         const int v = env_int("FRL_RC", 0);
         if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
     }
+    if (is_mappo_family(c.algo) && state_dim > 0 && lds_bytes_for(h, h.rc) > 160 * 1024)
+        return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns, %d of them the state's: state_dim)", T.name,
+                      lds_bytes_for(h, h.rc), kin, state_dim);
     if (is_mappo_family(c.algo) && lds_bytes_for(h, h.rc) > 160 * 1024)
         return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns)", T.name, lds_bytes_for(h, h.rc), kin);
     if (lds_bytes_for(h, h.rc) > 160 * 1024) return refuse("network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc));
@@ -743,7 +768,8 @@ extern "C" int frl_create(const frl_config* cfg, frl_engine** out) {
                               (const void*)reinforce_grad_kernel, (const void*)envelope_grad_kernel, (const void*)envelope_ddpg_critic_kernel,
                               (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
                               (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
-                              (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel})
+                              (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel,
+                              (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -783,6 +809,13 @@ extern "C" int frl_lds_bytes(const frl_engine* e, int* bytes_out, int* rc_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     if (bytes_out) *bytes_out = e->lds_bytes;
     if (rc_out) *rc_out = e->h.rc;
+    return FRL_OK;
+}
+
+extern "C" int frl_state_info(const frl_engine* e, int* state_dim_out, int* state_col_out) {
+    if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
+    if (state_dim_out) *state_dim_out = e->h.state_dim;
+    if (state_col_out) *state_col_out = e->h.state_off;
     return FRL_OK;
 }
 

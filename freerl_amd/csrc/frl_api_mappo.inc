@@ -22,6 +22,9 @@ extern "C" int frl_action_mask_set(frl_engine* e, int on) {
     const int first = 2 * e->h.n_agents;      // one log-prob and one adv_done column per agent come first
     if (R.extra < first + blocks)
         return fail(FRL_ERR_INVALID, "frl_action_mask_set: extra_cols %d < %d log-prob and adv_done columns + %d mask columns", R.extra, first, blocks);
+    if (R.extra < first + blocks + e->h.state_dim)      // the state block (frl_create_ex) is the last state_dim columns: the masks may not reach into it
+        return fail(FRL_ERR_INVALID, "frl_action_mask_set: extra_cols %d < %d log-prob and adv_done columns + %d mask columns + %d state columns", R.extra, first,
+                    blocks, e->h.state_dim);
     e->h.mask_off = on ? R.extra_off + first : 0;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
@@ -73,6 +76,11 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
     if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
     if (K < 1) return fail(FRL_ERR_INVALID, "k_epochs must be >= 1");
+    // a state engine with the reference's pairing (MAPPO_for_mask_action_state.py:371-373): torch.cat of obs_[index] with the unindexed
+    // `state` raises unless the minibatch is the whole horizon
+    if (h.state_dim > 0 && h.state_rows == FRL_STATE_ROWS_POSITION && mb != T)
+        return fail(FRL_ERR_INVALID, "minibatch %d != horizon %d on an engine with FRL_STATE_ROWS_POSITION (the state block is taken by position in the one "
+                                     "minibatch; FRL_STATE_ROWS_SAMPLE takes any minibatch)", mb, T);
     if (args->loss_kind != FRL_LOSS_MSE && args->loss_kind != FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "loss_kind %d (FRL_LOSS_MSE or FRL_LOSS_HUBER)", args->loss_kind);
     if (args->loss_kind == FRL_LOSS_HUBER && !(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "FRL_LOSS_HUBER needs huber_delta > 0");
     const int n_mb = (T + mb - 1) / mb;
@@ -144,7 +152,10 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     a.vtarget = q; q += U * T;
     a.trace = q;
     a.perm = e->d_perm;
-    hipLaunchKernelGGL(mappo_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    if (h.state_dim > 0)      // the critic's row from two segments (kernels_mappo_state.hip)
+        hipLaunchKernelGGL(mappo_state_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    else
+        hipLaunchKernelGGL(mappo_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
     hipLaunchKernelGGL(gae_dense_kernel, dim3((unsigned)U), dim3(256), 0, e->stream, a.td, a.advd, T, args->gamma * args->lmbda, a.adv_seq);
     hipLaunchKernelGGL(mappo_adv_kernel, dim3(h.P), dim3(256), 0, e->stream, e->d, a);
     HappoArgs x = {};
@@ -166,6 +177,9 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
         x.factor = x.old + P * T;
         for (x.k = 0; x.k < n; ++x.k)
             hipLaunchKernelGGL(happo_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, x);
+    } else if (h.state_dim > 0) {      // the critics' rows with the state block behind the observations (kernels_mappo_state.hip)
+        if (h.mask_off) hipLaunchKernelGGL(mappo_state_mask_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        else hipLaunchKernelGGL(mappo_state_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
     } else if (h.mask_off) {      // the discrete actors' rows under their mask blocks (kernels_mappo_mask.hip)
         hipLaunchKernelGGL(mappo_mask_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
     } else {

@@ -202,6 +202,12 @@ struct EngineDesc {
                           // ReLU mask bits of both hidden layers (device/mappo.hpp: carve_mappo); 0 on every other engine
     int mask_off;         // action-masked MAPPO (kernels_mappo_mask.hip, frl_action_mask_set): the record column of agent 0's mask block, the
                           // other agents' blocks of act_dim[i] floats behind it in agent order (nonzero = available); 0: masking is off
+    // MAPPO with a global-state critic (kernels_mappo_state.hip, frl_create_ex): every critic's input row is [obs_0 .. obs_{n-1} | state],
+    // the state block being the last state_dim columns of a record's extra block
+    int state_dim;        // 0: no state (every other engine)
+    int state_off;        // the record column of the state block: rec.extra_off + rec.extra - state_dim
+    int state_rows;       // which ring row a critic STEP reads minibatch row r's state block from: 0 (FRL_STATE_ROWS_POSITION) row s + r of the
+                          // ring, the reference's unindexed `state`; 1 (FRL_STATE_ROWS_SAMPLE) the sampled row perm[s + r]
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -202,6 +202,12 @@ __global__ void mappo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 __global__ void mappo_mask_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
 __global__ void mappo_mask_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a, const float* __restrict__ mask);
 
+// kernels_mappo_state.hip: MAPPO with a global-state critic (MAPPO_file/MAPPO_for_mask_action_state.py) on a FRL_ALGO_MAPPO engine with
+// EngineDesc::state_dim > 0 (frl_create_ex); the second update kernel when EngineDesc::mask_off is set as well
+__global__ void mappo_state_values_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_state_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_state_mask_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+
 // kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
 struct HappoArgs {
     const int* order;     // [P][n] the agent visited at each position

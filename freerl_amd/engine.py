@@ -18,7 +18,8 @@ def _fp(a):
 
 class Engine:
     def __init__(self, algo, obs_dim, act_dim, capacity, *, n_learners=1, discrete=False, hidden=128,
-                 hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0):
+                 hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0,
+                 state_dim=0, state_rows=N.STATE_ROWS_POSITION):
         obs_dim = list(obs_dim) if isinstance(obs_dim, (list, tuple)) else [int(obs_dim)]
         act_dim = list(act_dim) if isinstance(act_dim, (list, tuple)) else [int(act_dim)]
         assert len(obs_dim) == len(act_dim)
@@ -35,7 +36,13 @@ class Engine:
             cfg.c51_atoms, cfg.c51_vmin, cfg.c51_vmax = int(c51[0]), float(c51[1]), float(c51[2])
         self._L = N.lib()
         h = C.c_void_p()
-        N.check(self._L.frl_create(C.byref(cfg), C.byref(h)))
+        if state_rows and not state_dim:
+            raise ValueError("state_rows %r without a state_dim: there is no state block to pair" % (state_rows,))
+        if state_dim:                           # a global-state critic (FRL_ALGO_MAPPO): frl_config cannot grow, the extension block can
+            ext = N.ConfigExt(C.sizeof(N.ConfigExt), int(state_dim), int(state_rows))
+            N.check(self._L.frl_create_ex(C.byref(cfg), C.byref(ext), C.byref(h)))
+        else:
+            N.check(self._L.frl_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self.cfg = cfg
         self.algo = int(algo)
@@ -73,6 +80,12 @@ class Engine:
         b, r = C.c_int(0), C.c_int(0)
         N.check(self._L.frl_lds_bytes(self._h, C.byref(b), C.byref(r)))
         return b.value, r.value
+
+    def state_info(self):
+        """(state_dim, record column of the state block) of a global-state MAPPO engine (frl_state_info); (0, 0) without one."""
+        d, c = C.c_int(0), C.c_int(0)
+        N.check(self._L.frl_state_info(self._h, C.byref(d), C.byref(c)))
+        return d.value, c.value
 
     def learn_path(self, batch):
         """(chained, lds_bytes, rows_per_workgroup) of the kernel family learn() launches at this batch size."""

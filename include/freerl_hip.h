@@ -138,6 +138,28 @@ typedef struct frl_config {
                                      0 means 1, and every other algorithm ignores it */
 } frl_config;
 
+/* What frl_config cannot grow to hold (its last field is pinned): the extension block of frl_create_ex.
+ * state_dim > 0 (FRL_ALGO_MAPPO only): MAPPO_file/MAPPO_for_mask_action_state.py.  Every critic's first layer is sum_i obs_dim[i] +
+ * state_dim columns wide and reads [obs_0 | .. | obs_{n-1} | state]; the state block is the LAST state_dim columns of a record's extra
+ * block (frl_state_info), so extra_cols = the engine's columns without a state (log-probs, adv_done, optionally the mask blocks) +
+ * state_dim.  On a discrete engine both widths are accepted, and the width alone does not say which was meant (no masks and a
+ * state of S + sum act_dim columns, or masks and a state of S): the caller declares the mask blocks by calling frl_action_mask_set,
+ * which refuses unless they fit in front of the state block.  state_rows says which ring row a critic STEP takes the state block of its minibatch row r from (frl_state_rows); the
+ * value pass always reads V(s) = critic(obs(t), state(t)) and V(s') = critic(next_obs(t), state(t)): the same row, as the reference
+ * does (:322-323). */
+struct frl_config_ext {
+    int size;                     /* sizeof(frl_config_ext): for later growth */
+    int state_dim;                /* 0: no state (frl_create's engine exactly) */
+    int state_rows;               /* enum frl_state_rows */
+};
+typedef struct frl_config_ext frl_config_ext;
+enum frl_state_rows {
+    FRL_STATE_ROWS_POSITION = 0,  /* the reference's (:371-373): `state` is not indexed, so row r of the one minibatch is
+                                     [obs[perm[r]] | state[r]], regressed on v_target[perm[r]].  frl_mappo_learn then refuses
+                                     minibatch != horizon, where the reference raises */
+    FRL_STATE_ROWS_SAMPLE = 1     /* [obs[perm[r]] | state[perm[r]]]: the state of the sampled row; any minibatch */
+};
+
 /* Column layout of one replay record (all agents of one transition, fp32):
  * [obs_0..|act_0..|rew_0..|done_0..|next_obs_0..|extra] — see DESIGN.md "Data layout".  The reward block is one column per agent,
  * except on FRL_ALGO_ENVELOPE_DQN / _DDPG engines, where it is the reward VECTOR: done_off - rew_off = reward_dim columns. */
@@ -192,6 +214,13 @@ const char* frl_last_error(void);          /* message of the last failing call o
 int frl_version(void);
 int frl_device_count(int* n_out);
 int frl_create(const frl_config* cfg, frl_engine** out);
+/* frl_create with an extension block; ext == NULL or ext->state_dim == 0 builds frl_create's engine exactly (frl_create(cfg, out) is
+ * frl_create_ex(cfg, NULL, out)).  FRL_ERR_INVALID: ext->size != sizeof(frl_config_ext), state_dim < 0, a state_rows outside
+ * frl_state_rows, state_dim > 0 on any algorithm but FRL_ALGO_MAPPO, an extra_cols that cannot hold the state block behind the
+ * log-prob and adv_done columns, or a first layer of sum obs_dim + state_dim columns whose row chunk does not fit the 160 KB of LDS. */
+int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, frl_engine** out);
+/* the engine's state width and the record column of its state block (extra_off + extra - state_dim); 0 and 0 on engines without one */
+int frl_state_info(const frl_engine* e, int* state_dim_out, int* state_col_out);
 int frl_destroy(frl_engine* e);
 int frl_sync(frl_engine* e);               /* wait for the engine's stream */
 int frl_lds_bytes(const frl_engine* e, int* bytes_out, int* row_chunk_out);
@@ -431,9 +460,11 @@ int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* rows_host /*
  * the reference clamps the TARGET around V and takes torch.max of the two MEAN losses, which always steps like, and reports, the
  * unclipped loss (DESIGN.md "MAPPO / IPPO" has the argument).  Afterwards every ring cursor is (0, 0): Buffer_for_PPO.clear.
  * Refused before any launch with FRL_ERR_INVALID: horizon outside [2, capacity], minibatch outside [1, batch_max], k_epochs < 1, a
- * loss_kind other than FRL_LOSS_MSE / FRL_LOSS_HUBER, FRL_LOSS_HUBER with huber_delta <= 0, a permutation entry outside [0, horizon);
+ * loss_kind other than FRL_LOSS_MSE / FRL_LOSS_HUBER, FRL_LOSS_HUBER with huber_delta <= 0, a permutation entry outside [0, horizon),
+ * minibatch != horizon on an engine with a state block and FRL_STATE_ROWS_POSITION (frl_create_ex);
  * with FRL_ERR_STATE: engines of any other algorithm (FRL_ALGO_HAPPO among them: frl_happo_learn).  frl_act serves these engines with FRL_ACT_RAW (the critic's value on nets
- * 2i+1; a MAPPO critic's input row is [obs_0 | ... | obs_{n-1}]), FRL_ACT_TANHHEAD, FRL_ACT_ARGMAX, FRL_ACT_PPO_SAMPLE and
+ * 2i+1; a MAPPO critic's input row is [obs_0 | ... | obs_{n-1}], and [obs_0 | ... | obs_{n-1} | state], in_dim = sum obs_dim +
+ * state_dim, on an engine with a state block: frl_create_ex), FRL_ACT_TANHHEAD, FRL_ACT_ARGMAX, FRL_ACT_PPO_SAMPLE and
  * FRL_ACT_CAT_SAMPLE, through the same normalised forward as the update; every other learn, rollout or explore entry point returns
  * FRL_ERR_STATE for them. */
 struct frl_mappo_args {
@@ -471,7 +502,8 @@ int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm);
  * the WHOLE capacity in one minibatch whatever the cursor says (Buffer_for_PPO_mask.all()): pass horizon = minibatch = capacity; rows
  * never written read as zeros (frl_create zeroes the ring) and rows of earlier episodes stay (clear() resets the counters only).
  * on == 0: masking off, the blocks are ignored.  FRL_ERR_STATE on any engine but FRL_ALGO_MAPPO (IPPO and HAPPO engines too);
- * FRL_ERR_INVALID when the engine's actions are continuous or its extra_cols hold no mask blocks.  A refused call changes nothing. */
+ * FRL_ERR_INVALID when the engine's actions are continuous or its extra_cols hold no mask blocks (on an engine with a state block,
+ * frl_create_ex: no mask blocks in front of that block).  A refused call changes nothing. */
 int frl_action_mask_set(frl_engine* e, int on);
 /* select_action of such an engine: for every learner and row, CategoricalMasked(logits = actor `net`(in), masks = mask).sample() and
  * its log_prob.  in_host [P][n_rows][in_dim]; mask_host [P][n_rows][act_dim], nonzero = available; eps_host [P][n_rows][act_dim]
