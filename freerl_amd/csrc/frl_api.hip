@@ -13,6 +13,7 @@
 
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
+#include "engine_plan.hpp"
 #include "host_mem.hpp"
 
 #include "kernels.h"
@@ -80,18 +81,13 @@ struct HipMem {                   // host_mem.hpp's backend.  hipFree synchronis
 };
 using HostMem = frl::MemOwner<HipMem>;
 
-static inline int pad16(int x) { return (x + 15) / 16 * 16; }
-static inline int pad32(int x) { return (x + 31) / 32 * 32; }
-
 // developer / test knobs from the environment, read where they are used (most of them per call).  Three meanings, kept apart:
 // env_set: the variable is set at all; env_flag(name, false): set and nonzero; env_flag(name, true): a default-on path that "=0" switches off
 static bool env_set(const char* name) { return getenv(name) != nullptr; }
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
 
-// The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels and LDS bytes).
-// frl_create fixes the engine's chained family — or none: FAM_ROWCHUNK — with its parameter layout; learn_family() says what one call takes.
-enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16 };
+// (LearnFamily, the kernel family an engine's frl_learn() runs on: engine_plan.hpp; frl_api_learn.inc registers each family's kernels)
 using LearnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs);
 using SolowKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs);
 using SoloKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs, frl::SoloStepArgs);
@@ -113,44 +109,6 @@ struct LearnKernels {             // a family's kernels for one engine's shape (
     int lds_bytes = 0, block = 256;
 };
 
-// What the host API needs to know about an algorithm beyond its nets: one row per frl_algo, read through algo_traits().  A new algorithm
-// is a row here, a net-building branch in frl_create and its own learn entry point (DESIGN.md "Where an algorithm is registered on the host").
-static const char kFrlLearn[] = "frl_learn";
-struct AlgoTraits {
-    const char* name;          // in messages
-    const char* learn;         // the entry point that updates such an engine ("": none)
-    const char* act_hint;      // how to act when frl_act_explore (and with it frl_rollout's collection) does not serve the engine; "": it does
-    bool index_action;         // the record holds the action as one index column whatever frl_config.discrete says
-    bool discrete_head;        // n_discrete = act_dim[0]
-    bool vector_reward;        // reward_dim reward columns, the preference buffers (env_w), batch_max counting batch x weight_num rows
-    bool two_wg;               // row chunks at two workgroups per CU: hidden <= 256, <= 80 KB of LDS per chunk, no bump from 16 to 32 rows
-    bool row_walks_head;       // one thread per row walks the head's act_dim x reward_dim columns: at most kSacdMaxActions of them
-    bool act_spill;            // the actor stage parks activations in act_spill
-    bool rollout;              // frl_rollout collects for it
-};
-static const AlgoTraits kAlgo[] = {
-    // name            learn                      act_hint                                                                        index  disc   vecrew two_wg walks  spill  rollout
-    {"replay-only",    "",                        "",                                                                             false, false, false, false, false, false, false},
-    {"DQN",            kFrlLearn,                 "",                                                                             false, true,  false, false, false, false, true},
-    {"DDPG",           kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
-    {"TD3",            kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
-    {"SAC",            kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  true},
-    {"MADDPG",         kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
-    {"PPO",            "frl_ppo_learn",           "",                                                                             false, false, false, false, false, false, false},
-    {"discrete SAC",   kFrlLearn,                 "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX",                                          true,  true,  false, true,  true,  false, false},
-    {"REINFORCE",      "frl_reinforce_learn",     "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX",                                          true,  true,  false, true,  true,  false, false},
-    {"envelope DQN",   "frl_envelope_learn",      "FRL_ACT_RAW on [obs | preference]; the caller weighs the objectives",          true,  true,  true,  true,  true,  false, false},
-    {"envelope DDPG",  "frl_envelope_ddpg_learn", "FRL_ACT_TANHHEAD on net 0 with [obs | preference]",                            false, false, true,  true,  false, true,  false},
-    {"GAIL",           "frl_gail_learn",          "FRL_ACT_RAW on [obs | act]: the discriminator's logits; rewards: frl_gail_reward",   false, false, false, true,  false, false, false},
-    {"MAPPO",          "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
-    {"IPPO",           "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
-    {"HAPPO",          "frl_happo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
-};
-static bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
-static bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_HAPPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
-static const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
-
 // An entry point called on an engine of an algorithm it does not serve: the call, the algorithm and the entry point that updates it
 static int wrong_engine(const EngineDesc& h, const char* who, int code = FRL_ERR_STATE) {
     const AlgoTraits& T = algo_traits(h.algo);
@@ -158,16 +116,14 @@ static int wrong_engine(const EngineDesc& h, const char* who, int code = FRL_ERR
                 *T.act_hint ? "; such an engine acts through frl_act (" : "", T.act_hint, *T.act_hint ? ")" : "");
 }
 
-struct frl_engine {
+struct frl_engine : frl::EngineFacts {      // (what the plan fixed: family, lds_bytes, has_nets, the buffer sizes, n_cus — engine_plan.hpp)
     HostMem mem;                  // owns every device and pinned buffer below and in h: allocate through it and frl_destroy needs no line
     frl_config cfg;
     EngineDesc h;                 // host mirror of the device descriptor
     EngineDesc* d = nullptr;      // device copy
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_stage = nullptr;
-    int lds_bytes = 0;
-    LearnFamily family = FAM_ROWCHUNK;    // the chained kernel family the engine was created for (host only; frl_obsnorm_enable moves it to the row-chunk kernels for good)
-    LearnKernels kern;                    // ... its kernels (a DQN engine: the one-launch update's)
+    LearnKernels kern;                    // the kernels of the engine's family (a DQN engine: the one-launch update's)
     // replay cursors (host authoritative, reference semantics Buffer.py:23-24,36-38)
     std::vector<int> index, size;
     // pinned staging of not-yet-flushed adds
@@ -183,14 +139,12 @@ struct frl_engine {
     long long* h_idx64 = nullptr;
     long long* d_idx64 = nullptr;
     float* h_noise = nullptr;
-    size_t idx_count = 0, noise_count = 0;
     unsigned long long rng_counter = 0;
     // act scratch (device)
     // [slot][P][net size]: fragment-image nets re-laid out to Wk for act_kernel (wide chained engines), one slot per
     // (net, online | target), sized once at frl_create; a slot is re-laid out only when the engine's parameters have changed since
     // (param_version: bumped by frl_learn, frl_params_set and the obs-norm relayout)
     float* d_act_wk = nullptr;
-    size_t act_wk_slot = 0;               // floats per slot = P * largest net
     std::vector<unsigned long long> act_wk_version;   // [2 * n_nets], 0 = never laid out
     unsigned long long param_version = 1;
     // kernels_solo.hip (h.solo): per-workgroup gradient slabs, partial sums, the learners' grid-barrier counters
@@ -207,10 +161,7 @@ struct frl_engine {
     int* h_solo_err = nullptr;            // pinned: a solo workgroup that waited 2 s for its learner's others sets it (checked after syncs: solo_err_check)
     int* d_solo_ticket = nullptr;         // the rollout tail's learner ticket
     unsigned solo_bar_base = 0;           // arrivals every counter has seen (one counting barrier per launch: kSoloWG)
-    int solo_stride = 0;
-    int solow_wgs = 0;                    // kernels_solow.hip: workgroups per unit in its grids (row-tile workgroups + helpers for the update)
     unsigned* d_solow_bar2 = nullptr;     // [units][64] "critic stepped" flags of the helper workgroups (the fused policy step)
-    int solow_row_wgs = 0;                // ... of which own row tiles (16: one tile each; 8: two each, populations of 17 .. 32 units; 64: MADDPG's batches of 1024)
     float* d_act_in = nullptr;
     float* d_act_eps = nullptr;
     float* d_act_out = nullptr;
@@ -224,8 +175,6 @@ struct frl_engine {
     size_t ppo_cap = 0;
     int* d_perm = nullptr;
     size_t perm_cap = 0;
-    bool has_nets = false;
-    int noisy_per_set = 0;                // floats of device noise per (learner, forward): 2 * (k_pad + n_pad) of the head
     float* h_noisy = nullptr;             // pinned staging for uploaded noise
     // prioritised replay (frl_per_*): sum-tree + max-tree per learner, float64 like the reference's SumTree
     bool per_on = false;
@@ -242,8 +191,6 @@ struct frl_engine {
     float* h_gail_rows = nullptr;         // frl_gail_learn: pinned staging of the uploaded policy rows [P][batch_max][obs_dim + act_dim]
     float* h_env_w = nullptr;             // frl_envelope_learn / frl_envelope_ddpg_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
-    int n_cus = 256;                      // compute units of the device (how many one-per-CU workgroups are resident at once)
-    int lds_per_cu = 160 * 1024;          // LDS bytes of one compute unit
     int* stage_bucket = nullptr;          // PER, pinned: [off[P + 1] | size_before[P] | leaf[stage_cap]] of the flush being applied
     int* d_stage_bucket = nullptr;
     float* d_per_prio = nullptr;          // [P][batch_max] float32 priorities of the last sample
@@ -287,72 +234,6 @@ static void prof_collect(frl_engine* e) {
     e->prof_kind.clear();
 }
 
-// ------------------------------------------------------------------------------ descriptors
-static int build_net(NetDesc& N, const std::vector<std::pair<int, int>>& layers_in /* (out,in) */, int heads,
-                     int hidden_act, int out_act, int extra_n, int n_shadow = 0) {
-    memset(&N, 0, sizeof N);
-    std::vector<std::pair<int, int>> layers = layers_in;
-    for (int i = 0; i < n_shadow; ++i) layers.push_back(layers_in.back());       // sigma of a NoisyLinear head: same shape as the head
-    N.n_layers = (int)layers.size();
-    N.heads = heads;
-    N.hidden_act = hidden_act;
-    N.out_act = out_act;
-    int off = 0, np = 0;
-    for (int i = 0; i < N.n_layers; ++i) {
-        LayerDesc& L = N.L[i];
-        L.n = layers[i].first;
-        L.k = layers[i].second;
-        L.n_pad = pad16(L.n);
-        L.k_pad = pad16(L.k);
-        L.w_off = off;
-        off += L.n_pad * L.k_pad;
-        L.b_off = off;
-        off += L.n_pad;
-        np += L.n * L.k + L.n;
-    }
-    N.extra_off = -1;
-    N.extra_n = extra_n;
-    if (extra_n > 0) {
-        N.extra_off = off;
-        off += pad16(extra_n);
-        np += extra_n;
-    }
-    N.size = pad32(off);
-    N.n_params = np;
-    N.n_layers -= n_shadow;
-    N.n_shadow = n_shadow;
-    return 0;
-}
-
-static void build_record(RecordDesc& R, const frl_config& c) {
-    memset(&R, 0, sizeof R);
-    R.n_agents = c.n_agents;
-    const AlgoTraits& T = algo_traits(c.algo);
-    int off = 0;
-    for (int j = 0; j < c.n_agents; ++j) { R.obs_off[j] = off; R.obs_dim[j] = c.obs_dim[j]; off += c.obs_dim[j]; }
-    R.obs_total = off;
-    for (int j = 0; j < c.n_agents; ++j) {
-        R.act_off[j] = off;
-        R.act_dim[j] = (c.discrete || T.index_action) ? 1 : c.act_dim[j];
-        off += R.act_dim[j];
-    }
-    R.act_total = off - R.obs_total;
-    R.rew_off = off; off += T.vector_reward ? std::max(1, c.reward_dim) : c.n_agents;
-    R.done_off = off; off += c.n_agents;
-    for (int j = 0; j < c.n_agents; ++j) { R.nobs_off[j] = off; off += c.obs_dim[j]; }
-    R.extra_off = off;
-    R.extra = c.extra_cols;
-    off += c.extra_cols;
-    R.width = off;
-    R.stride = pad32(off);
-}
-
-static int lds_bytes_for(const EngineDesc& h, int rc) {
-    const int xp = h.lds_kin_pad + 4, hp = h.hidden + 4, op = h.lds_out_pad + 4, ap = h.lds_act_pad;
-    long long fl = (long long)rc * (xp + h.lds_hbufs * hp + op + 2 * ap + h.lds_row_extra) + h.lds_batch_pad + 8;
-    return (int)(fl * 4);
-}
-
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
 extern "C" int frl_version(void) { return 109; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info
@@ -379,263 +260,56 @@ extern "C" int frl_destroy(frl_engine* e) {
     return FRL_OK;
 }
 
-static LearnFamily choose_engine_family(frl_engine* e);       // frl_api_learn.inc
 static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, const EngineDesc& h);
 static hipError_t set_family_lds_attributes(LearnFamily fam);
 
 extern "C" int frl_create(const frl_config* cfg, frl_engine** out) { return frl_create_ex(cfg, nullptr, out); }
+
+// the developer / test knobs that are read once, at create, for plan_engine (every other knob is read where it is used, per call)
+static PlanKnobs create_knobs() {
+    auto tri = [](const char* name) { return env_set(name) ? (int)env_flag(name, false) : -1; };
+    PlanKnobs k;
+    k.assume_cus = env_int("FRL_ASSUME_CUS", k.assume_cus);
+    k.rc = env_int("FRL_RC", k.rc);
+    k.cps = env_int("FRL_CPS", k.cps);
+    k.solow_narrow = env_flag("FRL_SOLOW_NARROW", k.solow_narrow);
+    k.critic_v2 = tri("FRL_CRITIC_V2");
+    k.solo = tri("FRL_SOLO");
+    k.solo_maxp = env_int("FRL_SOLO_MAXP", k.solo_maxp);
+    k.solow = tri("FRL_SOLOW");
+    k.solow_helpers = env_flag("FRL_SOLOW_HELPERS", k.solow_helpers);
+    k.chain_waves = env_int("FRL_CHAIN_WAVES", k.chain_waves);
+    return k;
+}
 
 // ext: what frl_config cannot grow to hold (its last field is pinned).  NULL, or state_dim 0: frl_create's engine exactly
 extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, frl_engine** out) {
     if (!cfg || !out) return fail(FRL_ERR_INVALID, "cfg/out is NULL");
     *out = nullptr;
     const frl_config& c = *cfg;
-    int state_dim = 0, state_rows = FRL_STATE_ROWS_POSITION;
-    if (ext) {
-        if (ext->size != (int)sizeof(frl_config_ext)) return fail(FRL_ERR_INVALID, "frl_config_ext.size %d != sizeof(frl_config_ext) %d", ext->size, (int)sizeof(frl_config_ext));
-        if (ext->state_dim < 0) return fail(FRL_ERR_INVALID, "frl_config_ext.state_dim %d must be >= 0", ext->state_dim);
-        if (ext->state_rows != FRL_STATE_ROWS_POSITION && ext->state_rows != FRL_STATE_ROWS_SAMPLE)
-            return fail(FRL_ERR_INVALID, "frl_config_ext.state_rows %d (FRL_STATE_ROWS_POSITION or FRL_STATE_ROWS_SAMPLE)", ext->state_rows);
-        state_dim = ext->state_dim;
-        if (state_dim > 0) state_rows = ext->state_rows;
-    }
-    if (state_dim > 0 && c.algo != FRL_ALGO_MAPPO)
-        return fail(FRL_ERR_INVALID, "state_dim %d: a global-state critic belongs to FRL_ALGO_MAPPO engines (MAPPO_for_mask_action_state.py); algo %d has none", state_dim, c.algo);
-    if (c.n_learners < 1) return fail(FRL_ERR_INVALID, "n_learners must be >= 1");
-    if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return fail(FRL_ERR_INVALID, "n_agents out of range");
-    if (c.algo != FRL_ALGO_MADDPG && !is_mappo_family(c.algo) && c.n_agents != 1) return fail(FRL_ERR_INVALID, "n_agents > 1 needs FRL_ALGO_MADDPG");
-    if (c.capacity < 1) return fail(FRL_ERR_INVALID, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_HAPPO) return fail(FRL_ERR_INVALID, "unknown algo %d", c.algo);
-    for (int j = 0; j < c.n_agents; ++j)
-        if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return fail(FRL_ERR_INVALID, "obs_dim/act_dim must be >= 1");
+    std::string why;
+    if (const int rc = check_create_args(c, ext, &why)) return fail(rc, "%s", why.c_str());
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(FRL_ERR_NO_DEVICE, "no HIP device visible: the engine has no CPU fallback");
     if (c.device_id < 0 || c.device_id >= ndev) return fail(FRL_ERR_INVALID, "device_id %d of %d", c.device_id, ndev);
     HIP_TRY(hipSetDevice(c.device_id));
+    PlanLimits limits;      // what the device can hold resident at once: the solo kernels' flag hand-overs spin on every workgroup of a launch
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c.device_id) == hipSuccess) {
+        limits.n_cus = std::max(1, prop.multiProcessorCount);
+        limits.lds_per_cu = (int)std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock);
+    }
+    EnginePlan plan;
+    if (const int rc = plan_engine(c, ext, limits, create_knobs(), &plan, &why)) return fail(rc, "%s", why.c_str());
 
-    frl_engine* e = new frl_engine();
+    frl_engine* e = new frl_engine();      // (nothing is refused from here on: CREATE_TRY undoes what a failed HIP call leaves)
     e->cfg = c;
-    {   // what the device can hold resident at once: the solo kernels' flag hand-overs spin on every workgroup of a launch
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c.device_id) == hipSuccess) {
-            e->n_cus = std::max(1, prop.multiProcessorCount);
-            e->lds_per_cu = (int)std::max<size_t>(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock);
-        }
-        const int fc = env_int("FRL_ASSUME_CUS", 0);                    // (tests: a smaller / partitioned device)
-        if (fc > 0) e->n_cus = fc;
-    }
+    e->h = plan.h;
+    static_cast<EngineFacts&>(*e) = plan;
     EngineDesc& h = e->h;
-    memset(&h, 0, sizeof h);
-    h.algo = c.algo;
-    h.P = c.n_learners;
-    h.n_agents = c.n_agents;
-    h.hidden = c.hidden > 0 ? c.hidden : 128;
-    const AlgoTraits& T = algo_traits(c.algo);
-    auto refuse = [&](const char* fmt, auto... a) { delete e; return fail(FRL_ERR_INVALID, fmt, a...); };      // (before anything is allocated)
-    if (h.hidden % 16) return refuse("hidden must be a multiple of 16");
-    h.capacity = c.capacity;
-    h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
-    if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
-    h.seed = c.seed;
-    h.n_discrete = (T.discrete_head || (c.algo == FRL_ALGO_PPO && c.discrete)) ? c.act_dim[0] : 0;
-    if (is_mappo_family(c.algo)) {
-        // what kernels_mappo.hip handles (the LayerNorm mask is 256 bits per row; one thread per row walks a discrete head)
-        int amax = 0, lp_cols = 0;
-        for (int j = 0; j < c.n_agents; ++j) { amax = std::max(amax, c.act_dim[j]); lp_cols += c.discrete ? 1 : c.act_dim[j]; }
-        if (h.hidden > 256) return refuse("%s: hidden %d > 256 does not fit the row-chunk layout with LayerNorm", T.name, h.hidden);
-        if (c.discrete && amax > kSacdMaxActions) return refuse("%s: %d actions > %d head columns", T.name, amax, kSacdMaxActions);
-        if (c.hidden_act != FRL_ACT_RELU) return refuse("%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
-        if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0)
-            return refuse("%s: twin_critic, dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
-        // (a discrete FRL_ALGO_MAPPO engine may carry one mask block of act_dim[i] columns per agent behind them: frl_action_mask_set)
-        int mask_cols = 0;
-        for (int j = 0; j < c.n_agents; ++j) mask_cols += c.act_dim[j];
-        const bool with_masks = c.algo == FRL_ALGO_MAPPO && c.discrete && c.extra_cols == lp_cols + c.n_agents + mask_cols + state_dim;
-        if (state_dim > 0 && c.extra_cols != lp_cols + c.n_agents + state_dim && !with_masks)      // (the state block: the last state_dim columns)
-            return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns [+ %d mask columns] + %d state columns", T.name, c.extra_cols,
-                          lp_cols, c.n_agents, mask_cols, state_dim);
-        if (c.extra_cols != lp_cols + c.n_agents + state_dim && !with_masks)
-            return refuse("%s: extra_cols %d != %d log-prob columns + %d adv_done columns", T.name, c.extra_cols, lp_cols, c.n_agents);
-        if (c.discrete) h.n_discrete = amax;      // (a flag to these kernels: an agent's action count is its actor's head width)
-    }
-    h.reward_dim = 1;
-    if (T.vector_reward) {
-        if (c.reward_dim < 0) return refuse("%s: reward_dim %d must be >= 1 (0 means 1)", T.name, c.reward_dim);
-        h.reward_dim = std::max(1, c.reward_dim);
-    }
-    // what the kernels of these algorithms handle: one thread per row walks the head's columns; the row-chunk layout at two workgroups per CU
-    if (T.row_walks_head && (long long)c.act_dim[0] * h.reward_dim > kSacdMaxActions)
-        return refuse("%s: %d actions x %d reward columns > %d head columns", T.name, c.act_dim[0], h.reward_dim, kSacdMaxActions);
-    if (T.two_wg && h.hidden > 256) return refuse("%s: hidden %d > 256 does not fit the row-chunk layout at two workgroups per CU", T.name, h.hidden);
-    build_record(h.rec, c);
     const RecordDesc& R = h.rec;
-    const int H = h.hidden;
-    const int hact = c.hidden_act == FRL_ACT_TANH ? ACT_TANH : ACT_RELU;
-    if (c.hidden_act == FRL_ACT_LEAKY_RELU && c.algo != FRL_ALGO_GAIL) return refuse("FRL_ACT_LEAKY_RELU is the GAIL discriminator's hidden activation; %s engines do not take it", T.name);
-    // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
-    if (c.algo == FRL_ALGO_GAIL && c.hidden_act == FRL_ACT_TANH) return refuse("GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
-    e->has_nets = c.algo != FRL_ALGO_REPLAY_ONLY;
-    if (c.algo == FRL_ALGO_DQN) {
-        h.n_nets = 1;
-        h.dueling = c.dueling ? 1 : 0;
-        h.noisy = c.noisy ? 1 : 0;
-        h.c51_atoms = c.c51_atoms > 1 ? c.c51_atoms : 0;
-        if (h.c51_atoms > 64) return refuse("c51_atoms %d: the distribution arithmetic runs one wave lane per atom (<= 64; the reference uses 51)", h.c51_atoms);
-        h.c51_vmin = c.c51_vmin; h.c51_vmax = c.c51_vmax;
-        const int per_out = h.c51_atoms ? h.c51_atoms : 1;        // head rows: [V (per_out) ;] A (act_dim x per_out)
-        build_net(h.net[0], {{H, c.obs_dim[0]}, {(c.act_dim[0] + (c.dueling ? 1 : 0)) * per_out, H}}, 1, ACT_RELU, ACT_NONE, 0,
-                  c.noisy ? 1 : 0);                                                                      // MLP, DQN.py:32-45
-        h.noisy_split = c.dueling ? per_out : h.net[0].L[1].n_pad;
-    } else if (c.algo == FRL_ALGO_SAC_DISCRETE) {
-        // Actor_discrete_hands_on (SAC_add_discrete.py:137-150): O -> H -> H -> A, softmax on the head (in the kernels);
-        // Critic_discrete_hands_on (:152-177): two heads l1-l3 / l4-l6 on obs only, one value per action
-        h.n_nets = 2;
-        const int O = c.obs_dim[0], A = c.act_dim[0];
-        build_net(h.net[0], {{H, O}, {H, H}, {A, H}}, 1, ACT_RELU, ACT_NONE, 0);
-        build_net(h.net[1], {{H, O}, {H, H}, {A, H}, {H, O}, {H, H}, {A, H}}, 2, ACT_RELU, ACT_NONE, 0);
-    } else if (c.algo == FRL_ALGO_ENVELOPE_DQN) {
-        h.n_nets = 1;                                                   // MLP (ENVELOPE_DQN.py:36-59): [obs | w] -> H -> H -> A x R, with a target
-        build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0] * h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
-    } else if (c.algo == FRL_ALGO_ENVELOPE_DDPG) {
-        // Actor (ENVELOPE_DDPG.py:40-63): [obs | w] -> H -> H -> A, tanh; Critic (:65-91): [obs | act | w] -> H -> H -> R; each with a target
-        h.n_nets = 2;
-        build_net(h.net[0], {{H, c.obs_dim[0] + h.reward_dim}, {H, H}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_TANH, 0);
-        build_net(h.net[1], {{H, c.obs_dim[0] + c.act_dim[0] + h.reward_dim}, {H, H}, {h.reward_dim, H}}, 1, ACT_RELU, ACT_NONE, 0);
-    } else if (c.algo == FRL_ALGO_GAIL) {
-        h.n_nets = 1;                                                   // Discriminator (GAIL.py:17-28): mlp(s_dim + a_dim, [H, H], 1), no target
-        build_net(h.net[0], {{H, c.obs_dim[0] + c.act_dim[0]}, {H, H}, {1, H}}, 1, c.hidden_act == FRL_ACT_LEAKY_RELU ? ACT_LEAKY_RELU : ACT_RELU, ACT_NONE, 0);
-    } else if (c.algo == FRL_ALGO_REINFORCE) {
-        h.n_nets = 1;                                                   // Policy_MLP (REINFORCE.py:32-46): softmax in the kernels
-        build_net(h.net[0], {{H, c.obs_dim[0]}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
-    } else if (is_mappo_family(c.algo)) {
-        // Actor / Actor_discrete (MAPPO.py:123-186 = IPPO.py:57-116) on the agent's own observation; Critic on the global observation
-        // (MAPPO.py:188-218 = HAPPO.py:196-226) or on the agent's own (IPPO.py:118-153, with the agent's own index: its class counter is a defect)
-        h.n_nets = 2 * c.n_agents;
-        for (int j = 0; j < c.n_agents; ++j) {
-            build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[j]);
-            // (+ the global state behind the observations: MAPPO_for_mask_action_state.py:122-127; state_dim > 0 on FRL_ALGO_MAPPO only)
-            build_net(h.net[2 * j + 1], {{H, mappo_joint(c.algo) ? R.obs_total + state_dim : c.obs_dim[j]}, {H, H}, {1, H}}, 1, ACT_RELU, ACT_NONE, 0);
-        }
-    } else if (c.algo == FRL_ALGO_PPO) {
-        h.n_nets = 2;
-        if (c.discrete && c.actor_dist == 2) h.cat_logits = 1;     // PPO_file/PPO.py:78-90,176,257: raw logits into Categorical(logits=)
-        if (c.discrete)     // Actor_discrete (PPO_with_tricks.py:110-121): ReLU body, softmax over n_actions logits
-            build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, ACT_RELU, ACT_NONE, 0);
-        else if (c.actor_dist == 1) {   // Actor_Beta (:120-151): alpha_layer and beta_layer share the trunk = one 2A-wide head
-            build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {2 * c.act_dim[0], H}}, 1, hact, ACT_NONE, 0);
-            h.beta_actor = 1;
-        } else
-            build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, hact, ACT_TANH, c.act_dim[0]);
-        build_net(h.net[1], {{H, c.obs_dim[0]}, {H, H}, {1, H}}, 1, hact, ACT_NONE, 0);
-    } else if (e->has_nets) {
-        h.n_nets = 2 * c.n_agents;
-        const int cin = R.obs_total + R.act_total;
-        const int heads = c.twin_critic ? 2 : 1;
-        for (int j = 0; j < c.n_agents; ++j) {
-            const bool sac = c.algo == FRL_ALGO_SAC;
-            build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU,
-                      sac ? ACT_NONE : ACT_TANH, sac ? c.act_dim[j] : 0);
-            std::vector<std::pair<int, int>> ls;
-            for (int hd = 0; hd < heads; ++hd) { ls.push_back({H, cin}); ls.push_back({H, H}); ls.push_back({1, H}); }
-            build_net(h.net[2 * j + 1], ls, heads, ACT_RELU, ACT_NONE, 0);
-        }
-    }
-    int off = 0, kin = 16, outp = 16;
-    for (int i = 0; i < h.n_nets; ++i) {
-        h.net_off[i] = off;
-        off += h.net[i].size;
-        const int nl = h.net[i].n_layers / h.net[i].heads;
-        for (int hd = 0; hd < h.net[i].heads; ++hd) {
-            kin = std::max(kin, h.net[i].L[hd * nl].k_pad);
-            outp = std::max(outp, h.net[i].L[hd * nl + nl - 1].n_pad);
-        }
-    }
-    h.learner_stride = pad32(off);
-    e->family = choose_engine_family(e);
-    h.act_max = 1;
-    for (int j = 0; j < c.n_agents; ++j) h.act_max = std::max(h.act_max, R.act_dim[j]);
-    h.lds_kin_pad = kin;
-    h.state_dim = state_dim;
-    h.state_off = state_dim > 0 ? R.extra_off + R.extra - state_dim : 0;
-    h.state_rows = state_rows;
-    // one hidden-activation buffer is enough when every head is input -> hidden -> output (DQN's Q-net): 17 KB less per 32-row
-    // chunk, which puts the Categorical update's 32-row workgroups at two per CU
-    h.lds_hbufs = 1;
-    for (int i = 0; i < h.n_nets; ++i)
-        if (h.net[i].n_layers / std::max(1, h.net[i].heads) > 2) h.lds_hbufs = 2;
-    h.lds_out_pad = outp;
-    h.lds_batch_pad = 128;                                  // y holds one row chunk (rc <= 128) of TD targets
-    h.lds_act_pad = (std::max(R.act_total, 1) + 3) / 4 * 4; // abuf / dabuf are scalar-accessed: no tile padding
-    if (c.algo == FRL_ALGO_PPO && c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, pad16(c.act_dim[0]));   // logits' delta staging
-    if (c.algo == FRL_ALGO_PPO && c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
-    // projected distribution / probabilities per row, and the row's q value per action (more actions than atoms: 7 on 3 atoms)
-    if (h.c51_atoms) h.lds_act_pad = std::max(h.lds_act_pad, (std::max(h.c51_atoms, c.act_dim[0]) + 3) / 4 * 4);
-    if (c.algo == FRL_ALGO_SAC_DISCRETE) h.lds_act_pad = std::max(h.lds_act_pad, (c.act_dim[0] + 3) / 4 * 4);   // p' / min(Q1', Q2') per row
-    if (T.vector_reward) h.lds_act_pad = std::max(h.lds_act_pad, (h.reward_dim + 3) / 4 * 4);                    // the target vector per row
-    if (c.algo == FRL_ALGO_GAIL) h.lds_act_pad = std::max(h.lds_act_pad, ((H + 31) / 32 + 3) / 4 * 4);             // abuf / dabuf: a row's slope bits of h1 / h2
-    if (is_mappo_family(c.algo)) {
-        if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, outp);      // logits' delta staging
-        h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
-    }
-    // row chunk: the largest of {64,32,16} whose LDS footprint still lets TWO workgroups share a CU.  Measured
-    // (profiles/README.md v4): 64 rows x 2 workgroups beats 32 x 3, 32 x 4 and 128 x 1 — more rows per weight fragment
-    // fetched and half the gradient slabs, while two workgroups still overlap each other's barrier phases
-    h.rc = 64;
-    while (h.rc > 16 && lds_bytes_for(h, h.rc) > 80 * 1024) h.rc /= 2;   // two workgroups per CU (160 KB LDS)
-    // wide inputs (SAC on Humanoid: 393 input columns): 16 rows re-read every weight 16x per batch; 32 rows at ONE
-    // workgroup per CU measured +8 % over 16 rows at three (tools/config_bench.py, SAC C4)
-    if (h.rc == 16 && lds_bytes_for(h, 32) <= 160 * 1024 && !T.two_wg) h.rc = 32;
-    // small populations cannot fill 256 CUs with 64-row chunks (one learner = batch/64 workgroups): 32-row chunks double
-    // the workgroup count and measured +19 % (P = 1) / +13 % (P = 8) updates/s.  PPO's persistent kernel is one workgroup
-    // per net whatever rc is, and prefers the whole minibatch in one chunk.
-    if (c.algo != FRL_ALGO_PPO && h.rc == 64 && (long long)h.P * ((h.batch_max + 63) / 64) < 512) h.rc = 32;
-    // MAPPO / IPPO: one persistent workgroup per (learner, agent, net), like PPO's: the largest chunk one workgroup's LDS holds
-    if (is_mappo_family(c.algo)) {
-        h.rc = 64;
-        while (h.rc > 16 && lds_bytes_for(h, h.rc) > 160 * 1024) h.rc /= 2;
-    }
-    {   // developer knob: rows per workgroup (16 / 32 / 64 / 128)
-        const int v = env_int("FRL_RC", 0);
-        if (v == 16 || v == 32 || v == 64 || v == 128) h.rc = v;
-    }
-    if (is_mappo_family(c.algo) && state_dim > 0 && lds_bytes_for(h, h.rc) > 160 * 1024)
-        return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns, %d of them the state's: state_dim)", T.name,
-                      lds_bytes_for(h, h.rc), kin, state_dim);
-    if (is_mappo_family(c.algo) && lds_bytes_for(h, h.rc) > 160 * 1024)
-        return refuse("%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns)", T.name, lds_bytes_for(h, h.rc), kin);
-    if (lds_bytes_for(h, h.rc) > 160 * 1024) return refuse("network too wide for LDS (%d B at 16 rows)", lds_bytes_for(h, h.rc));
-    if (T.two_wg && lds_bytes_for(h, h.rc) > 80 * 1024)
-        return refuse("%s: %d B of LDS per row chunk > 80 KB (two workgroups per CU)", T.name, lds_bytes_for(h, h.rc));
-    e->lds_bytes = lds_bytes_for(h, h.rc);
-    // Row chunks per gradient workgroup.  With `units` (learner, agent) pairs and n_chunks chunks each, s slabs per unit cost
-    // ceil(units * s / slots) rounds of n_chunks / s chunk-times on the chip's resident-workgroup slots, and the reduce
-    // pass streams s slabs: take the fewest slabs (but two) among the cheapest schedules.  512 learners x 4 chunks of 64
-    // rows on 512 slots: two workgroups per learner walk 2 chunks each (2 slabs) instead of 4 workgroups writing 4 slabs.
-    {
-        // (GAIL: a call has up to batch_max expert rows AND up to batch_max policy rows)
-        const int n_chunks = ((c.algo == FRL_ALGO_GAIL ? 2 : 1) * h.batch_max + h.rc - 1) / h.rc;
-        // resident gradient workgroups: 256 CUs x (2 by registers — the kernels are built for FRL_GRAD_WGS = 2 — or 1 by LDS)
-        const long long slots = 256LL * std::max(1, std::min(2, (160 * 1024) / std::max(1, e->lds_bytes)));
-        const long long units = (long long)h.P * h.n_agents;
-        long long best_cost = -1;
-        h.cps = 1;
-        for (int cps = n_chunks; cps >= 1; --cps) {
-            if (n_chunks % cps) continue;
-            const int s = n_chunks / cps;
-            // measured (P = 512, 4 chunks): 2 slabs 529 k updates/s, 1 slab 524 k, 4 slabs 495 k — with a single slab every
-            // workgroup of the launch starts at once and they stay in step (gather bursts, barrier phases coincide)
-            if (s < 2 && n_chunks >= 2) continue;
-            const long long cost = ((units * s + slots - 1) / slots) * cps;
-            if (best_cost < 0 || cost < best_cost) { best_cost = cost; h.cps = cps; }
-        }
-        if (c.algo == FRL_ALGO_PPO || is_mappo_family(c.algo)) h.cps = 1;
-        {   // developer knob
-            const int v = env_int("FRL_CPS", 0);
-            if (v >= 1 && n_chunks % v == 0) h.cps = v;
-        }
-        h.S = n_chunks / h.cps;
-    }
+    const AlgoTraits& T = algo_traits(c.algo);
 
 #define CREATE_TRY(expr)                                                                           \
     do {                                                                                           \
@@ -664,21 +338,14 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
         CREATE_TRY(e->mem.alloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
         if (T.act_spill)
             CREATE_TRY(e->mem.alloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
-        h.Gmax = 1;
-        for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
         CREATE_TRY(e->mem.alloc_zero(&h.gsq, P * (size_t)h.n_agents * h.Gmax, e->stream));
-        e->idx_count = P * h.n_agents * h.batch_max;
         if (h.noisy) {
-            const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];
-            e->noisy_per_set = 2 * (HL.k_pad + HL.n_pad);
             CREATE_TRY(e->mem.alloc_zero(&h.theta_eff, P * 3 * ls, e->stream));
             CREATE_TRY(e->mem.alloc_zero(&h.noisy_eps, P * 3 * (size_t)e->noisy_per_set, e->stream));
             CREATE_TRY(e->mem.alloc(&e->h_noisy, P * 3 * (size_t)e->noisy_per_set, MEM_PINNED));
         }
         CREATE_TRY(e->mem.alloc_zero(&h.isw, P * (size_t)h.batch_max, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.td_err, P * (size_t)h.batch_max, e->stream));
-        h.noise_sets = std::max(2, h.n_agents);
-        e->noise_count = P * h.n_agents * h.noise_sets * (size_t)h.batch_max * h.act_max;
         CREATE_TRY(e->mem.alloc_zero(&h.idx, e->idx_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.noise, e->noise_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.stats, P * h.n_agents * ST_COUNT, e->stream));
@@ -702,18 +369,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
             CREATE_TRY(e->mem.alloc(&e->h_env_w, P * (size_t)h.batch_max * h.reward_dim, MEM_PINNED));
         }
         if (h.solo || h.solow) {
-            e->solo_stride = 0;
-            for (int i = 0; i < h.n_nets; ++i) e->solo_stride = std::max(e->solo_stride, h.net[i].size);
             const size_t U = P * (size_t)h.n_agents, NT = h.solow ? (size_t)h.solow : (size_t)kSoloWG;      // (kernels_solow.hip: units, row tiles per unit)
             CREATE_TRY(e->mem.alloc_zero(&e->d_solo_slab, U * NT * e->solo_stride, e->stream));
-            // (kernels_solow.hip: helper workgroups on the CUs a small population leaves idle take a share of the slab sum and of Adam —
-            //  FRL_SOLOW_HELPERS=0 switches them off; every workgroup of a launch must be resident)
-            e->solow_wgs = (int)NT;
-            if (h.solow) {
-                const int rw = e->solow_row_wgs;
-                const int per = std::min(64 / rw > 0 ? 64 / rw : 1, std::max(1, e->n_cus / (rw * (int)U)));      // (at most 64 workgroups per unit: the mailboxes are polled by one wave)
-                e->solow_wgs = env_flag("FRL_SOLOW_HELPERS", true) ? rw * per : rw;
-            }
             CREATE_TRY(e->mem.alloc_zero(&e->d_solo_part, U * (size_t)std::max((int)NT, e->solow_wgs) * kSoloPartHost, e->stream));
             CREATE_TRY(e->mem.alloc_zero(&e->d_solo_pre, 2 * U * (size_t)std::max(kSoloPre, 8 + h.batch_max), e->stream));
             CREATE_TRY(e->mem.alloc_zero(&e->d_solo_bar, 2 * U * NT + 2, e->stream));      // [units][tiles] slab flags, then as many "actor slice stepped" flags (kernels_solo.hip: offset P * 16),
@@ -727,18 +384,10 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
         }
         if (h.wide) CREATE_TRY(e->mem.alloc_zero(&h.wide_scr, P * (size_t)h.n_agents * h.wide_unit, e->stream));
         if (h.wide || h.solow) {                                           // select_action's Wk-layout copies of the nets (launch_act)
-            int biggest = 0;
-            for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);
-            e->act_wk_slot = P * (size_t)biggest;
             e->act_wk_version.assign(2 * (size_t)h.n_nets, 0ULL);
             CREATE_TRY(e->mem.alloc(&e->d_act_wk, 2 * (size_t)h.n_nets * e->act_wk_slot, MEM_DEVICE));
         }
-        {
-            int omax = 1;
-            for (int j = 0; j < c.n_agents; ++j) omax = std::max(omax, c.obs_dim[j]);
-            h.obsnorm_w = 1 + 3 * omax;
-            CREATE_TRY(e->mem.alloc_zero(&h.obsnorm, P * (size_t)c.n_agents * c.n_agents * h.obsnorm_w, e->stream));
-        }
+        CREATE_TRY(e->mem.alloc_zero(&h.obsnorm, P * (size_t)c.n_agents * c.n_agents * h.obsnorm_w, e->stream));
         CREATE_TRY(e->mem.alloc(&e->h_idx, e->idx_count, MEM_PINNED));
         CREATE_TRY(e->mem.alloc(&e->h_noise, e->noise_count, MEM_PINNED));
     }
@@ -754,9 +403,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
     e->index.assign(P, 0);
     e->size.assign(P, 0);
     e->staged_per_learner.assign(P, 0);
-    const int chain_waves = env_int("FRL_CHAIN_WAVES", 8) == 4 ? 4 : 8;      // waves per workgroup of the register-chained actor-critic kernels (4: round 5's)
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
-    if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, chain_waves, h);
+    if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, e->chain_waves, h);
     // (a vector reward: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
     if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || T.vector_reward))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
@@ -822,20 +470,7 @@ extern "C" int frl_state_info(const frl_engine* e, int* state_dim_out, int* stat
 // ----------------------------------------------------------------------------------- replay
 extern "C" int frl_record_layout_get(const frl_engine* e, frl_record_layout* out) {
     if (!e || !out) return fail(FRL_ERR_INVALID, "NULL argument");
-    const RecordDesc& R = e->h.rec;
-    memset(out, 0, sizeof *out);
-    out->n_agents = R.n_agents;
-    out->width = R.width;
-    out->stride = R.stride;
-    for (int j = 0; j < R.n_agents; ++j) {
-        out->obs_off[j] = R.obs_off[j]; out->obs_dim[j] = R.obs_dim[j];
-        out->act_off[j] = R.act_off[j]; out->act_dim[j] = R.act_dim[j];
-        out->next_obs_off[j] = R.nobs_off[j];
-    }
-    out->rew_off = R.rew_off;
-    out->done_off = R.done_off;
-    out->extra_off = R.extra_off;
-    out->extra = R.extra;
+    record_layout(e->h.rec, out);
     return FRL_OK;
 }
 

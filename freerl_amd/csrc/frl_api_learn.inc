@@ -1,64 +1,5 @@
-// frl_learn(): which kernel family an engine learns with, the ONE table of the families' kernels and LDS bytes (a new family is
-// registered there), a launcher per family, learn_impl and the work models.  Part of frl_api.hip.
-
-// ------------------------------------------------------------------------- shape predicates
-// One learner per workgroup, register-chained, Adam fused (kernels_critic2.hip / kernels_actor2.hip): the reference's standard
-// narrow shape at populations that give every CU a learner; everything else takes the row-chunk kernels + reduce / Adam
-// launches.  The family is chosen ONCE, at frl_create (chained_shape + population, FRL_CRITIC_V2=0/1 overrides the population
-// threshold — the tests run both families on the same inputs): the chained kernels keep the nets in fragment-image order in
-// HBM (NetDesc::frag), which the row-chunk kernels do not read.
-static bool chained_shape(const EngineDesc& h) {
-    const NetDesc &NA0 = h.net[0], &NC0 = h.net[1];
-    auto packed = [](const NetDesc& N) {          // every head block at the offsets the kernels hard-code (frl_desc.h: kL1w ...)
-        for (int hd = 0; hd < N.heads; ++hd) {
-            const LayerDesc* L = N.L + 3 * hd;
-            const int b = hd * kHeadFloats;
-            if (L[0].w_off != b + kL1w || L[0].b_off != b + kL1b || L[1].w_off != b + kL2w || L[1].b_off != b + kL2b ||
-                L[2].w_off != b + kL3w || L[2].b_off != b + kL3b) return false;
-        }
-        return N.extra_n == 0 || (N.heads == 1 && N.extra_off == kHeadFloats);
-    };
-    if (NA0.n_layers != 3 || NC0.n_layers != 3 * NC0.heads || h.hidden != 128 || !packed(NA0) || !packed(NC0)) return false;
-    // ([s | a] as one aligned slice of the record: the chained kernels read a lane's four columns of it as one dwordx4)
-    if (h.rec.obs_off[0] % 4 != 0 || h.rec.act_off[0] != h.rec.obs_off[0] + h.rec.obs_dim[0] || h.rec.obs_off[0] + 16 > h.rec.stride) return false;
-    return (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) && h.n_agents == 1 &&
-           NA0.L[0].k_pad == 16 && NC0.L[0].k_pad == 16 && h.rec.act_dim[0] <= 4 && NA0.L[2].n_pad == 16 &&
-           h.batch_max <= 256 && NA0.hidden_act == ACT_RELU && NC0.hidden_act == ACT_RELU;
-}
-// The K-sliced chained family (device/chain_wide.hpp): the reference's hidden-128 ReLU actor-critic nets with first layers of up
-// to 416 input columns and actor heads of up to 32 outputs that chained_shape() does not admit — SAC / TD3 / DDPG on wide
-// observations (config 4: Humanoid's 376 + 17), MADDPG_simple's per-agent actors and centralised critics (config 5).
-// MATD3 (MATD3_simple.py:195-262) is the same launch pair with twin critics, set j of the unit's noise on agent j's target action
-// and the host's delayed actor / soft-update stages.
-static bool wide_shape(const EngineDesc& h) {
-    const bool single = (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) && h.n_agents == 1;
-    const bool multi = h.algo == ALGO_MADDPG && h.n_agents >= 1;
-    const int H = h.hidden;                    // 128: chain_wide.hpp; 256: chain_wide16.hpp
-    if (!(single || multi) || (H != 128 && H != 256) || h.rec.act_total > kWideApitch) return false;
-    // WideNet::stage_idx (chain_wide.hpp; also the hidden-256 kernels') copies the batch's ring indices into the 64 KB LDS union:
-    // 2 * kWideSlice = 16384 ints.  Larger batches stay with the row-chunk family.
-    if (h.batch_max > 2 * kWideSlice) return false;
-    const int nt3 = h.net[0].L[2].n_pad;
-    for (int j = 0; j < h.n_agents; ++j) {
-        const NetDesc &NA0 = h.net[2 * j], &NC0 = h.net[2 * j + 1];
-        if (NA0.n_layers != 3 || NA0.heads != 1 || NC0.n_layers != 3 * NC0.heads || NC0.heads != h.net[1].heads) return false;
-        if (NA0.hidden_act != ACT_RELU || NC0.hidden_act != ACT_RELU) return false;
-        if (NA0.L[0].k_pad > 16 * kWideMaxKB1 || NC0.L[0].k_pad > 16 * kWideMaxKB1) return false;
-        if (NA0.L[2].n_pad != nt3 || nt3 > 32) return false;                 // one head-tile count for every agent's actor
-        for (int hd = 0; hd < NC0.heads; ++hd)
-            if (NC0.L[3 * hd].n_pad != H || NC0.L[3 * hd + 1].n_pad != H || NC0.L[3 * hd + 1].k_pad != H || NC0.L[3 * hd + 2].n_pad != 16) return false;
-        if (NA0.L[0].n_pad != H || NA0.L[1].n_pad != H || NA0.L[1].k_pad != H) return false;
-    }
-    return true;
-}
-// kernels_dqn2.hip: the reference's Q-net (obs -> 128 -> n_actions, or the Dueling [V ; A] head) with the TD update of DQN.py and
-// DQN_with_tricks.py's Double / PER-weighted variants (PER's importance weights, mean or per-row, are applied in the launch); Noisy and
-// Categorical heads take the row-chunk chain.
-static bool dqn_fused_shape(const EngineDesc& h, int batch) {
-    const NetDesc& N = h.net[0];
-    return h.algo == ALGO_DQN && !h.noisy && !h.c51_atoms && h.hidden == 128 && N.n_layers == 2 &&
-           N.L[0].k_pad == 16 && N.L[1].n_pad == 16 && batch <= kDqn2Batch && !h.obs_norm_on && N.hidden_act == ACT_RELU;
-}
+// frl_learn(): the ONE table of the kernel families' kernels and LDS bytes (a new family is registered there; which family an engine
+// learns with is engine_plan.hpp's decision), a launcher per family, learn_impl and the work models.  Part of frl_api.hip.
 
 // --------------------------------------------------------------------------- the family table
 enum LearnKernelStage { LK_CRITIC, LK_CRITIC_NV, LK_ACTOR, LK_STEP };
@@ -66,15 +7,11 @@ struct LearnKernelRow {
     LearnFamily fam;
     int stage;          // LK_CRITIC_NV: the 8-wave chained critic with aligned next_obs / (reward, done) loads; LK_STEP: a whole policy step
     int sub;            // FAM_CHAINED: waves per workgroup; FAM_SOLO: workgroups per learner; FAM_SOLOW: 1 single-agent, 2 (learner, agent) units
-    int lds_bytes;      // dynamic LDS of the launch = the kernels' hipFuncAttributeMaxDynamicSharedMemorySize
+    int lds_bytes;      // dynamic LDS of the launch = the kernels' hipFuncAttributeMaxDynamicSharedMemorySize (engine_plan.hpp: family_lds_bytes)
     KernelPtr k[2][2];  // [critic heads - 1][16-column tiles of the actor head - 1]
 };
-constexpr int kLdsChain4 = critic2_lds_floats() * (int)sizeof(float), kLdsChain8 = critic8_lds_floats() * (int)sizeof(float);
-constexpr int kLdsSolo = std::max(solo_lds_floats(), critic2_lds_floats()) * (int)sizeof(float);      // (critic2: the rollout tail's act_frag_body)
-constexpr int kLdsSolow = solow_lds_floats() * (int)sizeof(float);
-constexpr int kLdsWide = wide_lds_floats() * (int)sizeof(float), kLdsWide16 = wide16_lds_floats_host() * (int)sizeof(float);
 static const LearnKernelRow kLearnKernels[] = {
-    {FAM_DQN_FUSED, LK_CRITIC, 0, dqn2_lds_floats() * (int)sizeof(float), {{dqn_fused_kernel, dqn_fused_kernel}, {dqn_fused_kernel, dqn_fused_kernel}}},
+    {FAM_DQN_FUSED, LK_CRITIC, 0, kLdsDqnFused, {{dqn_fused_kernel, dqn_fused_kernel}, {dqn_fused_kernel, dqn_fused_kernel}}},
     // the register-chained family: one workgroup per learner with the nets as LDS images (156 KB)
     {FAM_CHAINED, LK_CRITIC, 8, kLdsChain8, {{ac_critic_v2_single_kernel, ac_critic_v2_single_kernel}, {ac_critic_v2_twin_kernel, ac_critic_v2_twin_kernel}}},
     {FAM_CHAINED, LK_CRITIC_NV, 8, kLdsChain8, {{ac_critic_v2_single_nv_kernel, ac_critic_v2_single_nv_kernel}, {ac_critic_v2_twin_nv_kernel, ac_critic_v2_twin_nv_kernel}}},
@@ -120,89 +57,10 @@ static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, cons
     return K;
 }
 
-// ------------------------------------------------------------------------- family selection
-// The chained family of the engine (and with it the parameter layout in HBM), fixed for the engine's life: sets h.solo / h.solow /
-// h.wide (+ its scratch geometry), NetDesc::frag and e->solow_row_wgs.  FAM_ROWCHUNK: none.
-static LearnFamily choose_engine_family(frl_engine* e) {
-    EngineDesc& h = e->h;
-    if (!e->has_nets) return FAM_ROWCHUNK;
-    // (FRL_SOLOW_NARROW=1, developer knob: the narrow standard shape on kernels_solow.hip — one first-layer k-tile — for A/Bs against kernels_solo.hip)
-    if (chained_shape(h) && !env_flag("FRL_SOLOW_NARROW", false)) {
-        const bool named = env_set("FRL_CRITIC_V2");
-        // measured (bench workload, updates/s): 128 learners are exactly one round of the row-chunk kernels' 512 resident
-        // workgroups — 484 k against 373 k for 128 one-learner workgroups on half the CUs; from 129 up the chained kernels win
-        // (160: 459 k / 393 k, 256: 694 k / 566 k) or tie (320: 472 k / 480 k)
-        // up to kSoloMaxP learners: one learner on sixteen workgroups (kernels_solo.hip; FRL_SOLO=0/1 overrides, FRL_CRITIC_V2 set
-        // means the caller asked for one of the other two families by name)
-        // (every one of its P x 16 workgroups — 156 KB of LDS each: one per CU — has to be RESIDENT: they wait for each other's flags.
-        //  On a device with fewer CUs, a CU-masked or partitioned one, the row-chunk kernels take the engine instead)
-        // h.solo = workgroups per learner: 16 (one 16-row tile each) up to 16 learners; 8 (two tiles each, a slab per tile) up to 32
-        // learners — populations the row-chunk kernels used to take at 150-160 us per learn() (kernels_solo.hip has the numbers;
-        // FRL_SOLO_MAXP: the largest population on this family, default 32)
-        const int solo_maxp = std::min(env_int("FRL_SOLO_MAXP", 2 * kSoloMaxP), 2 * kSoloMaxP);
-        int wgs = 0;
-        for (int cand : {16, 8})
-            if (wgs == 0 && (long long)h.P * cand <= e->n_cus && h.P * cand <= kSoloMaxP * kSoloWG) wgs = cand;
-        const bool solo_fits = wgs > 0 && h.P <= solo_maxp && e->lds_per_cu >= kLdsSolo;
-        h.solo = env_flag("FRL_SOLO", !named) && solo_fits ? wgs : 0;
-        if (h.solo || env_flag("FRL_CRITIC_V2", h.P > 128)) h.net[0].frag = h.net[1].frag = 1;
-        return h.solo ? FAM_SOLO : h.net[0].frag ? FAM_CHAINED : FAM_ROWCHUNK;
-    }
-    if (!wide_shape(h)) return FAM_ROWCHUNK;
-    // the K-sliced chained family (kernels_criticw.hip / kernels_actorw.hip): one workgroup per (learner, agent)
-    const bool named = env_set("FRL_CRITIC_V2");
-    // a handful of single-agent learners at hidden 128: sixteen workgroups per learner, W1 streamed from the block (kernels_solow.hip;
-    // FRL_SOLOW=0/1 overrides, FRL_CRITIC_V2 set means the caller asked for one of the other two families by name).  Every one of
-    // the P x 16 workgroups has to be resident, as for kernels_solo.hip.  [s | a] must be the record's first columns, 16-byte aligned
-    // ... MADDPG / MATD3 (config 5: three agents, batches of 1024): a unit = (learner, agent), 64 row tiles = 64 workgroups per unit; the
-    // updating agent's own observation rows sit behind the joint rows in LDS, so both first layers have at most kSoloWActorBase k-tiles
-    bool solow_shape = h.hidden == 128 && h.batch_max <= (h.n_agents == 1 ? 256 : 1024) && h.rec.stride % 4 == 0 && h.rec.obs_off[0] % 4 == 0 &&
-                       h.rec.act_off[0] == h.rec.obs_off[0] + h.rec.obs_total;
-    for (int i = 0; i < h.n_nets; ++i) solow_shape = solow_shape && h.net[i].L[0].k_pad <= 16 * (h.n_agents == 1 ? kSoloWMaxKB : kSoloWActorBase);
-    const int solow_tiles = h.batch_max <= 256 ? kSoloWG : 4 * kSoloWG;
-    const long long solow_units = (long long)h.P * h.n_agents;
-    // (two row tiles per workgroup for 17 .. 32 units: measured level with the row-chunk chain — kernels_solow.hip — and not built)
-    const int solow_rw = solow_tiles;
-    const bool solow_fits = solow_units <= kSoloMaxP && solow_units * solow_rw <= e->n_cus && e->lds_per_cu >= kLdsSolow + 256;
-    if (env_flag("FRL_SOLOW", !named) && solow_shape && solow_fits) {
-        for (int i = 0; i < h.n_nets; ++i) h.net[i].frag = 1;
-        h.solow = solow_tiles;
-        e->solow_row_wgs = solow_rw;
-        return FAM_SOLOW;
-    }
-    // from 129 (learner, agent) units up: hidden 128 (chain_wide.hpp) SAC at Humanoid dims 85.5 TFLOP/s against the row-chunk
-    // kernels' 46.2, MADDPG simple_spread 77.2 / 55.5; hidden 256 (chain_wide16.hpp: x-stationary sweeps) 71.1 / 56.9
-    // (profiles/r04, DESIGN.md 8)
-    // (profiles/r04/family_crossover.txt: hidden 128 ties at ~110-129 units; hidden 256 at 128 units 38.9 against 53.1, at 192
-    // 55.3 / 51.5, at 256 68.0 / 55.7 — its workgroups are twice as long, so the half-empty chip costs more: from 177 up)
-    if (!env_flag("FRL_CRITIC_V2", (long long)h.P * h.n_agents > (h.hidden == 256 ? 176 : 128))) return FAM_ROWCHUNK;
-    for (int i = 0; i < h.n_nets; ++i) h.net[i].frag = 1;
-    h.wide = h.hidden == 256 ? 2 : 1;
-    h.wide_bm = h.wide == 2 ? (h.batch_max + 255) / 256 * 256 : (h.batch_max + 63) / 64 * 64;      // (hidden 256 works in super-chunks of 256 rows)
-    h.wide_xp = h.net[1].L[0].k_pad;
-    h.wide_op = 16;
-    for (int j = 0; j < h.n_agents; ++j) h.wide_op = std::max(h.wide_op, h.net[2 * j].L[0].k_pad);
-    h.wide_unit = ((h.wide_xp + h.n_agents * h.wide_op + (h.wide == 2 ? kWide16ScratchPerRowHost : kWideScratchPerRow)) * h.wide_bm + 128 + 63) / 64 * 64;
-    return h.wide == 2 ? FAM_WIDE16 : FAM_WIDE;
-}
-
-// The family THIS call runs: Batch_ObsNorm can be switched on after create and FRL_DQN_FUSED=0/1 is a per-call override.  The narrow
-// families take batches of up to 256 rows; the others any batch <= batch_max (super-chunks of 256 rows / a 16-row tile per workgroup).
-static LearnFamily learn_family(const frl_engine* e, int batch) {
-    const EngineDesc& h = e->h;
-    if (dqn_fused_shape(h, batch) && env_flag("FRL_DQN_FUSED", true)) return FAM_DQN_FUSED;
-    const bool narrow = e->family == FAM_CHAINED || e->family == FAM_SOLO;
-    return (h.obs_norm_on || (narrow && batch > 256)) ? FAM_ROWCHUNK : e->family;
-}
-
-// workgroups per learner of the one-launch DQN update (kernels_dqn2.hip).  A few learners: one 64-row chunk per workgroup (the
-// last to arrive reduces and steps); populations: one workgroup each (measured: P = 64 x 4 workgroups 74 us, x 1 45 us).
-static int dqn_split_for(const EngineDesc& h, int batch, int pc) {
-    const int nchunks = (batch + 63) / 64;
-    int split = (pc <= 16) ? std::min(std::min(4, nchunks), h.S) : 1;
-    if (env_set("FRL_DQN_SPLIT")) split = std::max(1, std::min(std::min(env_int("FRL_DQN_SPLIT", 0), nchunks), h.S));
-    return split;
-}
+// The family THIS call runs and the workgroups per learner of its one-launch DQN update (engine_plan.hpp), under the per-call knobs
+// FRL_DQN_FUSED=0/1 and FRL_DQN_SPLIT
+static LearnFamily learn_family(const frl_engine* e, int batch) { return learn_family(e->h, e->family, batch, env_flag("FRL_DQN_FUSED", true)); }
+static int dqn_split_for(const EngineDesc& h, int batch, int pc) { return dqn_split_for(h, batch, pc, env_set("FRL_DQN_SPLIT") ? env_int("FRL_DQN_SPLIT", 0) : -1); }
 
 // frl_learn_path / frl_learn_work / frl_learn_work_executed describe frl_learn(): not the engines that learn through another entry point
 // (a PPO engine: frl_learn_path has always said FRL_ERR_INVALID, the work models report no work; a replay-only engine is let through)
@@ -217,19 +75,10 @@ extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, 
     const EngineDesc& h = e->h;
     if (const int rc = describes_learn_guard(h, "frl_learn_path", true)) return rc;
     if (batch <= 0 || batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch out of range");
-    const LearnFamily fam = learn_family(e, batch);
-    int bytes = e->kern.lds_bytes, rows = batch;
-    switch (fam) {
-        case FAM_ROWCHUNK: bytes = e->lds_bytes; rows = h.rc; break;
-        case FAM_DQN_FUSED: { const int sp = dqn_split_for(h, batch, h.P); rows = std::min(((batch + 63) / 64 + sp - 1) / sp * 64, batch); break; }
-        // kernels_solo.hip: 16-row tiles, 16 / h.solo of them per workgroup (its own carve; the launch carries the rollout tail's on top)
-        case FAM_SOLO: bytes = solo_lds_floats() * (int)sizeof(float); rows = 16 * (kSoloWG / h.solo); break;
-        case FAM_SOLOW: rows = 16 * (h.solow / std::max(1, e->solow_row_wgs)); break;      // one 16-row tile per workgroup
-        default: break;                                                                      // one workgroup per unit walks the batch
-    }
-    if (chained_out) *chained_out = fam != FAM_ROWCHUNK;
-    if (bytes_out) *bytes_out = bytes;
-    if (rows_out) *rows_out = rows;
+    const LearnPath path = learn_path(h, *e, learn_family(e, batch), batch, dqn_split_for(h, batch, h.P));
+    if (chained_out) *chained_out = path.chained;
+    if (bytes_out) *bytes_out = path.bytes;
+    if (rows_out) *rows_out = path.rows;
     return FRL_OK;
 }
 

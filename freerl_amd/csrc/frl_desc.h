@@ -45,6 +45,16 @@ struct NetDesc {
 constexpr int kL1w = 0, kL1b = kL1w + 128 * 16, kL2w = kL1b + 128, kL2b = kL2w + 128 * 128, kL3w = kL2b + 128,
               kL3b = kL3w + 16 * 128, kHeadFloats = kL3b + 16;
 
+// What the host's engine plan (engine_plan.hpp) sizes buffers and LDS by, next to the kernels that use it
+constexpr int kAdamVec = 8;              // kernels_update.hip: float4 per thread per workgroup (reduce_kernel / adam_kernel)
+constexpr int kSacdMaxActions = 64;      // kernels_sacd.hip and the other kernels whose threads walk a row's head columns: at most this many
+// kernels_critic2.hip / kernels_actor2.hip: the register-chained workgroups' carve
+constexpr int critic2_lds_floats() { return 8 * 256 + 64 * 256 + 8 * 256 + 2 * 8192 + 128 + 128 + 16 + 16 + 256 * 4 + 3 * 256 + 64; }
+constexpr int critic8_lds_floats() { return critic2_lds_floats() + 1024; }      // the eight-wave workgroups' carve (device/chain_net.hpp: chain8_lds_floats)
+// kernels_dqn2.hip: the one-launch DQN update
+constexpr int kDqn2Batch = 256;
+constexpr int dqn2_lds_floats() { return 4 * 8 * 256 + 8 * 4 * 256 + 4 * 256 + 2 * (128 + 16) + 64 + 64 * 16 + 2 * kDqn2Batch; }
+
 constexpr int kDrawTableHost = 8192;     // ints per half of draw_indices' duplicate table (device/net.hpp: kDrawTable), batches of 257 .. 2048 rows
 
 // One learner on sixteen workgroups (device/solo.hpp, kernels_solo.hip): the single-learner latency path

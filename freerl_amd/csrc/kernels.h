@@ -121,7 +121,7 @@ struct AdamArgs {
     int ragged;          // 1 (frl_reinforce_learn): learner p's batch is its own EngineDesc::ep_n[p] rows — its slabs are the workgroups that
                          // had rows, and a learner with none is skipped whole (slabs, step count, moments, statistics untouched)
 };
-constexpr int kAdamVec = 8;                              // float4 per thread per workgroup (reduce_kernel / adam_kernel)
+// (kAdamVec, float4 per thread per workgroup of reduce_kernel / adam_kernel: frl_desc.h)
 constexpr int kFusedThreads = 1024, kFusedVec = 12;      // adam_fused_kernel: one workgroup per net, gradient in registers
 constexpr int kFusedVecWide = 18;                        // adam_fused_wide_kernel: nets up to 73 k parameters (element-major slab sums)
 
@@ -139,7 +139,6 @@ __global__ void c51_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, 
 __global__ void ac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 
 // kernels_sacd.hip: discrete SAC (SAC_file/SAC_add_discrete.py), row-chunk gradient kernels
-constexpr int kSacdMaxActions = 64;
 __global__ void sacd_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 __global__ void sacd_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 
@@ -262,8 +261,6 @@ __global__ void ac_critic_v2_single_nv_kernel(const EngineDesc* __restrict__ Dp,
 // (round 2-5's four-wave form of the same stage, one wave per SIMD: FRL_CHAIN_WAVES=4, same-box A/B runs)
 __global__ void ac_critic_v2w4_twin_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);
 __global__ void ac_critic_v2w4_single_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);
-constexpr int critic2_lds_floats() { return 8 * 256 + 64 * 256 + 8 * 256 + 2 * 8192 + 128 + 128 + 16 + 16 + 256 * 4 + 3 * 256 + 64; }
-constexpr int critic8_lds_floats() { return critic2_lds_floats() + 1024; }      // the eight-wave workgroups' carve (device/chain_net.hpp: chain8_lds_floats)
 
 // kernels_criticw.hip / kernels_actorw.hip: the same two stages on the K-sliced chained design (device/chain_wide.hpp) for wide
 // first layers / heads and multi-agent critics; h<critic heads>a<actor head tiles>
@@ -353,8 +350,6 @@ __global__ void solow_step_h1a2_kernel(const EngineDesc* __restrict__ Dp, LearnA
 __global__ void solow_step_h2a1_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, SoloArgs s);
 __global__ void solow_step_h2a2_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, SoloArgs s);
 // kernels_dqn2.hip: draw + DQN / Double-DQN update + Adam + soft update of one learner in one launch
-constexpr int kDqn2Batch = 256;
-constexpr int dqn2_lds_floats() { return 4 * 8 * 256 + 8 * 4 * 256 + 4 * 256 + 2 * (128 + 16) + 64 + 64 * 16 + 2 * kDqn2Batch; }
 // The rollout loop's neighbours of learn() folded into the same launch (frl_rollout, DQN.py:294-339): add() of the vector
 // step's transitions before the sample, select_action + epsilon-greedy on the post-update net for the next step after it.
 struct DqnStepArgs {

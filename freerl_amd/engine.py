@@ -16,40 +16,50 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def make_config(algo, obs_dim, act_dim, capacity, *, n_learners=1, discrete=False, hidden=128,
+                hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0,
+                state_dim=0, state_rows=N.STATE_ROWS_POSITION):
+    """Engine's arguments as what frl_create / frl_create_ex take: (Config, ConfigExt or None).  Loads no library."""
+    obs_dim = list(obs_dim) if isinstance(obs_dim, (list, tuple)) else [int(obs_dim)]
+    act_dim = list(act_dim) if isinstance(act_dim, (list, tuple)) else [int(act_dim)]
+    assert len(obs_dim) == len(act_dim)
+    cfg = N.Config()
+    cfg.algo, cfg.n_learners, cfg.n_agents = int(algo), int(n_learners), len(obs_dim)
+    for j, (o, a) in enumerate(zip(obs_dim, act_dim)):
+        cfg.obs_dim[j], cfg.act_dim[j] = int(o), int(a)
+    cfg.discrete, cfg.hidden, cfg.hidden_act = int(bool(discrete)), int(hidden), int(hidden_act)
+    cfg.twin_critic, cfg.capacity, cfg.batch_max = int(bool(twin_critic)), int(capacity), int(batch_max)
+    cfg.extra_cols, cfg.device_id, cfg.seed = int(extra_cols), int(device_id), int(seed) & (2 ** 64 - 1)
+    cfg.actor_dist, cfg.dueling, cfg.noisy = int(actor_dist), int(bool(dueling)), int(bool(noisy))
+    cfg.reward_dim = int(reward_dim)          # envelope DQN / DDPG: objectives (0 = 1; ignored by the other algorithms)
+    if c51 is not None:                     # (atoms, v_min, v_max)
+        cfg.c51_atoms, cfg.c51_vmin, cfg.c51_vmax = int(c51[0]), float(c51[1]), float(c51[2])
+    if state_rows and not state_dim:
+        raise ValueError("state_rows %r without a state_dim: there is no state block to pair" % (state_rows,))
+    # a global-state critic (FRL_ALGO_MAPPO): frl_config cannot grow, the extension block can
+    return cfg, (N.ConfigExt(C.sizeof(N.ConfigExt), int(state_dim), int(state_rows)) if state_dim else None)
+
+
 class Engine:
     def __init__(self, algo, obs_dim, act_dim, capacity, *, n_learners=1, discrete=False, hidden=128,
                  hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0,
                  state_dim=0, state_rows=N.STATE_ROWS_POSITION):
-        obs_dim = list(obs_dim) if isinstance(obs_dim, (list, tuple)) else [int(obs_dim)]
-        act_dim = list(act_dim) if isinstance(act_dim, (list, tuple)) else [int(act_dim)]
-        assert len(obs_dim) == len(act_dim)
-        cfg = N.Config()
-        cfg.algo, cfg.n_learners, cfg.n_agents = int(algo), int(n_learners), len(obs_dim)
-        for j, (o, a) in enumerate(zip(obs_dim, act_dim)):
-            cfg.obs_dim[j], cfg.act_dim[j] = int(o), int(a)
-        cfg.discrete, cfg.hidden, cfg.hidden_act = int(bool(discrete)), int(hidden), int(hidden_act)
-        cfg.twin_critic, cfg.capacity, cfg.batch_max = int(bool(twin_critic)), int(capacity), int(batch_max)
-        cfg.extra_cols, cfg.device_id, cfg.seed = int(extra_cols), int(device_id), int(seed) & (2 ** 64 - 1)
-        cfg.actor_dist, cfg.dueling, cfg.noisy = int(actor_dist), int(bool(dueling)), int(bool(noisy))
-        cfg.reward_dim = int(reward_dim)          # envelope DQN / DDPG: objectives (0 = 1; ignored by the other algorithms)
-        if c51 is not None:                     # (atoms, v_min, v_max)
-            cfg.c51_atoms, cfg.c51_vmin, cfg.c51_vmax = int(c51[0]), float(c51[1]), float(c51[2])
+        cfg, ext = make_config(algo, obs_dim, act_dim, capacity, n_learners=n_learners, discrete=discrete, hidden=hidden, hidden_act=hidden_act,
+                               twin_critic=twin_critic, batch_max=batch_max, extra_cols=extra_cols, device_id=device_id, seed=seed, actor_dist=actor_dist,
+                               dueling=dueling, noisy=noisy, c51=c51, reward_dim=reward_dim, state_dim=state_dim, state_rows=state_rows)
         self._L = N.lib()
         h = C.c_void_p()
-        if state_rows and not state_dim:
-            raise ValueError("state_rows %r without a state_dim: there is no state block to pair" % (state_rows,))
-        if state_dim:                           # a global-state critic (FRL_ALGO_MAPPO): frl_config cannot grow, the extension block can
-            ext = N.ConfigExt(C.sizeof(N.ConfigExt), int(state_dim), int(state_rows))
+        if ext is not None:
             N.check(self._L.frl_create_ex(C.byref(cfg), C.byref(ext), C.byref(h)))
         else:
             N.check(self._L.frl_create(C.byref(cfg), C.byref(h)))
         self._h = h
         self.cfg = cfg
         self.algo = int(algo)
-        self.P = int(n_learners)
-        self.n_agents = len(obs_dim)
-        self.capacity = int(capacity)
-        self.batch_max = int(batch_max)
+        self.P = cfg.n_learners
+        self.n_agents = cfg.n_agents
+        self.capacity = cfg.capacity
+        self.batch_max = cfg.batch_max
         lay = N.RecordLayout()
         N.check(self._L.frl_record_layout_get(self._h, C.byref(lay)))
         self.layout = lay
