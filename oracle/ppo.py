@@ -72,6 +72,23 @@ class PPO:
         self.buffer = (BufferForPPO2 if rollout_values else BufferForPPO)(horizon, obs_dim, 1 if discrete else act_dim)
         self.actor_losses, self.critic_losses = [], []
         self.adv_raw = self.v_target = None
+        # test infrastructure: set to a list and every actor step appends its per-row (ratio, surr1 > surr2, raw log_std or None)
+        self.ratio_log = None
+        # ... and to a list: every actor and critic step appends the smallest |pre-activation| of its ReLU layers (the kink)
+        self.preact_log = None
+
+    def _log_preact(self, mlp, p, acts):
+        if self.preact_log is None:
+            return
+        L = len(mlp.names)
+        for i, n in enumerate(mlp.names):
+            if (mlp.hidden_act if i < L - 1 else mlp.out_act) == "relu":
+                self.preact_log.append(float(np.abs(nn.linear(acts[i], p, n)).min()))
+
+    def _log_ratio(self, ratio, surr1, surr2):
+        if self.ratio_log is not None:
+            ls = None if (self.discrete or self.beta) else self.actor["log_std"].reshape(-1).copy()
+            self.ratio_log.append((np.asarray(ratio, F32).reshape(-1).copy(), (surr1 > surr2).reshape(-1), ls))
 
     def _dist(self, obs):
         mean, acts = self.pi.forward({k: v for k, v in self.actor.items() if k != "log_std"}, obs)
@@ -109,6 +126,7 @@ class PPO:
         from scipy.special import digamma, gammaln, polygamma
         mb = obs.shape[0]
         al32, be32, (h, tacts, za, zb) = self._alpha_beta(obs)
+        self._log_preact(self.trunk, self.actor, tacts)
         al, be, x = al32.astype(np.float64), be32.astype(np.float64), action.astype(np.float64)
         lB = gammaln(al) + gammaln(be) - gammaln(al + be)
         logp = (al - 1) * np.log(x) + (be - 1) * np.log1p(-x) - lB
@@ -117,6 +135,7 @@ class PPO:
         surr1 = ratio * A
         surr2 = np.clip(ratio, 1 - clip_param, 1 + clip_param).astype(F32) * A
         aloss = F32(-np.mean(np.minimum(surr1, surr2), dtype=F32) - F32(ent_coef) * F32(np.mean(ent)))
+        self._log_ratio(ratio, surr1, surr2)
         coef = (np.where(surr1 <= surr2, A, F32(0)) * F32(-1.0 / mb) * ratio).astype(np.float64)
         ce = ent_coef / mb
         psi_ab, tri_ab = digamma(al + be), polygamma(1, al + be)
@@ -197,6 +216,7 @@ class PPO:
                 # ---- actor (:324-346)
                 body = {kk: vv for kk, vv in self.actor.items() if kk != "log_std"}
                 mean, acts = self.pi.forward(body, obs[ix])
+                self._log_preact(self.pi, body, acts)
                 raw = self.actor["log_std"]
                 log_std = np.clip(np.broadcast_to(raw, mean.shape), -20, 2).astype(F32)
                 std = np.exp(log_std)
@@ -209,6 +229,7 @@ class PPO:
                 surr1 = ratio * A
                 surr2 = np.clip(ratio, 1 - clip_param, 1 + clip_param).astype(F32) * A
                 aloss = F32(-np.mean(np.minimum(surr1, surr2), dtype=F32) - F32(ent_coef) * np.mean(ent, dtype=F32))
+                self._log_ratio(ratio, surr1, surr2)
                 # backward: d min / d ratio = A where surr1 <= surr2 (ties: both branches pass
                 # the clamp, half each, summing to A), else 0 (clamped branch has zero slope)
                 dratio = np.where(surr1 <= surr2, A, F32(0)) * F32(-1.0 / mb)
@@ -228,6 +249,7 @@ class PPO:
     def _critic_step(self, obs, v_target):
         """critic (:349-351): mse(v_target[idx], V(obs[idx]))"""
         v_s, vacts = self.v.forward(self.critic, obs)
+        self._log_preact(self.v, self.critic, vacts)
         closs, dv = nn.mse(v_s, v_target)
         _, gc = self.v.backward(self.critic, vacts, dv, need_dx=False)
         gc = {kk: gc[kk] for kk in self.critic}
@@ -240,6 +262,7 @@ class PPO:
         log-prob from the clamped, renormalised probabilities."""
         mb = obs.shape[0]
         z, acts = self.pi.forward(self.actor, obs)
+        self._log_preact(self.pi, self.actor, acts)
         zs = z - z.max(axis=1, keepdims=True)
         e = np.exp(zs)
         p = (e / e.sum(axis=1, keepdims=True)).astype(F32)
@@ -253,6 +276,7 @@ class PPO:
         surr1 = ratio * A
         surr2 = np.clip(ratio, 1 - clip_param, 1 + clip_param).astype(F32) * A
         aloss = F32(-np.mean(np.minimum(surr1, surr2), dtype=F32) - F32(ent_coef) * np.mean(ent, dtype=F32))
+        self._log_ratio(ratio, surr1, surr2)
         coef = np.where(surr1 <= surr2, A, F32(0)) * F32(-1.0 / mb) * ratio
         onehot = np.zeros_like(p)
         onehot[np.arange(mb), a] = 1

@@ -291,9 +291,9 @@ def ppo_inputs(c):
     tab["logp"] = (-0.5 * g.standard_normal((T, A)) ** 2 - 0.9).astype(np.float32)  # stored per dim
     # adv_done = terminated or truncated (PPO_with_tricks.py:291-295)
     tab["adv_done"] = np.logical_or(tab["done"], g.random(T) < 0.03)
-    actor = synth.mlp_params(c["param_seed"], actor_layers(O, A, head="mean_layer"))
+    actor = synth.mlp_params(c["param_seed"], actor_layers(O, A, head="mean_layer", hidden=c.get("hidden", H)))
     actor = dict([("log_std", g.uniform(-0.5, 0.3, (1, A)).astype(np.float32))] + list(actor.items()))
-    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O))
+    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O, hidden=c.get("hidden", H)))
     perms = [synth.permutation(c["perm_seed"] + k, T) for k in range(c["k_epochs"])]
     if "last_value" in c:                      # PPO_2: the critic's value of each step as select_action returned it
         tab["value"] = (0.8 * g.standard_normal(T)).astype(np.float32)
@@ -316,9 +316,9 @@ def ppo_beta_inputs(c):
     tab["act"] = g.uniform(0.03, 0.97, (T, A)).astype(np.float32)        # Beta samples live in (0, 1)
     tab["logp"] = (0.4 * g.standard_normal((T, A)) + 0.1).astype(np.float32)
     tab["adv_done"] = np.logical_or(tab["done"], g.random(T) < 0.03)
-    H_ = H
+    H_ = c.get("hidden", H)
     actor = synth.mlp_params(c["param_seed"], [("l1", H_, O), ("l2", H_, H_), ("alpha_layer", A, H_), ("beta_layer", A, H_)])
-    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O))
+    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O, hidden=H_))
     perms = [synth.permutation(c["perm_seed"] + k, T) for k in range(c["k_epochs"])]
     return dict(table=tab, params=dict(actor=actor, critic=critic), perms=perms)
 
@@ -329,11 +329,11 @@ def ppo_discrete_inputs(c):
     g = np.random.default_rng(c["table_seed"] + 1)
     tab["logp"] = (-np.abs(g.standard_normal((T, 1))) - 0.7).astype(np.float32)    # one stored log-prob per step
     tab["adv_done"] = np.logical_or(tab["done"], g.random(T) < 0.03)
-    actor = synth.mlp_params(c["param_seed"], actor_layers(O, nA, head="l3"))
+    actor = synth.mlp_params(c["param_seed"], actor_layers(O, nA, head="l3", hidden=c.get("hidden", H)))
     if c.get("logit_gain"):
         actor["l3.weight"] = (actor["l3.weight"] * np.float32(c["logit_gain"])).astype(np.float32)
         actor["l3.bias"] = (actor["l3.bias"] * np.float32(c["logit_gain"])).astype(np.float32)
-    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O))
+    critic = synth.mlp_params(c["param_seed"] + 1, critic_layers(O, hidden=c.get("hidden", H)))
     perms = [synth.permutation(c["perm_seed"] + k, T) for k in range(c["k_epochs"])]
     return dict(table=tab, params=dict(actor=actor, critic=critic), perms=perms)
 
