@@ -29,6 +29,7 @@ ALGO_ENVELOPE_DDPG = 9
 ALGO_GAIL = 10
 ALGO_MAPPO, ALGO_IPPO = 11, 12
 ALGO_HAPPO = 13
+ALGO_MADDPG_ATT = 14        # MADDPG_simple_with_tricks.py, trick['ATT']: a MADDPG engine whose critics are attention critics (frl_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only

@@ -53,21 +53,25 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"MAPPO",          "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"IPPO",           "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"HAPPO",          "frl_happo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
+    {"ATT-MADDPG",     kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
 };
+inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_HAPPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MADDPG_ATT - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
 // plan_engine fixes the engine's chained family — or none: FAM_ROWCHUNK — with its parameter layout; learn_family() says what one call takes.
-enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16 };
+// FAM_ATT: the attention critic's row-chunk kernels (kernels_att.hip) — what every FRL_ALGO_MADDPG_ATT engine learns with, and nothing else does
+enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16, FAM_ATT };
 // dynamic LDS of a family's launches = its kernels' hipFuncAttributeMaxDynamicSharedMemorySize
 constexpr int kLdsDqnFused = dqn2_lds_floats() * (int)sizeof(float);
 constexpr int kLdsChain4 = critic2_lds_floats() * (int)sizeof(float), kLdsChain8 = critic8_lds_floats() * (int)sizeof(float);
 constexpr int kLdsSolo = std::max(solo_lds_floats(), critic2_lds_floats()) * (int)sizeof(float);      // (critic2: the rollout tail's act_frag_body)
 constexpr int kLdsSolow = solow_lds_floats() * (int)sizeof(float);
 constexpr int kLdsWide = wide_lds_floats() * (int)sizeof(float), kLdsWide16 = wide16_lds_floats_host() * (int)sizeof(float);
+constexpr int kLdsAtt = 160 * 1024;       // the most a FAM_ATT launch may carve; a launch carves its engine's own row-chunk bytes (plan_sizes refuses more)
 
 struct PlanLimits {               // of the device
     int n_cus = 256;              // compute units (how many one-per-CU workgroups are resident at once)
@@ -269,6 +273,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
     EngineDesc& h = pl.h;
     const int n_cus = pl.n_cus, lds_per_cu = pl.lds_per_cu;
     if (!pl.has_nets) return FAM_ROWCHUNK;
+    if (h.algo == ALGO_MADDPG_ATT) return FAM_ATT;      // (no chained, solo, solow or wide kernel knows the attention critic: the shapes below never see it)
     const bool named = knobs.critic_v2 >= 0;
     if (chained_shape(h) && !knobs.solow_narrow) {
         // measured (bench workload, updates/s): 128 learners are exactly one round of the row-chunk kernels' 512 resident
@@ -332,6 +337,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
 // (super-chunks of 256 rows / a 16-row tile per workgroup).
 inline LearnFamily learn_family(const EngineDesc& h, LearnFamily family, int batch, bool dqn_fused_on) {
     if (dqn_fused_shape(h, batch) && dqn_fused_on) return FAM_DQN_FUSED;
+    if (family == FAM_ATT) return FAM_ATT;
     const bool narrow = family == FAM_CHAINED || family == FAM_SOLO;
     return (h.obs_norm_on || (narrow && batch > 256)) ? FAM_ROWCHUNK : family;
 }
@@ -355,6 +361,7 @@ inline int family_lds_bytes(LearnFamily fam, int chain_waves) {
         case FAM_SOLOW: return kLdsSolow;
         case FAM_WIDE: return kLdsWide;
         case FAM_WIDE16: return kLdsWide16;
+        case FAM_ATT: return kLdsAtt;
         case FAM_ROWCHUNK: break;
     }
     return 0;
@@ -365,14 +372,14 @@ struct LearnPath { bool chained; int bytes, rows; };
 inline LearnPath learn_path(const EngineDesc& h, const EngineFacts& f, LearnFamily fam, int batch, int dqn_split) {
     int bytes = family_lds_bytes(fam, f.chain_waves), rows = batch;
     switch (fam) {
-        case FAM_ROWCHUNK: bytes = f.lds_bytes; rows = h.rc; break;
+        case FAM_ROWCHUNK: case FAM_ATT: bytes = f.lds_bytes; rows = h.rc; break;      // (FAM_ATT: row chunks too, its own carve behind the common one)
         case FAM_DQN_FUSED: rows = std::min(((batch + 63) / 64 + dqn_split - 1) / dqn_split * 64, batch); break;
         // kernels_solo.hip: 16-row tiles, 16 / h.solo of them per workgroup (its own carve; the launch carries the rollout tail's on top)
         case FAM_SOLO: bytes = solo_lds_floats() * (int)sizeof(float); rows = 16 * (kSoloWG / h.solo); break;
         case FAM_SOLOW: rows = 16 * (h.solow / std::max(1, f.solow_row_wgs)); break;      // one 16-row tile per workgroup
         default: break;                                                                 // one workgroup per unit walks the batch
     }
-    return {fam != FAM_ROWCHUNK, bytes, rows};
+    return {fam != FAM_ROWCHUNK && fam != FAM_ATT, bytes, rows};
 }
 
 // ------------------------------------------------------------------------------- the plan
@@ -390,9 +397,9 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
         return plan_refuse(message, "state_dim %d: a global-state critic belongs to FRL_ALGO_MAPPO engines (MAPPO_for_mask_action_state.py); algo %d has none", state_dim, c.algo);
     if (c.n_learners < 1) return plan_refuse(message, "n_learners must be >= 1");
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
-    if (c.algo != FRL_ALGO_MADDPG && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
+    if (!is_maddpg(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_HAPPO) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MADDPG_ATT) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -433,6 +440,16 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
                 return plan_refuse(message, "%s: extra_cols %d != %d log-prob columns + %d adv_done columns", T.name, c.extra_cols, lp_cols, c.n_agents);
             return FRL_OK;      // (its hidden_act rule has covered FRL_ACT_LEAKY_RELU)
         }
+        case FRL_ALGO_MADDPG_ATT:
+            // what kernels_att.hip handles (ATT.py:181-229: the decoder reads the OTHER agents' actions; Critic_TD3 has no attention form)
+            if (c.n_agents < 2) return plan_refuse(message, "%s: n_agents %d < 2: the decoder's input is the other agents' actions and would be empty", T.name, c.n_agents);
+            if (c.twin_critic) return plan_refuse(message, "%s: twin_critic is refused (the attention critic has one Q head; MATD3 keeps the plain critic)", T.name);
+            if (c.discrete) return plan_refuse(message, "%s: discrete is refused (continuous actions only, as MADDPG_simple_with_tricks.py:139-144)", T.name);
+            if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0) return plan_refuse(message, "%s: dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
+            if (c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
+            if (h.hidden % 16 || h.hidden > 128)
+                return plan_refuse(message, "%s: hidden %d is refused: the row chunk's 16 rows of x_e, x_d, e, g, the %d heads, d, u, c and y fit a CU's LDS up to hidden 128", T.name, h.hidden, kAttHeads);
+            return FRL_OK;
         case FRL_ALGO_GAIL:     // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
             if (c.hidden_act == FRL_ACT_TANH) return plan_refuse(message, "GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
             return FRL_OK;
@@ -516,6 +533,16 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
                 build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, hact, ACT_TANH, c.act_dim[0]);
             build_net(h.net[1], {{H, c.obs_dim[0]}, {H, H}, {1, H}}, 1, hact, ACT_NONE, 0);
             break;
+        case FRL_ALGO_MADDPG_ATT:
+            // Actor (MADDPG_simple_with_tricks.py:57-69) as MADDPG's; ATT_critic (ATT.py:181-229) as the seven layers of AttLayer: the encoder
+            // reads [every observation | a_i], the decoder the other agents' actions, the four heads are one layer of 4 H outputs
+            h.n_nets = 2 * c.n_agents;
+            for (int j = 0; j < c.n_agents; ++j) {
+                build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, ACT_TANH, 0);
+                build_net(h.net[2 * j + 1], {{H, H}, {kAttHeads * H, H}, {H, H}, {H, R.obs_total + R.act_dim[j]}, {H, R.act_total - R.act_dim[j]}, {H, H}, {1, H}},
+                          1, ACT_RELU, ACT_NONE, 0);
+            }
+            break;
         default: {      // DDPG, TD3, SAC, MADDPG: an actor and a (twin) critic on the joint [obs | act] per agent
             h.n_nets = 2 * c.n_agents;
             const int cin = R.obs_total + R.act_total;
@@ -536,6 +563,10 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
         h.net_off[i] = off;
         off += h.net[i].size;
         const int nl = h.net[i].n_layers / h.net[i].heads;
+        if (c.algo == FRL_ALGO_MADDPG_ATT && (i & 1)) {      // no chain: xin holds x_e, the first-layer input of the encoder branch
+            kin = std::max(kin, h.net[i].L[ATT_E].k_pad);
+            continue;
+        }
         for (int hd = 0; hd < h.net[i].heads; ++hd) {
             kin = std::max(kin, h.net[i].L[hd * nl].k_pad);
             outp = std::max(outp, h.net[i].L[hd * nl + nl - 1].n_pad);
@@ -588,6 +619,12 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
             h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
             one_wg_per_net = whole_cu = true;
             break;
+        case FRL_ALGO_MADDPG_ATT: {      // device/att.hpp: carve_att behind the common carve
+            int xd = 16;
+            for (int j = 0; j < c.n_agents; ++j) xd = std::max(xd, h.net[2 * j + 1].L[ATT_D].k_pad);
+            h.lds_row_extra = att_row_extra(H, xd);
+            break;
+        }
         default: break;
     }
     h.rc = 64;
@@ -606,6 +643,12 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         if (!one_wg_per_net && h.rc == 64 && (long long)h.P * ((h.batch_max + 63) / 64) < 512) h.rc = 32;
     }
     if (knobs.rc == 16 || knobs.rc == 32 || knobs.rc == 64 || knobs.rc == 128) h.rc = knobs.rc;      // developer knob
+    if (c.algo == FRL_ALGO_MADDPG_ATT) {      // one workgroup per CU at 16 rows: the family's row chunk is a constant (DESIGN.md "ATT-MADDPG")
+        h.rc = kAttRc;
+        if (lds_bytes_for(h, h.rc) > kLdsAtt)
+            return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB (encoder input %d columns, decoder input at most %d)", T.name, lds_bytes_for(h, h.rc),
+                               h.lds_kin_pad, h.lds_row_extra - 4 - 4 * (H + 4) - (kAttHeads * H + 4));
+    }
     if (whole_cu && h.state_dim > 0 && lds_bytes_for(h, h.rc) > 160 * 1024)
         return plan_refuse(message, "%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns, %d of them the state's: state_dim)", T.name,
                            lds_bytes_for(h, h.rc), h.lds_kin_pad, h.state_dim);

@@ -47,6 +47,7 @@
 #include "kernels_happo.hip"
 #include "kernels_mappo_mask.hip"
 #include "kernels_mappo_state.hip"
+#include "kernels_att.hip"
 #endif
 
 using namespace frl;
@@ -92,17 +93,20 @@ using LearnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs);
 using SolowKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs);
 using SoloKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::SoloArgs, frl::SoloStepArgs);
 using DqnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, frl::DqnStepArgs);
+using RowKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs, int);      // the row-chunk launch shape: (unit, slab) workgroups, ns slabs per unit
 struct KernelPtr {                // one typed member per kernel signature; a family uses the one its kernels have
     LearnKernel k = nullptr;
     SolowKernel kw = nullptr;
     SoloKernel ks = nullptr;
     DqnKernel kd = nullptr;
+    RowKernel kr = nullptr;
     KernelPtr() = default;
+    KernelPtr(RowKernel f) : kr(f) {}
     KernelPtr(LearnKernel f) : k(f) {}
     KernelPtr(SolowKernel f) : kw(f) {}
     KernelPtr(SoloKernel f) : ks(f) {}
     KernelPtr(DqnKernel f) : kd(f) {}
-    const void* address() const { return k ? (const void*)k : kw ? (const void*)kw : ks ? (const void*)ks : (const void*)kd; }
+    const void* address() const { return k ? (const void*)k : kw ? (const void*)kw : ks ? (const void*)ks : kd ? (const void*)kd : (const void*)kr; }
 };
 struct LearnKernels {             // a family's kernels for one engine's shape (resolve_learn_kernels)
     KernelPtr critic, critic_nv, actor, step;
@@ -236,7 +240,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 109; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info
+extern "C" int frl_version(void) { return 110; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -417,7 +421,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)envelope_ddpg_actor_kernel, (const void*)gail_disc_kernel, (const void*)gail_forward_kernel, (const void*)act_kernel,
                               (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
                               (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel,
-                              (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel})
+                              (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
+                              (const void*)att_q_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -803,7 +808,9 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     const NetDesc& N = e->h.net[net];
     if (head < 0 || head >= N.heads) return fail(FRL_ERR_INVALID, "head out of range");
     const int nl = N.n_layers / N.heads;
-    if (in_dim != N.L[head * nl].k) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, N.L[head * nl].k);
+    // (an attention critic's rows are [all obs | all actions]: x_e and x_d are cut from them in the kernel)
+    const int want_in = (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total : N.L[head * nl].k;
+    if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
     if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0) return fail(FRL_ERR_INVALID, "net has no log_std");
     if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev && !(ex && ex->device_eps)) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE needs the Exp(1) draws in eps");
     if (n_rows < 1) return fail(FRL_ERR_INVALID, "n_rows must be >= 1");
@@ -833,6 +840,12 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (is_mappo_family(e->h.algo)) {        // the normalised forward (kernels_mappo.hip) in front of act_kernel's epilogue
         if (mode == FRL_ACT_SAC_SAMPLE || ex) return fail(FRL_ERR_INVALID, "a %s engine acts through FRL_ACT_RAW, _TANHHEAD, _ARGMAX, _PPO_SAMPLE or _CAT_SAMPLE", algo_traits(e->h.algo).name);
         hipLaunchKernelGGL(mappo_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
+    if (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) {      // the attention critic is no chain: its own forward (kernels_att.hip), Q of [all obs | all actions]
+        if (mode != FRL_ACT_RAW || ex) return fail(FRL_ERR_INVALID, "an ATT-MADDPG critic acts through FRL_ACT_RAW on rows [all obs | all actions] (its Q value)");
+        hipLaunchKernelGGL(att_q_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
         return FRL_OK;
     }
@@ -1110,6 +1123,7 @@ extern "C" int frl_timer_stop(frl_engine* e, float* ms_out) {
 extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
+    if (e->h.algo == ALGO_MADDPG_ATT) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MADDPG_simple_with_tricks.py has no Batch_ObsNorm and the attention critic's kernels do not normalise");
     if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
     if (on && e->h.net[0].frag) {
         // Batch_ObsNorm belongs to the row-chunk family: an engine created for the register-chained kernels (parameters in

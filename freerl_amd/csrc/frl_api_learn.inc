@@ -31,6 +31,9 @@ static const LearnKernelRow kLearnKernels[] = {
     {FAM_WIDE, LK_ACTOR, 0, kLdsWide, {{ac_actor_wide_a1_kernel, ac_actor_wide_a2_kernel}, {ac_actor_wide_a1_kernel, ac_actor_wide_a2_kernel}}},
     {FAM_WIDE16, LK_CRITIC, 0, kLdsWide16, {{ac_critic_x_h1a1_kernel, ac_critic_x_h1a2_kernel}, {ac_critic_x_h2a1_kernel, ac_critic_x_h2a2_kernel}}},
     {FAM_WIDE16, LK_ACTOR, 0, kLdsWide16, {{ac_actor_x_a1_kernel, ac_actor_x_a2_kernel}, {ac_actor_x_a1_kernel, ac_actor_x_a2_kernel}}},
+    // the attention critic of ATT-MADDPG on the row-chunk skeleton (kernels_att.hip): kLdsAtt is the launches' limit, a launch carves the engine's own bytes
+    {FAM_ATT, LK_CRITIC, 0, kLdsAtt, {{att_critic_kernel, att_critic_kernel}, {att_critic_kernel, att_critic_kernel}}},
+    {FAM_ATT, LK_ACTOR, 0, kLdsAtt, {{att_actor_kernel, att_actor_kernel}, {att_actor_kernel, att_actor_kernel}}},
 };
 
 // every kernel of the family may carve its row's LDS bytes, whichever of them the engine's shape resolves to
@@ -138,13 +141,15 @@ static void launch_dqn_fused(frl_engine* e, const LearnStage& s, LearnArgs a, co
 }
 
 // the row-chunk kernels: a gradient launch over (unit, slab) workgroups, then reduce + clip + Adam
-static void launch_rowchunk(frl_engine* e, const LearnStage& s, const LearnArgs& a) {
+// att: FAM_ATT's launcher — the same launch shape and the same reduce + clip + Adam behind the family's own gradient kernels
+static void launch_rowchunk(frl_engine* e, const LearnStage& s, const LearnArgs& a, bool att = false) {
     const EngineDesc& h = e->h;
-    const bool actor = s.stage == 1, sac = h.algo == ALGO_SAC || h.algo == ALGO_SAC_DISCRETE, maddpg = h.algo == ALGO_MADDPG;
+    const bool actor = s.stage == 1, sac = h.algo == ALGO_SAC || h.algo == ALGO_SAC_DISCRETE, maddpg = is_maddpg(h.algo);
     const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
     const dim3 grid_chunks(((s.units + 7) / 8) * 8 * ns), grid_adam(s.units * h.Gmax);
     auto k = actor ? (h.algo == ALGO_SAC_DISCRETE ? sacd_actor_kernel : ac_actor_kernel)
                    : (h.algo == ALGO_DQN ? (h.c51_atoms ? c51_grad_kernel : dqn_grad_kernel) : h.algo == ALGO_SAC_DISCRETE ? sacd_critic_kernel : ac_critic_kernel);
+    if (att) k = actor ? e->kern.actor.kr : e->kern.critic.kr;
     prof_begin(e, actor ? PK_GRAD_ACTOR : PK_GRAD_CRITIC);
     hipLaunchKernelGGL(k, grid_chunks, dim3(256), e->lds_bytes, s.st, e->d, a, ns);
     prof_end(e);
@@ -251,6 +256,9 @@ static void launch_solow(frl_engine* e, const LearnStage& s, const LearnArgs& a,
     prof_end(e);
 }
 
+// kernels_att.hip: ATT-MADDPG's gradient launches over (unit, slab) workgroups, then reduce + clip + Adam as the row-chunk family
+static void launch_att(frl_engine* e, const LearnStage& s, const LearnArgs& a) { launch_rowchunk(e, s, a, true); }
+
 static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, LearnArgs a, int stage, int p0, int pc, bool dev_rng, bool needs_noise,
                                const DqnStepArgs* step = nullptr, const SoloStepArgs* sstep = nullptr) {
     const EngineDesc& h = e->h;
@@ -280,6 +288,7 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, L
         case FAM_SOLO: launch_solo(e, s, a, sstep); break;
         case FAM_SOLOW: launch_solow(e, s, a, ma_predraw, ma_use_pre); break;
         case FAM_WIDE: case FAM_WIDE16: launch_wide(e, s, a); break;
+        case FAM_ATT: launch_att(e, s, a); break;
         case FAM_DQN_FUSED: break;
     }
 }
@@ -303,8 +312,9 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     const bool dev_rng = (args->idx == nullptr) && !args->per;
     if (dev_rng && min_size < 2 * args->batch)
         return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
-    const bool td3_like = (h.algo == ALGO_TD3 || h.algo == ALGO_MADDPG);       // MADDPG + noise/delay = MATD3_simple.py
+    const bool td3_like = (h.algo == ALGO_TD3 || is_maddpg(h.algo));           // MADDPG + noise/delay = MATD3_simple.py (ATT-MADDPG: do_actor only)
     const bool needs_noise = (h.algo == ALGO_SAC) || (td3_like && args->use_policy_noise);
+    if (h.algo == ALGO_MADDPG_ATT && args->use_policy_noise) return fail(FRL_ERR_INVALID, "ATT-MADDPG has no target policy smoothing: use_policy_noise must be 0");
     if (!dev_rng && needs_noise && !args->noise) return fail(FRL_ERR_INVALID, "idx given without noise: both or neither");
     int rc = flush_stage(e);
     if (rc) return rc;
@@ -344,7 +354,7 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     // the gradient kernel's (2 x 80 KB of LDS and 448 of 512 VGPRs per SIMD are taken).
     const LearnFamily fam = learn_family(e, a.batch);
     // (kernels_solow.hip moves MADDPG's targets at the end of its actor launch)
-    const bool actor_stage = (h.algo != ALGO_DQN && a.do_actor), soft_stage = (h.algo == ALGO_MADDPG && a.do_actor && fam != FAM_SOLOW);
+    const bool actor_stage = (h.algo != ALGO_DQN && a.do_actor), soft_stage = (is_maddpg(h.algo) && a.do_actor && fam != FAM_SOLOW);
     if (h.noisy) {
         // the reference draws noise per forward in program order: [online(s') if Double,] target(s'), online(s)
         const int first = a.double_dqn ? 0 : 1;

@@ -4,14 +4,15 @@
 
 namespace frl {
 
-constexpr int kMaxLayers = 6;     // twin critic = 2 x 3 layers in ONE net (one optimiser, one clip norm)
+constexpr int kMaxLayers = 7;     // twin critic = 2 x 3 layers in ONE net (one optimiser, one clip norm); the attention critic: 7 (AttLayer)
 constexpr int kMaxAgents = 8;
 constexpr int kMaxNets = 2 * kMaxAgents;
 
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: the GAIL discriminator's hidden layers only)
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
-                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13 };
+                  ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
+                  ALGO_MADDPG_ATT = 14 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -88,6 +89,16 @@ constexpr int mappo_row_extra(int hidden) { return (hidden + 4) + 2 + 2 * kMappo
 // MAPPO and HAPPO engines (not IPPO): every critic reads the concatenated observation, actor and critic use all n advantage / target
 // columns of a row, adv_norm runs over the whole [T][n] matrix (host and device)
 constexpr bool mappo_joint(int algo) { return algo == ALGO_MAPPO || algo == ALGO_HAPPO; }
+
+// The attention critic of ATT-MADDPG (device/att.hpp, kernels_att.hip; MADDPG_file/ATT.py:181-229): the layers of net 2i+1 of an
+// ALGO_MADDPG_ATT engine in the reference's state_dict order, the four fc_encoder_heads stacked into ONE layer of 4 x hidden outputs
+// (head k = output rows [k hidden, (k + 1) hidden)), so that every layer is a plain Wk[k_pad][n_pad] block.  The net is no chain:
+// NetDesc::heads stays 1 and nothing that walks L[0] .. L[n_layers - 1] as an MLP may be given it.
+constexpr int kAttHeads = 4;             // ATT_critic(dim_info) always builds head_count = 4
+enum AttLayer : int { ATT_EI = 0, ATT_HEADS = 1, ATT_DI = 2, ATT_E = 3, ATT_D = 4, ATT_FC1 = 5, ATT_FC2 = 6, ATT_LAYERS = 7 };
+// floats per chunk row behind carve_lds()'s region (device/att.hpp: carve_att): x_d, then d, u, c, y at the hidden pitch, then the heads
+constexpr int att_row_extra(int hidden, int xd_pad) { return (xd_pad + 4) + 4 * (hidden + 4) + (kAttHeads * hidden + 4); }
+constexpr int kAttRc = 16;               // rows per chunk of this family: 16 rows of its ~6 KB per row fit a CU's LDS, 32 do not at hidden 128
 
 // float index of W[out n][in k] inside a layer's weight block (host and device)
 #if defined(__HIPCC__)

@@ -207,6 +207,12 @@ __global__ void mappo_state_values_kernel(const EngineDesc* __restrict__ Dp, Map
 __global__ void mappo_state_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
 __global__ void mappo_state_mask_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
 
+// kernels_att.hip: ATT-MADDPG (MADDPG_file/MADDPG_simple_with_tricks.py with trick['ATT'], ATT.py): the attention critic's gradient kernels
+// of an ALGO_MADDPG_ATT engine in the row-chunk launch shape, and the critic's forward for frl_act
+__global__ void att_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void att_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void att_q_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
 struct HappoArgs {
     const int* order;     // [P][n] the agent visited at each position

@@ -39,6 +39,7 @@ _MAPPO_TRICK = {"adv_norm": False, "ObsNorm": False, "reward_norm": False, "rewa
                 "adam_eps": False, "lr_decay": False, "ValueClip": False, "huber_loss": False, "LayerNorm": False, "feature_norm": False}
 
 _MA_PPO = ("mappo", "ippo", "happo")      # the multi-agent PPO scripts: one loop (_run_mappo)
+_MADDPG = ("maddpg", "maddpg_att")        # MADDPG_simple.py and MADDPG_simple_with_tricks.py: one loop (_run_maddpg)
 
 FLAGS = {
     "dqn": dict(env_name="BipedalWalker-v3", policy_name="DQN", device="cuda", is_dis_to_con=True,
@@ -77,6 +78,10 @@ FLAGS = {
                    flags=_COMMON + _AC + _REPLAY + _GAUSS + [("N", int, 5)],
                    overrides=dict(seed=100, max_episodes=600, save_freq=600 // 4, gamma=0.95, gauss_sigma=1,
                                   gauss_init_scale=1), trick=None),
+    # MADDPG_simple_with_tricks.py:283-311: the attention critic of ATT-MADDPG by default; no --save_freq (the loop saves once, at the end)
+    "maddpg_att": dict(env_name="simple_spread_v3", policy_name="MADDPG_simple", device="cpu", is_dis_to_con=False,
+                       flags=[f for f in _COMMON if f[0] != "save_freq"] + _AC + _REPLAY + _GAUSS + [("N", int, 5)],
+                       overrides=dict(seed=0, max_episodes=600, gamma=0.95, gauss_sigma=1, gauss_init_scale=1), trick={"ATT": True}),
     # MAPPO_file/MAPPO.py:533-571 and IPPO.py:409-449: the two scripts' own defaults
     "mappo": dict(env_name="simple_spread_v3", policy_name="MAPPO", device="cuda", is_dis_to_con=False,
                   flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=200, save_freq=5000 // 4, start_steps=0,
@@ -522,7 +527,7 @@ def _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log=
             episode_reward = {a: 0 for a in agents}
         if step > args.start_steps and step % args.learn_steps_interval == 0:
             policy.learn(args.batch_size, args.gamma, args.tau)
-        if episode_num % args.save_freq == 0:
+        if getattr(args, "save_freq", None) and episode_num % args.save_freq == 0:      # (MADDPG_simple_with_tricks.py has no such block)
             policy.save(model_dir)
     log("total_time:", time.time() - t0)
     policy.save(model_dir)
@@ -637,12 +642,12 @@ def run(algo, argv=None, env=None, log=print):
     device = torch.device(args.device) if torch.cuda.is_available() else torch.device("cpu")
     if algo in _MA_PPO:
         _mappo_policy_name(args, algo.upper())
-    if algo == "maddpg" or algo in _MA_PPO:
-        if algo != "maddpg" and not args.continuous_actions and env is None:
+    if algo in _MADDPG or algo in _MA_PPO:
+        if algo not in _MADDPG and not args.continuous_actions and env is None:
             raise ValueError("the in-repo multi-agent environments have continuous actions: pass --continuous_actions True, or an env of your own")
         env = env if env is not None else _envs.make_parallel(args.env_name, args.N)
         env.reset()
-        is_continue = algo == "maddpg" or hasattr(env.action_space(env.agents[0]), "low")
+        is_continue = algo in _MADDPG or hasattr(env.action_space(env.agents[0]), "low")
         dim_info = {a: [env.observation_space(a).shape[0], env.action_space(a).shape[0] if is_continue else env.action_space(a).n] for a in env.agents}
         max_action = 1 if is_continue else None
     else:
@@ -701,6 +706,12 @@ def run(algo, argv=None, env=None, log=print):
         hooks = _PPOHooks(args, env, policy, dim_info, max_action)
     elif algo == "maddpg":
         from .MADDPG import MADDPG
+        policy = MADDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
+        out = _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log)
+        writer.close()
+        return dict(out, model_dir=model_dir, policy=policy, args=args)
+    elif algo == "maddpg_att":
+        from .MADDPG_simple_with_tricks import MADDPG
         policy = MADDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
         out = _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log)
         writer.close()

@@ -71,9 +71,17 @@ enum frl_algo {
                                   column per agent.  capacity = horizon.  hidden <= 256, ReLU only, <= 64 discrete actions */
     FRL_ALGO_IPPO = 12,        /* MAPPO_file/IPPO.py:57-347: the same, but the critic of agent i takes agent i's OWN observation and every
                                   agent is an independent PPO learner */
-    FRL_ALGO_HAPPO = 13        /* MAPPO_file/HAPPO.py:128-458: a FRL_ALGO_MAPPO engine in every respect at create (nets, the critic on the
+    FRL_ALGO_HAPPO = 13,       /* MAPPO_file/HAPPO.py:128-458: a FRL_ALGO_MAPPO engine in every respect at create (nets, the critic on the
                                   concatenated observation, record layout, limits), for heterogeneous agents updated one after another
                                   in a random order: updated by frl_happo_learn, not by frl_mappo_learn */
+    FRL_ALGO_MADDPG_ATT = 14   /* MADDPG_file/MADDPG_simple_with_tricks.py with trick['ATT'] (ATT.py:81-103,181-229): a FRL_ALGO_MADDPG engine
+                                  (records, net 2i the actor of agent i, frl_learn with the same arguments) whose net 2i+1 is agent i's
+                                  ATTENTION critic with a target copy: encoder_input_fc on [all obs | a_i], decoder_input_fc on the other
+                                  agents' actions, fc_encoder_input, 4 fc_encoder_heads, fc_decoder_input, a softmax over the heads'
+                                  scores against the decoder, fc1, fc2.  2 <= n_agents <= FRL_MAX_AGENTS, continuous actions, no twin
+                                  critic.  frl_act with FRL_ACT_RAW on net 2i+1 takes rows [all obs | all actions] and returns Q.
+                                  frl_params_get / _set order of net 2i+1: fc_encoder_input, the 4 heads' weights stacked [4 hidden][hidden]
+                                  then their biases [4 hidden], fc_decoder_input, encoder_input_fc, decoder_input_fc, fc1, fc2 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,

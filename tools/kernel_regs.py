@@ -51,7 +51,13 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # kernels_mappo_state.hip: mappo_steps with the critic's row filled from two segments (kState): mappo_state_update_kernel and
           # mappo_state_mask_update_kernel 366 VGPRs + 110 AGPRs and 72 bytes of scratch, mappo_state_values_kernel = mappo_values_kernel's
           # 224 + 40 and 56 bytes; no spilled VGPR in any of the three (the other kernels of the family keep their figures)
-          ("mappo_state_", 0), ("", 20)]
+          ("mappo_state_", 0),
+          # kernels_att.hip (figures of the unit compiled on its own, profiles/att/README.md): the attention critic's forward and backward are
+          # two non-inlined device functions (device/att.hpp), so their ~25 linear_* call sites' lane addresses live inside them instead of
+          # at the kernels' top: att_critic_kernel 256 VGPRs + 44 AGPRs, no spilled VGPR, 96 bytes of scratch (the Lds / AttLds structs the
+          # calls pass by reference); att_q_kernel the same, none spilled; att_actor_kernel 77 spilled and 368 bytes: the actor's own inlined
+          # mlp_fwd_rows / mlp_bwd addresses, stored at entry and reloaded at the start of a barrier phase, none inside an MFMA k-loop
+          ("att_critic_", 0), ("att_actor_", 77), ("att_q_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
