@@ -30,6 +30,7 @@ ALGO_GAIL = 10
 ALGO_MAPPO, ALGO_IPPO = 11, 12
 ALGO_HAPPO = 13
 ALGO_MADDPG_ATT = 14        # MADDPG_simple_with_tricks.py, trick['ATT']: a MADDPG engine whose critics are attention critics (frl_learn)
+ALGO_MASAC = 15             # MAAC_file/MASAC.py: MADDPG's records and net numbering, stacked [mean | log_std] actors, twin critics, one alpha per agent (frl_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only
@@ -190,6 +191,8 @@ SIGNATURES = {
     "frl_opt_step_set": (_i, [_vp, _i, _i, _i]),
     "frl_alpha_get": (_i, [_vp, _i, _fp, _ip]),
     "frl_alpha_set": (_i, [_vp, _i, _fp, _i]),
+    "frl_alpha_get_agent": (_i, [_vp, _i, _i, _fp, _ip]),
+    "frl_alpha_set_agent": (_i, [_vp, _i, _i, _fp, _i]),
     "frl_obsnorm_enable": (_i, [_vp, _i]),
     "frl_obsnorm_get": (_i, [_vp, _i, _fp]),
     "frl_obsnorm_set": (_i, [_vp, _i, _fp]),

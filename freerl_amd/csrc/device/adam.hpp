@@ -71,13 +71,12 @@ __device__ __forceinline__ float actor_loss_stat(bool sac, float qtot, float lpt
 }
 
 // SAC's alpha step on the batch's entropy (SAC.py:154-169,257-260): Adam on log_alpha with torch's default eps 1e-8 (not the nets'
-// adam_eps) and its own step count steps[kMaxNets].  al = {log_alpha, m, v, alpha}, alpha = al[3] before the step; st = the unit's
-// stats row.
-__device__ __forceinline__ void sac_alpha_step(float* al, float* st, int* steps, float alpha, float ent_mean, float target_entropy,
-                                               float beta1, float beta2, float alpha_lr) {
+// adam_eps) and its own step count *count.  al = {log_alpha, m, v, alpha}, alpha = al[3] before the step; st = the unit's stats row.
+__device__ __forceinline__ void sac_alpha_step_at(float* al, float* st, int* count, float alpha, float ent_mean, float target_entropy,
+                                                  float beta1, float beta2, float alpha_lr) {
     const float mean_term = ent_mean - target_entropy;
     const float gl = alpha * mean_term;                                // d alpha_loss / d log_alpha
-    const int ta = steps[kMaxNets] + 1;
+    const int ta = *count + 1;
     float mi = al[1], vi = al[2];
     mi = mi + (gl - mi) * (1.f - beta1);
     vi = vi * beta2 + ((1.f - beta2) * gl) * gl;
@@ -87,10 +86,22 @@ __device__ __forceinline__ void sac_alpha_step(float* al, float* st, int* steps,
     al[1] = mi;
     al[2] = vi;
     al[3] = expf(al[0]);
-    steps[kMaxNets] = ta;
+    *count = ta;
     st[ST_ALPHA_LOSS] = alpha * mean_term;
     st[ST_ALPHA] = al[3];
     st[ST_ENTROPY] = ent_mean;
+}
+// ... of a single-agent SAC engine: the learner's one alpha block, its step count in steps[kMaxNets]
+__device__ __forceinline__ void sac_alpha_step(float* al, float* st, int* steps, float alpha, float ent_mean, float target_entropy,
+                                               float beta1, float beta2, float alpha_lr) {
+    sac_alpha_step_at(al, st, steps + kMaxNets, alpha, ent_mean, target_entropy, beta1, beta2, alpha_lr);
+}
+// MASAC (MASAC.py:124-139,271-273): agent ag's own alpha block of EngineDesc::alpha [P][n][4], its step count behind the nets' counters,
+// target entropy -act_dim[ag]
+__device__ __forceinline__ void masac_alpha_step(const EngineDesc& D, int p, int ag, float* st, float ent_mean, float beta1, float beta2, float alpha_lr) {
+    float* al = D.alpha + ((size_t)p * D.n_agents + ag) * 4;
+    int* count = D.steps + (size_t)D.P * (kMaxNets + 1) + (size_t)p * D.n_agents + ag;
+    sac_alpha_step_at(al, st, count, al[3], ent_mean, -(float)D.rec.act_dim[ag], beta1, beta2, alpha_lr);
 }
 
 }  // namespace frl

@@ -83,4 +83,17 @@ __device__ __forceinline__ float sac_log_std_grad(float d, float raw_log_std, fl
     return d * expf(ls) * eps - alpha * invB;
 }
 
+// The per-row log_std forms (MASAC.py:37-68: log_std is a head column beside the mean, clamped per row) of an actor loss whose Q
+// term and entropy term come from TWO draws of the same forward (MASAC.py:254-261): a1 = tanh(mean + sd eps1) went into Q, dq = d loss /
+// d a1; the entropy is -log pi of u2 = mean + sd eps2, weighted alpha / B.  d log pi / d u2 = 2 tanh(u2) (the Normal term's own
+// dependence on the mean cancels under rsample), d log pi / d log_std = 2 tanh(u2) sd eps2 - 1.  kernels_masac.hip.
+__device__ __forceinline__ float sac2_mean_delta(float dq, float a1, float t2, float alpha, float invB) {
+    return dq * (1.f - a1 * a1) + (alpha * invB) * (2.f * t2);
+}
+__device__ __forceinline__ float sac2_log_std_delta(float dq, float a1, float t2, float raw_log_std, float eps1, float eps2, float alpha, float invB) {
+    if (!log_std_grad_open(raw_log_std)) return 0.f;      // torch.clamp passes no gradient outside its (closed) bounds
+    const float sd = expf(clamp_log_std(raw_log_std));
+    return dq * (1.f - a1 * a1) * (sd * eps1) + (alpha * invB) * ((2.f * t2) * (sd * eps2) - 1.f);
+}
+
 }  // namespace frl

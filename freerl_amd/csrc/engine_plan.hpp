@@ -54,23 +54,29 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"IPPO",           "frl_mappo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"HAPPO",          "frl_happo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"ATT-MADDPG",     kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
+    {"MASAC",          kFrlLearn,                 "FRL_ACT_SAC_SAMPLE / FRL_ACT_TANHHEAD on net 2i with agent i's observation",   false, false, false, false, false, true,  false},
 };
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
+// (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
+//  policy noise and its own launch order — learn_impl and the launchers ask for it by name)
+inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MADDPG_ATT - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MASAC - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
 // plan_engine fixes the engine's chained family — or none: FAM_ROWCHUNK — with its parameter layout; learn_family() says what one call takes.
 // FAM_ATT: the attention critic's row-chunk kernels (kernels_att.hip) — what every FRL_ALGO_MADDPG_ATT engine learns with, and nothing else does
-enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16, FAM_ATT };
+// FAM_MASAC: MASAC's row-chunk kernels (kernels_masac.hip): one critic launch, then one actor launch per agent — every FRL_ALGO_MASAC engine, nothing else
+enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16, FAM_ATT, FAM_MASAC };
 // dynamic LDS of a family's launches = its kernels' hipFuncAttributeMaxDynamicSharedMemorySize
 constexpr int kLdsDqnFused = dqn2_lds_floats() * (int)sizeof(float);
 constexpr int kLdsChain4 = critic2_lds_floats() * (int)sizeof(float), kLdsChain8 = critic8_lds_floats() * (int)sizeof(float);
 constexpr int kLdsSolo = std::max(solo_lds_floats(), critic2_lds_floats()) * (int)sizeof(float);      // (critic2: the rollout tail's act_frag_body)
 constexpr int kLdsSolow = solow_lds_floats() * (int)sizeof(float);
 constexpr int kLdsWide = wide_lds_floats() * (int)sizeof(float), kLdsWide16 = wide16_lds_floats_host() * (int)sizeof(float);
+constexpr int kLdsMasac = 160 * 1024;     // ... and a FAM_MASAC launch (the row chunk is chosen for two workgroups per CU where the nets allow it)
 constexpr int kLdsAtt = 160 * 1024;       // the most a FAM_ATT launch may carve; a launch carves its engine's own row-chunk bytes (plan_sizes refuses more)
 
 struct PlanLimits {               // of the device
@@ -100,6 +106,7 @@ struct EngineFacts {
     bool has_nets = false;
     int noisy_per_set = 0;        // floats of device noise per (learner, forward): 2 * (k_pad + n_pad) of the head
     size_t idx_count = 0, noise_count = 0;      // ints / floats of the idx and noise uploads
+    size_t alpha_count = 0, steps_count = 0;    // floats of EngineDesc::alpha, ints of EngineDesc::steps (MASAC: per-agent alpha blocks and counters)
     int solo_stride = 0;          // floats per gradient slab of kernels_solo.hip / kernels_solow.hip: the largest net
     int solow_row_wgs = 0;        // kernels_solow.hip: workgroups per unit that own row tiles (16: one tile each; 64: MADDPG's batches of 1024)
     int solow_wgs = 0;            // ... workgroups per unit in its grids (row-tile workgroups + helpers for the update)
@@ -273,6 +280,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
     EngineDesc& h = pl.h;
     const int n_cus = pl.n_cus, lds_per_cu = pl.lds_per_cu;
     if (!pl.has_nets) return FAM_ROWCHUNK;
+    if (h.algo == ALGO_MASAC) return FAM_MASAC;         // (nor the stacked [mean | log_std] head, the all-actors actor loss or the per-agent launches)
     if (h.algo == ALGO_MADDPG_ATT) return FAM_ATT;      // (no chained, solo, solow or wide kernel knows the attention critic: the shapes below never see it)
     const bool named = knobs.critic_v2 >= 0;
     if (chained_shape(h) && !knobs.solow_narrow) {
@@ -337,7 +345,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
 // (super-chunks of 256 rows / a 16-row tile per workgroup).
 inline LearnFamily learn_family(const EngineDesc& h, LearnFamily family, int batch, bool dqn_fused_on) {
     if (dqn_fused_shape(h, batch) && dqn_fused_on) return FAM_DQN_FUSED;
-    if (family == FAM_ATT) return FAM_ATT;
+    if (family == FAM_ATT || family == FAM_MASAC) return family;
     const bool narrow = family == FAM_CHAINED || family == FAM_SOLO;
     return (h.obs_norm_on || (narrow && batch > 256)) ? FAM_ROWCHUNK : family;
 }
@@ -362,6 +370,7 @@ inline int family_lds_bytes(LearnFamily fam, int chain_waves) {
         case FAM_WIDE: return kLdsWide;
         case FAM_WIDE16: return kLdsWide16;
         case FAM_ATT: return kLdsAtt;
+        case FAM_MASAC: return kLdsMasac;
         case FAM_ROWCHUNK: break;
     }
     return 0;
@@ -372,14 +381,14 @@ struct LearnPath { bool chained; int bytes, rows; };
 inline LearnPath learn_path(const EngineDesc& h, const EngineFacts& f, LearnFamily fam, int batch, int dqn_split) {
     int bytes = family_lds_bytes(fam, f.chain_waves), rows = batch;
     switch (fam) {
-        case FAM_ROWCHUNK: case FAM_ATT: bytes = f.lds_bytes; rows = h.rc; break;      // (FAM_ATT: row chunks too, its own carve behind the common one)
+        case FAM_ROWCHUNK: case FAM_ATT: case FAM_MASAC: bytes = f.lds_bytes; rows = h.rc; break;      // (FAM_ATT: row chunks too, its own carve behind the common one)
         case FAM_DQN_FUSED: rows = std::min(((batch + 63) / 64 + dqn_split - 1) / dqn_split * 64, batch); break;
         // kernels_solo.hip: 16-row tiles, 16 / h.solo of them per workgroup (its own carve; the launch carries the rollout tail's on top)
         case FAM_SOLO: bytes = solo_lds_floats() * (int)sizeof(float); rows = 16 * (kSoloWG / h.solo); break;
         case FAM_SOLOW: rows = 16 * (h.solow / std::max(1, f.solow_row_wgs)); break;      // one 16-row tile per workgroup
         default: break;                                                                 // one workgroup per unit walks the batch
     }
-    return {fam != FAM_ROWCHUNK && fam != FAM_ATT, bytes, rows};
+    return {fam != FAM_ROWCHUNK && fam != FAM_ATT && fam != FAM_MASAC, bytes, rows};
 }
 
 // ------------------------------------------------------------------------------- the plan
@@ -397,9 +406,9 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
         return plan_refuse(message, "state_dim %d: a global-state critic belongs to FRL_ALGO_MAPPO engines (MAPPO_for_mask_action_state.py); algo %d has none", state_dim, c.algo);
     if (c.n_learners < 1) return plan_refuse(message, "n_learners must be >= 1");
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
-    if (!is_maddpg(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
+    if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MADDPG_ATT) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MASAC) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -449,6 +458,14 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
             if (c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
             if (h.hidden % 16 || h.hidden > 128)
                 return plan_refuse(message, "%s: hidden %d is refused: the row chunk's 16 rows of x_e, x_d, e, g, the %d heads, d, u, c and y fit a CU's LDS up to hidden 128", T.name, h.hidden, kAttHeads);
+            return FRL_OK;
+        case FRL_ALGO_MASAC:
+            // what kernels_masac.hip handles (MASAC.py:32-97: ReLU nets, a twin critic in one net, tanh-Gaussian actors)
+            if (c.discrete)
+                return plan_refuse(message, "%s: discrete is refused (continuous actions only: the reference's discrete branch calls Agent.argmax, which does not exist, MASAC.py:185)", T.name);
+            if (!c.twin_critic) return plan_refuse(message, "%s: twin_critic = 0 is refused (Critic holds Q1 and Q2 in one net and the update takes their minimum, MASAC.py:72-97)", T.name);
+            if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0) return plan_refuse(message, "%s: dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
+            if (c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
             return FRL_OK;
         case FRL_ALGO_GAIL:     // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
             if (c.hidden_act == FRL_ACT_TANH) return plan_refuse(message, "GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
@@ -543,6 +560,17 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
                           1, ACT_RELU, ACT_NONE, 0);
             }
             break;
+        case FRL_ALGO_MASAC: {
+            // Actor (MASAC.py:32-47): l1, l2 and mean_layer / log_std_layer as ONE head of 2 A outputs, rows [0, A) the mean and [A, 2 A) log_std
+            // (no extra vector); Critic (:72-97): Q1 = l1, l2, l3 and Q2 = l1_2, l2_2, l3_2 on [all obs | all actions] in one net
+            h.n_nets = 2 * c.n_agents;
+            const int cin = R.obs_total + R.act_total;
+            for (int j = 0; j < c.n_agents; ++j) {
+                build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {2 * c.act_dim[j], H}}, 1, ACT_RELU, ACT_NONE, 0);
+                build_net(h.net[2 * j + 1], {{H, cin}, {H, H}, {1, H}, {H, cin}, {H, H}, {1, H}}, 2, ACT_RELU, ACT_NONE, 0);
+            }
+            break;
+        }
         default: {      // DDPG, TD3, SAC, MADDPG: an actor and a (twin) critic on the joint [obs | act] per agent
             h.n_nets = 2 * c.n_agents;
             const int cin = R.obs_total + R.act_total;
@@ -619,6 +647,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
             h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
             one_wg_per_net = whole_cu = true;
             break;
+        case FRL_ALGO_MASAC:             // device/masac.hpp: the updating actor's head row behind the common carve
+            h.lds_row_extra = masac_row_extra(h.act_max);
+            break;
         case FRL_ALGO_MADDPG_ATT: {      // device/att.hpp: carve_att behind the common carve
             int xd = 16;
             for (int j = 0; j < c.n_agents; ++j) xd = std::max(xd, h.net[2 * j + 1].L[ATT_D].k_pad);
@@ -649,6 +680,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
             return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB (encoder input %d columns, decoder input at most %d)", T.name, lds_bytes_for(h, h.rc),
                                h.lds_kin_pad, h.lds_row_extra - 4 - 4 * (H + 4) - (kAttHeads * H + 4));
     }
+    if (c.algo == FRL_ALGO_MASAC && lds_bytes_for(h, h.rc) > kLdsMasac)
+        return plan_refuse(message, "%s: hidden %d is refused: %d B of LDS per %d-row chunk > 160 KB (the joint critic input is %d columns wide)", T.name, H,
+                           lds_bytes_for(h, h.rc), h.rc, h.lds_kin_pad);
     if (whole_cu && h.state_dim > 0 && lds_bytes_for(h, h.rc) > 160 * 1024)
         return plan_refuse(message, "%s: %d B of LDS per row chunk > 160 KB (a first layer of %d input columns, %d of them the state's: state_dim)", T.name,
                            lds_bytes_for(h, h.rc), h.lds_kin_pad, h.state_dim);
@@ -692,7 +726,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];
         pl.noisy_per_set = 2 * (HL.k_pad + HL.n_pad);
     }
-    h.noise_sets = std::max(2, h.n_agents);
+    h.noise_sets = c.algo == FRL_ALGO_MASAC ? 2 * h.n_agents + 1 : std::max(2, h.n_agents);      // (MASAC: frl_desc.h, EngineDesc::noise_sets)
+    pl.alpha_count = P * (c.algo == FRL_ALGO_MASAC ? (size_t)h.n_agents : 1) * 4;
+    pl.steps_count = P * (kMaxNets + 1) + (c.algo == FRL_ALGO_MASAC ? P * (size_t)h.n_agents : 0);
     pl.noise_count = P * h.n_agents * h.noise_sets * (size_t)h.batch_max * h.act_max;
     int biggest = 0;
     for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);

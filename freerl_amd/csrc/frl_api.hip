@@ -48,6 +48,7 @@
 #include "kernels_mappo_mask.hip"
 #include "kernels_mappo_state.hip"
 #include "kernels_att.hip"
+#include "kernels_masac.hip"
 #endif
 
 using namespace frl;
@@ -240,7 +241,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 110; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT
+extern "C" int frl_version(void) { return 111; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -353,9 +354,9 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
         CREATE_TRY(e->mem.alloc_zero(&h.idx, e->idx_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.noise, e->noise_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.stats, P * h.n_agents * ST_COUNT, e->stream));
-        CREATE_TRY(e->mem.alloc_zero(&h.steps, P * (kMaxNets + 1), e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.steps, e->steps_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.ticket, P + 1, e->stream));
-        CREATE_TRY(e->mem.alloc_zero(&h.alpha, P * 4, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.alpha, e->alpha_count, e->stream));
         if (c.algo == FRL_ALGO_REINFORCE) {
             CREATE_TRY(e->mem.alloc_zero(&h.ep_n, P, e->stream));
             CREATE_TRY(e->mem.alloc(&e->h_ep_n, 2 * P, MEM_PINNED));
@@ -422,7 +423,7 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
                               (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel,
                               (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
-                              (const void*)att_q_kernel})
+                              (const void*)att_q_kernel, (const void*)masac_act_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -698,16 +699,20 @@ static int params_xfer(frl_engine* e, int learner, int net, int kind, float* hos
     size_t o = 0;
     for (int i = 0; i < N.n_layers + N.n_shadow; ++i) {       // shadow layers (a noisy head's sigma) follow the forward ones
         const LayerDesc& L = N.L[i];
-        for (int r = 0; r < L.n; ++r)
-            for (int c = 0; c < L.k; ++c) {
-                float& d = blk[L.w_off + weight_index(N, L, r, c)];
+        // (a MASAC actor's head is mean_layer and log_std_layer stacked: the host order is each nn.Linear's weight then bias, MASAC.py:37-38)
+        const int parts = (e->h.algo == ALGO_MASAC && !(net & 1) && i == N.n_layers - 1) ? 2 : 1, rows = L.n / parts;
+        for (int part = 0; part < parts; ++part) {
+            for (int r = part * rows; r < (part + 1) * rows; ++r)
+                for (int c = 0; c < L.k; ++c) {
+                    float& d = blk[L.w_off + weight_index(N, L, r, c)];
+                    if (to_device) d = host[o]; else host[o] = d;
+                    ++o;
+                }
+            for (int r = part * rows; r < (part + 1) * rows; ++r) {
+                float& d = blk[L.b_off + r];
                 if (to_device) d = host[o]; else host[o] = d;
                 ++o;
             }
-        for (int r = 0; r < L.n; ++r) {
-            float& d = blk[L.b_off + r];
-            if (to_device) d = host[o]; else host[o] = d;
-            ++o;
         }
     }
     for (int j = 0; j < N.extra_n; ++j) {
@@ -770,9 +775,34 @@ extern "C" int frl_opt_step_set(frl_engine* e, int learner, int net, int t) {
     return FRL_OK;
 }
 
+// MASAC: one alpha block per (learner, agent), the agents' step counts behind the nets' (frl_desc.h: EngineDesc::alpha, ::steps)
+static int masac_alpha_xfer(frl_engine* e, int learner, int agent, float* vals4, int* step, bool to_device) {
+    const EngineDesc& h = e->h;
+    float* al = h.alpha + ((size_t)learner * h.n_agents + agent) * 4;
+    int* cnt = h.steps + (size_t)h.P * (kMaxNets + 1) + (size_t)learner * h.n_agents + agent;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(to_device ? (void*)al : (void*)vals4, to_device ? (const void*)vals4 : (const void*)al, 4 * sizeof(float), to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+    if (step) HIP_TRY(hipMemcpy(to_device ? (void*)cnt : (void*)step, to_device ? (const void*)step : (const void*)cnt, sizeof(int), to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost));
+    return FRL_OK;
+}
+extern "C" int frl_alpha_get_agent(frl_engine* e, int learner, int agent, float* vals4_out, int* step_out) {
+    ENG(e);
+    if (!e->has_nets || learner < 0 || learner >= e->h.P || agent < 0 || agent >= e->h.n_agents || !vals4_out) return fail(FRL_ERR_INVALID, "bad argument");
+    if (e->h.algo != ALGO_MASAC) return agent == 0 ? frl_alpha_get(e, learner, vals4_out, step_out) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
+    return masac_alpha_xfer(e, learner, agent, vals4_out, step_out, false);
+}
+extern "C" int frl_alpha_set_agent(frl_engine* e, int learner, int agent, const float* vals4, int step) {
+    ENG(e);
+    if (!e->has_nets || learner < 0 || learner >= e->h.P || agent < 0 || agent >= e->h.n_agents || !vals4) return fail(FRL_ERR_INVALID, "bad argument");
+    if (e->h.algo != ALGO_MASAC) return agent == 0 ? frl_alpha_set(e, learner, vals4, step) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
+    return masac_alpha_xfer(e, learner, agent, const_cast<float*>(vals4), &step, true);
+}
+
 extern "C" int frl_alpha_get(frl_engine* e, int learner, float* vals4_out, int* step_out) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || !vals4_out) return fail(FRL_ERR_INVALID, "bad argument");
+    if (e->h.algo == ALGO_MASAC)
+        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_get: a MASAC engine has one alpha per agent: frl_alpha_get_agent") : masac_alpha_xfer(e, learner, 0, vals4_out, step_out, false);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(vals4_out, e->h.alpha + (size_t)learner * 4, 4 * sizeof(float), hipMemcpyDeviceToHost));
     if (step_out) return frl_opt_step_get(e, learner, kMaxNets, step_out);
@@ -781,6 +811,8 @@ extern "C" int frl_alpha_get(frl_engine* e, int learner, float* vals4_out, int* 
 extern "C" int frl_alpha_set(frl_engine* e, int learner, const float* vals4, int step) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || !vals4) return fail(FRL_ERR_INVALID, "bad argument");
+    if (e->h.algo == ALGO_MASAC)
+        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_set: a MASAC engine has one alpha per agent: frl_alpha_set_agent") : masac_alpha_xfer(e, learner, 0, const_cast<float*>(vals4), &step, true);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->h.alpha + (size_t)learner * 4, vals4, 4 * sizeof(float), hipMemcpyHostToDevice));
     return frl_opt_step_set(e, learner, kMaxNets, step);
@@ -811,7 +843,8 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     // (an attention critic's rows are [all obs | all actions]: x_e and x_d are cut from them in the kernel)
     const int want_in = (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total : N.L[head * nl].k;
     if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
-    if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0) return fail(FRL_ERR_INVALID, "net has no log_std");
+    const bool masac_actor = e->h.algo == ALGO_MASAC && !(net & 1);      // its log_std is the head's second half, not an extra vector
+    if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0 && !(masac_actor && mode == FRL_ACT_SAC_SAMPLE)) return fail(FRL_ERR_INVALID, "net has no log_std");
     if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev && !(ex && ex->device_eps)) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE needs the Exp(1) draws in eps");
     if (n_rows < 1) return fail(FRL_ERR_INVALID, "n_rows must be >= 1");
     const bool no_norm = (mode_flags & FRL_ACT_NO_OBSNORM) != 0;
@@ -846,6 +879,13 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) {      // the attention critic is no chain: its own forward (kernels_att.hip), Q of [all obs | all actions]
         if (mode != FRL_ACT_RAW || ex) return fail(FRL_ERR_INVALID, "an ATT-MADDPG critic acts through FRL_ACT_RAW on rows [all obs | all actions] (its Q value)");
         hipLaunchKernelGGL(att_q_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
+    if (masac_actor && mode != FRL_ACT_RAW) {      // the stacked [mean | log_std] head (kernels_masac.hip); FRL_ACT_RAW and the critics: act_kernel below
+        if ((mode != FRL_ACT_SAC_SAMPLE && mode != FRL_ACT_TANHHEAD) || ex) return fail(FRL_ERR_INVALID, "a MASAC actor acts through FRL_ACT_SAC_SAMPLE, FRL_ACT_TANHHEAD or FRL_ACT_RAW");
+        if (mode == FRL_ACT_SAC_SAMPLE && !eps_dev) return fail(FRL_ERR_INVALID, "FRL_ACT_SAC_SAMPLE on a MASAC actor needs the N(0,1) draws in eps");
+        hipLaunchKernelGGL(masac_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
         return FRL_OK;
     }
@@ -909,7 +949,8 @@ extern "C" int frl_act(frl_engine* e, int net, int mode, int head, int use_targe
     const NetDesc& N = e->h.net[net];
     const int nl = N.n_layers / N.heads;
     if (head < 0 || head >= N.heads) return fail(FRL_ERR_INVALID, "head out of range");
-    const int nout = N.L[head * nl + nl - 1].n;
+    int nout = N.L[head * nl + nl - 1].n;
+    if (e->h.algo == ALGO_MASAC && !(net & 1) && (mode & ~FRL_ACT_NO_OBSNORM) != FRL_ACT_RAW) nout /= 2;      // an action, not the [mean | log_std] head row
     const size_t rows = (size_t)e->h.P * n_rows;
     const size_t in_n = rows * in_dim, out_n = rows * nout;
     int rc = act_scratch(e, in_n, out_n);
@@ -938,6 +979,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
     if (is_mappo_family(h.algo)) return wrong_engine(h, "frl_act_explore");
+    if (h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_act_explore does not serve a MASAC engine: %s", algo_traits(h.algo).act_hint);
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
@@ -1123,6 +1165,7 @@ extern "C" int frl_timer_stop(frl_engine* e, float* ms_out) {
 extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
+    if (e->h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MASAC.py has no Batch_ObsNorm and kernels_masac.hip does not normalise");
     if (e->h.algo == ALGO_MADDPG_ATT) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MADDPG_simple_with_tricks.py has no Batch_ObsNorm and the attention critic's kernels do not normalise");
     if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
     if (on && e->h.net[0].frag) {

@@ -34,6 +34,9 @@ static const LearnKernelRow kLearnKernels[] = {
     // the attention critic of ATT-MADDPG on the row-chunk skeleton (kernels_att.hip): kLdsAtt is the launches' limit, a launch carves the engine's own bytes
     {FAM_ATT, LK_CRITIC, 0, kLdsAtt, {{att_critic_kernel, att_critic_kernel}, {att_critic_kernel, att_critic_kernel}}},
     {FAM_ATT, LK_ACTOR, 0, kLdsAtt, {{att_actor_kernel, att_actor_kernel}, {att_actor_kernel, att_actor_kernel}}},
+    // MASAC on the row-chunk skeleton (kernels_masac.hip): the critic launch over (learner, agent) units, the actor launch over learners for one agent
+    {FAM_MASAC, LK_CRITIC, 0, kLdsMasac, {{masac_critic_kernel, masac_critic_kernel}, {masac_critic_kernel, masac_critic_kernel}}},
+    {FAM_MASAC, LK_ACTOR, 0, kLdsMasac, {{masac_actor_kernel, masac_actor_kernel}, {masac_actor_kernel, masac_actor_kernel}}},
 };
 
 // every kernel of the family may carve its row's LDS bytes, whichever of them the engine's shape resolves to
@@ -259,6 +262,27 @@ static void launch_solow(frl_engine* e, const LearnStage& s, const LearnArgs& a,
 // kernels_att.hip: ATT-MADDPG's gradient launches over (unit, slab) workgroups, then reduce + clip + Adam as the row-chunk family
 static void launch_att(frl_engine* e, const LearnStage& s, const LearnArgs& a) { launch_rowchunk(e, s, a, true); }
 
+// kernels_masac.hip.  Stage 0: every (learner, agent) critic unit in one launch, then their reduce + clip + Adam (targets untouched: the soft
+// stage moves them).  Stage 1, once per agent in agent order (a.agent): the actor launch over LEARNERS for that agent, its reduce + clip +
+// Adam and the agent's alpha step — stream order makes agent i's launch read the actors of agents j < i as stepped (MASAC.py:221,254)
+static void launch_masac(frl_engine* e, const LearnStage& s, const LearnArgs& a) {
+    const EngineDesc& h = e->h;
+    const bool actor = s.stage == 1;
+    const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
+    const int units = actor ? s.pc : s.units;
+    prof_begin(e, actor ? PK_GRAD_ACTOR : PK_GRAD_CRITIC);
+    hipLaunchKernelGGL(actor ? e->kern.actor.kr : e->kern.critic.kr, dim3(((units + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, s.st, e->d, a, ns);
+    prof_end(e);
+    AdamArgs ad{};
+    ad.ns = ns; ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm;
+    ad.tau = a.tau; ad.alpha_lr = a.alpha_lr; ad.p0 = s.p0; ad.G = h.Gmax; ad.soft = 0; ad.wd = 0.f;
+    if (actor) { ad.which = 1; ad.lr = a.actor_lr; ad.sac_alpha = 2; ad.agent1 = a.agent + 1; }
+    else { ad.which = 0; ad.lr = a.critic_lr; }
+    prof_begin(e, actor ? PK_ADAM_ACTOR : PK_ADAM_CRITIC);
+    launch_adam(e, s.st, ad, units, dim3(units * h.Gmax));
+    prof_end(e);
+}
+
 static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, LearnArgs a, int stage, int p0, int pc, bool dev_rng, bool needs_noise,
                                const DqnStepArgs* step = nullptr, const SoloStepArgs* sstep = nullptr) {
     const EngineDesc& h = e->h;
@@ -289,6 +313,7 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, L
         case FAM_SOLOW: launch_solow(e, s, a, ma_predraw, ma_use_pre); break;
         case FAM_WIDE: case FAM_WIDE16: launch_wide(e, s, a); break;
         case FAM_ATT: launch_att(e, s, a); break;
+        case FAM_MASAC: launch_masac(e, s, a); break;
         case FAM_DQN_FUSED: break;
     }
 }
@@ -313,7 +338,9 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
     if (dev_rng && min_size < 2 * args->batch)
         return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
     const bool td3_like = (h.algo == ALGO_TD3 || is_maddpg(h.algo));           // MADDPG + noise/delay = MATD3_simple.py (ATT-MADDPG: do_actor only)
-    const bool needs_noise = (h.algo == ALGO_SAC) || (td3_like && args->use_policy_noise);
+    const bool needs_noise = (h.algo == ALGO_SAC) || h.algo == ALGO_MASAC || (td3_like && args->use_policy_noise);
+    if (h.algo == ALGO_MASAC && args->use_policy_noise) return fail(FRL_ERR_STATE, "frl_learn: MASAC has no target policy smoothing (MATD3's): use_policy_noise must be 0");
+    if (h.algo == ALGO_MASAC && args->loss_kind == FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "MASAC's critic loss is F.mse_loss (MASAC.py:241): no Huber variant");
     if (h.algo == ALGO_MADDPG_ATT && args->use_policy_noise) return fail(FRL_ERR_INVALID, "ATT-MADDPG has no target policy smoothing: use_policy_noise must be 0");
     if (!dev_rng && needs_noise && !args->noise) return fail(FRL_ERR_INVALID, "idx given without noise: both or neither");
     int rc = flush_stage(e);
@@ -375,8 +402,12 @@ static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepAr
         s1.head = 0; s1.tail = 1;
     }
     launch_learn_stage(e, lst, fam, a, 0, 0, h.P, dev_rng, needs_noise, step, sstep ? &s0 : nullptr);
-    if (actor_stage && !a.fuse_actor) launch_learn_stage(e, lst, fam, a, 1, 0, h.P, dev_rng, needs_noise, nullptr, sstep ? &s1 : nullptr);
-    if (soft_stage) launch_learn_stage(e, lst, fam, a, 2, 0, h.P, dev_rng, needs_noise);
+    if (fam == FAM_MASAC) {      // DESIGN.md "MASAC": behind all the critics the agents' actor + alpha steps one after the other, then every target
+        for (int ag = 0; ag < h.n_agents; ++ag) { a.agent = ag; launch_learn_stage(e, lst, fam, a, 1, 0, h.P, dev_rng, needs_noise); }
+    } else if (actor_stage && !a.fuse_actor) {
+        launch_learn_stage(e, lst, fam, a, 1, 0, h.P, dev_rng, needs_noise, nullptr, sstep ? &s1 : nullptr);
+    }
+    if (soft_stage || fam == FAM_MASAC) launch_learn_stage(e, lst, fam, a, 2, 0, h.P, dev_rng, needs_noise);
     HIP_TRY(hipGetLastError());
     if (sstep) return FRL_OK;
     if (args->stats_out) return frl_stats_get(e, args->stats_out);

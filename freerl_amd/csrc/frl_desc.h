@@ -12,7 +12,7 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
-                  ALGO_MADDPG_ATT = 14 };
+                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -100,6 +100,10 @@ enum AttLayer : int { ATT_EI = 0, ATT_HEADS = 1, ATT_DI = 2, ATT_E = 3, ATT_D = 
 constexpr int att_row_extra(int hidden, int xd_pad) { return (xd_pad + 4) + 4 * (hidden + 4) + (kAttHeads * hidden + 4); }
 constexpr int kAttRc = 16;               // rows per chunk of this family: 16 rows of its ~6 KB per row fit a CU's LDS, 32 do not at hidden 128
 
+// MASAC (kernels_masac.hip, device/masac.hpp; MAAC_file/MASAC.py): floats per chunk row behind carve_lds()'s region — the updating actor's
+// head row [mean | log_std] (2 x act_dim columns), kept from its forward until its head delta is formed behind the two critic passes
+constexpr int masac_row_extra(int act_max) { return (2 * act_max + 3) / 4 * 4; }
+
 // float index of W[out n][in k] inside a layer's weight block (host and device)
 #if defined(__HIPCC__)
 __host__ __device__
@@ -157,11 +161,12 @@ struct EngineDesc {
     int* idx;             // [P][n_agents][batch_max] sampled row indices
     float* noise;         // [P][n_agents][noise_sets][batch_max][act_max] standard-normal draws: set 0 = TD3 policy noise /
                           // SAC eps', set 1 = SAC eps; MATD3: set j = the policy noise on agent j's target action
-    int noise_sets;       // max(2, n_agents)
+    int noise_sets;       // max(2, n_agents); ALGO_MASAC: 2 n_agents + 1 — per updating agent the n target actors' draws (sets 0 .. n-1),
+                          // the n online actors' (n .. 2n-1) and the second draw of the agent's own actor for the entropy (2n)
     float* stats;         // [P][n_agents][ST_COUNT]
-    int* steps;           // [P][kMaxNets + 1] Adam step counters (+1: SAC alpha)
+    int* steps;           // [P][kMaxNets + 1] Adam step counters (+1: SAC alpha); ALGO_MASAC: behind them [P][n_agents] the agents' alpha steps
     int* ticket;          // [P + 1] arrival counters in dqn_fused_kernel: a learner's workgroups; [P]: the learners (zero between launches)
-    float* alpha;         // [P][4]: log_alpha, m, v, alpha (SAC)
+    float* alpha;         // [P][4]: log_alpha, m, v, alpha (SAC); ALGO_MASAC: [P][n_agents][4], one block per agent
     unsigned long long seed;
     int act_max;          // max act_dim over agents (row pitch of `noise`)
     // LDS carve parameters (must match between host lds_bytes() and device carve_lds())
@@ -256,6 +261,7 @@ struct LearnArgs {
     int fuse_actor;       // kernels_solow.hip: this call's critic AND actor stage run in one launch (solow_step_*); frl_learn skips the actor launch
     int huber;            // TD loss: 0 F.mse_loss (every hot-path loss of the reference), 1 Huber with `huber_delta`
     float huber_delta;    // (the reference's huber_loss, MAPPO_file/MAPPO.py:273-276: e^2/2 if |e| <= d else d(|e| - d/2), mean)
+    int agent;            // masac_actor_kernel: the ONE agent whose actor this launch differentiates (units = learners); unused elsewhere
 };
 
 }  // namespace frl

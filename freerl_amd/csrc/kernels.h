@@ -120,6 +120,8 @@ struct AdamArgs {
     float lr, eps, beta1, beta2, wd, clip, tau, alpha_lr, target_entropy;
     int ragged;          // 1 (frl_reinforce_learn): learner p's batch is its own EngineDesc::ep_n[p] rows — its slabs are the workgroups that
                          // had rows, and a learner with none is skipped whole (slabs, step count, moments, statistics untouched)
+    int agent1;          // > 0 (MASAC's actor steps, one agent after the other): the launch's units are LEARNERS and every one of them steps
+                         // agent agent1 - 1; 0: units = (learner, agent) pairs.  sac_alpha = 2 with it: that agent's own alpha step
 };
 // (kAdamVec, float4 per thread per workgroup of reduce_kernel / adam_kernel: frl_desc.h)
 constexpr int kFusedThreads = 1024, kFusedVec = 12;      // adam_fused_kernel: one workgroup per net, gradient in registers
@@ -212,6 +214,13 @@ __global__ void mappo_state_mask_update_kernel(const EngineDesc* __restrict__ Dp
 __global__ void att_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 __global__ void att_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 __global__ void att_q_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
+// kernels_masac.hip: MASAC (MAAC_file/MASAC.py): the gradient kernels of an ALGO_MASAC engine in the row-chunk launch shape — the critic
+// launch over (learner, agent) units, the actor launch over learners for the ONE agent LearnArgs::agent — and the stacked
+// [mean | log_std] head's forward for frl_act (FRL_ACT_TANHHEAD / FRL_ACT_SAC_SAMPLE)
+__global__ void masac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void masac_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void masac_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
 // kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
 struct HappoArgs {

@@ -120,6 +120,12 @@ __device__ __forceinline__ int adam_unit_ns(const EngineDesc& D, const AdamArgs&
     return ((D.ep_n[p] + D.rc - 1) / D.rc + D.cps - 1) / D.cps;
 }
 
+// unit u of a reduce / Adam launch -> (learner, agent): every agent of learners p0 .., or the one agent AdamArgs::agent1 - 1 of each
+__device__ __forceinline__ void adam_unit(const EngineDesc& D, const AdamArgs& a, int u, int& p, int& ag) {
+    if (a.agent1) { p = a.p0 + u; ag = a.agent1 - 1; }
+    else { p = a.p0 + u / D.n_agents; ag = u % D.n_agents; }
+}
+
 // thread 0 of a unit's first Adam workgroup: losses of the step, SAC's alpha update (SAC.py:154-169,257-260)
 __device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs& a, int ns, int p, int ag, float total, int* steps) {
     const int n = D.n_agents;
@@ -130,7 +136,9 @@ __device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs
     const float invB = 1.f / (float)a.batch;
     st[a.which == 0 ? ST_CRITIC_LOSS : ST_ACTOR_LOSS] = l0 * invB;
     st[a.which == 0 ? ST_CRITIC_GNORM : ST_ACTOR_GNORM] = total;
-    if (a.sac_alpha) {
+    if (a.sac_alpha == 2) {
+        masac_alpha_step(D, p, ag, st, l1 * invB, a.beta1, a.beta2, a.alpha_lr);
+    } else if (a.sac_alpha) {
         float* al = D.alpha + p * 4;
         sac_alpha_step(al, st, steps, al[3], l1 * invB, a.target_entropy, a.beta1, a.beta2, a.alpha_lr);
     }
@@ -141,7 +149,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(const EngineDesc* __restric
     lds_f red = (lds_f)red_s;
     const EngineDesc& D = *Dp;
     const int n = D.n_agents, wg = blockIdx.x % a.G;
-    const int p = a.p0 + (blockIdx.x / a.G) / n, ag = (blockIdx.x / a.G) % n, unit = p * n + ag;
+    int p, ag;
+    adam_unit(D, a, blockIdx.x / a.G, p, ag);
+    const int unit = p * n + ag;
     const int net = adam_net_index(D, a.which, ag);
     const int ns = adam_unit_ns(D, a, p);
     if (ns == 0) return;
@@ -193,7 +203,9 @@ __global__ __launch_bounds__(256) void reduce_kernel(const EngineDesc* __restric
 __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict__ Dp, AdamArgs a) {
     const EngineDesc& D = *Dp;
     const int n = D.n_agents, wg = blockIdx.x % a.G;
-    const int p = a.p0 + (blockIdx.x / a.G) / n, ag = (blockIdx.x / a.G) % n, unit = p * n + ag;
+    int p, ag;
+    adam_unit(D, a, blockIdx.x / a.G, p, ag);
+    const int unit = p * n + ag;
     const int net = adam_net_index(D, a.which, ag);
     const int ns = adam_unit_ns(D, a, p);
     if (ns == 0) return;
@@ -239,7 +251,8 @@ __global__ __launch_bounds__(256) void adam_kernel(const EngineDesc* __restrict_
 template <int VEC, bool WIDE>
 __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamArgs& a, float* red) {
     const int n = D.n_agents;
-    const int p = a.p0 + blockIdx.x / n, ag = blockIdx.x % n;
+    int p, ag;
+    adam_unit(D, a, blockIdx.x, p, ag);
     const int net = adam_net_index(D, a.which, ag);
     const int ns = adam_unit_ns(D, a, p);
     if (ns == 0) return;

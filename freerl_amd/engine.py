@@ -65,6 +65,8 @@ class Engine:
         self.layout = lay
         self.width = lay.width
         self.act_max = max(lay.act_dim[j] for j in range(self.n_agents))
+        # draw sets per (learner, updating agent) of learn()'s `noise` (include/freerl_hip.h: frl_learn_args.noise)
+        self.noise_sets = 2 * self.n_agents + 1 if self.algo == N.ALGO_MASAC else max(2, self.n_agents)
         self.reward_dim = lay.done_off - lay.rew_off if self.n_agents == 1 else 1      # (envelope DQN / DDPG: the reward vector's columns)
         n = C.c_int(0)
         N.check(self._L.frl_net_count(self._h, C.byref(n)))
@@ -190,6 +192,17 @@ class Engine:
         v = np.ascontiguousarray(vals4, dtype=F32)
         N.check(self._L.frl_alpha_set(self._h, int(learner), _fp(v), int(step)))
 
+    def alpha_state_agent(self, agent, learner=0):
+        """({log_alpha, exp_avg, exp_avg_sq, alpha}, Adam step) of ONE agent's alpha (frl_alpha_get_agent: MASAC engines)."""
+        v = np.zeros(4, dtype=F32)
+        t = C.c_int(0)
+        N.check(self._L.frl_alpha_get_agent(self._h, int(learner), int(agent), _fp(v), C.byref(t)))
+        return v, t.value
+
+    def set_alpha_state_agent(self, agent, vals4, step=0, learner=0):
+        v = np.ascontiguousarray(vals4, dtype=F32)
+        N.check(self._L.frl_alpha_set_agent(self._h, int(learner), int(agent), _fp(v), int(step)))
+
     # ------------------------------------------------------------------ forward
     def act(self, net, mode, obs, *, eps=None, head=0, use_target=False, out_dim=None, want_logp=False, normalize=True):
         """obs [P, n_rows, in_dim] (or [n_rows, in_dim] when P == 1) -> out [P, n_rows, out_dim]."""
@@ -257,7 +270,7 @@ class Engine:
             keep.append(ix)
             a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
         if noise is not None:
-            nz = np.ascontiguousarray(noise, dtype=F32).reshape(self.P, self.n_agents, max(2, self.n_agents), int(batch), self.act_max)
+            nz = np.ascontiguousarray(noise, dtype=F32).reshape(self.P, self.n_agents, self.noise_sets, int(batch), self.act_max)
             keep.append(nz)
             a.noise = _fp(nz)
         stats = None

@@ -40,6 +40,7 @@ _MAPPO_TRICK = {"adv_norm": False, "ObsNorm": False, "reward_norm": False, "rewa
 
 _MA_PPO = ("mappo", "ippo", "happo")      # the multi-agent PPO scripts: one loop (_run_mappo)
 _MADDPG = ("maddpg", "maddpg_att")        # MADDPG_simple.py and MADDPG_simple_with_tricks.py: one loop (_run_maddpg)
+_MA_REPLAY = _MADDPG + ("masac",)         # ... and MAAC_file/MASAC.py (_run_masac): continuous parallel envs, dict in / dict out
 
 FLAGS = {
     "dqn": dict(env_name="BipedalWalker-v3", policy_name="DQN", device="cuda", is_dis_to_con=True,
@@ -82,6 +83,11 @@ FLAGS = {
     "maddpg_att": dict(env_name="simple_spread_v3", policy_name="MADDPG_simple", device="cpu", is_dis_to_con=False,
                        flags=[f for f in _COMMON if f[0] != "save_freq"] + _AC + _REPLAY + _GAUSS + [("N", int, 5)],
                        overrides=dict(seed=0, max_episodes=600, gamma=0.95, gauss_sigma=1, gauss_init_scale=1), trick={"ATT": True}),
+    # MAAC_file/MASAC.py:360-387: the script's own defaults (N = None: the env's own agent count)
+    "masac": dict(env_name="simple_spread_v3", policy_name="MASAC", device="cpu", is_dis_to_con=False,
+                  flags=_COMMON + _AC + _REPLAY + [("N", int, None)],
+                  overrides=dict(seed=100, max_episodes=40000, save_freq=600 // 4, start_steps=500, gamma=0.95, tau=0.01, actor_lr=1e-4, critic_lr=1e-4),
+                  trick=None),
     # MAPPO_file/MAPPO.py:533-571 and IPPO.py:409-449: the two scripts' own defaults
     "mappo": dict(env_name="simple_spread_v3", policy_name="MAPPO", device="cuda", is_dis_to_con=False,
                   flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=200, save_freq=5000 // 4, start_steps=0,
@@ -537,6 +543,51 @@ def _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log=
     return dict(returns=arr, steps=step, seconds=time.time() - t0)
 
 
+def _run_masac(args, env, policy, dim_info, max_action, model_dir, writer, log=print):
+    """MASAC.py:417-474: the policy samples its own exploration (no action noise), the env is reset without a seed, and the returns are
+    kept for every 100th episode only."""
+    agents = list(env.agents)
+    episode_num, step = 0, 0
+    episode_reward = {a: 0 for a in agents}
+    returns = {a: [] for a in agents}
+    obs, _ = env.reset()
+    for a in agents:
+        env.action_space(a).seed(seed=args.seed)
+    t0 = time.time()
+    while episode_num < args.max_episodes:
+        step += 1
+        if step < args.random_steps:
+            env_action = {a: env.action_space(a).sample() for a in agents}
+            action = {a: (env_action[a] * 2 - 1) * max_action for a in agents}
+        else:
+            action = policy.select_action(obs)
+            env_action = {a: (action[a] + 1) / 2 * max_action for a in agents}
+        next_obs, reward, terminated, truncated, _ = env.step(env_action)
+        done = {a: terminated[a] or truncated[a] for a in agents}
+        policy.add(obs, action, reward, next_obs, {a: done[a] if not truncated[a] else False for a in agents})
+        episode_reward = {a: episode_reward[a] + reward[a] for a in agents}
+        obs = next_obs
+        if any(done.values()):
+            if (episode_num + 1) % 100 == 0:
+                log("episode: {}, reward: {}".format(episode_num + 1, episode_reward))
+                for a in agents:
+                    writer.add_scalar("reward_%s" % a, episode_reward[a], episode_num + 1)
+                    returns[a].append(episode_reward[a])
+            episode_num += 1
+            obs, _ = env.reset()
+            episode_reward = {a: 0 for a in agents}
+        if step > args.start_steps and step % args.learn_steps_interval == 0:
+            policy.learn(args.batch_size, args.gamma, args.tau)
+        if episode_num % args.save_freq == 0:
+            policy.save(model_dir)
+    log("total_time:", time.time() - t0)
+    policy.save(model_dir)
+    arr = np.array([returns[a] for a in agents])
+    suffix = "" if args.N is None else "_N_%d" % len(agents)
+    np.save(os.path.join(model_dir, "%s_seed_%d%s.npy" % (args.policy_name, args.seed, suffix)), arr)
+    return dict(returns=arr, steps=step, seconds=time.time() - t0)
+
+
 def _mappo_policy_name(args, base):
     """MAPPO.py:573-588 / IPPO.py:451-465 / HAPPO.py:586-601: the policy name decides the tricks — `MAPPO` switches all on but reward_norm and lr_decay,
     `MAPPO_simple` all off"""
@@ -642,12 +693,12 @@ def run(algo, argv=None, env=None, log=print):
     device = torch.device(args.device) if torch.cuda.is_available() else torch.device("cpu")
     if algo in _MA_PPO:
         _mappo_policy_name(args, algo.upper())
-    if algo in _MADDPG or algo in _MA_PPO:
-        if algo not in _MADDPG and not args.continuous_actions and env is None:
+    if algo in _MA_REPLAY or algo in _MA_PPO:
+        if algo not in _MA_REPLAY and not args.continuous_actions and env is None:
             raise ValueError("the in-repo multi-agent environments have continuous actions: pass --continuous_actions True, or an env of your own")
         env = env if env is not None else _envs.make_parallel(args.env_name, args.N)
         env.reset()
-        is_continue = algo in _MADDPG or hasattr(env.action_space(env.agents[0]), "low")
+        is_continue = algo in _MA_REPLAY or hasattr(env.action_space(env.agents[0]), "low")
         dim_info = {a: [env.observation_space(a).shape[0], env.action_space(a).shape[0] if is_continue else env.action_space(a).n] for a in env.agents}
         max_action = 1 if is_continue else None
     else:
@@ -714,6 +765,12 @@ def run(algo, argv=None, env=None, log=print):
         from .MADDPG_simple_with_tricks import MADDPG
         policy = MADDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
         out = _run_maddpg(args, env, policy, dim_info, max_action, model_dir, writer, log)
+        writer.close()
+        return dict(out, model_dir=model_dir, policy=policy, args=args)
+    elif algo == "masac":
+        from .MASAC import MASAC
+        policy = MASAC(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
+        out = _run_masac(args, env, policy, dim_info, max_action, model_dir, writer, log)
         writer.close()
         return dict(out, model_dir=model_dir, policy=policy, args=args)
     elif algo in _MA_PPO:

@@ -74,7 +74,7 @@ enum frl_algo {
     FRL_ALGO_HAPPO = 13,       /* MAPPO_file/HAPPO.py:128-458: a FRL_ALGO_MAPPO engine in every respect at create (nets, the critic on the
                                   concatenated observation, record layout, limits), for heterogeneous agents updated one after another
                                   in a random order: updated by frl_happo_learn, not by frl_mappo_learn */
-    FRL_ALGO_MADDPG_ATT = 14   /* MADDPG_file/MADDPG_simple_with_tricks.py with trick['ATT'] (ATT.py:81-103,181-229): a FRL_ALGO_MADDPG engine
+    FRL_ALGO_MADDPG_ATT = 14,  /* MADDPG_file/MADDPG_simple_with_tricks.py with trick['ATT'] (ATT.py:81-103,181-229): a FRL_ALGO_MADDPG engine
                                   (records, net 2i the actor of agent i, frl_learn with the same arguments) whose net 2i+1 is agent i's
                                   ATTENTION critic with a target copy: encoder_input_fc on [all obs | a_i], decoder_input_fc on the other
                                   agents' actions, fc_encoder_input, 4 fc_encoder_heads, fc_decoder_input, a softmax over the heads'
@@ -82,6 +82,23 @@ enum frl_algo {
                                   critic.  frl_act with FRL_ACT_RAW on net 2i+1 takes rows [all obs | all actions] and returns Q.
                                   frl_params_get / _set order of net 2i+1: fc_encoder_input, the 4 heads' weights stacked [4 hidden][hidden]
                                   then their biases [4 hidden], fc_decoder_input, encoder_input_fc, decoder_input_fc, fc1, fc2 */
+    FRL_ALGO_MASAC = 15        /* MAAC_file/MASAC.py:32-302 (entropy_way_c = entropy_way_a = action_way = '1', adaptive alpha): MADDPG's
+                                  records and net numbering, updated by frl_learn.  Net 2i: agent i's tanh-Gaussian actor obs_dim[i] ->
+                                  hidden -> hidden -> [mean_layer | log_std_layer] (ONE head of 2 act_dim[i] outputs, log_std clamped to
+                                  [-20, 2] per row), with a target copy that the TD target samples from; net 2i+1: its twin critic on
+                                  [all obs | all actions] (l1, l2, l3 and l1_2, l2_2, l3_2 in one net, one optimiser).  One alpha per
+                                  (learner, agent): frl_alpha_get_agent / frl_alpha_set_agent.  Per frl_learn call, for agent 0, 1, ..
+                                  in order: critic step (every target actor sampled, the agent's own log-prob and alpha in the target),
+                                  actor step (fresh actions of ALL online actors — agents j < i as just stepped — through the agent's
+                                  own twin critic, min(Q1, Q2), entropy from a second draw of its own actor), alpha step (target entropy
+                                  -act_dim[i]; frl_learn_args.target_entropy is unused); then every target is soft-updated.
+                                  frl_params_get / _set order: actor l1, l2, mean_layer (weight, bias), log_std_layer (weight, bias);
+                                  critic l1, l2, l3, l1_2, l2_2, l3_2.  frl_act on net 2i: FRL_ACT_SAC_SAMPLE = tanh(mean + std eps),
+                                  FRL_ACT_TANHHEAD = tanh(mean) (act_dim[i] columns), FRL_ACT_RAW = [mean | log_std]; on net 2i+1:
+                                  FRL_ACT_RAW on rows [all obs | all actions] = Q of `head` 0 / 1, online or target.
+                                  Refused at create: discrete, twin_critic = 0, hidden_act != FRL_ACT_RELU, a row chunk that does not
+                                  fit a CU's LDS.  Refused at the call (FRL_ERR_STATE): frl_obsnorm_enable, use_policy_noise,
+                                  frl_rollout, frl_act_explore.  frl_version() 111 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -208,6 +225,9 @@ typedef struct frl_learn_args {
     const float* noise;        /* host [P][n_agents][S][batch][act_max], S = max(2, n_agents): N(0,1) draws the reference
                                   takes from torch's generator (TD3.py:197 slot 0; SAC.py:227 slot 0, :244 slot 1;
                                   MATD3_simple.py:200: slot j = randn_like(action[agent j]) inside agent i's sample());
+                                  FRL_ALGO_MASAC: S = 2 n_agents + 1, per updating agent i in the reference's order: slot j =
+                                  actor_target_j's rsample in sample() (MASAC.py:214), slot n + j = actor_j's in the actor loss (:254),
+                                  slot 2n = the second draw of actor_i for the entropy (:261);
                                   NULL: drawn on the device */
     float* stats_out;          /* host [P][n_agents][FRL_STAT_COUNT] or NULL (NULL: call is asynchronous) */
     int loss_kind;             /* TD loss of the Q / critic update: FRL_LOSS_MSE = F.mse_loss, what every hot-path learn() of the
@@ -280,6 +300,11 @@ int frl_opt_step_set(frl_engine* e, int learner, int net, int t);
 /* SAC Alpha (SAC.py:154-169): vals = {log_alpha, exp_avg, exp_avg_sq, alpha} */
 int frl_alpha_get(frl_engine* e, int learner, float* vals4_out, int* step_out);
 int frl_alpha_set(frl_engine* e, int learner, const float* vals4, int step);
+/* ... of ONE agent of a FRL_ALGO_MASAC engine (MASAC.py:124-139: one Alpha per agent), `step` its Adam step count.  On every other
+ * engine agent must be 0 and the pair is frl_alpha_get / _set.  On a FRL_ALGO_MASAC engine with n_agents > 1 frl_alpha_get / _set
+ * return FRL_ERR_STATE (there is no one alpha to name); with n_agents = 1 they serve agent 0. */
+int frl_alpha_get_agent(frl_engine* e, int learner, int agent, float* vals4_out, int* step_out);
+int frl_alpha_set_agent(frl_engine* e, int learner, int agent, const float* vals4, int step);
 
 /* Batch_ObsNorm (`Normalization_batch_size`, PPO_file/normalization.py:53-84; SAC.py:181-182,215-217;
  * DDPG.py:160-161,190-192; PPO_with_tricks.py:225-226,297-299): when enabled, every learn call first

@@ -57,7 +57,12 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # at the kernels' top: att_critic_kernel 256 VGPRs + 44 AGPRs, no spilled VGPR, 96 bytes of scratch (the Lds / AttLds structs the
           # calls pass by reference); att_q_kernel the same, none spilled; att_actor_kernel 77 spilled and 368 bytes: the actor's own inlined
           # mlp_fwd_rows / mlp_bwd addresses, stored at entry and reloaded at the start of a barrier phase, none inside an MFMA k-loop
-          ("att_critic_", 0), ("att_actor_", 77), ("att_q_", 0), ("", 20)]
+          ("att_critic_", 0), ("att_actor_", 77), ("att_q_", 0),
+          # kernels_masac.hip (figures of the unit compiled on its own, DESIGN.md "MASAC"): masac_critic_kernel 256 VGPRs, no spilled VGPR, 56 bytes of
+          # scratch (a row lambda's captures); masac_act_kernel 188 VGPRs + 40 AGPRs, none spilled; masac_actor_kernel 256 VGPRs with 52 spilled and
+          # 232 bytes: the two NetDescs' layer offsets, the three draw-set bases and the chunk loop's bounds, stored at entry and reloaded at the
+          # start of a barrier phase or between two tile blocks, none inside an innermost MFMA k-loop (some outer layer / tile-block loops hold them)
+          ("masac_critic_", 0), ("masac_actor_", 52), ("masac_act_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
