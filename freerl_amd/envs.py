@@ -220,15 +220,18 @@ class SpreadEnv:
     5, soft contact forces; observation = [vel(2), pos(2), landmark offsets(2N), other agents'
     offsets(2(N-1)), comm(2(N-1)) zeros] (18 floats at N = 3); action = 5 floats in [0,1]
     (no-op, left, right, down, up); reward = 0.5*(-sum over landmarks of the closest agent distance)
-    + 0.5*(-collisions of the agent); episode truncates after `max_cycles` (25) steps."""
+    + 0.5*(-collisions of the agent); episode truncates after `max_cycles` (25) steps.
+    `continuous_actions=False`: a `Discrete(5)` action space, and `step` takes the action's index and applies the force of its one-hot
+    vector, as PettingZoo's discrete MPE does (MAAC_discrete.py's env)."""
 
-    def __init__(self, N=3, max_cycles=25, local_ratio=0.5):
+    def __init__(self, N=3, max_cycles=25, local_ratio=0.5, continuous_actions=True):
         self.N, self.max_cycles, self.local_ratio = int(N), int(max_cycles), local_ratio
+        self.continuous_actions = bool(continuous_actions)
         self.possible_agents = ["agent_%d" % i for i in range(self.N)]
         self.agents = list(self.possible_agents)
         od = 4 + 2 * self.N + 4 * (self.N - 1)
         self._obs_space = {a: Box(-np.inf, np.inf, shape=(od,)) for a in self.agents}
-        self._act_space = {a: Box(0.0, 1.0, shape=(5,)) for a in self.agents}
+        self._act_space = {a: Box(0.0, 1.0, shape=(5,)) if self.continuous_actions else Discrete(5) for a in self.agents}
         self.size, self.damping, self.dt, self.sens = 0.15, 0.25, 0.1, 5.0
         self.contact_force, self.contact_margin = 1e2, 1e-3
         self.np_random = np.random.default_rng()
@@ -261,7 +264,7 @@ class SpreadEnv:
     def step(self, actions):
         force = np.zeros((self.N, 2))
         for i, a in enumerate(self.agents):
-            u = np.asarray(actions[a], dtype=np.float64)
+            u = np.asarray(actions[a], dtype=np.float64) if self.continuous_actions else np.eye(5)[int(np.asarray(actions[a]))]
             force[i] = self.sens * np.array([u[2] - u[1], u[4] - u[3]])
         dmin = 2 * self.size
         for i in range(self.N):
@@ -288,14 +291,14 @@ class SpreadEnv:
                 {a: {} for a in self.agents})
 
 
-def make_parallel(env_name, N=None, max_cycles=25, prefer_pettingzoo=True):
+def make_parallel(env_name, N=None, max_cycles=25, prefer_pettingzoo=True, continuous_actions=True):
     """`importlib.import_module(f'pettingzoo.mpe.{env_name}').parallel_env(...)` (MADDPG_simple.py:214-225)
     when pettingzoo is importable, else the in-repo restatement of simple_spread."""
     if prefer_pettingzoo:
         try:
             import importlib
             mod = importlib.import_module("pettingzoo.mpe.%s" % env_name)
-            kw = dict(max_cycles=max_cycles, continuous_actions=True)
+            kw = dict(max_cycles=max_cycles, continuous_actions=bool(continuous_actions))
             if N is not None:
                 kw["N"] = N
             return mod.parallel_env(**kw)
@@ -303,4 +306,4 @@ def make_parallel(env_name, N=None, max_cycles=25, prefer_pettingzoo=True):
             pass
     if not env_name.startswith("simple_spread"):
         raise KeyError("only simple_spread is restated in-repo; %r needs pettingzoo" % env_name)
-    return SpreadEnv(N if N is not None else 3, max_cycles)
+    return SpreadEnv(N if N is not None else 3, max_cycles, continuous_actions=continuous_actions)
