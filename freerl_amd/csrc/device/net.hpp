@@ -10,6 +10,7 @@
 // plain read-modify-write).  Parameters / Adam state / targets are streamed once per step by the Adam kernels.
 #pragma once
 #include "../frl_desc.h"
+#include "../rowchunk_layout.h"
 #include "adam.hpp"
 #include "policy.hpp"
 #include "rng.hpp"
@@ -83,7 +84,7 @@ __device__ __forceinline__ Lds carve_lds(float* smem, int rc, int hidden, int ki
     Lds S;
     S.rc = rc;
     S.xp = kin_pad_max + 4;
-    S.hp = hidden + 4;
+    S.hp = hidden_pitch(hidden);
     S.op = out_pad_max + 4;
     S.ap = act_pad;
     lds_f p = (lds_f)smem;
@@ -203,9 +204,7 @@ __device__ __forceinline__ void linear_bwd_dx(const LayerDesc& L, g_cf theta, ld
 }
 
 // G.Wk[k_pad][n_pad] (=|+=) X^T * dY ;  G.b (=|+=) column sums of dY
-// How a gradient tile reaches its slab: GS_STREAM the slab is written once and read once by reduce_kernel (non-temporal
-// store), GS_STORE first of several row chunks (plain store: the next chunk reads it back), GS_ADD a later chunk.
-enum GradStore : int { GS_STREAM = 0, GS_STORE = 1, GS_ADD = 2 };
+// (how a gradient tile reaches its slab — GradStore: rowchunk_layout.h)
 
 // bias = false: the weight block only (an outer product that is no layer's backward: device/gail.hpp)
 __device__ __forceinline__ void linear_bwd_dw(const LayerDesc& L, g_f G, lds_cf dY, int ldy, lds_cf X, int ldx, int rc,

@@ -14,6 +14,7 @@
 
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
+#include "rowchunk_layout.h"
 
 namespace frl {
 
@@ -106,6 +107,7 @@ struct EngineFacts {
     bool has_nets = false;
     int noisy_per_set = 0;        // floats of device noise per (learner, forward): 2 * (k_pad + n_pad) of the head
     size_t idx_count = 0, noise_count = 0;      // ints / floats of the idx and noise uploads
+    size_t slab_count = 0, part_count = 0, act_spill_count = 0;      // floats of the row-chunk kernels' slab, part and act_spill (rowchunk_layout.h; act_spill: 0 where no actor stage parks)
     size_t alpha_count = 0, steps_count = 0;    // floats of EngineDesc::alpha, ints of EngineDesc::steps (MASAC: per-agent alpha blocks and counters)
     int solo_stride = 0;          // floats per gradient slab of kernels_solo.hip / kernels_solow.hip: the largest net
     int solow_row_wgs = 0;        // kernels_solow.hip: workgroups per unit that own row tiles (16: one tile each; 64: MADDPG's batches of 1024)
@@ -209,7 +211,7 @@ inline void record_layout(const RecordDesc& R, frl_record_layout* out) {
 }
 
 inline int lds_bytes_for(const EngineDesc& h, int rc) {
-    const int xp = h.lds_kin_pad + 4, hp = h.hidden + 4, op = h.lds_out_pad + 4, ap = h.lds_act_pad;
+    const int xp = h.lds_kin_pad + 4, hp = hidden_pitch(h.hidden), op = h.lds_out_pad + 4, ap = h.lds_act_pad;
     long long fl = (long long)rc * (xp + h.lds_hbufs * hp + op + 2 * ap + h.lds_row_extra) + h.lds_batch_pad + 8;
     return (int)(fl * 4);
 }
@@ -721,6 +723,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     const size_t P = h.P;
     h.Gmax = 1;
     for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
+    pl.slab_count = slab_floats(h);
+    pl.part_count = part_floats(h);
+    pl.act_spill_count = T.act_spill ? act_spill_floats(h) : 0;
     pl.idx_count = P * h.n_agents * h.batch_max;
     if (h.noisy) {
         const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];

@@ -339,10 +339,9 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
         CREATE_TRY(e->mem.alloc_zero(&h.m, P * ls, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.v, P * ls, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.grad, P * ls, e->stream));
-        CREATE_TRY(e->mem.alloc_zero(&h.slab, P * (size_t)h.S * ls, e->stream));
-        CREATE_TRY(e->mem.alloc_zero(&h.part, P * (size_t)h.n_agents * h.S * 4, e->stream));
-        if (T.act_spill)
-            CREATE_TRY(e->mem.alloc_zero(&h.act_spill, P * (size_t)h.n_agents * h.S * 2 * h.rc * (h.hidden + 4), e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.slab, e->slab_count, e->stream));
+        CREATE_TRY(e->mem.alloc_zero(&h.part, e->part_count, e->stream));
+        if (e->act_spill_count) CREATE_TRY(e->mem.alloc_zero(&h.act_spill, e->act_spill_count, e->stream));
         CREATE_TRY(e->mem.alloc_zero(&h.gsq, P * (size_t)h.n_agents * h.Gmax, e->stream));
         if (h.noisy) {
             CREATE_TRY(e->mem.alloc_zero(&h.theta_eff, P * 3 * ls, e->stream));

@@ -55,7 +55,7 @@ static int envelope_prelude(frl_engine* e, const EnvelopeCall& c, std::initializ
     a.p0 = 0; a.p_count = P;
     ++e->param_version;
     out->rows = B * W;
-    out->ns = ((out->rows + h.rc - 1) / h.rc + h.cps - 1) / h.cps;
+    out->ns = rowchunk_ns(h, out->rows);
     if (dev_idx) {
         LearnArgs la;
         memset(&la, 0, sizeof la);
@@ -77,19 +77,12 @@ extern "C" int frl_envelope_learn(frl_engine* e, const frl_envelope_args* args) 
     EnvelopeLaunch L;
     if (const int rc = envelope_prelude(e, {args->batch, args->weight_num, args->gamma, args->beta, args->idx, args->weights},
                                         {args->gamma, args->tau, args->lr, args->beta}, "gamma / tau / lr / beta", &L)) return rc;
-    const int P = h.P;
-    prof_begin(e, PK_GRAD_ACTOR);
-    hipLaunchKernelGGL(envelope_grad_kernel, dim3(((P + 7) / 8) * 8 * L.ns), dim3(256), e->lds_bytes, e->stream, e->d, L.a, L.ns);
-    prof_end(e);
-    AdamArgs ad;
-    memset(&ad, 0, sizeof ad);
+    AdamArgs ad{};
     ad.which = 1;                                  // net 0, statistics in the actor slots
-    ad.ns = L.ns; ad.batch = L.rows;               // the loss partials are per row: beta d^2 + (1 - beta) / R sum_k e_k^2
+    ad.batch = L.rows;                             // the loss partials are per row: beta d^2 + (1 - beta) / R sum_k e_k^2
     ad.lr = args->lr; ad.eps = 1e-8f; ad.beta1 = 0.9f; ad.beta2 = 0.999f;
-    ad.clip = 0.f; ad.soft = 1; ad.tau = args->tau; ad.p0 = 0; ad.G = h.Gmax;
-    prof_begin(e, PK_ADAM_ACTOR);
-    launch_adam(e, e->stream, ad, P, dim3(P * h.Gmax));
-    prof_end(e);
+    ad.clip = 0.f; ad.soft = 1; ad.tau = args->tau;
+    launch_rowchunk_update(e, e->stream, h.P, 0, L.ns, ad, envelope_grad_kernel, L.a);
     HIP_TRY(hipGetLastError());
     if (!args->loss_out && !args->weights_out) return FRL_OK;
     return read_back(e, args->weights_out, args->weight_num, {ST_ACTOR_LOSS, args->loss_out});

@@ -16,27 +16,14 @@ extern "C" int frl_envelope_ddpg_learn(frl_engine* e, const frl_envelope_ddpg_ar
     if (const int rc = envelope_prelude(e, {args->batch, args->weight_num, args->gamma, args->beta, args->idx, args->weights},
                                         {args->gamma, args->tau, args->actor_lr, args->critic_lr, args->beta},
                                         "gamma / tau / actor_lr / critic_lr / beta", &L)) return rc;
-    const int P = h.P;
-    const dim3 grid_chunks(((P + 7) / 8) * 8 * L.ns), grid_adam(P * h.Gmax);
-    AdamArgs ad;
-    memset(&ad, 0, sizeof ad);
-    ad.ns = L.ns; ad.batch = L.rows;               // the loss partials are per row
+    AdamArgs ad{};
+    ad.batch = L.rows;                             // the loss partials are per row
     ad.eps = 1e-8f; ad.beta1 = 0.9f; ad.beta2 = 0.999f;
-    ad.clip = 0.5f; ad.soft = 1; ad.tau = args->tau; ad.p0 = 0; ad.G = h.Gmax;
-    prof_begin(e, PK_GRAD_CRITIC);
-    hipLaunchKernelGGL(envelope_ddpg_critic_kernel, grid_chunks, dim3(256), e->lds_bytes, e->stream, e->d, L.a, L.ns);
-    prof_end(e);
+    ad.clip = 0.5f; ad.soft = 1; ad.tau = args->tau;
     ad.which = 0; ad.lr = args->critic_lr;         // net 1: beta d^2 + (1 - beta) / R sum_k e_k^2 per row
-    prof_begin(e, PK_ADAM_CRITIC);
-    launch_adam(e, e->stream, ad, P, grid_adam);
-    prof_end(e);
-    prof_begin(e, PK_GRAD_ACTOR);
-    hipLaunchKernelGGL(envelope_ddpg_actor_kernel, grid_chunks, dim3(256), e->lds_bytes, e->stream, e->d, L.a, L.ns);
-    prof_end(e);
+    launch_rowchunk_update(e, e->stream, h.P, 0, L.ns, ad, envelope_ddpg_critic_kernel, L.a);
     ad.which = 1; ad.lr = args->actor_lr;          // net 0: -sum_k Q_k / R per row
-    prof_begin(e, PK_ADAM_ACTOR);
-    launch_adam(e, e->stream, ad, P, grid_adam);
-    prof_end(e);
+    launch_rowchunk_update(e, e->stream, h.P, 0, L.ns, ad, envelope_ddpg_actor_kernel, L.a);
     HIP_TRY(hipGetLastError());
     if (!args->critic_loss_out && !args->actor_loss_out && !args->weights_out) return FRL_OK;
     return read_back(e, args->weights_out, args->weight_num, {ST_CRITIC_LOSS, args->critic_loss_out}, {ST_ACTOR_LOSS, args->actor_loss_out});

@@ -45,25 +45,19 @@ extern "C" int frl_gail_learn(frl_engine* e, const frl_gail_args* args) {
     a.n_expert = E; a.n_policy = NP; a.gp = args->gp; a.gp_weight = args->gp_weight;
     a.size = min_size; a.p0 = 0; a.p_count = P;
     ++e->param_version;
-    const int ns = ((E + NP + h.rc - 1) / h.rc + h.cps - 1) / h.cps;
+    const int ns = rowchunk_ns(h, E + NP);
     if (!args->idx) {
         a.rng_counter = e->rng_counter++;
         prof_begin(e, PK_DRAW);
         hipLaunchKernelGGL(gail_draw_kernel, dim3(P), dim3(256), 0, e->stream, e->d, a);
         prof_end(e);
     }
-    prof_begin(e, PK_GRAD_ACTOR);
-    hipLaunchKernelGGL(gail_disc_kernel, dim3(((P + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, e->stream, e->d, a, ns);
-    prof_end(e);
-    AdamArgs ad;
-    memset(&ad, 0, sizeof ad);
+    AdamArgs ad{};
     ad.which = 1;                                  // net 0, statistics in the actor slots (gail_stats_kernel rewrites the loss slot)
-    ad.ns = ns; ad.batch = E + NP;
+    ad.batch = E + NP;
     ad.lr = args->lr; ad.eps = args->adam_eps; ad.beta1 = args->beta1; ad.beta2 = args->beta2;
-    ad.clip = 0.f; ad.soft = 0; ad.p0 = 0; ad.G = h.Gmax;
-    prof_begin(e, PK_ADAM_ACTOR);
-    launch_adam(e, e->stream, ad, P, dim3(P * h.Gmax));
-    prof_end(e);
+    ad.clip = 0.f; ad.soft = 0;
+    launch_rowchunk_update(e, e->stream, P, 0, ns, ad, gail_disc_kernel, a);
     hipLaunchKernelGGL(gail_stats_kernel, dim3((P + 255) / 256), dim3(256), 0, e->stream, e->d, a, ns);
     HIP_TRY(hipGetLastError());
     if (!args->out && !args->idx_out) return FRL_OK;

@@ -143,31 +143,45 @@ static void launch_dqn_fused(frl_engine* e, const LearnStage& s, LearnArgs a, co
     prof_end(e);
 }
 
-// the row-chunk kernels: a gradient launch over (unit, slab) workgroups, then reduce + clip + Adam
-// att: FAM_ATT's launcher — the same launch shape and the same reduce + clip + Adam behind the family's own gradient kernels
-static void launch_rowchunk(frl_engine* e, const LearnStage& s, const LearnArgs& a, bool att = false) {
+// One update on the row-chunk launch shape (rowchunk_layout.h): the gradient kernel over units x ns workgroups on the 8-aligned grid
+// (a unit's slices on one XCD), then reduce + clip + Adam of the units' net ad.which (1: the actor slots, 0: the critic's).  The caller
+// brings the kernel's own arguments and ad's hyper-parameters; the launch shape's fields of ad are set here.
+template <class Kernel, class... Args>
+static void launch_rowchunk_update(frl_engine* e, hipStream_t st, int units, int p0, int ns, AdamArgs ad, Kernel k, const Args&... args) {
+    const bool actor = ad.which == 1;
+    prof_begin(e, actor ? PK_GRAD_ACTOR : PK_GRAD_CRITIC);
+    hipLaunchKernelGGL(k, dim3(((units + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, st, e->d, args..., ns);
+    prof_end(e);
+    ad.ns = ns; ad.p0 = p0; ad.G = e->h.Gmax;
+    prof_begin(e, actor ? PK_ADAM_ACTOR : PK_ADAM_CRITIC);
+    launch_adam(e, st, ad, units, dim3(units * e->h.Gmax));      // (a NoisyLinear head's sigma gradients are derived in its slab sums)
+    prof_end(e);
+}
+// what frl_learn's row-chunk families hand their Adam launches out of the call's arguments
+static AdamArgs learn_adam_args(const LearnArgs& a, bool actor) {
+    AdamArgs ad{};
+    ad.which = actor ? 1 : 0; ad.lr = actor ? a.actor_lr : a.critic_lr;
+    ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm; ad.tau = a.tau; ad.alpha_lr = a.alpha_lr;
+    return ad;
+}
+
+// the row-chunk kernels of DQN / C51 / DDPG / TD3 / SAC / MADDPG / discrete SAC, and FAM_ATT's own (e->kern) on the same launch shape
+// (what launch_att forwarded to: FAM_ATT's case of launch_learn_stage calls this directly)
+static void launch_rowchunk(frl_engine* e, const LearnStage& s, const LearnArgs& a, LearnFamily fam) {
     const EngineDesc& h = e->h;
     const bool actor = s.stage == 1, sac = h.algo == ALGO_SAC || h.algo == ALGO_SAC_DISCRETE, maddpg = is_maddpg(h.algo);
-    const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
-    const dim3 grid_chunks(((s.units + 7) / 8) * 8 * ns), grid_adam(s.units * h.Gmax);
     auto k = actor ? (h.algo == ALGO_SAC_DISCRETE ? sacd_actor_kernel : ac_actor_kernel)
                    : (h.algo == ALGO_DQN ? (h.c51_atoms ? c51_grad_kernel : dqn_grad_kernel) : h.algo == ALGO_SAC_DISCRETE ? sacd_critic_kernel : ac_critic_kernel);
-    if (att) k = actor ? e->kern.actor.kr : e->kern.critic.kr;
-    prof_begin(e, actor ? PK_GRAD_ACTOR : PK_GRAD_CRITIC);
-    hipLaunchKernelGGL(k, grid_chunks, dim3(256), e->lds_bytes, s.st, e->d, a, ns);
-    prof_end(e);
-    AdamArgs ad{};
-    ad.ns = ns; ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm;
-    ad.tau = a.tau; ad.alpha_lr = a.alpha_lr; ad.target_entropy = a.target_entropy; ad.p0 = s.p0; ad.G = h.Gmax;
+    if (fam == FAM_ATT) k = actor ? e->kern.actor.kr : e->kern.critic.kr;
+    AdamArgs ad = learn_adam_args(a, actor);
+    ad.target_entropy = a.target_entropy;
     if (actor) {
-        ad.which = 1; ad.lr = a.actor_lr; ad.wd = 0.f; ad.soft = maddpg ? 0 : 1; ad.sac_alpha = sac ? 1 : 0;
+        ad.soft = maddpg ? 0 : 1; ad.sac_alpha = sac ? 1 : 0;
     } else {
-        ad.which = 0; ad.lr = a.critic_lr; ad.wd = a.critic_wd;
+        ad.wd = a.critic_wd;
         ad.soft = (h.algo == ALGO_DQN) ? 1 : ((!maddpg && a.do_actor) ? 1 : 0);
     }
-    prof_begin(e, actor ? PK_ADAM_ACTOR : PK_ADAM_CRITIC);
-    launch_adam(e, s.st, ad, s.units, grid_adam);      // (a NoisyLinear head's sigma gradients are derived in its slab sums)
-    prof_end(e);
+    launch_rowchunk_update(e, s.st, s.units, s.p0, rowchunk_ns(h, a.batch), ad, k, a);
 }
 
 // kernels_critic2.hip / kernels_actor2.hip: a whole stage of DDPG / TD3 / SAC in one launch, one workgroup per learner
@@ -259,28 +273,14 @@ static void launch_solow(frl_engine* e, const LearnStage& s, const LearnArgs& a,
     prof_end(e);
 }
 
-// kernels_att.hip: ATT-MADDPG's gradient launches over (unit, slab) workgroups, then reduce + clip + Adam as the row-chunk family
-static void launch_att(frl_engine* e, const LearnStage& s, const LearnArgs& a) { launch_rowchunk(e, s, a, true); }
-
 // kernels_masac.hip.  Stage 0: every (learner, agent) critic unit in one launch, then their reduce + clip + Adam (targets untouched: the soft
 // stage moves them).  Stage 1, once per agent in agent order (a.agent): the actor launch over LEARNERS for that agent, its reduce + clip +
 // Adam and the agent's alpha step — stream order makes agent i's launch read the actors of agents j < i as stepped (MASAC.py:221,254)
 static void launch_masac(frl_engine* e, const LearnStage& s, const LearnArgs& a) {
-    const EngineDesc& h = e->h;
     const bool actor = s.stage == 1;
-    const int ns = ((a.batch + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) per unit
-    const int units = actor ? s.pc : s.units;
-    prof_begin(e, actor ? PK_GRAD_ACTOR : PK_GRAD_CRITIC);
-    hipLaunchKernelGGL(actor ? e->kern.actor.kr : e->kern.critic.kr, dim3(((units + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, s.st, e->d, a, ns);
-    prof_end(e);
-    AdamArgs ad{};
-    ad.ns = ns; ad.batch = a.batch; ad.eps = a.adam_eps; ad.beta1 = a.beta1; ad.beta2 = a.beta2; ad.clip = a.clip_norm;
-    ad.tau = a.tau; ad.alpha_lr = a.alpha_lr; ad.p0 = s.p0; ad.G = h.Gmax; ad.soft = 0; ad.wd = 0.f;
-    if (actor) { ad.which = 1; ad.lr = a.actor_lr; ad.sac_alpha = 2; ad.agent1 = a.agent + 1; }
-    else { ad.which = 0; ad.lr = a.critic_lr; }
-    prof_begin(e, actor ? PK_ADAM_ACTOR : PK_ADAM_CRITIC);
-    launch_adam(e, s.st, ad, units, dim3(units * h.Gmax));
-    prof_end(e);
+    AdamArgs ad = learn_adam_args(a, actor);
+    if (actor) { ad.sac_alpha = 2; ad.agent1 = a.agent + 1; }
+    launch_rowchunk_update(e, s.st, actor ? s.pc : s.units, s.p0, rowchunk_ns(e->h, a.batch), ad, actor ? e->kern.actor.kr : e->kern.critic.kr, a);
 }
 
 static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, LearnArgs a, int stage, int p0, int pc, bool dev_rng, bool needs_noise,
@@ -307,12 +307,11 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, L
         launch_draw_and_prologue(e, s, a, dev_rng && !ma_use_pre && !draws_in_critic);
     }
     switch (fam) {
-        case FAM_ROWCHUNK: launch_rowchunk(e, s, a); break;
+        case FAM_ROWCHUNK: case FAM_ATT: launch_rowchunk(e, s, a, fam); break;
         case FAM_CHAINED: launch_chained(e, s, a); break;
         case FAM_SOLO: launch_solo(e, s, a, sstep); break;
         case FAM_SOLOW: launch_solow(e, s, a, ma_predraw, ma_use_pre); break;
         case FAM_WIDE: case FAM_WIDE16: launch_wide(e, s, a); break;
-        case FAM_ATT: launch_att(e, s, a); break;
         case FAM_MASAC: launch_masac(e, s, a); break;
         case FAM_DQN_FUSED: break;
     }

@@ -35,23 +35,17 @@ extern "C" int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args
     HIP_TRY(hipEventRecord(e->ev_ep[slot], e->stream));
     ++e->param_version;
 
-    const int ns = ((n_max + h.rc - 1) / h.rc + h.cps - 1) / h.cps;      // workgroups (= slabs) of the longest episode
+    const int ns = rowchunk_ns(h, n_max);          // workgroups (= slabs) of the longest episode
     prof_begin(e, PK_DRAW);
     hipLaunchKernelGGL(reinforce_returns_kernel, dim3(P), dim3(256), 0, e->stream, e->d, args->gamma);
     prof_end(e);
-    prof_begin(e, PK_GRAD_ACTOR);
-    hipLaunchKernelGGL(reinforce_grad_kernel, dim3(((P + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, e->stream, e->d, 0, P, ns);
-    prof_end(e);
-    AdamArgs ad;
-    memset(&ad, 0, sizeof ad);
+    AdamArgs ad{};
     ad.which = 1;                                  // net 0, statistics in the actor slots
-    ad.ns = ns; ad.ragged = 1;
+    ad.ragged = 1;
     ad.batch = 1;                                  // the loss is a sum
     ad.lr = args->lr; ad.eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f; ad.beta1 = 0.9f; ad.beta2 = 0.999f;
-    ad.clip = 0.f; ad.p0 = 0; ad.G = h.Gmax;
-    prof_begin(e, PK_ADAM_ACTOR);
-    launch_adam(e, e->stream, ad, P, dim3(P * h.Gmax));
-    prof_end(e);
+    ad.clip = 0.f;
+    launch_rowchunk_update(e, e->stream, P, 0, ns, ad, reinforce_grad_kernel, 0, P);
     HIP_TRY(hipGetLastError());
     for (int p = 0; p < P; ++p)
         if (hn[p] > 0) { e->index[p] = 0; e->size[p] = 0; }              // self.rewards = [] ... (:125-127)

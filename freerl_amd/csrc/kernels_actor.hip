@@ -13,22 +13,20 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count * n) return;
-    const int p = a.p0 + us.unit / n, ag = us.unit % n, sl = us.slice;
+    const RowUnit U = agent_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[2 * ag];
     const NetDesc& NC = D.net[2 * ag + 1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
+    const RowWalk W = U.walk(B);
     const bool sac = (D.algo == ALGO_SAC);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[2 * ag]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf thA = U.theta(2 * ag);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_f slab = U.slab(2 * ag);
+    g_cf ring = U.ring();
     const int am = D.act_max;
     const int heads = NC.heads, ql = NC.n_layers / heads;
     const int OT = R.obs_total, AT = R.act_total, kc0 = NC.L[0].k_pad;
@@ -48,12 +46,12 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
 
     FRL_PHASE_INIT(S);
     float alossp = 0.f, entp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
-    g_cf noise1 = as_global(D.noise + (((size_t)p * n + ag) * D.noise_sets + 1) * D.batch_max * am + (size_t)r0 * am);
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const RowChunk c = row_chunk(W.cr, ck);
+    const bool first = c.first;
+    const int gs = c.gs, nv = c.nv;
+    g_ci idx = U.idx(c.r0);
+    g_cf noise1 = U.noise(1, c.r0);
     if (!first) lds_barrier();
     // -- a = actor(obs)
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[ag], Oa, 0);
@@ -62,8 +60,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
     FRL_PHASE(S);
     // park the actor's hidden activations in HBM: the critic pass below reuses h1 / h2, the actor's backward needs them
     // again, and a second actor forward cost 16 % of this kernel (tools/phase_timing.py actor)
-    const int spill_n4 = 2 * rc * S.hp / 4;                 // h1 and h2 are adjacent in LDS
-    FRL_GLB f32x4* spill = (FRL_GLB f32x4*)(D.act_spill + (((size_t)p * n + ag) * D.S + sl) * 2 * rc * S.hp);
+    FRL_GLB f32x4* spill = U.spill();
     float lp = 0.f;
     // the action of row r in the finalize phase of the actor; single agent: straight into the critic's input row (xin[:, 0:O)
     // still holds the normalised obs, the columns past the action are zero), which saves the [s|a] gather of the first head
@@ -78,9 +75,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
             S.dabuf[r * S.ap + c] = 0.f;
             if (direct) S.xin[r * S.xp + OT + c] = av;
         }
-    }, [&]() {
-        for (int i = threadIdx.x; i < spill_n4; i += kWG) spill[i] = ld4((lds_cf)(S.h1 + 4 * i));
-    });
+    }, [&]() { park_hidden(S, spill); });
     // -- dQ/da through the critic head(s)
     float qsum = 0.f;
     for (int h = 0; h < nq; ++h) {
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
         }
     }
     // -- the actor's activations back from HBM (same thread, same addresses as the spill), its input back in xin
-    for (int i = threadIdx.x; i < spill_n4; i += kWG) st4(S.h1 + 4 * i, spill[i]);
+    restore_hidden(S, spill);
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[ag], Oa, 0);    // (the critic's dX1 landed on xin)
     zero_cols(S.xin, S.xp, rc, Oa, NA.L[0].k_pad);
     if (bn) { lds_barrier(); normalize_cols(S.xin, S.xp, nv, 0, Oa, bn_own, Oa); }
@@ -154,10 +149,6 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_actor_kernel(const Engin
     FRL_PHASE_DUMP(S, 1);
     const float la = block_sum(alossp, S.red);
     const float le = sac ? block_sum(entp, S.red) : 0.f;
-    if (threadIdx.x == 0) {
-        float* pt = D.part + (((size_t)p * n + ag) * D.S + sl) * 4;
-        pt[0] = la;
-        pt[1] = le;
-    }
+    store_loss_parts(U, la, le);
 }
 }  // namespace frl

@@ -29,21 +29,19 @@ __device__ __forceinline__ void att_gather_stored(const EngineDesc& D, const Lds
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count * n) return;
-    const int p = a.p0 + us.unit / n, ag = us.unit % n, sl = us.slice;
+    const RowUnit U = agent_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag, sl = U.sl;
     const RecordDesc& R = D.rec;
     const NetDesc& NC = D.net[2 * ag + 1];
     const Lds S = carve(D, smem);
     const AttLds A = carve_att(D, S, smem);
     const int rc = D.rc, B = a.batch;
     const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_cf tgC = as_global(D.target + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag + 1]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_cf tgC = U.target(2 * ag + 1);
+    g_f slab = U.slab(2 * ag + 1);
+    g_cf ring = U.ring();
     const int OT = R.obs_total, AT = R.act_total, Aa = R.act_dim[ag], a0 = R.act_off[ag] - R.act_off[0];
     const float invB = 1.f / (float)B;
 
@@ -52,12 +50,12 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_critic_kernel(const Eng
     const bool first = (ck == cr.c0);
     const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
     const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
+    g_ci idx = U.idx(r0);
     if (!first) lds_barrier();
     // ---- a'_j = actor_target_j(o'_j) for every agent j (MADDPG_simple_with_tricks.py:168), all agents' columns of abuf
     for (int j = 0; j < n; ++j) {
         const NetDesc& NJ = D.net[2 * j];
-        g_cf tgJ = as_global(D.target + lbase + D.net_off[2 * j]);
+        g_cf tgJ = U.target(2 * j);
         const int Oj = R.obs_dim[j], Aj = R.act_dim[j], cj = R.act_off[j] - R.act_off[0];
         gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[j], Oj, 0);
         zero_cols(S.xin, S.xp, rc, Oj, NJ.L[0].k_pad);
@@ -101,8 +99,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_critic_kernel(const Eng
     FRL_PHASE(S);
     att_bwd(NC, thC, slab, S, A, gs, false, 0, 0);
     }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[(((size_t)p * n + ag) * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 
 // -------------------------------------------------------------------------------------- actor
@@ -111,10 +108,9 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_critic_kernel(const Eng
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count * n) return;
-    const int p = a.p0 + us.unit / n, ag = us.unit % n, sl = us.slice;
+    const RowUnit U = agent_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag, sl = U.sl;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[2 * ag];
     const NetDesc& NC = D.net[2 * ag + 1];
@@ -122,11 +118,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_actor_kernel(const Engi
     const AttLds A = carve_att(D, S, smem);
     const int rc = D.rc, B = a.batch;
     const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[2 * ag]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf thA = U.theta(2 * ag);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_f slab = U.slab(2 * ag);
+    g_cf ring = U.ring();
     const int OT = R.obs_total, Oa = R.obs_dim[ag], Aa = R.act_dim[ag];
     const float invB = 1.f / (float)B;
     const int ct0 = OT / 16, ct1 = (OT + Aa + 15) / 16;      // the own-action columns of x_e: OT .. OT + Aa - 1
@@ -136,14 +131,14 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_actor_kernel(const Engi
     const bool first = (ck == cr.c0);
     const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
     const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
+    g_ci idx = U.idx(r0);
     if (!first) lds_barrier();
     // -- a = actor(obs); its hidden rows parked in act_spill while the critic pass reuses h1 / h2 (as ac_actor_kernel does)
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[ag], Oa, 0);
     zero_cols(S.xin, S.xp, rc, Oa, NA.L[0].k_pad);
     FRL_PHASE(S);
-    const int spill_n4 = 2 * rc * S.hp / 4;                 // h1 and h2 are adjacent in LDS
-    FRL_GLB f32x4* spill = (FRL_GLB f32x4*)(D.act_spill + (((size_t)p * n + ag) * D.S + sl) * 2 * rc * S.hp);
+    const int spill_n4 = 2 * rc * S.hp / 4;                 // h1 | h2, adjacent in LDS: act_spill_pitch(D) floats (rc = D.rc, S.hp = hidden_pitch(D.hidden))
+    FRL_GLB f32x4* spill = U.spill();
     mlp_fwd_rows(NA, 0, NA.n_layers, thA, S, ACT_TANH, [&](int r) {
         for (int c = 0; c < Aa; ++c) S.abuf[r * S.ap + c] = S.outb[r * S.op + c];
     }, [&]() {
@@ -185,11 +180,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void att_actor_kernel(const Engi
     mlp_bwd(NA, 0, NA.n_layers, thA, slab, S, gs, false, 0, 0);
     }
     const float la = block_sum(alossp, S.red);
-    if (threadIdx.x == 0) {
-        float* pt = D.part + (((size_t)p * n + ag) * D.S + sl) * 4;
-        pt[0] = la;
-        pt[1] = 0.f;
-    }
+    store_loss_parts(U, la, 0.f);
 }
 
 // ------------------------------------------------------------------------------------ forward

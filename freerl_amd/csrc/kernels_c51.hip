@@ -4,6 +4,7 @@
 // them is vector work, one thread per (row, action) pair or per row.
 #include <hip/hip_runtime.h>
 
+#include "device/update_common.hpp"
 #include "kernels.h"
 #include "device/c51.hpp"
 #include "device/net.hpp"
@@ -13,22 +14,21 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void c51_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const int group = 8 * ns, gq = blockIdx.x / group, lq = blockIdx.x - gq * group;
-    const int unit = gq * 8 + (lq & 7), sl = lq >> 3;
-    if (unit >= a.p_count) return;
-    const int p = a.p0 + unit;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const NetDesc& N = D.net[0];
     const RecordDesc& R = D.rec;
-    const Lds S = carve_lds(smem, D.rc, D.hidden, D.lds_kin_pad, D.lds_out_pad, D.lds_batch_pad, D.lds_act_pad, D.lds_hbufs);
+    const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch, nl = N.n_layers;
-    const int nchunks = (B + rc - 1) / rc, ck0 = sl * D.cps, ck1 = min(ck0 + D.cps, nchunks);
+    const RowWalk W = U.walk(B);
     const size_t base = (size_t)p * D.learner_stride + D.net_off[0];
     g_cf eff = D.noisy ? as_global(D.theta_eff + (size_t)p * 3 * D.learner_stride + D.net_off[0]) : nullptr;
     g_cf theta_next = D.noisy ? eff : as_global(D.theta + base);
     g_cf target = D.noisy ? eff + D.learner_stride : as_global(D.target + base);
     g_cf theta = D.noisy ? eff + 2 * (size_t)D.learner_stride : as_global(D.theta + base);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     const int O = R.obs_dim[0], nA = D.n_discrete, atoms = D.c51_atoms, npad = N.L[nl - 1].n_pad, k0pad = N.L[0].k_pad;
     const bool duel = D.dueling != 0;
     const float vmin = D.c51_vmin, vmax = D.c51_vmax, dz = (vmax - vmin) / (float)(atoms - 1);
@@ -37,12 +37,11 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void c51_grad_kernel(const Engin
     const int ap = S.ap;
     float lossp = 0.f;
     FRL_PHASE_INIT(S);
-    for (int ck = ck0; ck < ck1; ++ck) {            // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == ck0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.n_agents * D.batch_max + r0);
-    if (!first) FRL_PHASE(S);
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const RowChunk c = row_chunk(W.cr, ck);
+    const int r0 = c.r0, nv = c.nv;
+    g_ci idx = U.idx(r0);
+    if (!c.first) FRL_PHASE(S);
 
     // q[r][a] of the logits in outb -> qb, then argmax into S.y (one thread per (row, action), then per row)
     auto pick_action = [&]() {
@@ -195,11 +194,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void c51_grad_kernel(const Engin
         }
     }
     FRL_PHASE(S);
-    mlp_bwd(N, 0, nl, theta, slab, S, gs, false, 0, 0);
+    mlp_bwd(N, 0, nl, theta, slab, S, c.gs, false, 0, 0);
     }
     FRL_PHASE_DUMP(S, 2);
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.n_agents * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 
 }  // namespace frl

@@ -13,23 +13,20 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count * n) return;
-    const int p = a.p0 + us.unit / n, ag = us.unit % n, sl = us.slice;
+    const RowUnit U = agent_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag;
     const RecordDesc& R = D.rec;
     const NetDesc& NC = D.net[2 * ag + 1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
+    const RowWalk W = U.walk(B);
     const bool sac = (D.algo == ALGO_SAC);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_cf tgC = as_global(D.target + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag + 1]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_cf tgC = U.target(2 * ag + 1);
+    g_f slab = U.slab(2 * ag + 1);
+    g_cf ring = U.ring();
     const int am = D.act_max;
-    const int heads = NC.heads, ql = NC.n_layers / heads;
     const int OT = R.obs_total, AT = R.act_total, kc0 = NC.L[0].k_pad;
     const float alpha = sac ? D.alpha[p * 4 + 3] : 0.f;
     const float invB = 1.f / (float)B;
@@ -41,30 +38,18 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const Engi
             normalize_cols(S.xin, S.xp, nvalid, R.obs_off[j] - R.obs_off[0], R.obs_dim[j], bn + (size_t)j * D.obsnorm_w, R.obs_dim[j]);
     };
     FRL_PHASE_INIT(S);
-#ifdef FRL_EXP_TOUCH      // experiment: pull every weight line this kernel will read into L2 up front
-    {
-        float acc_t = 0.f;
-        g_cf spans[3] = {as_global(D.target + lbase + D.net_off[2 * ag]), tgC, thC};
-        const int sizes[3] = {D.net[2 * ag].size, NC.size, NC.size};
-        for (int sidx = 0; sidx < 3; ++sidx)
-            for (int o = threadIdx.x * 32; o < sizes[sidx]; o += kWG * 32) acc_t += spans[sidx][o];
-        if (acc_t == 123456.789f) S.red[0] = acc_t;
-    }
-#endif
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
-    g_cf noise_u = as_global(D.noise + ((size_t)p * n + ag) * D.noise_sets * D.batch_max * am + (size_t)r0 * am);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int nv = c.nv;
+    g_ci idx = c.idx;
+    g_cf noise_u = c.noise;
     // ---- a' = actor_target_j(s'_j) for every agent j (MADDPG_simple.py:155; n = 1 otherwise)
     float lp_next = 0.f;                            // SAC: log pi(a'|s') of row threadIdx.x
     for (int j = 0; j < n; ++j) {
         const NetDesc& NJ = D.net[2 * j];
-        g_cf tgJ = as_global(D.target + lbase + D.net_off[2 * j]);
+        g_cf tgJ = U.target(2 * j);
         const int Oj = R.obs_dim[j], Aj = R.act_dim[j], cj = R.act_off[j] - R.act_off[0];
         g_cf noise0 = noise_u + (size_t)j * D.batch_max * am;     // set j (n = 1: set 0); MATD3_simple.py:199-201
         gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[j], Oj, 0);
@@ -96,27 +81,11 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const Engi
     // single agent: xin[:, 0:O) still holds the (normalised) next_obs the target actor has just read
     if (!direct) {
         if (n > 1) gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], OT, 0);
-        for (int e = threadIdx.x; e < rc * AT; e += kWG) {
-            const int r = e / AT, c = e - r * AT;
-            S.xin[r * S.xp + OT + c] = S.abuf[r * S.ap + c];
-        }
-        zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
+        joint_actions_to_xin(S, OT, AT, kc0);
         if (bn && n > 1) { lds_barrier(); normalize_joint(nv); }
         FRL_PHASE(S);
     }
-    float q = 0.f;
-    if (twin_target_fusable(NC)) {
-        twin_target_fwd(NC, tgC, S);
-        if (threadIdx.x < rc) q = fminf(twin_target_q(NC, tgC, S, threadIdx.x, 0), twin_target_q(NC, tgC, S, threadIdx.x, 1));
-    } else {
-        mlp_fwd(NC, 0, ql, tgC, S, ACT_NONE);
-        if (threadIdx.x < rc) q = S.outb[threadIdx.x * S.op];
-        if (heads == 2) {
-            FRL_PHASE(S);
-            mlp_fwd(NC, ql, ql, tgC, S, ACT_NONE);
-            if (threadIdx.x < rc) q = fminf(q, S.outb[threadIdx.x * S.op]);
-        }
-    }
+    const float q = target_q_min(NC, tgC, S);
     if (threadIdx.x < nv) {
         g_cf rec = ring + (size_t)idx[threadIdx.x] * R.stride;
         const float rew = rec[R.rew_off + ag], done = rec[R.done_off + ag];
@@ -124,32 +93,13 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void ac_critic_kernel(const Engi
     }
     FRL_PHASE(S);
 
-    // ---- critic heads: forward, MSE delta, backward
-    for (int h = 0; h < heads; ++h) {
-        if (h == 0) {           // the second head reads the same [obs | act] rows: nothing in between writes xin
-            gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], OT + AT, 0);
-            zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
-            if (bn) { lds_barrier(); normalize_joint(nv); }
-        }
-        FRL_PHASE(S);
-        const int npad = NC.L[h * ql + ql - 1].n_pad;
-        mlp_fwd_rows(NC, h * ql, ql, thC, S, ACT_NONE, [&](int r) {     // MSE delta of row r in the finalize phase
-            lds_f o = S.outb + r * S.op;
-            float d = 0.f;
-            if (r < nv) {
-                float lrow, grow;
-                td_loss_row(a, o[0] - S.y[r], lrow, grow);
-                d = grow * invB;
-                lossp += lrow;
-            }
-            o[0] = d;
-            for (int c = 1; c < npad; ++c) o[c] = 0.f;
-        });
-        mlp_bwd(NC, h * ql, ql, thC, slab, S, gs, false, 0, 0);
-    }
+    // ---- critic heads on the stored [obs | act] rows: forward, TD delta, backward
+    gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], OT + AT, 0);
+    zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
+    if (bn) { lds_barrier(); normalize_joint(nv); }
+    critic_heads_td(NC, thC, slab, S, a, nv, c.gs, invB, lossp);
     }
     FRL_PHASE_DUMP(S, 0);
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[(((size_t)p * n + ag) * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 }  // namespace frl

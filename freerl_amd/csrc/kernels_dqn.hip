@@ -13,22 +13,22 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const NetDesc& N = D.net[0];
     const RecordDesc& R = D.rec;
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch, nl = N.n_layers;
-    const ChunkRange cr = chunk_range(D, B, sl);
+    const RowWalk W = U.walk(B);
     const size_t base = (size_t)p * D.learner_stride + D.net_off[0];
     // noisy head: the three forwards read the effective parameter sets frl_learn has materialised (kernels_noisy.hip)
     g_cf eff = D.noisy ? as_global(D.theta_eff + (size_t)p * 3 * D.learner_stride + D.net_off[0]) : nullptr;
     g_cf theta_next = D.noisy ? eff : as_global(D.theta + base);                              // online net on s' (Double)
     g_cf target = D.noisy ? eff + D.learner_stride : as_global(D.target + base);              // target net on s'
     g_cf theta = D.noisy ? eff + 2 * (size_t)D.learner_stride : as_global(D.theta + base);    // online net on s (differentiated)
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     const int O = R.obs_dim[0], nA = D.n_discrete, npad = N.L[nl - 1].n_pad, k0pad = N.L[0].k_pad;
     const bool duel = D.dueling != 0;
     // Q(s, j) of row r out of the head in outb: plain, or Dueling's V + A_j - mean(A) with the head laid out [V ; A]
@@ -48,12 +48,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void dqn_grad_kernel(const Engin
         wbar = block_sum(ws, S.red) / (float)B;
     }
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.n_agents * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int r0 = c.r0, nv = c.nv;
+    g_ci idx = c.idx;
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], O, 0);
     zero_cols(S.xin, S.xp, rc, O, k0pad);
     lds_barrier();
@@ -114,9 +112,8 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void dqn_grad_kernel(const Engin
         }
     }
     lds_barrier();
-    mlp_bwd(N, 0, nl, theta, slab, S, gs, false, 0, 0);
+    mlp_bwd(N, 0, nl, theta, slab, S, c.gs, false, 0, 0);
     }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.n_agents * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 }  // namespace frl

@@ -57,19 +57,18 @@ __global__ __launch_bounds__(256) void envelope_weights_kernel(const EngineDesc*
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_grad_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& N = D.net[0];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch, NR = B * a.weight_num;
-    const ChunkRange cr = chunk_range(D, NR, sl);
-    const size_t lbase = (size_t)p * D.learner_stride + D.net_off[0];
-    g_cf theta = as_global(D.theta + lbase);
-    g_cf target = as_global(D.target + lbase);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(NR);
+    g_cf theta = U.theta(0);
+    g_cf target = U.target(0);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     g_cf wts = as_global(D.env_w + (size_t)p * D.batch_max * D.reward_dim);
     const int nl = N.n_layers;
     const int O = R.obs_dim[0], A = D.n_discrete, RD = D.reward_dim, k0pad = N.L[0].k_pad, npad = N.L[nl - 1].n_pad;
@@ -78,12 +77,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_grad_kernel(const 
     const float l_mse = (1.f - a.beta) / (float)RD;
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, NR - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, r0 = c.r0, nv = c.nv;
+    g_ci idx = c.idx;
     // ---- online net on [s' | w]: a' in y
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], O, 0);
     put_weights(S.xin, S.xp, rc, nv, wts, r0, B, RD, O);
@@ -140,7 +137,6 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_grad_kernel(const 
     });
     mlp_bwd(N, 0, nl, theta, slab, S, gs, false, 0, 0);
     }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 }  // namespace frl

@@ -27,32 +27,29 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_critic_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[0];
     const NetDesc& NC = D.net[1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch, NR = B * a.weight_num;
-    const ChunkRange cr = chunk_range(D, NR, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[0]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[1]);
-    g_cf tgC = as_global(D.target + lbase + D.net_off[1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[1]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(NR);
+    g_cf thA = U.theta(0);
+    g_cf thC = U.theta(1);
+    g_cf tgC = U.target(1);
+    g_f slab = U.slab(1);
+    g_cf ring = U.ring();
     g_cf wts = as_global(D.env_w + (size_t)p * D.batch_max * D.reward_dim);
     const int O = R.obs_dim[0], A = R.act_dim[0], RD = D.reward_dim;
     const int ka0 = NA.L[0].k_pad, kc0 = NC.L[0].k_pad, npad = NC.L[NC.n_layers - 1].n_pad;
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, NR - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, r0 = c.r0, nv = c.nv;
+    g_ci idx = c.idx;
     // ---- online actor on [s' | w]: a' straight into the critic's input row (the first layer has read xin by then)
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], O, 0);
     put_weights(S.xin, S.xp, rc, nv, wts, r0, B, RD, O);
@@ -101,8 +98,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_critic_kernel
     });
     mlp_bwd(NC, 0, NC.n_layers, thC, slab, S, gs, false, 0, 0);
     }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 
 // -------------------------------------------------------------------------------------- actor
@@ -112,20 +108,19 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_critic_kernel
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_actor_kernel(const EngineDesc* __restrict__ Dp, EnvelopeArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[0];
     const NetDesc& NC = D.net[1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch, NR = B * a.weight_num;
-    const ChunkRange cr = chunk_range(D, NR, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[0]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(NR);
+    g_cf thA = U.theta(0);
+    g_cf thC = U.theta(1);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     g_cf wts = as_global(D.env_w + (size_t)p * D.batch_max * D.reward_dim);
     const int O = R.obs_dim[0], A = R.act_dim[0], RD = D.reward_dim;
     const int ka0 = NA.L[0].k_pad, kc0 = NC.L[0].k_pad;
@@ -133,16 +128,13 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_actor_kernel(
     const int ct0 = O / 16, ct1 = (O + A + 15) / 16;            // the action's column tiles of the critic's input
     const float dq = -1.f / ((float)NR * (float)RD), invR = 1.f / (float)RD;
     // the actor's hidden activations park in HBM over the critic pass, as in ac_actor_kernel
-    const int spill_n4 = 2 * rc * S.hp / 4;                     // h1 and h2 are adjacent in LDS
-    FRL_GLB f32x4* spill = (FRL_GLB f32x4*)(D.act_spill + ((size_t)p * D.S + sl) * 2 * rc * S.hp);
+    FRL_GLB f32x4* spill = U.spill();
 
     float alossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, NR - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, r0 = c.r0, nv = c.nv;
+    g_ci idx = c.idx;
     // ---- a = actor([s | w]): kept in abuf for tanh', and written into the critic's input row
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], O, 0);
     put_weights(S.xin, S.xp, rc, nv, wts, r0, B, RD, O);
@@ -154,9 +146,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_actor_kernel(
             S.abuf[r * S.ap + c] = av;
             S.xin[r * S.xp + O + c] = av;
         }
-    }, [&]() {
-        for (int i = threadIdx.x; i < spill_n4; i += kWG) spill[i] = ld4((lds_cf)(S.h1 + 4 * i));
-    });
+    }, [&]() { park_hidden(S, spill); });
     // ---- critic on [s | a | w]: the sum of its R outputs, the constant head delta, dX into the action column tiles
     put_weights(S.xin, S.xp, rc, nv, wts, r0, B, RD, O + A);
     zero_cols(S.xin, S.xp, rc, O + A + RD, kc0);
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_actor_kernel(
     }
     FRL_PHASE(S);
     // ---- the actor's activations back from HBM (same thread, same addresses as the spill), its input back in xin
-    for (int i = threadIdx.x; i < spill_n4; i += kWG) st4(S.h1 + 4 * i, spill[i]);
+    restore_hidden(S, spill);
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], O, 0);      // (the critic's dX landed on xin)
     put_weights(S.xin, S.xp, rc, nv, wts, r0, B, RD, O);
     zero_cols(S.xin, S.xp, rc, O + RD, ka0);
@@ -190,7 +180,6 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void envelope_ddpg_actor_kernel(
     FRL_PHASE(S);
     mlp_bwd(NA, 0, NA.n_layers, thA, slab, S, gs, false, 0, 0);
     }
-    const float la = block_sum(alossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.S + sl) * 4] = la;
+    store_loss_part(U, S, alossp);
 }
 }  // namespace frl

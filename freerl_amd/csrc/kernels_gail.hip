@@ -39,30 +39,28 @@ __global__ __launch_bounds__(256) void gail_draw_kernel(const EngineDesc* __rest
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void gail_disc_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& N = D.net[0];
     const Lds S = carve(D, smem);
     const int rc = D.rc, E = a.n_expert, NR = E + a.n_policy;
-    const ChunkRange cr = chunk_range(D, NR, sl);
-    g_cf theta = as_global(D.theta + (size_t)p * D.learner_stride + D.net_off[0]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(NR, a.gp != 0);
+    g_cf theta = U.theta(0);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     const int IN = R.obs_dim[0] + R.act_dim[0], k0pad = N.L[0].k_pad, npad = N.L[2].n_pad, H = N.L[0].n;
     g_cf rows = as_global(D.gail_rows + (size_t)p * D.batch_max * IN);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max);
+    g_ci idx = U.idx(0);                                            // (gail_gather indexes from the call's first row)
     lds_u bits1 = (lds_u)S.abuf, bits2 = (lds_u)S.dabuf;            // the slope bits of h1 / h2, S.ap words per row
     const float slope = N.hidden_act == ACT_LEAKY_RELU ? kLeakySlope : 0.f;
     const bool fuse = head_fusable(N, 0, 3);
 
     float sum[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};              // GailPart, per thread (= per row of a chunk)
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? ((D.cps > 1 || a.gp) ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc;
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, r0 = c.r0;
     gail_gather(S.xin, S.xp, rc, r0, E, NR, idx, ring, R.stride, R.obs_off[0], rows, IN);
     zero_cols(S.xin, S.xp, rc, IN, k0pad);
     FRL_PHASE(S);
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void gail_disc_kernel(const Engi
         else linear_bwd_dw(N.L[2], slab, S.outb, S.op, S.h2, S.hp, rc, GS_ADD, false);
     }
     }
-    g_f part = as_global(D.gail_part + ((size_t)p * D.S + sl) * GP_COUNT);
+    g_f part = as_global(D.gail_part + unit_slice_index(D, p, 0, U.sl) * GP_COUNT);
     for (int i = 0; i < 7; ++i) {
         const float s = block_sum(sum[i], S.red);
         if (threadIdx.x == 0) part[i] = s;
@@ -156,7 +154,7 @@ __global__ __launch_bounds__(256) void gail_stats_kernel(const EngineDesc* __res
     if (p >= D.P) return;
     float s[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < ns; ++k)
-        for (int i = 0; i < 7; ++i) s[i] += D.gail_part[((size_t)p * D.S + k) * GP_COUNT + i];
+        for (int i = 0; i < 7; ++i) s[i] += D.gail_part[unit_slice_index(D, p, 0, k) * GP_COUNT + i];
     const float invE = 1.f / (float)a.n_expert, invN = 1.f / (float)a.n_policy;
     float* o = D.gail_out + (size_t)p * 8;
     float* st = D.stats + (size_t)p * ST_COUNT;

@@ -22,20 +22,18 @@ namespace frl {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count * n) return;
-    const int p = a.p0 + us.unit / n, ag = us.unit % n, sl = us.slice;
+    const RowUnit U = agent_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag;
     const RecordDesc& R = D.rec;
     const NetDesc& NC = D.net[2 * ag + 1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_cf tgC = as_global(D.target + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag + 1]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(B);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_cf tgC = U.target(2 * ag + 1);
+    g_f slab = U.slab(2 * ag + 1);
+    g_cf ring = U.ring();
     const int am = D.act_max;
     const int heads = NC.heads, ql = NC.n_layers / heads;
     const int OT = R.obs_total, AT = R.act_total, kc0 = NC.L[0].k_pad;
@@ -43,18 +41,16 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_critic_kernel(const E
     const float invB = 1.f / (float)B;
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
-    g_cf noise_u = as_global(D.noise + ((size_t)p * n + ag) * D.noise_sets * D.batch_max * am + (size_t)r0 * am);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int nv = c.nv;
+    g_ci idx = c.idx;
+    g_cf noise_u = c.noise;
     // ---- a'_j, log pi_j = actor_target_j(s'_j) for every agent j (MASAC.py:214): the sample into abuf, the updating agent's log-prob kept
     float lp_next = 0.f;
     for (int j = 0; j < n; ++j) {
         const NetDesc& NJ = D.net[2 * j];
-        g_cf tgJ = as_global(D.target + lbase + D.net_off[2 * j]);
+        g_cf tgJ = U.target(2 * j);
         const int Oj = R.obs_dim[j], Aj = R.act_dim[j], cj = R.act_off[j] - R.act_off[0];
         g_cf noise0 = noise_u + (size_t)j * D.batch_max * am;
         gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[j], Oj, 0);
@@ -72,23 +68,9 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_critic_kernel(const E
     }
     // ---- the twin target critic on [next_obs_all | a'_all], the minimum per row
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], OT, 0);
-    for (int e = threadIdx.x; e < rc * AT; e += kWG) {
-        const int r = e / AT, c = e - r * AT;
-        S.xin[r * S.xp + OT + c] = S.abuf[r * S.ap + c];
-    }
-    zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
+    joint_actions_to_xin(S, OT, AT, kc0);
     FRL_PHASE(S);
-    float q = 0.f;
-    if (twin_target_fusable(NC)) {
-        twin_target_fwd(NC, tgC, S);
-        if (threadIdx.x < rc) q = fminf(twin_target_q(NC, tgC, S, threadIdx.x, 0), twin_target_q(NC, tgC, S, threadIdx.x, 1));
-    } else {
-        mlp_fwd(NC, 0, ql, tgC, S, ACT_NONE);
-        if (threadIdx.x < rc) q = S.outb[threadIdx.x * S.op];
-        FRL_PHASE(S);
-        mlp_fwd(NC, ql, ql, tgC, S, ACT_NONE);
-        if (threadIdx.x < rc) q = fminf(q, S.outb[threadIdx.x * S.op]);
-    }
+    const float q = target_q_min(NC, tgC, S);
     if (threadIdx.x < nv) {
         g_cf rec = ring + (size_t)idx[threadIdx.x] * R.stride;
         S.y[threadIdx.x] = td_target_sac(rec[R.rew_off + ag], rec[R.done_off + ag], a.gamma, q, alpha, lp_next);
@@ -96,30 +78,11 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_critic_kernel(const E
     FRL_PHASE(S);
 
     // ---- both online heads on the stored row: forward, MSE delta, backward
-    for (int h = 0; h < heads; ++h) {
-        if (h == 0) {           // the second head reads the same [obs | act] rows: nothing in between writes xin
-            gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], OT + AT, 0);
-            zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
-        }
-        FRL_PHASE(S);
-        const int npad = NC.L[h * ql + ql - 1].n_pad;
-        mlp_fwd_rows(NC, h * ql, ql, thC, S, ACT_NONE, [&](int r) {
-            lds_f o = S.outb + r * S.op;
-            float d = 0.f;
-            if (r < nv) {
-                float lrow, grow;
-                td_loss_row(a, o[0] - S.y[r], lrow, grow);
-                d = grow * invB;
-                lossp += lrow;
-            }
-            o[0] = d;
-            for (int c = 1; c < npad; ++c) o[c] = 0.f;
-        });
-        mlp_bwd(NC, h * ql, ql, thC, slab, S, gs, false, 0, 0);
+    gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], OT + AT, 0);
+    zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
+    critic_heads_td(NC, thC, slab, S, a, nv, c.gs, invB, lossp);
     }
-    }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[(((size_t)p * n + ag) * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 
 // -------------------------------------------------------------------------------------- actor
@@ -130,22 +93,20 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_critic_kernel(const E
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    const int n = D.n_agents;
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, ag = a.agent, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count, a.agent);
+    if (U.none) return;
+    const int n = D.n_agents, p = U.p, ag = U.ag;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[2 * ag];
     const NetDesc& NC = D.net[2 * ag + 1];
     const Lds S = carve(D, smem);
     const MasacLds M = carve_masac(D, S, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[2 * ag]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[2 * ag + 1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[2 * ag]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(B);
+    g_cf thA = U.theta(2 * ag);
+    g_cf thC = U.theta(2 * ag + 1);
+    g_f slab = U.slab(2 * ag);
+    g_cf ring = U.ring();
     const int am = D.act_max;
     const int ql = NC.n_layers / NC.heads;
     const int OT = R.obs_total, AT = R.act_total, kc0 = NC.L[0].k_pad;
@@ -155,25 +116,22 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_actor_kernel(const En
     const int ct0 = (OT + acol) / 16, ct1 = (OT + acol + Aa + 15) / 16;
     const size_t set = (size_t)D.batch_max * am;
 
+    FRL_GLB f32x4* spill = U.spill();
     float alossp = 0.f, entp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + ((size_t)p * n + ag) * D.batch_max + r0);
-    g_cf noise_u = as_global(D.noise + ((size_t)p * n + ag) * D.noise_sets * set + (size_t)r0 * am);
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, nv = c.nv;
+    g_ci idx = c.idx;
+    g_cf noise_u = c.noise;
     g_cf eps_own = noise_u + (size_t)(n + ag) * set, eps_ent = noise_u + (size_t)(2 * n) * set;
-    if (!first) lds_barrier();
     // -- a_j = actor_j(s_j) for every agent, the updating one LAST: its hidden rows stay in h1 / h2 until they are parked in act_spill
     //    (the critic passes reuse h1 / h2, as in ac_actor_kernel), its head row goes to M.head, its second draw's log-prob to lp2
-    const int spill_n4 = 2 * rc * S.hp / 4;                 // h1 and h2 are adjacent in LDS
-    FRL_GLB f32x4* spill = (FRL_GLB f32x4*)(D.act_spill + (((size_t)p * n + ag) * D.S + sl) * 2 * rc * S.hp);
     float lp2 = 0.f;
     for (int jj = 0; jj < n; ++jj) {
         const int j = jj == n - 1 ? ag : (jj < ag ? jj : jj + 1);
         const bool own = (j == ag);
         const NetDesc& NJ = D.net[2 * j];
-        g_cf thJ = as_global(D.theta + lbase + D.net_off[2 * j]);
+        g_cf thJ = U.theta(2 * j);
         const int Oj = R.obs_dim[j], Aj = R.act_dim[j], cj = R.act_off[j] - R.act_off[0];
         g_cf eps1 = noise_u + (size_t)(n + j) * set;
         gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[j], Oj, 0);
@@ -193,19 +151,14 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_actor_kernel(const En
             }
             if (own) lp2 = l2;
         }, [&]() {
-            if (own)
-                for (int i = threadIdx.x; i < spill_n4; i += kWG) spill[i] = ld4((lds_cf)(S.h1 + 4 * i));
+            if (own) park_hidden(S, spill);
         });
     }
     // -- Q1, Q2 on [obs_all | a_all] and dQ_h / da_i of each head; the row's weight of head 0 in S.y once both values are known
     float q0 = 0.f, q1 = 0.f;
     for (int h = 0; h < 2; ++h) {
         gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], OT, 0);
-        for (int e = threadIdx.x; e < rc * AT; e += kWG) {
-            const int r = e / AT, c = e - r * AT;
-            S.xin[r * S.xp + OT + c] = S.abuf[r * S.ap + c];
-        }
-        zero_cols(S.xin, S.xp, rc, OT + AT, kc0);
+        joint_actions_to_xin(S, OT, AT, kc0);
         FRL_PHASE(S);
         const int npad = NC.L[h * ql + ql - 1].n_pad;
         mlp_fwd_rows(NC, h * ql, ql, thC, S, ACT_NONE, [&](int r) {
@@ -235,7 +188,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_actor_kernel(const En
         entp += -lp2;
     }
     // -- the actor's activations back (same thread, same addresses as the spill), its input back in xin, the head delta of both routes
-    for (int i = threadIdx.x; i < spill_n4; i += kWG) st4(S.h1 + 4 * i, spill[i]);
+    restore_hidden(S, spill);
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[ag], Oa, 0);
     zero_cols(S.xin, S.xp, rc, Oa, NA.L[0].k_pad);
     const int napad = NA.L[NA.n_layers - 1].n_pad;
@@ -257,11 +210,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void masac_actor_kernel(const En
     }
     const float la = block_sum(alossp, S.red);
     const float le = block_sum(entp, S.red);
-    if (threadIdx.x == 0) {
-        float* pt = D.part + (((size_t)p * n + ag) * D.S + sl) * 4;
-        pt[0] = la;
-        pt[1] = le;
-    }
+    store_loss_parts(U, la, le);
 }
 
 // ------------------------------------------------------------------------------------ forward

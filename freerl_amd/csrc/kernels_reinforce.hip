@@ -122,30 +122,28 @@ __device__ __forceinline__ void load_rows(lds_f X, int ldx, int rc, int nvalid, 
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void reinforce_grad_kernel(const EngineDesc* __restrict__ Dp, int p0, int p_count, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= p_count) return;
-    const int p = p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, p0, p_count);
+    if (U.none) return;
+    const int p = U.p;
     const int n = D.ep_n[p];
-    const ChunkRange cr = chunk_range(D, n, sl);
-    if (cr.c0 >= cr.c1) return;                    // the learner sits out, or its rows end before this workgroup's chunks
+    const RowWalk W = U.walk(n);
+    if (W.cr.c0 >= W.cr.c1) return;                    // the learner sits out, or its rows end before this workgroup's chunks
     const NetDesc& N = D.net[0];
     const RecordDesc& R = D.rec;
     const Lds S = carve(D, smem);
     const int rc = D.rc, nl = N.n_layers;
-    g_cf theta = as_global(D.theta + (size_t)p * D.learner_stride + D.net_off[0]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    g_cf theta = U.theta(0);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     g_cf gw = as_global(D.isw + (size_t)p * D.batch_max);
     const int O = R.obs_dim[0], A = D.n_discrete, npad = N.L[nl - 1].n_pad, k0pad = N.L[0].k_pad;
     constexpr float kEps = 1.1920929e-07f;         // torch.finfo(float32).eps
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, n - r0);
-    g_cf rows = ring + (size_t)r0 * R.stride;
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, r0 = c.r0, nv = c.nv;
+    g_cf rows = ring + (size_t)r0 * R.stride;      // a workgroup's chunks are consecutive ring rows: no idx
     load_rows(S.xin, S.xp, rc, nv, rows, R.stride, R.obs_off[0], O);
     zero_cols(S.xin, S.xp, rc, O, k0pad);
     lds_barrier();
@@ -171,7 +169,6 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void reinforce_grad_kernel(const
     });
     mlp_bwd(N, 0, nl, theta, slab, S, gs, false, 0, 0);
     }
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 }  // namespace frl

@@ -40,21 +40,20 @@ __device__ __forceinline__ float sacd_softmax(lds_cf o, lds_f p, int A) {
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[0];
     const NetDesc& NC = D.net[1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[0]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[1]);
-    g_cf tgC = as_global(D.target + lbase + D.net_off[1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[1]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(B);
+    g_cf thA = U.theta(0);
+    g_cf thC = U.theta(1);
+    g_cf tgC = U.target(1);
+    g_f slab = U.slab(1);
+    g_cf ring = U.ring();
     const int ql = NC.n_layers / NC.heads;
     const int O = R.obs_dim[0], A = D.n_discrete, kc0 = NC.L[0].k_pad;
     const float alpha = D.alpha[p * 4 + 3];
@@ -63,12 +62,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_critic_kernel(const En
     FRL_PHASE_INIT(S);
 
     float lossp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {       // the row chunks of this workgroup, their gradients summed in its slab
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, nv = c.nv;
+    g_ci idx = c.idx;
     // ---- p' = actor(s') and H(p'): softmax in the finalize phase, p' parked in abuf, H(p') in y (nothing per row stays in a
     // register across the forward passes: each finalize step reads what it needs from LDS or the ring)
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.nobs_off[0], O, 0);
@@ -115,8 +112,7 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_critic_kernel(const En
     }
     }
     FRL_PHASE_DUMP(S, 10);
-    const float ls = block_sum(lossp, S.red);
-    if (threadIdx.x == 0) D.part[((size_t)p * D.S + sl) * 4] = ls;
+    store_loss_part(U, S, lossp);
 }
 
 // -------------------------------------------------------------------------------------- actor
@@ -127,20 +123,19 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_critic_kernel(const En
 __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const EngineDesc& D = *Dp;
-    const UnitSlice us = unit_slice(ns);
-    if (us.unit >= a.p_count) return;
-    const int p = a.p0 + us.unit, sl = us.slice;
+    const RowUnit U = learner_unit(D, ns, a.p0, a.p_count);
+    if (U.none) return;
+    const int p = U.p;
     const RecordDesc& R = D.rec;
     const NetDesc& NA = D.net[0];
     const NetDesc& NC = D.net[1];
     const Lds S = carve(D, smem);
     const int rc = D.rc, B = a.batch;
-    const ChunkRange cr = chunk_range(D, B, sl);
-    const size_t lbase = (size_t)p * D.learner_stride;
-    g_cf thA = as_global(D.theta + lbase + D.net_off[0]);
-    g_cf thC = as_global(D.theta + lbase + D.net_off[1]);
-    g_f slab = as_global(D.slab + ((size_t)p * D.S + sl) * D.learner_stride + D.net_off[0]);
-    g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
+    const RowWalk W = U.walk(B);
+    g_cf thA = U.theta(0);
+    g_cf thC = U.theta(1);
+    g_f slab = U.slab(0);
+    g_cf ring = U.ring();
     const int ql = NC.n_layers / NC.heads;
     const int O = R.obs_dim[0], A = D.n_discrete, kc0 = NA.L[0].k_pad;
     const int napad = NA.L[NA.n_layers - 1].n_pad;
@@ -150,12 +145,10 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_actor_kernel(const Eng
     FRL_PHASE_INIT(S);
 
     float alossp = 0.f, entp = 0.f;
-    for (int ck = cr.c0; ck < cr.c1; ++ck) {
-    const bool first = (ck == cr.c0);
-    const int gs = first ? (D.cps > 1 ? GS_STORE : GS_STREAM) : GS_ADD;
-    const int r0 = ck * rc, nv = min(rc, B - r0);
-    g_ci idx = as_global_i(D.idx + (size_t)p * D.batch_max + r0);
-    if (!first) lds_barrier();
+    for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {
+    const UnitChunk c = W.chunk(ck);
+    const int gs = c.gs, nv = c.nv;
+    g_ci idx = c.idx;
     gather_cols(S.xin, S.xp, rc, nv, idx, ring, R.stride, R.obs_off[0], O, 0);
     zero_cols(S.xin, S.xp, rc, O, kc0);
     if (bn) { lds_barrier(); normalize_cols(S.xin, S.xp, nv, 0, O, bn, O); }
@@ -194,10 +187,6 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void sacd_actor_kernel(const Eng
     FRL_PHASE_DUMP(S, 11);
     const float la = block_sum(alossp, S.red);
     const float le = block_sum(entp, S.red);
-    if (threadIdx.x == 0) {
-        float* pt = D.part + ((size_t)p * D.S + sl) * 4;
-        pt[0] = la;
-        pt[1] = le;
-    }
+    store_loss_parts(U, la, le);
 }
 }  // namespace frl

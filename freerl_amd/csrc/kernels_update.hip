@@ -129,7 +129,7 @@ __device__ __forceinline__ void adam_unit(const EngineDesc& D, const AdamArgs& a
 // thread 0 of a unit's first Adam workgroup: losses of the step, SAC's alpha update (SAC.py:154-169,257-260)
 __device__ __forceinline__ void adam_publish(const EngineDesc& D, const AdamArgs& a, int ns, int p, int ag, float total, int* steps) {
     const int n = D.n_agents;
-    const float* pt = D.part + ((size_t)p * n + ag) * D.S * 4;
+    const float* pt = D.part + part_offset(D, p, ag, 0);      // the unit's slots of slices 0 .. ns-1 (rowchunk_layout.h)
     float l0 = 0.f, l1 = 0.f;
     for (int k = 0; k < ns; ++k) { l0 += pt[4 * k]; l1 += pt[4 * k + 1]; }
     float* st = D.stats + ((size_t)p * n + ag) * ST_COUNT;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(const EngineDesc* __restric
     const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
     const int n4 = N.size / 4;
     FRL_GLB f32x4* g = (FRL_GLB f32x4*)(D.grad + off);
-    const FRL_GLB f32x4* slab = (const FRL_GLB f32x4*)(D.slab + (size_t)p * D.S * D.learner_stride + D.net_off[net]);
+    const FRL_GLB f32x4* slab = (const FRL_GLB f32x4*)(D.slab + slab_offset(D, p, 0, net));      // slice 0; slice k lies k learner strides further
     const size_t ls4 = (size_t)D.learner_stride / 4;
     float ss = 0.f;
     const int base = wg * (kWG * kAdamVec);
@@ -259,7 +259,7 @@ __device__ __forceinline__ void adam_fused_body(const EngineDesc& D, const AdamA
     const NetDesc& N = D.net[net];
     const size_t off = (size_t)p * D.learner_stride + D.net_off[net];
     const int n4 = N.size / 4;
-    const FRL_GLB f32x4* slab = (const FRL_GLB f32x4*)(D.slab + (size_t)p * D.S * D.learner_stride + D.net_off[net]);
+    const FRL_GLB f32x4* slab = (const FRL_GLB f32x4*)(D.slab + slab_offset(D, p, 0, net));      // slice 0; slice k lies k learner strides further
     const size_t ls4 = (size_t)D.learner_stride / 4;
     int* steps = D.steps + (size_t)p * (kMaxNets + 1);
     const int t = steps[net] + 1;                             // in flight with the slab loads

@@ -40,6 +40,7 @@ def test_kernel_unit_is_built_and_listed():
     assert '#include "kernels_att.hip"' in api
     learn = open(os.path.join(ROOT, "freerl_amd", "csrc", "frl_api_learn.inc")).read()
     assert "{FAM_ATT, LK_CRITIC, 0, kLdsAtt" in learn and "{FAM_ATT, LK_ACTOR, 0, kLdsAtt" in learn and "launch_att" in learn
+    assert "case FAM_ATT: launch_rowchunk(e, s, a, fam)" in learn          # FAM_ATT is dispatched to the row-chunk launcher
 
 
 @pytest.fixture(scope="module")

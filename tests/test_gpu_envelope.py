@@ -148,6 +148,29 @@ def test_ragged_rows(N, B, W):
     e.close()
 
 
+@pytest.mark.parametrize("B,W", [(16, 2), (37, 1)])
+def test_two_chunks_per_workgroup(N, B, W, monkeypatch):
+    """FRL_RC=16, FRL_CPS=2, one learner: a workgroup walks two row chunks and its second chunk ADDS to the slab its first one stored.
+    16 x 2 = 32 rows: one workgroup, two full chunks; 37 rows: a second workgroup with the ragged 5-row chunk."""
+    monkeypatch.setenv("FRL_RC", "16")
+    monkeypatch.setenv("FRL_CPS", "2")
+    c, inp = ragged_inputs(B, W, 9100, calls=2)
+    e = _engine(N, c, batch_max=64)
+    # rc from the engine; its cps (no getter in the C ABI) is pinned for exactly this engine by the plan on the CPU:
+    # tests/test_engine_plan.py::test_rowchunk_addresses_stay_inside_the_plans_buffers ("rc 16 cps 2 S 2")
+    assert e.lds_bytes()[1] == 16
+    _load(e, inp["params"])
+    e.add_batch(_records(e, inp["table"]))
+    o = eo.make(c, inp)
+    for k in range(2):
+        got = _learn(e, c, inp["idx"][k][None], inp["weights"][k][None])[0]
+        want = o.learn_with(inp["idx"][k], inp["weights"][k], c["gamma"], c["tau"], c["beta"])
+        np.testing.assert_allclose(got, want, rtol=1e-4, atol=1e-6, err_msg="cps2 B %d W %d call %d" % (B, W, k))
+    assert o.min_gap >= eo.MARGIN, "the inputs' argmax margin %.3g" % o.min_gap
+    _check_state(e, o, c, 2, "cps2 B%d W%d" % (B, W))
+    e.close()
+
+
 POP = dict(obs_dim=4, n_act=3, rdim=2, hidden=32, batch=16, weight_num=4, n_table=40)
 POP_SEED = 9503      # the first base from 9500 up whose checked learners (all three populations) meet the margin
 

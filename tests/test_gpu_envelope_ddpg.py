@@ -157,6 +157,30 @@ def test_ragged_rows(N, B, W, A, H):
     e.close()
 
 
+@pytest.mark.parametrize("B,W", [(16, 2), (37, 1)])
+def test_two_chunks_per_workgroup(N, B, W, monkeypatch):
+    """FRL_RC=16, FRL_CPS=2, one learner: a workgroup walks two row chunks and its second chunk ADDS to the slab its first one stored,
+    in the critic and in the actor launch (whose parked activations follow the chunk).  16 x 2 = 32 rows: one workgroup, two full
+    chunks; 37 rows: a second workgroup with the ragged 5-row chunk."""
+    monkeypatch.setenv("FRL_RC", "16")
+    monkeypatch.setenv("FRL_CPS", "2")
+    c = dict(eo.COMMON, **RAGGED, batch=B, weight_num=W, seed=9700 + 10 * B + W)
+    inp = eo.inputs(c, n_learn=2)
+    e = _engine(N, c, batch_max=64)
+    # rc from the engine; its cps (no getter in the C ABI) is pinned for exactly this engine by the plan on the CPU:
+    # tests/test_engine_plan.py::test_rowchunk_addresses_stay_inside_the_plans_buffers ("rc 16 cps 2 S 2")
+    assert e.lds_bytes()[1] == 16
+    _load(e, inp)
+    e.add_batch(_records(e, inp["table"]))
+    o = eo.make(c, inp)
+    for k in range(2):
+        got = _learn(e, c, inp["idx"][k][None], inp["weights"][k][None])
+        want = o.learn_with(inp["idx"][k], inp["weights"][k], c["gamma"], c["tau"], c["beta"])
+        _assert_losses((got[0][0], got[1][0]), want, "cps2 B %d W %d call %d" % (B, W, k))
+    _check_state(e, o, c, 2, "cps2 B%d W%d" % (B, W))
+    e.close()
+
+
 POP = dict(obs_dim=4, act_dim=3, rdim=2, hidden=32, batch=16, weight_num=4, n_table=40)
 
 

@@ -143,6 +143,23 @@ def test_ragged_shapes(N, E, NP, IN, H, gp_coef):
 
 
 @pytest.mark.parametrize("gp_coef", [0.0, 10.0])
+@pytest.mark.parametrize("E,NP", [(16, 16), (20, 17)])
+def test_two_chunks_per_workgroup(N, E, NP, gp_coef, monkeypatch):
+    """FRL_RC=16, FRL_CPS=2, one learner: a workgroup walks two row chunks and its second chunk ADDS to the slab its first one stored
+    (and, with the penalty, to what the chunk's own backward stored).  16 + 16 = 32 rows: one workgroup, two full chunks, one of each
+    kind; 20 + 17 = 37 rows: the kinds meet inside the second chunk and a second workgroup takes the ragged 5-row chunk."""
+    monkeypatch.setenv("FRL_RC", "16")
+    monkeypatch.setenv("FRL_CPS", "2")
+    c = dict(go.COMMON, gp_coef=gp_coef, seed=12500 + 7 * E + 3 * NP, hidden=32, n_expert=E, n_policy=NP, n_table=60)
+    inp = go.inputs(c, n_learn=2, in_dim=4)
+    e, _, _ = _run_against_oracle(N, c, inp, 2, "cps2 E%d N%d gp%g" % (E, NP, gp_coef), in_dim=4, batch_max=32)
+    # rc from the engine; its cps (no getter in the C ABI) is pinned for exactly this engine by the plan on the CPU:
+    # tests/test_engine_plan.py::test_rowchunk_addresses_stay_inside_the_plans_buffers ("rc 16 cps 2 S 2")
+    assert e.lds_bytes()[1] == 16
+    e.close()
+
+
+@pytest.mark.parametrize("gp_coef", [0.0, 10.0])
 def test_relu_hidden_activation(N, gp_coef):
     c = dict(go.COMMON, gp_coef=gp_coef, seed=12500, activation="ReLU")
     inp = go.inputs(c)

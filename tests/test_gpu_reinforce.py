@@ -157,6 +157,19 @@ def _ragged(N, P, lens_by_call, watch, cap=96):
     return e
 
 
+@pytest.mark.parametrize("T", [32, 37])
+def test_two_chunks_per_workgroup(N, T, monkeypatch):
+    """FRL_RC=16, FRL_CPS=2, one learner, two episodes of T steps: a workgroup walks two row chunks and its second chunk ADDS to the
+    slab its first one stored.  32 steps: one workgroup, two full chunks; 37: a second workgroup with the ragged 5-row chunk."""
+    monkeypatch.setenv("FRL_RC", "16")
+    monkeypatch.setenv("FRL_CPS", "2")
+    e = _ragged(N, 1, [[T], [T]], watch=[0], cap=64)
+    # rc from the engine; its cps (no getter in the C ABI) is pinned for exactly this engine by the plan on the CPU:
+    # tests/test_engine_plan.py::test_rowchunk_addresses_stay_inside_the_plans_buffers ("rc 16 cps 2 S 2")
+    assert e.lds_bytes()[1] == 16
+    e.close()
+
+
 def test_ragged_population_p5(N):
     """Lengths [33, 0, 2, capacity, 17] in one call (capacity 96: 32-row chunks, three of them for learner 3), then [0, 40, 0, 16, 0].
     Learner 1 holds its 40 steps through the first call untouched — parameters, m, v, step and cursor."""

@@ -146,6 +146,30 @@ def test_ragged_batches(N, batch, n_act):
     e.close()
 
 
+@pytest.mark.parametrize("batch", [32, 37])
+def test_two_chunks_per_workgroup(N, batch, monkeypatch):
+    """FRL_RC=16, FRL_CPS=2, one learner: a workgroup walks two row chunks and its second chunk ADDS to the slab its first one stored,
+    in both launches.  32 rows: one workgroup, two full chunks; 37 rows: a second workgroup with the ragged 5-row chunk."""
+    monkeypatch.setenv("FRL_RC", "16")
+    monkeypatch.setenv("FRL_CPS", "2")
+    c = dict(so.case("o8_a4_bn"), batch=batch, n_table=256, n_learn=2, seed=7700 + batch)
+    inp = so.inputs(c)
+    e = _engine(N, c, batch_max=64)
+    # rc from the engine; its cps (no getter in the C ABI) is pinned for exactly this engine by the plan on the CPU:
+    # tests/test_engine_plan.py::test_rowchunk_addresses_stay_inside_the_plans_buffers ("rc 16 cps 2 S 2")
+    assert e.lds_bytes()[1] == 16
+    _load(e, inp)
+    e.add_batch(records([inp["table"]]))
+    o = so.make(c, inp)
+    for k in range(c["n_learn"]):
+        st = _learn(N, e, c, inp["idx"][k][None, None])
+        cl, al, ll = o.learn_with(inp["idx"][k], c["gamma"], c["tau"])
+        np.testing.assert_allclose(st[0, 0, [N.STAT_CRITIC_LOSS, N.STAT_ACTOR_LOSS, N.STAT_ALPHA_LOSS]], [cl, al, ll],
+                                   rtol=1e-4, atol=1e-6, err_msg="cps2 batch %d call %d" % (batch, k))
+    _check_state(e, o, c, c["n_learn"], "cps2 batch %d" % batch)
+    e.close()
+
+
 @pytest.mark.parametrize("P", [1, 40, 512])
 def test_population(N, P):
     """P learners in one launch chain, each with its own parameters, table and rows; learners 0, the middle two and the last

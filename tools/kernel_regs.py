@@ -28,10 +28,10 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # kernels_envelope.hip: envelope_weights_kernel 38 VGPRs, none spilled; envelope_grad_kernel 256 VGPRs with 8 spilled and 88 bytes of
           # scratch (the Lds carve and the chunk loop's bounds, as in sacd_critic_kernel: reloaded per pass or per row chunk, none in an MFMA loop)
           ("envelope_weights_", 0), ("envelope_grad_", 8),
-          # kernels_envelope_ddpg.hip: both kernels 256 VGPRs with 18 spilled and 128 bytes of scratch (two NetDescs' layer offsets, the Lds carve
+          # kernels_envelope_ddpg.hip: both kernels 256 VGPRs; the actor 18 spilled and 128 bytes of scratch, the critic 15 and 116 (two NetDescs' layer offsets, the Lds carve
           # and the chunk loop's bounds: stored at entry, reloaded per pass or per row chunk, none in an MFMA loop)
           ("envelope_ddpg_critic_", 18), ("envelope_ddpg_actor_", 18),
-          # kernels_gail.hip: gail_disc_kernel 256 VGPRs with 70 spilled and 288 bytes of scratch: values that live across the whole chunk loop
+          # kernels_gail.hip: gail_disc_kernel 256 VGPRs with 69 spilled and 288 bytes of scratch: values that live across the whole chunk loop
           # (the per-row partial sums, the layers' offsets, the Lds carve, the row counts) are stored at entry (55 of the 62 scratch stores) and
           # reloaded at the start of a barrier phase or between two tile blocks of a dW phase (tools/asm_spills.py), none inside an MFMA k-loop;
           # gail_forward_kernel 188 VGPRs, gail_draw_kernel 28, gail_stats_kernel 19, none spilled
@@ -59,8 +59,8 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # mlp_fwd_rows / mlp_bwd addresses, stored at entry and reloaded at the start of a barrier phase, none inside an MFMA k-loop
           ("att_critic_", 0), ("att_actor_", 77), ("att_q_", 0),
           # kernels_masac.hip (figures of the unit compiled on its own, DESIGN.md "MASAC"): masac_critic_kernel 256 VGPRs, no spilled VGPR, 56 bytes of
-          # scratch (a row lambda's captures); masac_act_kernel 188 VGPRs + 40 AGPRs, none spilled; masac_actor_kernel 256 VGPRs with 52 spilled and
-          # 232 bytes: the two NetDescs' layer offsets, the three draw-set bases and the chunk loop's bounds, stored at entry and reloaded at the
+          # scratch (a row lambda's captures); masac_act_kernel 188 VGPRs + 40 AGPRs, none spilled; masac_actor_kernel 256 VGPRs with 49 spilled and
+          # 220 bytes: the two NetDescs' layer offsets, the three draw-set bases and the chunk loop's bounds, stored at entry and reloaded at the
           # start of a barrier phase or between two tile blocks, none inside an innermost MFMA k-loop (some outer layer / tile-block loops hold them)
           ("masac_critic_", 0), ("masac_actor_", 52), ("masac_act_", 0), ("", 20)]
 bad = []
