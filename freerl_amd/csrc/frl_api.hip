@@ -88,6 +88,7 @@ using HostMem = frl::MemOwner<HipMem>;
 static bool env_set(const char* name) { return getenv(name) != nullptr; }
 static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
 static bool env_flag(const char* name, bool dflt) { const char* v = getenv(name); return v ? atoi(v) != 0 : dflt; }
+static double env_double(const char* name, double dflt) { const char* v = getenv(name); return v ? atof(v) : dflt; }
 
 // (LearnFamily, the kernel family an engine's frl_learn() runs on: engine_plan.hpp; frl_api_learn.inc registers each family's kernels)
 using LearnKernel = void (*)(const frl::EngineDesc*, frl::LearnArgs);

@@ -317,11 +317,15 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, L
     }
 }
 
-// `step` (frl_rollout only, DQN engines on the fused path): the vector step's add() and the next select_action in the same launch
-// size_override >= 0: the rings' common size WHEN THE LAUNCH RUNS (a pre-armed launch of frl_rollout is enqueued before the step's rows
-// are counted in e->size)
-static int learn_impl(frl_engine* e, const frl_learn_args* args, const DqnStepArgs* step, const SoloStepArgs* sstep = nullptr, int size_override = -1,
-                      hipStream_t stream_override = nullptr) {
+// What frl_rollout folds into a learn step (nullptr: a plain frl_learn).  dqn (DQN engines on the fused path) / solo (kernels_solo.hip): the
+// vector step's add() and the next select_action in the same launches.  size_at_launch >= 0: the rings' common size WHEN THE LAUNCH RUNS (a
+// pre-armed launch is enqueued before the step's rows are counted in e->size).  stream: non-null for the pool's second stream
+struct StepFold { const DqnStepArgs* dqn; const SoloStepArgs* solo; int size_at_launch; hipStream_t stream; };
+static int learn_impl(frl_engine* e, const frl_learn_args* args, const StepFold* fold) {
+    const DqnStepArgs* step = fold ? fold->dqn : nullptr;
+    const SoloStepArgs* sstep = fold ? fold->solo : nullptr;
+    const int size_override = fold ? fold->size_at_launch : -1;
+    hipStream_t stream_override = fold ? fold->stream : nullptr;
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;

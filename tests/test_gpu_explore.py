@@ -417,3 +417,51 @@ def test_a_slow_env_step_does_not_cost_the_prearmed_update(N, monkeypatch, secon
     assert a[0] == b[0] > 40 and a[1] == b[1] and a[6] == b[6]
     for k in (2, 3, 4, 5):
         np.testing.assert_array_equal(a[k], b[k])
+
+
+class _RaiseOnce:
+    """An in-repo env whose k-th step raises, once, before the env itself is stepped."""
+
+    def __init__(self, env, k):
+        self.env, self.k, self.n = env, k, 0
+        self.observation_space, self.action_space = env.observation_space, env.action_space
+
+    def reset(self, seed=None):
+        return self.env.reset(seed=seed)
+
+    def step(self, a):
+        self.n += 1
+        if self.n == self.k:
+            raise RuntimeError("env step %d failed" % self.k)
+        return self.env.step(a)
+
+
+def test_an_env_exception_with_a_launch_armed_leaves_the_engine_where_a_plain_step_would(N, monkeypatch):
+    """An error return of frl_rollout while a pre-armed launch waits on its doorbell: env.step raises at step 90 of a 120-step DQN call
+    (learning since step 65, so step 90's launch is armed).  The call cancels the launch through the doorbell (-1) and puts back every
+    counter the arming advanced; 40 more steps on the same pool then end in the ring, nets, Adam moments, step count and last drawn
+    rows of the run that never arms, bit for bit."""
+    from freerl_amd import envs as E
+    from freerl_amd.engine import Engine
+    from freerl_amd.envpool import CallbackEnvPool, rollout
+    monkeypatch.delenv("FRL_ROLLOUT_ARM_PATIENCE_MS", raising=False)
+    res = []
+    for arm in ("0", "1"):
+        monkeypatch.setenv("FRL_ROLLOUT_PREARM", arm)
+        pool = CallbackEnvPool([_RaiseOnce(E.make("CartPole-v1", prefer_gymnasium=False), 90)], seed=7)
+        e = Engine(N.ALGO_DQN, 4, 2, 400, discrete=True, batch_max=32, n_learners=1, seed=4)
+        _rand_params(e, N, 0.2, seed=5)
+        kw = dict(envs_per_learner=1, start_steps=64, learn_every=1, epsilon=0.3, batch=32, critic_lr=1e-3, tau=0.05)
+        with pytest.raises(RuntimeError, match="env step 90 failed"):
+            rollout(e, pool, 120, **kw)
+        assert e.cursor(0) == (89, 89)                       # the failed step added nothing
+        out = rollout(e, pool, 40, **kw)
+        res.append((out["updates"], out["return_sum"], e.read_rows(0, 0, 400), e.opt_step(0), e.last_indices(32),
+                    [e.get_params(0, k) for k in (N.PARAM_ONLINE, N.PARAM_TARGET, N.PARAM_ADAM_M, N.PARAM_ADAM_V)]))
+        pool.close(); e.close()
+    a, b = res
+    assert a[0] == b[0] == 40 and a[1] == b[1] and a[3] == b[3] > 60
+    np.testing.assert_array_equal(a[2], b[2])
+    np.testing.assert_array_equal(a[4], b[4])
+    for x, y in zip(a[5], b[5]):
+        np.testing.assert_array_equal(x, y)
