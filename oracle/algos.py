@@ -246,9 +246,11 @@ class DQN:
     def learn(self, batch_size, gamma, tau):
         return self.learn_with(_choice(len(self.buffer), batch_size), gamma, tau)
 
-    def learn_with(self, idx, gamma, tau, double=False, is_weight=None, noisy_eps=None):
+    def learn_with(self, idx, gamma, tau, double=False, is_weight=None, noisy_eps=None, per_row=False):
         """DQN.py:104-118; `double` / `is_weight`: DQN_with_tricks.py:263-265 / :276-279 (returns the TD errors too).
-        noisy_eps = [eps of Qnet(next_obs) (Double only, else None), eps of Qnet_target(next_obs), eps of Qnet(obs)]."""
+        noisy_eps = [eps of Qnet(next_obs) (Double only, else None), eps of Qnet_target(next_obs), eps of Qnet(obs)].
+        per_row (with is_weight): the weights as prioritised replay defines them, loss = mean(w_i * td_i^2) — the engine's
+        per = 2 (include/freerl_hip.h); False keeps the reference's broadcast arithmetic."""
         obs, act, rew, nobs, done = self.buffer.sample(idx)
         B = obs.shape[0]
         fwd = (lambda p, x, j: self.net.forward(p, x, noisy_eps[j])) if self.noisy else (lambda p, x, j: self.net.forward(p, x))
@@ -264,6 +266,11 @@ class DQN:
         cur = q[np.arange(B), a].reshape(-1, 1)
         if is_weight is None:
             loss, dcur = getattr(self, "td_loss", nn.mse)(cur, y)      # `td_loss = nn.huber(delta)`: the Huber option
+        elif per_row:
+            w = nn.f32(is_weight).reshape(-1, 1)
+            td = cur - y
+            loss = F32(np.mean(w * (td * td), dtype=F32))
+            dcur = (F32(2.0 / B) * w * td).astype(F32)
         else:
             # DQN_with_tricks.py:277-278: `is_weight` is a 1-D [B] tensor and `td_error ** 2` is [B,1], so their product
             # broadcasts to [B,B] and `.mean()` = mean(w) * mean(td^2): every sample is weighted by the MEAN weight
