@@ -94,6 +94,16 @@ class ReinforceArgs(C.Structure):
                 ("loss_out", C.POINTER(C.c_float)), ("returns_out", C.POINTER(C.c_float))]
 
 
+HER_SPARSE, HER_SHAPING = 0, 1          # enum frl_her_mode
+
+
+class HerArgs(C.Structure):             # frl_her_args
+    _fields_ = [("n_episodes", C.c_int), ("learners", C.POINTER(C.c_int)), ("lengths", C.POINTER(C.c_int)),
+                ("state_dim", C.c_int), ("goal_dim", C.c_int), ("sample_num", C.c_int), ("sample_range", C.c_int),
+                ("mode", C.c_int), ("weights", C.POINTER(C.c_double)), ("tolerance", C.c_double),
+                ("env_actions", C.POINTER(C.c_float)), ("picks", C.POINTER(C.c_int32)), ("rows_out", C.POINTER(C.c_int))]
+
+
 class EnvelopeArgs(C.Structure):
     _fields_ = [("batch", C.c_int), ("weight_num", C.c_int), ("gamma", C.c_float), ("tau", C.c_float), ("lr", C.c_float),
                 ("beta", C.c_float), ("idx", C.POINTER(C.c_int64)), ("weights", C.POINTER(C.c_float)),
@@ -182,6 +192,7 @@ SIGNATURES = {
     "frl_buffer_sample": (_i, [_vp, _i, _i64p, _i, _i, _ip, _ip, _P(_vp)]),
     "frl_buffer_read": (_i, [_vp, _i, _i, _i, _fp]),
     "frl_buffer_fill_synthetic": (_i, [_vp, _i, C.c_uint64]),
+    "frl_her_relabel": (_i, [_vp, _P(HerArgs)]),
     "frl_net_count": (_i, [_vp, _ip]),
     "frl_net_num_params": (_i, [_vp, _i, _ip]),
     "frl_params_get": (_i, [_vp, _i, _i, _i, _fp]),

@@ -14,6 +14,7 @@
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
 #include "engine_plan.hpp"
+#include "her_plan.h"
 #include "host_mem.hpp"
 
 #include "kernels.h"
@@ -49,6 +50,7 @@
 #include "kernels_mappo_state.hip"
 #include "kernels_att.hip"
 #include "kernels_masac.hip"
+#include "kernels_her.hip"
 #endif
 
 using namespace frl;
@@ -196,6 +198,13 @@ struct frl_engine : frl::EngineFacts {      // (what the plan fixed: family, lds
     unsigned ep_seq = 0;
     float* h_gail_rows = nullptr;         // frl_gail_learn: pinned staging of the uploaded policy rows [P][batch_max][obs_dim + act_dim]
     float* h_env_w = nullptr;             // frl_envelope_learn / frl_envelope_ddpg_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
+    // frl_her_relabel: the call's small arrays in one pinned block and its device copy (both grow on demand), the event behind the copy
+    unsigned char* h_her = nullptr;
+    unsigned char* d_her = nullptr;
+    size_t her_cap_h = 0, her_cap_d = 0;
+    hipEvent_t ev_her = nullptr;
+    bool her_inflight = false;
+    unsigned long long her_calls = 0;     // relabel calls that drew on the device: the Philox counter of the next one
     int* d_size = nullptr;                // [2][P]: size before the flush being applied / current size
     int* stage_bucket = nullptr;          // PER, pinned: [off[P + 1] | size_before[P] | leaf[stage_cap]] of the flush being applied
     int* d_stage_bucket = nullptr;
@@ -242,7 +251,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 111; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent
+extern "C" int frl_version(void) { return 112; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -259,7 +268,7 @@ extern "C" int frl_destroy(frl_engine* e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     e->mem.release_all();
     for (hipEvent_t ev : e->ev_ep) if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : {e->ev0, e->ev1, e->ev_stage}) if (ev) hipEventDestroy(ev);
+    for (hipEvent_t ev : {e->ev0, e->ev1, e->ev_stage, e->ev_her}) if (ev) hipEventDestroy(ev);
     for (hipEvent_t ev : e->prof_ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
     delete e;
@@ -1364,4 +1373,5 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_mappo.inc"
 #include "frl_api_happo.inc"
 #include "frl_api_rollout.inc"
+#include "frl_api_her.inc"
 #include "frl_api_comm.inc"

@@ -257,6 +257,19 @@ __global__ void replay_read_kernel(const float* __restrict__ ring, long long row
 __global__ void replay_commit_kernel(float* __restrict__ ring, RecordDesc rec, int capacity, CommitArgs c);
 __global__ void replay_fill_kernel(float* __restrict__ ring, long long rows, RecordDesc rec, int n_discrete, unsigned long long seed);
 
+// kernels_her.hip: hindsight relabelling of finished episodes inside the ring (frl_her_relabel; addressing: her_plan.h)
+enum HerEp : int { HER_EP_LEARNER = 0, HER_EP_L = 1, HER_EP_CURSOR = 2, HER_EP_PICK0 = 3, HER_EP_ACT0 = 4, HER_EP_INTS = 5 };
+struct HerArgs {
+    const int* eps;               // [n_episodes][HER_EP_INTS]: learner, L, cursor before the call, first entry of `picks`, first row of `env_actions`
+    const int* picks;             // [sum total] offset in [0, m_i) of every output row, or nullptr: drawn here (Philox, Floyd's k-subset)
+    const float* env_actions;     // [sum L][A] the action column block of the relabelled rows, or nullptr: the source row's stored action
+    const double* weights;        // [G]
+    double tolerance;
+    int capacity, S, G, A, sample_num, sample_range, mode;      // mode 0: reward = cost < tolerance ? 0 : -1; 1: reward = -cost
+    unsigned long long counter, seed;                           // device draws: the relabel call's number, the engine's key
+};
+__global__ void her_relabel_kernel(float* __restrict__ ring, RecordDesc rec, HerArgs a);
+
 // kernels_update.hip
 __global__ void relayout_to_wk_kernel(const EngineDesc* __restrict__ Dp, float* scratch);      // scratch: [4][P][learner_stride]
 __global__ void frag_to_wk_kernel(const EngineDesc* __restrict__ Dp, int net, int use_target, float* dst);   // dst: [P][NetDesc::size]

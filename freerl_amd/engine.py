@@ -150,6 +150,43 @@ class Engine:
     def fill_synthetic(self, rows, seed=0):
         N.check(self._L.frl_buffer_fill_synthetic(self._h, int(rows), int(seed)))
 
+    def her_relabel(self, learners, lengths, *, state_dim, goal_dim, sample_num=4, sample_range=200, mode=N.HER_SPARSE, weights=None,
+                    tolerance=0.5, env_actions=None, picks=None):
+        """Hindsight relabelling of the finished episodes of `learners` (frl_her_relabel): learner learners[e]'s episode is the
+        lengths[e] rows behind its cursor.  `env_actions` [sum L][A] replaces the action columns of the relabelled rows (None: the
+        stored action), `picks` int32 [sum rows] injects the offset j - i of every row (None: drawn on the device), `weights`
+        [goal_dim] float64 (None: the script's 1, 1, 0.1).  -> the rows written per episode, int32 [n]."""
+        ln = np.ascontiguousarray(np.asarray(learners, dtype=np.int32).reshape(-1))
+        ls = np.ascontiguousarray(np.asarray(lengths, dtype=np.int32).reshape(-1))
+        assert ln.size == ls.size, (ln.size, ls.size)
+        a = N.HerArgs()
+        a.n_episodes = ln.size
+        a.learners, a.lengths = ln.ctypes.data_as(C.POINTER(C.c_int)), ls.ctypes.data_as(C.POINTER(C.c_int))
+        a.state_dim, a.goal_dim, a.sample_num, a.sample_range = int(state_dim), int(goal_dim), int(sample_num), int(sample_range)
+        a.mode, a.tolerance = int(mode), float(tolerance)
+        keep = []
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            assert w.size == int(goal_dim), (w.size, goal_dim)
+            a.weights = w.ctypes.data_as(C.POINTER(C.c_double))
+            keep.append(w)
+        if env_actions is not None:
+            ea = np.ascontiguousarray(env_actions, dtype=F32).reshape(-1)
+            assert ea.size == int(ls.sum()) * self.layout.act_dim[0], (ea.size, int(ls.sum()), self.layout.act_dim[0])
+            a.env_actions = _fp(ea)
+            keep.append(ea)
+        if picks is not None:
+            pk = np.ascontiguousarray(picks, dtype=np.int32).reshape(-1)
+            q = min(int(sample_num), int(sample_range))
+            want = sum(sum(min(q, int(L) - i) for i in range(max(int(L) - q, 0), int(L))) + max(int(L) - q, 0) * q for L in ls) if q >= 1 else 0
+            assert pk.size == want, (pk.size, want)
+            a.picks = pk.ctypes.data_as(C.POINTER(C.c_int32))
+            keep.append(pk)
+        rows = np.zeros(ln.size, dtype=np.int32)
+        a.rows_out = rows.ctypes.data_as(C.POINTER(C.c_int))
+        N.check(self._L.frl_her_relabel(self._h, C.byref(a)))
+        return rows
+
     # ------------------------------------------------------------------ parameters
     def num_params(self, net):
         if net not in self._nparams:

@@ -1,7 +1,7 @@
 """Training loops: the counterpart of the `__main__` blocks of the reference scripts
 (`DQN_file/DQN.py:227-349`, `DDPG_file/DDPG_simple.py:238-362`, `TD3_file/TD3.py:315-456`,
 `SAC_file/SAC.py:429-586`, `SAC_file/SAC_add_discrete.py:461-580`, `PPO_file/PPO_with_tricks.py:435-584`,
-`REINFORCE_file/REINFORCE.py:227-329`,
+`REINFORCE_file/REINFORCE.py:227-329`, `DDPG_file/DDPG_simple_try_HER.py:295-458`,
 `MADDPG_file/MADDPG_simple.py:268-395`), driving freerl_amd's GPU-backed policies.
 
     python -m freerl_amd.train td3 --env_name Pendulum-v1 --seed 0 --max_episodes 500
@@ -48,6 +48,9 @@ FLAGS = {
                 trick={"Double": False, "Dueling": False, "PER": False, "Noisy": False, "N_Step": False, "Categorical": False}),
     "ddpg": dict(env_name="Pendulum-v1", policy_name="DDPG_simple", device="cuda", is_dis_to_con=False,
                  flags=_COMMON + _AC + _REPLAY + _GAUSS, trick=None),
+    # DDPG_simple_try_HER.py:298-326: DDPG_simple's flags, tau 0.01, both lrs 1e-3, start_steps 500, device cpu
+    "her": dict(env_name="Pendulum-v1", policy_name="DDPG_simple_HER", device="cpu", is_dis_to_con=False,
+                flags=_COMMON + _AC + _REPLAY + _GAUSS, trick=None),
     "td3": dict(env_name="MountainCarContinuous-v0", policy_name="TD3", device="cpu", is_dis_to_con=False,
                 flags=_COMMON + _AC + _REPLAY + _GAUSS + [("policy_noise", float, 0.1), ("noise_clip", float, 0.5),
                                                            ("policy_freq", int, 2), ("policy_noise_scale", float, 1),
@@ -310,6 +313,44 @@ class _GaussHooks(_Hooks):
                               a.policy_noise_scale)
         else:
             self.policy.learn(a.batch_size, a.gamma, a.tau)
+
+
+class _HERHooks(_GaussHooks):
+    """DDPG_simple_try_HER.py:357-442: observations are [state | goal]; the stored reward is calcu_reward(goal, obs) of the observation
+    before the step; at an episode's end the hindsight rows are written inside the ring (HindsightReplay.end_episode) before the reset,
+    and the next goal is drawn after it.  The env action reaches `store` as act()'s extra field."""
+
+    def begin(self, obs):
+        from .DDPG_simple_try_HER import HindsightReplay
+        a = self.args
+        self.state_dim = self.dim_info[0] // 2
+        self.her = HindsightReplay(self.policy, self.state_dim, self.state_dim, sample_num=4, sample_range=200, mode="her",
+                                   rng="device" if a.rng == "device" else "host")
+        self.goal = np.array([1, 0, 0], dtype=np.float32)            # :377
+        return np.concatenate((super().begin(obs), self.goal))
+
+    def act(self, step, obs):
+        action, env_action, _ = super().act(step, obs)
+        return action, env_action, env_action
+
+    def observe(self, next_obs, reward):
+        return np.concatenate((next_obs, self.goal)), reward        # :396
+
+    def store(self, obs, action, reward, next_obs, terminated, done, env_action):
+        from .DDPG_simple_try_HER import calcu_reward
+        self.policy.add(obs, action, calcu_reward(self.goal, obs, env_action), next_obs, terminated)      # :397,402
+        self.her.step(obs, env_action, next_obs)                    # :398
+
+    def episode_end(self, episode_num):
+        super().episode_end(episode_num)
+        self.her.end_episode()                                      # :421-428
+
+    def after_reset(self, obs):
+        # the next goal: a point on the unit circle's first quadrant and a spin in [0, 2), two NumPy draws taken after env.reset
+        # and in this order (:435-439)
+        u, v = np.random.rand(), np.random.rand()
+        self.goal = np.array([u, np.sqrt(1 - u ** 2), 2 * v])
+        return np.concatenate((obs, self.goal))
 
 
 class _SACHooks(_Hooks):
@@ -728,6 +769,15 @@ def run(algo, argv=None, env=None, log=print):
         from .DDPG import DDPG
         policy = DDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick, **kw)
         hooks = _GaussHooks(args, env, policy, dim_info, max_action)
+    elif algo == "her":
+        import random
+        from .DDPG_simple_try_HER import DDPG
+        if not is_continue:
+            raise ValueError("her trains on continuous action spaces (DDPG_simple_try_HER.py); %s is discrete" % args.env_name)
+        random.seed(args.seed)                      # :342, the relabel's random.sample stream
+        dim_info = [dim_info[0] + dim_info[0], dim_info[1]]         # obs + goal (:357)
+        policy = DDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick, **kw)
+        hooks = _HERHooks(args, env, policy, dim_info, max_action)
     elif algo == "td3":
         from .TD3 import TD3
         policy = TD3(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick,

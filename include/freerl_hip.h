@@ -281,6 +281,44 @@ int frl_buffer_read(frl_engine* e, int learner, int row0, int n, float* out_host
 /* synthetic fill of the first `rows` rows of every learner's ring (bench only) */
 int frl_buffer_fill_synthetic(frl_engine* e, int rows, uint64_t seed);
 
+/* ---------------------------------------------------------------- hindsight experience replay (DDPG_file/DDPG_simple_try_HER.py)
+ * The script's loop at an episode's end (:421-428) for the listed learners in ONE launch.  A stored observation is
+ * [state (state_dim) | goal (goal_dim)], the achieved goal of a transition is next_state[0:goal_dim].  Learner learners[e]'s episode
+ * is the lengths[e] rows behind its ring cursor, in time order.  For i = 0 .. L-1 the candidates are transitions i .. i + m_i - 1
+ * with m_i = min(sample_range, L - i); all of them in order when m_i < sample_num, else sample_num distinct ones
+ * (random.sample; m_i == sample_num is a shuffle).  For every pick j one row is appended at the cursor:
+ *   obs = [state_i | g], action = env_actions row i (NULL: the stored action), reward = calcu_reward(g, state_i), next_obs =
+ *   [next_state_i | g], done = 0, g = next_state_j[0:goal_dim];
+ * calcu_reward (:247-265): cost = sum_c weights[c] (g_c - s_c)^2 in float64, left to right, from the stored float32 values without
+ * fused multiply-adds; FRL_HER_SPARSE: cost < tolerance ? 0 : -1; FRL_HER_SHAPING: -cost.  Afterwards the cursor of each listed
+ * learner stands where rows_out[e] = sum_i min(sample_num, sample_range, L - i) calls of frl_buffer_add would have left it.
+ * Staged adds are flushed first.  Asynchronous (the next synchronising call waits for it).
+ * Refused before any launch, ring and cursors untouched — FRL_ERR_INVALID: n_episodes < 1 or > n_learners, NULL learners / lengths,
+ * a learner out of range or listed twice, sample_num outside [1, 8], sample_range < 1, goal_dim outside [1, state_dim], state_dim +
+ * goal_dim != obs_dim, a mode outside the enum, a NaN tolerance, weights NULL with goal_dim != 3, L < 1, L + rows > capacity, a pick
+ * outside [0, m_i); FRL_ERR_STATE: L > the learner's stored rows, a prioritised engine (the rows would bypass the priority trees),
+ * an engine that is not FRL_ALGO_DDPG, FRL_ALGO_TD3 or FRL_ALGO_SAC. */
+enum frl_her_mode { FRL_HER_SPARSE = 0, FRL_HER_SHAPING = 1 };
+struct frl_her_args {
+    int n_episodes;
+    const int* learners;        /* host [n_episodes], each learner at most once */
+    const int* lengths;         /* host [n_episodes]: L of each episode */
+    int state_dim, goal_dim;
+    int sample_num, sample_range;
+    int mode;                   /* enum frl_her_mode */
+    const double* weights;      /* host [goal_dim], or NULL: the script's 1, 1, 0.1 (goal_dim == 3 only) */
+    double tolerance;           /* FRL_HER_SPARSE: the script's 0.5 */
+    const float* env_actions;   /* host [sum L][act_dim], episode after episode: the action column block of the relabelled rows (the
+                                   script stores the env-unit, noised, clipped action there, not the policy output of the real row);
+                                   NULL: the stored action of transition i */
+    const int32_t* picks;       /* host [sum rows], episode after episode in output order: the offset j - i in [0, m_i) of every
+                                   row (for m_i < sample_num: 0, 1, ...); NULL: drawn on the device (Philox keyed by the engine's
+                                   seed, the relabel call, the learner and i; uniform over the sample_num-subsets) */
+    int* rows_out;              /* host [n_episodes] or NULL: the rows written per episode */
+};
+typedef struct frl_her_args frl_her_args;
+int frl_her_relabel(frl_engine* e, const frl_her_args* args);
+
 /* ---------------------------------------------------------------- parameters (state_dict)
  * Nets: DQN 0 = Qnet; DDPG/TD3/SAC/PPO 0 = actor, 1 = critic; MADDPG 2i = actor_i, 2i+1 = critic_i.
  * Flat layout = the reference state_dict tensors in layer order (l1.weight[out][in], l1.bias, l2...,

@@ -62,7 +62,9 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # scratch (a row lambda's captures); masac_act_kernel 188 VGPRs + 40 AGPRs, none spilled; masac_actor_kernel 256 VGPRs with 49 spilled and
           # 220 bytes: the two NetDescs' layer offsets, the three draw-set bases and the chunk loop's bounds, stored at entry and reloaded at the
           # start of a barrier phase or between two tile blocks, none inside an innermost MFMA k-loop (some outer layer / tile-block loops hold them)
-          ("masac_critic_", 0), ("masac_actor_", 52), ("masac_act_", 0), ("", 20)]
+          ("masac_critic_", 0), ("masac_actor_", 52), ("masac_act_", 0),
+          # kernels_her.hip (the unit compiled on its own): her_relabel_kernel 29 VGPRs, 60 SGPRs, no spilled VGPR, no scratch (byte work)
+          ("her_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
