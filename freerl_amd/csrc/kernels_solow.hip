@@ -21,6 +21,16 @@ namespace frl {
 
 namespace {
 
+// NetDesc::size is pad32 of the net's 16-float blocks (engine_plan.hpp: build_net): behind the last block there are none or sixteen floats
+// that no backward pass writes, while solow_update sums the WHOLE slab of every tile — left as the launch before wrote them (the other
+// net's gradients at those offsets) they are a gradient: in the norm that clips the step, and through Adam in the padding.  Every tile's
+// slab gets them as zeros.
+__device__ __forceinline__ void slab_tail_zero(g_f slab, const NetDesc& N) {
+    const LayerDesc& L = N.L[N.n_layers - 1];
+    const int end = N.extra_n > 0 ? N.extra_off + ((N.extra_n + 15) & ~15) : L.b_off + L.n_pad;
+    if ((int)threadIdx.x < N.size - end) slab[end + (int)threadIdx.x] = 0.f;
+}
+
 // the policy head's row rule on this lane's outputs z[t][r] = component 16 t + 4 q + r of its row: a = tanh(.) [TARGET, TD3 / MATD3:
 // + clipped smoothing noise, TD3.py:196-198; SAC: the tanh-Gaussian sample and the row's log-prob, SAC.py:70-97].  Returns the row's
 // log pi (summed over the lanes of the row); lsv: log_std as stored (the actor stage's backward needs it)
@@ -264,6 +274,7 @@ __device__ __forceinline__ void solow_critic_body(const EngineDesc& D, const Lea
             N.head_bwd_q<true>(slab, L, dz, h2o, d2o);
             N.hidden_bwd<true>(slab, L, KB1c, d2o, h1o, d1o);
         }
+        slab_tail_zero(slab, NC);
         lossp = SoloNet::rows_sum(lossp);
         if (tid == 0) part[bt * kSoloPart + 0] = lossp;
     }
@@ -497,9 +508,12 @@ __device__ __forceinline__ void solow_actor_body(const EngineDesc& D, const Lear
                 for (int r = 0; r < 4; ++r) {
                     const int c = 16 * t + 4 * q + r;
                     const float sgl = SoloNet::rows_sum(gls[t][r]);
-                    if (w == 0 && i16 == 0 && c < Ai) slab[NA.extra_off + c] = log_std_grad_open(lsv[t][r]) ? sgl : 0.f;
+                    // (every slot of the padded block, 16 NT3 floats: solow_update sums the whole slab, and a slot left as the critic's pass
+                    //  wrote it is a gradient — in the norm, and through Adam in the padding)
+                    if (w == 0 && i16 == 0) slab[NA.extra_off + c] = (c < Ai && log_std_grad_open(lsv[t][r])) ? sgl : 0.f;
                 }
         }
+        slab_tail_zero(slab, NA);
         lp = valid ? lpr : 0.f;
         qrow = SoloNet::rows_sum(qrow);
         lp = SoloNet::rows_sum(lp);

@@ -53,9 +53,10 @@ KINK = 1e-6                            # a hidden pre-activation this close to 0
 KWG, WAVE = 256, 64                    # gae_scan's workgroup and wave
 
 
-def case(name, kind, O, A, T, mb, K, seed, tanh=False, adam_eps=False, adv_norm=False, logits=False, hidden=128, c_adamw=False):
+def case(name, kind, O, A, T, mb, K, seed, tanh=False, adam_eps=False, adv_norm=False, logits=False, hidden=128, c_adamw=False, log_std=None):
+    """log_std: (column, raw value) pairs set over the golden builder's interior draw, before the stored actions are drawn."""
     return dict(name=name, kind=kind, O=O, A=A, T=T, mb=mb, K=K, seed=seed, tanh=tanh, adam_eps=adam_eps, adv_norm=adv_norm,
-                logits=logits, hidden=hidden, c_adamw=c_adamw)
+                logits=logits, hidden=hidden, c_adamw=c_adamw, log_std=log_std)
 
 
 # (a) hidden 128, both kernels.  name, kind, obs, act (classes), horizon, minibatch, epochs, seed
@@ -70,6 +71,9 @@ ONCHIP = [
     case("cat-4-5-100-24", "cat", 4, 5, 100, 24, 2, 2, adv_norm=True),
     case("cat-4-16-100-24", "cat", 4, 16, 100, 24, 2, 1, adv_norm=True),
     case("logits-4-5-100-24", "cat", 4, 5, 100, 24, 2, 2, adv_norm=True, logits=True),
+    # the first shape with one raw log_std past the clamp (2.5: std = e^2, no gradient; 0.5 from the bound, so the condition on log_std
+    # below holds as it stands) and the other interior: the gated column stays bit-unchanged and its Adam moments 0 (tests/test_gpu_ppo_edges.py)
+    case("relu-8-2-100-24-clamp", "gauss", 8, 2, 100, 24, 2, 0, log_std=((0, 2.5),)),
 ]
 # (b) shapes only the streaming kernel serves
 STREAMING_ONLY = [
@@ -112,11 +116,13 @@ def fill(orc, tab, values=None):
                 tab["logp"][i], bool(tab["adv_done"][i]), *extra)
 
 
-def _inputs(name, kind, O, A, T, K, seed, hidden, tanh, logits):
+def _inputs(name, kind, O, A, T, K, seed, hidden, tanh, logits, log_std=None):
     g = dict(obs_dim=O, act_dim=A, n_actions=A, horizon=T, k_epochs=K, hidden=hidden, table_seed=52000 + 10 * seed, param_seed=53000 + 10 * seed,
              perm_seed=54000 + 10 * seed)
     inp = {"gauss": gcases.ppo_inputs, "cat": gcases.ppo_discrete_inputs, "beta": gcases.ppo_beta_inputs}[kind](g)
     tab = inp["table"]
+    for col, v in log_std or ():
+        inp["params"]["actor"]["log_std"][0, col] = F32(v)
     c = case(name, kind, O, A, T, T, K, seed, tanh=tanh, logits=logits, hidden=hidden)
     orc = new_oracle(c, inp["params"])
     r = np.random.default_rng(55000 + 10 * seed)
@@ -138,7 +144,7 @@ def _inputs(name, kind, O, A, T, K, seed, hidden, tanh, logits):
 def inputs(c):
     """dict(table, params, perms) of a case: the golden builders' table, parameters and permutations, stored actions and
     log-probs from the oracle's policy (module docstring).  Cached: do not write into it."""
-    return _cached_inputs(c["name"], c["kind"], c["O"], c["A"], c["T"], c["K"], c["seed"], c["hidden"], c["tanh"], c["logits"])
+    return _cached_inputs(c["name"], c["kind"], c["O"], c["A"], c["T"], c["K"], c["seed"], c["hidden"], c["tanh"], c["logits"], c["log_std"])
 
 
 _cached_inputs = functools.lru_cache(maxsize=None)(_inputs)

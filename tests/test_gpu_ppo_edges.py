@@ -1,7 +1,7 @@
 """frl_ppo_learn at its minibatch, horizon and head-width edges, at Engine level, against the oracle (oracle/ppo.py:
 PPO.learn_with) on the same seeded inputs (tests/ppo_edge_cases.py): the on-chip kernel (kernels_ppo2.hip) with minibatches that
 are no multiple of its 64-row chunk nor of a wave's 16 rows, short last minibatches, head widths 1 / 5 / 16, k_pad exactly 16
-and 32, Categorical heads of 2 / 5 / 16 classes; the streaming kernel (kernels_ppo.hip, FRL_PPO_STREAMING=1) on the same cases
+and 32, Categorical heads of 2 / 5 / 16 classes, one raw log_std past the clamp (its column bit-unchanged, its Adam m 0); the streaming kernel (kernels_ppo.hip, FRL_PPO_STREAMING=1) on the same cases
 and on the shapes only it serves (obs 33, head 17, hidden 64 / 256, Beta, cautious AdamW); the two kernels against each
 other; the GAE scans (gae_scan, ppo_gae_sb3_kernel, frl_gae) at horizons with a short last segment, empty trailing segments
 and fewer rows than a wave, with adv_done on segment and wave seams; a population of three learners.
@@ -91,9 +91,13 @@ def learn(e, c, perms, **over):
 
 
 def result(e, c, out, like, learner=0):
-    return dict(trace=out["trace"][learner].copy(), adv=out["adv"][learner].copy(), v_target=out["v_target"][learner].copy(),
-                actor=actor_unflat(c, e.get_params(0, learner=learner), like["actor"]), critic=unflat_params(e.get_params(1, learner=learner), like["critic"], AC_NAMES),
-                steps=(e.opt_step(0, learner), e.opt_step(1, learner)), cursor=e.cursor(learner))
+    from freerl_amd import _native
+    r = dict(trace=out["trace"][learner].copy(), adv=out["adv"][learner].copy(), v_target=out["v_target"][learner].copy(),
+             actor=actor_unflat(c, e.get_params(0, learner=learner), like["actor"]), critic=unflat_params(e.get_params(1, learner=learner), like["critic"], AC_NAMES),
+             steps=(e.opt_step(0, learner), e.opt_step(1, learner)), cursor=e.cursor(learner))
+    if c["log_std"]:              # a case with a raw log_std past the clamp: the actor's Adam m as well
+        r["actor_m"] = actor_unflat(c, e.get_params(0, _native.PARAM_ADAM_M, learner=learner), like["actor"])
+    return r
 
 
 _RUNS = {}
@@ -141,6 +145,14 @@ def assert_against_oracle(c, got, label):
     np.testing.assert_allclose(got["v_target"], want["v_target"], err_msg=label + " v_target", **ADV_TOL)
     assert got["steps"] == (n, n) and n == c["K"] * -(-c["T"] // c["mb"]), (label, got["steps"])
     assert got["cursor"] == (0, 0), label
+    for col, v in c["log_std"] or ():
+        # torch.clamp passes no gradient past its bounds: after all n steps the gated column holds the bits that were set and its Adam m is 0,
+        # while the interior column has moved
+        assert not -20 <= v <= 2, (label, v)
+        assert got["actor"]["log_std"][0, col].view(np.uint32) == F32(v).view(np.uint32), (label, "the clamped log_std column moved", got["actor"]["log_std"])
+        assert got["actor_m"]["log_std"][0, col] == 0.0, (label, "Adam's m of the clamped log_std column", got["actor_m"]["log_std"])
+        others = np.delete(np.arange(c["A"]), [cc for cc, _ in c["log_std"]])
+        assert (got["actor"]["log_std"][0, others] != pc.inputs(c)["params"]["actor"]["log_std"][0, others]).all() and got["actor_m"]["log_std"][0, others].all(), label
 
 
 # ------------------------------------------------------------------------------------------------ (a), (b): the two kernels
