@@ -16,10 +16,17 @@ net and Adam's state stay on the GPU.  `gp_coef > 0` (the shipped config: 10) tr
 reference's literal 5 x the penalty on the expert rows and Adam betas (0.5, 0.9); `gp_coef == 0` on sigmoid + BCE with betas
 (0.9, 0.999).
 
-Not ported: GAIL_file/PPO2.py, the policy side of the reference's loop (a different PPO from PPO_file's: tanh on the mean, one Adam
-over two learning-rate groups, old log-probabilities recomputed inside PPO_learn, unbiased-std advantage normalisation).  `ppo` is
-stored and never called; `train()` raises NotImplementedError.  Any policy class of this package can feed `trian_D` rows and take
-`compute_reward`'s rewards back.
+The policy side is `freerl_amd.PPO2.PPO` (GAIL_file/PPO2.py on kernels_gail_ppo.hip).  Pass one to take part in the loop:
+
+    gail = GAIL(config, ppo=PPO(config))                 # the reference's `self.ppo = PPO(config)`, made by the caller
+    loader = create_expert_loader(dataset, config)       # infinite: torch.randint batches of config['PPO']['horizon'] rows
+    gail.train(gymEnvWrapper(env, config), loader, num_episodes)
+
+`train` is GAIL.py:122-179: explore one horizon, `trian_D` on an expert batch and the policy's rows, `compute_reward`, the rewards
+replace the env's in the batch, `last_value = ppo.value(ppo.state)`, `PPO_learn`, `eval_and_save`; `train_post` at the end.  The
+rewards make one host round trip of 4 x horizon bytes between the two engines.  Without a `ppo`, `train()` raises
+NotImplementedError.  A discrete policy is refused in `train` (ValueError): the reference concatenates the long action index into the
+discriminator's float input, and its shipped discrete config has a_dim = 2 against the one stored column.
 
 Refused with ValueError: an activation other than 'LeakyReLU' / 'ReLU', `layernorm=True`, `dropout > 0` — the penalty's
 closed form needs a piecewise-linear net, and nothing in the shipped config uses them — and an expert column that is constant (the
@@ -108,7 +115,9 @@ class GAIL:
         self._betas = (0.5, 0.9) if self.gp else (0.9, 0.999)
         self._e = None
         self._make_engine(1, None)
-        self.ppo = ppo                                     # stored, never called: GAIL_file/PPO2.py is not ported
+        self.ppo = ppo                                     # a freerl_amd.PPO2.PPO, or None: train() needs one
+        if ppo is not None and hasattr(ppo, "consume_init_draws"):
+            ppo.consume_init_draws()                       # GAIL.py:49 constructs its PPO here: re-seed, the draws of P and V
         self._expert = None
 
     def _make_engine(self, capacity, rows):
@@ -188,6 +197,65 @@ class GAIL:
         rows = np.concatenate([_np(states), _np(actions)], axis=1)
         return torch.from_numpy(self._e.gail_reward(rows[None], gp=self.gp)[0])
 
-    def train(self, *a, **k):
-        raise NotImplementedError("GAIL.train drives GAIL_file/PPO2.py, which is not ported: collect rows with a policy class of this "
-                                  "package, call trian_D / compute_reward, and hand the rewards to that policy's learn()")
+    def train(self, env_wrapper=None, expert_loader=None, num_episodes=None, model_path=None):
+        """GAIL.train (:122-179) with `self.ppo` a freerl_amd.PPO2.PPO."""
+        if self.ppo is None or not all(hasattr(self.ppo, m) for m in ("PPO_learn", "explore_env", "train_init", "value")):
+            # (nothing, or something that is no PPO2-shaped policy: nothing of it is called)
+            raise NotImplementedError("GAIL.train drives GAIL_file/PPO2.py, the policy side: pass one at construction, "
+                                      "GAIL(config, ppo=PPO(config)) with freerl_amd.PPO2.PPO")
+        ppo = self.ppo
+        if ppo.config.get("discrete", False):
+            raise ValueError("GAIL.train with a discrete policy is refused: the reference concatenates the long action index into the "
+                             "discriminator's float input and its shipped discrete config has a_dim = 2 against one stored column")
+        if isinstance(expert_loader, ExpertLoader) and self._expert is not expert_loader.dataset:
+            self.load_expert(expert_loader.dataset)        # the loader's rows become the ring: trian_D_indices below
+        ppo.train_init(env_wrapper, num_episodes, model_path)
+        self.episode_num = ppo.episode_num
+        self.d_history = []                                # trian_D's 4-tuple of every iteration
+        while ppo.episode_num < ppo.max_episodes:
+            batch = ppo.explore_env(env_wrapper)
+            ppo.memory.clear()
+            if batch is None:
+                break
+            policy_states, policy_actions = batch["states"], batch["actions"]
+            expert_states, expert_actions = next(expert_loader)
+            if isinstance(expert_loader, ExpertLoader) and self._expert is expert_loader.dataset:
+                out = self.trian_D_indices(expert_loader.last_indices, policy_states, policy_actions)
+            else:
+                out = self.trian_D(expert_states, expert_actions, policy_states, policy_actions)
+            d_loss, expert_prob, policy_prob, w_dis = out
+            self.d_history.append(out)
+            ppo.writer.add_scalar("Discriminator/Loss", d_loss, ppo.episode_num)
+            ppo.writer.add_scalar("Discriminator/Expert", expert_prob, ppo.episode_num)
+            ppo.writer.add_scalar("Discriminator/Policy", policy_prob, ppo.episode_num)
+            if self.gp:
+                ppo.writer.add_scalar("Discriminator/Wasserstein_Dis", w_dis, ppo.episode_num)
+            batch["rewards"] = self.compute_reward(policy_states, policy_actions)
+            last_value = ppo.value(torch.as_tensor(ppo.state, dtype=torch.float32).unsqueeze(0)).squeeze()
+            ppo.PPO_learn(batch, last_value)
+            ppo.eval_and_save(env_wrapper)
+        return ppo.train_post(env_wrapper)
+
+
+class ExpertLoader:
+    """GAIL_utils.create_expert_loader's InfiniteDataLoader over InfiniteUniformSampler: `next(loader)` is a (states, actions) batch of
+    `batch_size` rows drawn with replacement by torch.randint (`GAIL.next_expert_indices`' draw); `last_indices` names them.  Creating
+    it takes one int64 draw from torch's generator, as a DataLoader iterator does for its base seed; batches are drawn when asked for
+    (a DataLoader with num_workers = 0; worker processes would draw ahead)."""
+
+    def __init__(self, dataset, batch_size):
+        self.dataset, self.batch_size = dataset, int(batch_size)
+        self.last_indices = None
+        torch.empty((), dtype=torch.int64).random_()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        self.last_indices = torch.randint(high=len(self.dataset), size=(self.batch_size,), dtype=torch.int64).numpy()
+        return self.dataset[self.last_indices]
+
+
+def create_expert_loader(dataset, config):
+    """GAIL_utils.create_expert_loader: batches of config['PPO']['horizon'] rows (+ 1 for algo 'MAIL')."""
+    return ExpertLoader(dataset, config["PPO"]["horizon"] + 1 if config.get("algo") == "MAIL" else config["PPO"]["horizon"])

@@ -31,9 +31,10 @@ ALGO_MAPPO, ALGO_IPPO = 11, 12
 ALGO_HAPPO = 13
 ALGO_MADDPG_ATT = 14        # MADDPG_simple_with_tricks.py, trick['ATT']: a MADDPG engine whose critics are attention critics (frl_learn)
 ALGO_MASAC = 15             # MAAC_file/MASAC.py: MADDPG's records and net numbering, stacked [mean | log_std] actors, twin critics, one alpha per agent (frl_learn)
+ALGO_GAIL_PPO = 16          # GAIL_file/PPO2.py: GAIL's policy side — actor + critic with LeakyReLU / ReLU hidden layers (frl_gail_ppo_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
-ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL engines only
+ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL and GAIL_PPO engines only
 PARAM_ONLINE, PARAM_TARGET, PARAM_ADAM_M, PARAM_ADAM_V, PARAM_GRAD = 0, 1, 2, 3, 4
 ACT_RAW, ACT_ARGMAX, ACT_TANHHEAD, ACT_SAC_SAMPLE, ACT_PPO_SAMPLE, ACT_CAT_SAMPLE = 0, 1, 2, 3, 4, 5
 ACT_NO_OBSNORM = 0x100
@@ -121,6 +122,15 @@ class GailArgs(C.Structure):
     _fields_ = [("n_expert", C.c_int), ("n_policy", C.c_int), ("gp", C.c_int), ("gp_weight", C.c_float), ("lr", C.c_float),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("adam_eps", C.c_float), ("idx", C.POINTER(C.c_int64)),
                 ("policy_rows", C.POINTER(C.c_float)), ("out", C.POINTER(C.c_float)), ("idx_out", C.POINTER(C.c_int64))]
+
+
+class GailPpoArgs(C.Structure):         # frl_gail_ppo_args
+    _fields_ = [("horizon", C.c_int), ("minibatch", C.c_int), ("k_epochs", C.c_int),
+                ("gamma", C.c_float), ("lam", C.c_float), ("clip", C.c_float), ("ent_weight", C.c_float), ("value_loss_coef", C.c_float),
+                ("p_lr", C.c_float), ("v_lr", C.c_float), ("clip_norm", C.c_float),
+                ("last_value", C.POINTER(C.c_float)), ("rewards", C.POINTER(C.c_float)), ("perms", C.POINTER(C.c_int64)),
+                ("adv_out", C.POINTER(C.c_float)), ("returns_out", C.POINTER(C.c_float)), ("logp_old_out", C.POINTER(C.c_float)),
+                ("loss_trace_out", C.POINTER(C.c_float))]
 
 
 class MappoArgs(C.Structure):
@@ -228,6 +238,9 @@ SIGNATURES = {
     "frl_envelope_ddpg_learn": (_i, [_vp, _P(EnvelopeDdpgArgs)]),
     "frl_gail_learn": (_i, [_vp, _P(GailArgs)]),
     "frl_gail_reward": (_i, [_vp, _i, _i, _fp, _fp]),
+    "frl_gail_ppo_learn": (_i, [_vp, _P(GailPpoArgs)]),
+    "frl_log_std_range_set": (_i, [_vp, _f, _f]),
+    "frl_log_std_range_get": (_i, [_vp, _fp, _fp]),
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),

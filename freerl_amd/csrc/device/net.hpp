@@ -112,7 +112,7 @@ __device__ __forceinline__ f32x4 act_apply4(f32x4 v) {
     }
     return v;
 }
-// LEAKY: the call site may meet ACT_LEAKY_RELU (the GAIL discriminator's kernels only).  Every other call site keeps its three
+// LEAKY: the call site may meet ACT_LEAKY_RELU (kernels_gail.hip and kernels_gail_ppo.hip only).  Every other call site keeps its three
 // instantiations: a fourth copy of the MFMA block in each of them costs the 64-row kernels registers (see for_il_blocks).
 template <bool LEAKY = false, class F>
 __device__ __forceinline__ void dispatch_act(int act, F f) {

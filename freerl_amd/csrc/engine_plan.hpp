@@ -56,6 +56,7 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"HAPPO",          "frl_happo_learn",         "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
     {"ATT-MADDPG",     kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
     {"MASAC",          kFrlLearn,                 "FRL_ACT_SAC_SAMPLE / FRL_ACT_TANHHEAD on net 2i with agent i's observation",   false, false, false, false, false, true,  false},
+    {"GAIL-PPO",       "frl_gail_ppo_learn",      "FRL_ACT_PPO_SAMPLE / FRL_ACT_TANHHEAD / FRL_ACT_CAT_SAMPLE on net 0, FRL_ACT_RAW on net 1: the value", false, false, false, false, false, false, false},
 };
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 // (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
@@ -63,7 +64,7 @@ inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_
 inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MASAC - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_GAIL_PPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
@@ -410,7 +411,7 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
     if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MASAC) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_GAIL_PPO) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -471,6 +472,17 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
             return FRL_OK;
         case FRL_ALGO_GAIL:     // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
             if (c.hidden_act == FRL_ACT_TANH) return plan_refuse(message, "GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
+            return FRL_OK;
+        case FRL_ALGO_GAIL_PPO:
+            // what kernels_gail_ppo.hip handles (GAIL_file/PPO2.py:20-79: two 3-layer nets, LeakyReLU in GAIL's config and ReLU in PPO's own)
+            if (c.hidden_act == FRL_ACT_TANH) return plan_refuse(message, "%s: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU: the shipped configs have no other)", T.name);
+            if (c.hidden_act != FRL_ACT_LEAKY_RELU && c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)", T.name, c.hidden_act);
+            if (h.hidden > 256) return plan_refuse(message, "%s: hidden %d > 256 is refused, as for the discriminator it trains against", T.name, h.hidden);
+            if (c.extra_cols != 0) return plan_refuse(message, "%s: extra_cols %d must be 0 (the old log-prob is recomputed, not stored: PPO2.py:240-250)", T.name, c.extra_cols);
+            if (c.discrete && c.act_dim[0] < 2) return plan_refuse(message, "%s: a Categorical policy needs act_dim >= 2 logits", T.name);
+            if (c.discrete && c.act_dim[0] > kSacdMaxActions) return plan_refuse(message, "%s: %d actions > %d head columns", T.name, c.act_dim[0], kSacdMaxActions);
+            if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0)
+                return plan_refuse(message, "%s: twin_critic, dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
             return FRL_OK;
         case FRL_ALGO_DQN:
             if (const int rc = no_leaky_relu()) return rc;
@@ -552,6 +564,16 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
                 build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, hact, ACT_TANH, c.act_dim[0]);
             build_net(h.net[1], {{H, c.obs_dim[0]}, {H, H}, {1, H}}, 1, hact, ACT_NONE, 0);
             break;
+        case FRL_ALGO_GAIL_PPO: {
+            // Actor / ActorDiscrete and Critic (GAIL_file/PPO2.py:20-64): mlp(s_dim, [H, H], a_dim | 1); tanh on the mean, raw logits when discrete
+            h.n_nets = 2;
+            const int lact = c.hidden_act == FRL_ACT_LEAKY_RELU ? ACT_LEAKY_RELU : ACT_RELU;
+            if (c.discrete) { h.n_discrete = c.act_dim[0]; h.cat_logits = 1; }
+            build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, lact, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[0]);
+            build_net(h.net[1], {{H, c.obs_dim[0]}, {H, H}, {1, H}}, 1, lact, ACT_NONE, 0);
+            h.log_std_min = -10.f; h.log_std_max = 2.f;      // PPO2's shipped range; frl_log_std_range_set
+            break;
+        }
         case FRL_ALGO_MADDPG_ATT:
             // Actor (MADDPG_simple_with_tricks.py:57-69) as MADDPG's; ATT_critic (ATT.py:181-229) as the seven layers of AttLayer: the encoder
             // reads [every observation | a_i], the decoder the other agents' actions, the four heads are one layer of 4 H outputs
@@ -635,6 +657,10 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         case FRL_ALGO_PPO:
             if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, pad16(c.act_dim[0]));   // logits' delta staging
             if (c.actor_dist == 1) h.lds_act_pad = std::max(h.lds_act_pad, pad16(2 * c.act_dim[0]));
+            one_wg_per_net = true;
+            break;
+        case FRL_ALGO_GAIL_PPO:          // two persistent workgroups per learner, like PPO's
+            if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, pad16(c.act_dim[0]));   // logits' delta staging (continuous: act_dim columns of log_std terms)
             one_wg_per_net = true;
             break;
         case FRL_ALGO_SAC_DISCRETE:

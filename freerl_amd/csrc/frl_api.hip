@@ -44,6 +44,7 @@
 #include "kernels_envelope.hip"
 #include "kernels_envelope_ddpg.hip"
 #include "kernels_gail.hip"
+#include "kernels_gail_ppo.hip"
 #include "kernels_mappo.hip"
 #include "kernels_happo.hip"
 #include "kernels_mappo_mask.hip"
@@ -251,7 +252,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 112; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel
+extern "C" int frl_version(void) { return 113; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -432,7 +433,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)ppo_update_kernel, (const void*)mappo_values_kernel, (const void*)mappo_update_kernel, (const void*)mappo_act_kernel,
                               (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel,
                               (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
-                              (const void*)att_q_kernel, (const void*)masac_act_kernel})
+                              (const void*)att_q_kernel, (const void*)masac_act_kernel, (const void*)gail_ppo_prepare_kernel,
+                              (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -854,7 +856,8 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
     const bool masac_actor = e->h.algo == ALGO_MASAC && !(net & 1);      // its log_std is the head's second half, not an extra vector
     if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0 && !(masac_actor && mode == FRL_ACT_SAC_SAMPLE)) return fail(FRL_ERR_INVALID, "net has no log_std");
-    if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev && !(ex && ex->device_eps)) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE needs the Exp(1) draws in eps");
+    const bool gail_ppo = e->h.algo == ALGO_GAIL_PPO;      // (its sampling modes draw for themselves when no eps is given: below)
+    if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev && !(ex && ex->device_eps) && !gail_ppo) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE needs the Exp(1) draws in eps");
     if (n_rows < 1) return fail(FRL_ERR_INVALID, "n_rows must be >= 1");
     const bool no_norm = (mode_flags & FRL_ACT_NO_OBSNORM) != 0;
     ActArgs a;
@@ -895,6 +898,18 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
         if ((mode != FRL_ACT_SAC_SAMPLE && mode != FRL_ACT_TANHHEAD) || ex) return fail(FRL_ERR_INVALID, "a MASAC actor acts through FRL_ACT_SAC_SAMPLE, FRL_ACT_TANHHEAD or FRL_ACT_RAW");
         if (mode == FRL_ACT_SAC_SAMPLE && !eps_dev) return fail(FRL_ERR_INVALID, "FRL_ACT_SAC_SAMPLE on a MASAC actor needs the N(0,1) draws in eps");
         hipLaunchKernelGGL(masac_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
+    if (gail_ppo) {      // LeakyReLU hidden layers and the engine's own log_std range: kernels_gail_ppo.hip's forward
+        const bool disc = e->h.n_discrete > 0, actor = net == 0;
+        const bool ok = mode == FRL_ACT_RAW || (actor && !disc && (mode == FRL_ACT_TANHHEAD || mode == FRL_ACT_PPO_SAMPLE)) ||
+                        (actor && disc && (mode == FRL_ACT_CAT_SAMPLE || mode == FRL_ACT_ARGMAX));
+        if (!ok || use_target || ex)
+            return fail(FRL_ERR_INVALID, "a GAIL-PPO engine acts through FRL_ACT_RAW (either net, online), FRL_ACT_TANHHEAD / FRL_ACT_PPO_SAMPLE (continuous actor) or "
+                                         "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX (discrete actor)");
+        if ((mode == FRL_ACT_PPO_SAMPLE || mode == FRL_ACT_CAT_SAMPLE) && !eps_dev) { a.device_eps = 1; a.rng_counter = e->rng_counter++; }      // Philox, as PPO's collectors draw
+        hipLaunchKernelGGL(gail_ppo_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
         return FRL_OK;
     }
@@ -1175,6 +1190,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (e->h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MASAC.py has no Batch_ObsNorm and kernels_masac.hip does not normalise");
+    if (e->h.algo == ALGO_GAIL_PPO) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: PPO2.py has no Batch_ObsNorm (its env wrapper scales observations) and kernels_gail_ppo.hip does not normalise");
     if (e->h.algo == ALGO_MADDPG_ATT) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MADDPG_simple_with_tricks.py has no Batch_ObsNorm and the attention critic's kernels do not normalise");
     if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
     if (on && e->h.net[0].frag) {
@@ -1370,6 +1386,7 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_envelope.inc"
 #include "frl_api_envelope_ddpg.inc"
 #include "frl_api_gail.inc"
+#include "frl_api_gail_ppo.inc"
 #include "frl_api_mappo.inc"
 #include "frl_api_happo.inc"
 #include "frl_api_rollout.inc"

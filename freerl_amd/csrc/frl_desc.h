@@ -8,11 +8,11 @@ constexpr int kMaxLayers = 7;     // twin critic = 2 x 3 layers in ONE net (one 
 constexpr int kMaxAgents = 8;
 constexpr int kMaxNets = 2 * kMaxAgents;
 
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: the GAIL discriminator's hidden layers only)
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };      // (ACT_LEAKY_RELU: GAIL's discriminator and its policy side, ALGO_GAIL_PPO, only)
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
-                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15 };
+                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16 };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -234,6 +234,9 @@ struct EngineDesc {
     int state_off;        // the record column of the state block: rec.extra_off + rec.extra - state_dim
     int state_rows;       // which ring row a critic STEP reads minibatch row r's state block from: 0 (FRL_STATE_ROWS_POSITION) row s + r of the
                           // ring, the reference's unindexed `state`; 1 (FRL_STATE_ROWS_SAMPLE) the sampled row perm[s + r]
+    // GAIL's policy side (kernels_gail_ppo.hip, ALGO_GAIL_PPO): the clamp range of the actor's log_std (GAIL_file/PPO2.py:38), engine state
+    // set by frl_log_std_range_set.  No other algorithm's kernel reads it: theirs is device/policy.hpp's [-20, 2]
+    float log_std_min, log_std_max;
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

@@ -178,6 +178,28 @@ __global__ void gail_disc_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, 
 __global__ void gail_stats_kernel(const EngineDesc* __restrict__ Dp, GailArgs a, int ns);
 __global__ void gail_forward_kernel(const EngineDesc* __restrict__ Dp, int mode, int n_rows, const float* __restrict__ in, float* __restrict__ out);
 
+// kernels_gail_ppo.hip: GAIL's policy side (GAIL_file/PPO2.py) on an ALGO_GAIL_PPO engine
+struct GailPpoArgs {
+    int horizon, minibatch, k_epochs;
+    float gamma, c;            // c = float32(double(gamma) * double(lam)), as torch forms `gamma * lam * masks_2[t]`
+    float clip, ent_weight, value_loss_coef;
+    float p_lr, v_lr, clip_norm;
+    float* vs;                 // [P][T] V(s_t) before the update
+    float* logp_old;           // [P][T] log pi_old(a_t | s_t), summed over dimensions
+    float* td;                 // [P][T] td_t
+    float* adv_raw;            // [P][T] advantages before normalisation
+    float* adv;                // [P][T] normalised
+    float* returns;            // [P][T] adv_raw + V
+    float* trace;              // [P][k_epochs * n_mb][2]
+    const int* perm;           // [P][k_epochs][T]
+    const float* last_value;   // [P] device
+    const float* rewards;      // [P][T] device, or nullptr: the ring's reward column
+};
+__global__ void gail_ppo_prepare_kernel(const EngineDesc* __restrict__ Dp, GailPpoArgs a);
+__global__ void gail_ppo_gae_kernel(const EngineDesc* __restrict__ Dp, GailPpoArgs a);
+__global__ void gail_ppo_update_kernel(const EngineDesc* __restrict__ Dp, GailPpoArgs a);
+__global__ void gail_ppo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_mappo.hip: MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py): a unit = (learner, agent); nets 2i / 2i+1 = agent i's actor / critic
 struct MappoArgs {
     int horizon, minibatch, k_epochs, adv_norm;

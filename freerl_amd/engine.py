@@ -417,6 +417,48 @@ class Engine:
         N.check(self._L.frl_ppo_learn(self._h, C.byref(a)))
         return out
 
+    def gail_ppo_learn(self, horizon, minibatch, k_epochs, *, gamma, lam, clip, ent_weight, value_loss_coef, p_lr, v_lr, clip_norm=0.5,
+                       last_value=None, rewards=None, perms=None, want=()):
+        """GAIL_file/PPO2.py's PPO_learn on a GAIL_PPO engine (frl_gail_ppo_learn).  last_value [P], rewards [P, horizon] (in place of the
+        ring's reward column), perms [P, k_epochs, horizon] (torch.randperm draws; None: drawn on the device).  want: any of "adv" (before
+        normalisation), "returns", "logp_old", "trace" -> the dict's arrays."""
+        T, K = int(horizon), int(k_epochs)
+        a = N.GailPpoArgs()
+        a.horizon, a.minibatch, a.k_epochs = T, int(minibatch), K
+        a.gamma, a.lam, a.clip, a.ent_weight, a.value_loss_coef = gamma, lam, clip, ent_weight, value_loss_coef
+        a.p_lr, a.v_lr, a.clip_norm = p_lr, v_lr, clip_norm
+        keep = []
+        if last_value is not None:
+            lv = np.ascontiguousarray(np.broadcast_to(np.asarray(last_value, dtype=F32).reshape(-1), (self.P,)))
+            keep.append(lv)
+            a.last_value = _fp(lv)
+        if rewards is not None:
+            rw = np.ascontiguousarray(rewards, dtype=F32).reshape(self.P, T)
+            keep.append(rw)
+            a.rewards = _fp(rw)
+        if perms is not None:
+            pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, K, T)
+            keep.append(pm)
+            a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
+        n_mb = (T + int(minibatch) - 1) // max(int(minibatch), 1)
+        out = {}
+        for name, field, shape in (("adv", "adv_out", (self.P, T)), ("returns", "returns_out", (self.P, T)),
+                                   ("logp_old", "logp_old_out", (self.P, T)), ("trace", "loss_trace_out", (self.P, max(K, 0) * n_mb, 2))):
+            if name in want:
+                out[name] = np.zeros(shape, dtype=F32)
+                setattr(a, field, _fp(out[name]))
+        N.check(self._L.frl_gail_ppo_learn(self._h, C.byref(a)))
+        return out
+
+    def set_log_std_range(self, lo, hi):
+        """The actor's log_std clamp range of a GAIL_PPO engine (frl_log_std_range_set)."""
+        N.check(self._L.frl_log_std_range_set(self._h, float(lo), float(hi)))
+
+    def log_std_range(self):
+        lo, hi = C.c_float(0), C.c_float(0)
+        N.check(self._L.frl_log_std_range_get(self._h, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
     def reinforce_learn(self, *, gamma, lr, n_steps=None, adam_eps=1e-8, want_loss=False, want_returns=False):
         """REINFORCE.learn(gamma) for every learner (frl_reinforce_learn): learner p trains on ring rows 0..n_steps[p]-1
         (None: its cursor size; 0: it sits the call out).  -> dict with `loss` [P] and / or `returns` [P][capacity]

@@ -42,6 +42,11 @@ _MA_PPO = ("mappo", "ippo", "happo")      # the multi-agent PPO scripts: one loo
 _MADDPG = ("maddpg", "maddpg_att")        # MADDPG_simple.py and MADDPG_simple_with_tricks.py: one loop (_run_maddpg)
 _MA_REPLAY = _MADDPG + ("masac",)         # ... and MAAC_file/MASAC.py (_run_masac): continuous parallel envs, dict in / dict out
 
+# what GAIL_file/config.py's two dicts share (their 'PPO' sections but the activation, the learning rates and eval_interval)
+_GAIL_PPO = [("seed", int, 42), ("env_reproducible", bool, True), ("discrete", bool, False), ("policy_mlp_dim", int, 128),
+             ("log_std_min", float, -10), ("log_std_max", float, 2), ("horizon", int, 2048), ("gamma", float, 0.99), ("lam", float, 0.95),
+             ("clip_epsilon", float, 0.2), ("K_epochs", int, 10), ("value_loss_coef", float, 1), ("ent_weight", float, 0.01),
+             ("mini_batch_size", int, 64), ("eval_episodes", int, 1)]
 FLAGS = {
     "dqn": dict(env_name="BipedalWalker-v3", policy_name="DQN", device="cuda", is_dis_to_con=True,
                 flags=_COMMON + _REPLAY + [("Qnet_lr", float, 1e-3), ("epsilon", float, 0.1)],
@@ -70,6 +75,15 @@ FLAGS = {
                       flags=[("seed", int, 100), ("max_episodes", int, 1000), ("save_freq", int, 500 // 4), ("start_steps", int, 500),
                              ("random_steps", int, 0), ("learn_steps_interval", int, 1), ("learn_episodes_interval", int, 1),
                              ("gamma", float, 0.99), ("policy_net_lr", float, 1e-3)], trick=None),
+    # GAIL_file/config.py: PPO_COBFIG (PPO2.py's __main__: 500 episodes) and GAIL_COBFIG (GAIL.py's __main__: 2000 episodes), restated
+    "gail_ppo": dict(env_name="Pendulum-v1", policy_name="PPO2", device="cuda", is_dis_to_con=False,
+                     flags=_GAIL_PPO + [("max_episodes", int, 500), ("activation", str, "ReLU"), ("p_lr", float, 1e-3), ("v_lr", float, 1e-3),
+                                        ("eval_interval", int, 2), ("collect_eval_data", bool, True)], trick=None),
+    "gail": dict(env_name="Pendulum-v1", policy_name="GAIL", device="cuda", is_dis_to_con=False,
+                 flags=_GAIL_PPO + [("max_episodes", int, 2000), ("activation", str, "LeakyReLU"), ("p_lr", float, 1e-4), ("v_lr", float, 3e-4),
+                                    ("eval_interval", int, 10), ("collect_eval_data", bool, False), ("expert", str, None),
+                                    ("d_mlp_dim", int, 128), ("d_activation", str, "LeakyReLU"), ("d_lr", float, 4e-4), ("gp_coef", float, 10.0)],
+                 trick=None),
     "ppo": dict(env_name="CartPole-v1", policy_name="PPO", device="cpu", is_dis_to_con=False,
                 flags=_COMMON + _AC + [("horizon", int, 2048), ("clip_param", float, 0.2), ("K_epochs", int, 10),
                                        ("entropy_coefficient", float, 0.01), ("minibatch_size", int, 64),
@@ -724,6 +738,8 @@ def run(algo, argv=None, env=None, log=print):
     """Parse the reference's flags for `algo`, build env + policy, run the loop, return a dict
     (model_dir, returns, steps, seconds, policy)."""
     args = build_parser(algo).parse_args(argv)
+    if algo in ("gail_ppo", "gail"):
+        return _run_gail(algo, args, env, log)
     if algo == "td3" and args.policy_name == "TD3":
         args.realize = {"clip_double": True, "policy_noise": True, "twin_delay": True}      # TD3.py:357-358
     if algo == "ppo" and args.trick["reward_norm"] and args.trick["reward_scaling"]:
@@ -839,6 +855,40 @@ def run(algo, argv=None, env=None, log=print):
     out = _run_loop(args, env, policy, hooks, model_dir, writer, log)
     writer.close()
     return dict(out, model_dir=model_dir, policy=policy, args=args)
+
+
+def _run_gail(algo, args, env, log):
+    """`python GAIL_file/PPO2.py` (gail_ppo: the policy alone, eval_data.npz written at the end) and `python GAIL_file/GAIL.py` (gail:
+    the adversarial loop on --expert, an eval_data.npz such a run wrote) with config.py's values as flags."""
+    from .PPO2 import PPO, gymEnvWrapper
+    env = env if env is not None else _envs.make(args.env_name)
+    s_dim = env.observation_space.shape[0]
+    a_dim = env.action_space.n if args.discrete else env.action_space.shape[0]
+    config = dict(id=args.env_name, log_dir=os.path.join(args.results_root, args.env_name), algo="PPO" if algo == "gail_ppo" else "GAIL", seed=args.seed,
+                  env_reproducible=args.env_reproducible, collect_eval_data=args.collect_eval_data, num_workers=1, use_gpu=True, s_dim=s_dim,
+                  a_dim=a_dim, discrete=args.discrete,
+                  PPO=dict(policy_mlp_dim=args.policy_mlp_dim, activation=args.activation, dropout=0.0, layernorm=False, log_std_min=args.log_std_min,
+                           log_std_max=args.log_std_max, p_lr=args.p_lr, v_lr=args.v_lr, horizon=args.horizon, gamma=args.gamma, lam=args.lam,
+                           clip_epsilon=args.clip_epsilon, K_epochs=args.K_epochs, value_loss_coef=args.value_loss_coef, ent_weight=args.ent_weight,
+                           mini_batch_size=args.mini_batch_size, eval_interval=args.eval_interval, eval_episodes=args.eval_episodes))
+    log(config)
+    t0 = time.time()
+    wrapper = gymEnvWrapper(env, config)
+    if algo == "gail_ppo":
+        ppo = PPO(config, rng="device" if args.rng == "device" else "host", seed=args.seed)
+        ppo.train(wrapper, num_episodes=args.max_episodes)
+        policy = ppo
+    else:
+        from .GAIL import GAIL, ExpertDataset, create_expert_loader
+        if not args.expert:
+            raise ValueError("gail needs --expert PATH: an eval_data.npz with `states` and `actions` (what `gail_ppo` writes at the end)")
+        config["expert_data_path"] = args.expert
+        config["D"] = dict(d_mlp_dim=args.d_mlp_dim, activation=args.d_activation, dropout=0.0, layernorm=False, d_lr=args.d_lr, gp_coef=args.gp_coef)
+        gail = GAIL(config, ppo=PPO(config, rng="device" if args.rng == "device" else "host", seed=args.seed), max_rows=args.horizon, seed=args.seed)
+        gail.train(wrapper, create_expert_loader(ExpertDataset(args.expert), config), args.max_episodes)
+        policy, ppo = gail, gail.ppo
+    return dict(model_dir=ppo.config["log_dir"], returns=[float(r) for r in ppo.train_return], steps=ppo.step, seconds=time.time() - t0, policy=policy,
+                args=args)
 
 
 def _space_info(env, is_dis_to_con):

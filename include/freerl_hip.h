@@ -82,7 +82,7 @@ enum frl_algo {
                                   critic.  frl_act with FRL_ACT_RAW on net 2i+1 takes rows [all obs | all actions] and returns Q.
                                   frl_params_get / _set order of net 2i+1: fc_encoder_input, the 4 heads' weights stacked [4 hidden][hidden]
                                   then their biases [4 hidden], fc_decoder_input, encoder_input_fc, decoder_input_fc, fc1, fc2 */
-    FRL_ALGO_MASAC = 15        /* MAAC_file/MASAC.py:32-302 (entropy_way_c = entropy_way_a = action_way = '1', adaptive alpha): MADDPG's
+    FRL_ALGO_MASAC = 15,       /* MAAC_file/MASAC.py:32-302 (entropy_way_c = entropy_way_a = action_way = '1', adaptive alpha): MADDPG's
                                   records and net numbering, updated by frl_learn.  Net 2i: agent i's tanh-Gaussian actor obs_dim[i] ->
                                   hidden -> hidden -> [mean_layer | log_std_layer] (ONE head of 2 act_dim[i] outputs, log_std clamped to
                                   [-20, 2] per row), with a target copy that the TD target samples from; net 2i+1: its twin critic on
@@ -99,10 +99,19 @@ enum frl_algo {
                                   Refused at create: discrete, twin_critic = 0, hidden_act != FRL_ACT_RELU, a row chunk that does not
                                   fit a CU's LDS.  Refused at the call (FRL_ERR_STATE): frl_obsnorm_enable, use_policy_noise,
                                   frl_rollout, frl_act_explore.  frl_version() 111 */
+    FRL_ALGO_GAIL_PPO = 16     /* GAIL_file/PPO2.py:20-307, the policy side of GAIL (and PPO2.py's own loop): net 0 the actor obs_dim ->
+                                  hidden -> hidden -> act_dim with tanh on the mean and a state-independent log_std [act_dim] (zeros at
+                                  create) clamped to the ENGINE's range (frl_log_std_range_set; [-10, 2] at create, PPO2's shipped
+                                  config), or, with discrete, the logits of Categorical(logits=); net 1 the critic obs_dim -> hidden ->
+                                  hidden -> 1.  hidden_act FRL_ACT_LEAKY_RELU or FRL_ACT_RELU (FRL_ACT_TANH is refused), hidden <= 256,
+                                  the standard record with extra_cols = 0: `done` holds 1 - mask, the next_obs block is never read.
+                                  Updated by frl_gail_ppo_learn only.  frl_act: FRL_ACT_RAW (net 1: value; net 0: the head),
+                                  FRL_ACT_TANHHEAD (pi(return_mean=True)), FRL_ACT_PPO_SAMPLE (mean + std eps under the engine's
+                                  range, eps given or drawn), FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX (discrete).  frl_version() 113 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
-                      FRL_ACT_LEAKY_RELU = 3 /* slope 0.01; FRL_ALGO_GAIL engines only (frl_create refuses it elsewhere) */ };
+                      FRL_ACT_LEAKY_RELU = 3 /* slope 0.01; FRL_ALGO_GAIL and FRL_ALGO_GAIL_PPO engines only (frl_create refuses it elsewhere) */ };
 
 /* which copy of a net's parameters frl_params_get/set addresses.  FRL_PARAM_GRAD is a debugging view of the reduced
  * gradient block: PPO engines, noisy DQN engines and nets wider than the fused Adam kernel materialise it; the other
@@ -515,6 +524,42 @@ struct frl_gail_args {
 typedef struct frl_gail_args frl_gail_args;
 int frl_gail_learn(frl_engine* e, const frl_gail_args* args);
 int frl_gail_reward(frl_engine* e, int gp, int n_rows, const float* rows_host /* [P][n_rows][obs_dim + act_dim] */, float* reward_out /* [P][n_rows] */);
+
+/* ---------------------------------------------------------------- GAIL's policy side (GAIL_file/PPO2.py) on a FRL_ALGO_GAIL_PPO engine
+ * `PPO.PPO_learn(batch, last_value)` (:235-307) for every learner in one launch chain over ring rows 0 .. horizon-1:
+ *     V(s_t) and the old log-prob of the stored action under the actor BEFORE the update (summed over dimensions; the log-softmax entry
+ *     for Categorical), both over the whole horizon;
+ *     td_t = r_t + gamma V(s_{t+1}) - V(s_t) with V(s_{t+1}) the NEXT ROW's value also across an episode end (mask_1 == 1) and
+ *     last_value[p] behind the last row;  A_t = td_t + c (1 - done_t) A_{t+1}, c = float32(double(gamma) * double(lam));
+ *     returns = A + V;  A <- (A - mean) / (unbiased std + 1e-8);
+ *     k_epochs x ceil(horizon / minibatch) steps: actor loss -mean(min(ratio A, clip(ratio, 1 -+ clip) A)) - ent_weight mean(entropy),
+ *     critic loss value_loss_coef x mse(V, returns); each net clipped at global norm clip_norm on its own, then Adam (betas 0.9 / 0.999,
+ *     eps 1e-8) with p_lr / v_lr; both nets count the same steps, as the reference's single optimiser does.  A last minibatch shorter than
+ *     `minibatch` is averaged over its own size.
+ * r_t is the ring's reward column, or rewards[p][t] when `rewards` is given (the discriminator's).  The call does NOT reset the ring's
+ * cursors (the reference clears its memory in the loop): frl_buffer_cursor_set does.
+ * Refused before any launch with FRL_ERR_INVALID: horizon < 2 (the unbiased std of one row is NaN) or > capacity, minibatch < 1 or
+ * > batch_max, k_epochs < 1, a permutation entry outside [0, horizon); with FRL_ERR_STATE: engines of any other algorithm.  frl_learn,
+ * frl_ppo_learn, the rollout and explore entry points return FRL_ERR_STATE for a FRL_ALGO_GAIL_PPO engine. */
+struct frl_gail_ppo_args {
+    int horizon, minibatch, k_epochs;
+    float gamma, lam, clip, ent_weight, value_loss_coef;
+    float p_lr, v_lr, clip_norm;   /* clip_norm: the reference's literal 0.5 (<= 0: no clipping) */
+    const float* last_value;       /* host [P] V of the state behind the last row, or NULL: 0 */
+    const float* rewards;          /* host [P][horizon] replacing the ring's reward column, or NULL */
+    const int64_t* perms;          /* host [P][k_epochs][horizon] torch.randperm draws, or NULL: drawn on the device */
+    float* adv_out;                /* host [P][horizon] advantages BEFORE normalisation, or NULL */
+    float* returns_out;            /* host [P][horizon], or NULL */
+    float* logp_old_out;           /* host [P][horizon], or NULL */
+    float* loss_trace_out;         /* host [P][k_epochs * ceil(horizon / minibatch)][2] (actor, critic) loss of every step, or NULL */
+};
+typedef struct frl_gail_ppo_args frl_gail_ppo_args;
+int frl_gail_ppo_learn(frl_engine* e, const frl_gail_ppo_args* args);
+/* The clamp range of the actor's log_std on a FRL_ALGO_GAIL_PPO engine (config['PPO']['log_std_min' / 'log_std_max']): read by the
+ * update kernels (closed-bound gradient gate, as torch.clamp) and by frl_act's FRL_ACT_PPO_SAMPLE.  FRL_ERR_INVALID unless lo < hi and
+ * both are finite; FRL_ERR_STATE on engines of any other algorithm (theirs is compiled in: [-20, 2]). */
+int frl_log_std_range_set(frl_engine* e, float lo, float hi);
+int frl_log_std_range_get(const frl_engine* e, float* lo_out, float* hi_out);
 
 /* ---------------------------------------------------------------- MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py)
  * `MAPPO.learn / IPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner in

@@ -35,6 +35,10 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # (the per-row partial sums, the layers' offsets, the Lds carve, the row counts) are stored at entry (55 of the 62 scratch stores) and
           # reloaded at the start of a barrier phase or between two tile blocks of a dW phase (tools/asm_spills.py), none inside an MFMA k-loop;
           # gail_forward_kernel 188 VGPRs, gail_draw_kernel 28, gail_stats_kernel 19, none spilled
+          # kernels_gail_ppo.hip (the unit compiled on its own, profiles/gail_ppo/README.md): gail_ppo_update_kernel 296 VGPRs + 48 AGPRs (one
+          # persistent workgroup per net, one wave per SIMD), gail_ppo_prepare_kernel 192 + 40, gail_ppo_act_kernel 188 + 40, gail_ppo_gae_kernel 16;
+          # no spilled VGPR in any, 56 bytes of scratch in the three forward kernels (a lambda's captures, as in reinforce_grad_kernel)
+          ("gail_ppo_", 0),
           ("gail_disc_", 70), ("gail_forward_", 0), ("gail_draw_", 0), ("gail_stats_", 0),
           # kernels_mappo.hip: mappo_update_kernel 366 VGPRs + 110 AGPRs (one persistent workgroup per CU: one wave per SIMD, 512 registers),
           # mappo_values_kernel 224 + 40, mappo_act_kernel 188 + 40, mappo_adv_kernel 19; no spilled VGPR in any, 56 bytes of scratch in the three
