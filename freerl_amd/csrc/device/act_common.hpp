@@ -3,7 +3,7 @@
 // tail of kernels_solo.hip's launches in the rollout loop (the next step's select_action folded into the update's launch).
 #pragma once
 #include "c51.hpp"
-#include "net.hpp"
+#include "onpolicy.hpp"
 #include "chain_net.hpp"
 
 namespace frl {
@@ -65,16 +65,13 @@ __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs&
     }
     if (a.mode == ACTM_CAT_SAMPLE) {        // PPO_with_tricks.py:249-251 (torch single-draw multinomial)
         for (int r = threadIdx.x; r < nv; r += kWG) {
-            float mx = outb[r * op];
-            for (int j = 1; j < nout; ++j) mx = fmaxf(mx, outb[r * op + j]);
-            float sum = 0.f;
-            for (int j = 0; j < nout; ++j) sum += expf(outb[r * op + j] - mx);
+            CatRow cq = cat_softmax(outb + r * op, nout);            // psum: added up in the draw loop below
             const size_t row = (size_t)p * a.n_rows + r0 + r;
             int best = 0;
-            float bestv = -1.f, pbest = 0.f, psum = 0.f;
+            float bestv = -1.f, pbest = 0.f;
             for (int j = 0; j < nout; ++j) {
-                const float pj = expf(outb[r * op + j] - mx) / sum;
-                psum += pj;
+                const float pj = cq.prob(outb[r * op + j]);
+                cq.psum += pj;
                 // q ~ Exp(1): injected, or -log(u) from the launch's Philox stream
                 const float qj = a.device_eps ? -logf(u01(philox4x32_10(a.rng_counter, 0x9100u, (unsigned)((r0 + r) * nout + j), key).x))
                                               : a.eps[row * nout + j];
@@ -84,10 +81,10 @@ __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs&
             a.out[row] = (float)best;
             if (a.env_out) a.env_out[row] = (float)best;
             if (a.out_logp) {
-                const float qc = fminf(fmaxf(pbest / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f);
+                const float qc = cq.clamped(pbest);
                 // (REINFORCE records this value as the step's log-prob: the correctly rounded logarithm, so that a clamped row reads
                 // log(eps) / log(1 - eps) to the bit as it does in the reference; logf is one ulp off at eps)
-                a.out_logp[row] = D.cat_logits ? (outb[r * op + best] - mx) - logf(sum)          // Categorical(logits=)
+                a.out_logp[row] = D.cat_logits ? cq.logit(outb[r * op + best])                   // Categorical(logits=)
                                                : (D.algo == ALGO_REINFORCE ? (float)log((double)qc) : logf(qc));
             }
         }

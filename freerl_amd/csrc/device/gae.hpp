@@ -1,4 +1,6 @@
-// The GAE recurrence as an affine suffix scan, shared by kernels_ppo.hip (ppo_gae_kernel, gae_dense_kernel) and kernels_gail_ppo.hip.
+// The GAE recurrence as an affine suffix scan, shared by kernels_ppo.hip (ppo_gae_kernel, and gae_dense_kernel, which kernels_mappo /
+// _mappo_mask / _mappo_state / _happo launch too) and kernels_gail_ppo.hip; the affine map itself also in float64 for ppo_gae_sb3_kernel
+// and kernels_reinforce.hip's returns.
 #pragma once
 #include "net.hpp"
 
@@ -8,8 +10,11 @@ namespace frl {
 // Affine maps m_t(x) = delta_t + g_t*x compose associatively; each thread folds a contiguous
 // segment, a wave-shuffle suffix scan + 4 wave totals in LDS give every segment its incoming
 // value, and the segment is replayed.  One workgroup per sequence.
-struct Affine { float a, b; };
-__device__ __forceinline__ Affine compose(Affine f, Affine g) { return Affine{f.a * g.a, f.a * g.b + f.b}; }   // f(g(x))
+template <class T> struct AffineT { T a, b; };
+using Affine = AffineT<float>;
+using AffineD = AffineT<double>;
+template <class T>
+__device__ __forceinline__ AffineT<T> compose(AffineT<T> f, AffineT<T> g) { return AffineT<T>{f.a * g.a, f.a * g.b + f.b}; }   // f(g(x))
 
 __device__ __forceinline__ void gae_scan(g_cf delta, g_cf ring, int stride, int adv_done_col, int T, float c, g_f adv,
                                          lds_f lds) {

@@ -1,8 +1,8 @@
 // MAPPO / IPPO / HAPPO device code (MAPPO_file/MAPPO.py, IPPO.py, HAPPO.py): the normalised forward and backward of one row chunk, the
-// per-row head arithmetic of the clipped surrogate and of the critic's regression over one or n_agents advantage / target columns, the
-// per-row log-probability, and the K_epochs x minibatch steps of one net that kernels_mappo.hip and kernels_happo.hip both run; and
-// the row arithmetic of CategoricalMasked (MAPPO_for_mask_action.py) for kernels_mappo_mask.hip's update and act kernels; and the
-// critic's second input segment (MAPPO_for_mask_action_state.py) for kernels_mappo_state.hip.
+// clipped surrogate of a row over one or n_agents advantage columns, and the K_epochs x minibatch steps of one net that kernels_mappo,
+// _mappo_mask, _mappo_state and _happo all run; and the critic's second input segment (MAPPO_for_mask_action_state.py) for
+// kernels_mappo_state.hip.  The head arithmetic itself — the surrogate term, the Normal and the (masked) categorical head, the
+// critic's row, the advantage normalisation — is device/onpolicy.hpp's, shared with the PPO and GAIL-PPO kernels.
 //
 // Forward: [feature_norm] -> l1 -> ReLU -> [LN] -> l2 -> ReLU -> [LN] -> head, both norms F.layer_norm without affine part, biased
 // variance, eps 1e-5.  Without LayerNorm this is device/net.hpp's mlp_fwd / mlp_bwd as they are (feature_norm rewrites xin only and
@@ -12,7 +12,7 @@
 // with dn written to a third hidden buffer (dbuf) so that xhat survives until the row's two means are taken.  One wave walks a row and
 // both means are a fixed butterfly over its 64 lanes: the same bits on every run.
 #pragma once
-#include "net.hpp"
+#include "onpolicy.hpp"
 #include "../kernels.h"
 
 namespace frl {
@@ -119,101 +119,12 @@ __device__ __forceinline__ void mappo_bwd(const EngineDesc& D, const NetDesc& N,
 // ---- per-row head arithmetic.  `adv` / `vt` point at the learner's [T][n_agents] matrices, row t's columns [c0, c1) take part:
 // one column (the agent's own) on IPPO engines, all of them on MAPPO engines (MAPPO.py:410-412: ratios [m, 1] x adv[index] [m, n]).
 
-// the clipped surrogate of one row: adds sum_j -min(ratio A_j, clamp(ratio) A_j) to `loss`, returns d (that sum) / d (sum of log-probs)
+// the clipped surrogate of one row (onpolicy.hpp's surrogate_term per column): adds sum_j -min(ratio A_j, clamp(ratio) A_j) to `loss`,
+// returns d (that sum) / d (sum of log-probs).  The critic's side of the same columns is onpolicy.hpp's value_row.
 __device__ __forceinline__ float surrogate_row(float ratio, g_cf adv_row, int c0, int c1, float clip, float& loss) {
     float open = 0.f;
-    for (int j = c0; j < c1; ++j) {
-        const float A = adv_row[j];
-        const float s1 = ratio * A, s2 = fminf(fmaxf(ratio, 1.f - clip), 1.f + clip) * A;
-        loss += -fminf(s1, s2);
-        open += s1 <= s2 ? A : 0.f;
-    }
+    for (int j = c0; j < c1; ++j) open += surrogate_term(ratio, adv_row[j], clip, loss);
     return -open * ratio;
-}
-
-// the critic's regression of one row: v against the targets y_j (MAPPO.py:418-436: v_s repeated n times).  ValueClip is absent on
-// purpose: torch.max(original.mean(), clipped.mean()) always steps like, and reports, the original loss (DESIGN.md "MAPPO / IPPO").
-// Adds sum_j l(y_j - v) to `loss`, returns d (that sum) / d v.
-__device__ __forceinline__ float value_row(const LearnArgs& la, float v, g_cf vt_row, int c0, int c1, float& loss) {
-    float dv = 0.f;
-    for (int j = c0; j < c1; ++j) {
-        float l, g;
-        td_loss_row(la, vt_row[j] - v, l, g);
-        loss += l;
-        dv -= g;
-    }
-    return dv;
-}
-
-// ---- the per-row log-probability of the stored action under the actor's head row: ONE definition for the update step and for HAPPO's
-// two horizon passes (kernels_happo.hip), so that the ratio of a step and the factor of a later agent cannot drift apart.
-
-// Normal(mean, exp(clamp(log_std))).log_prob(action) summed over the agent's A action columns; `mean` is the head row after tanh
-__device__ __forceinline__ float normal_row_logp(g_cf act, lds_cf mean, g_cf log_std_raw, int A) {
-    float lp = 0.f;
-    for (int c = 0; c < A; ++c) {
-        const float ls = clamp_log_std(log_std_raw[c]);
-        lp += normal_logp(act[c] - mean[c], expf(ls), ls);
-    }
-    return lp;
-}
-
-// Categorical(probs = softmax(z)): torch renormalises the probabilities and clamps them to [eps, 1 - eps] before the logarithm
-struct CatRow {
-    float mx, sum, psum;
-    __device__ __forceinline__ float prob(float z) const { return expf(z - mx) / sum; }
-    __device__ __forceinline__ float logp(float pc) const { return logf(fminf(fmaxf(pc / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f)); }
-};
-__device__ __forceinline__ CatRow cat_row(lds_cf z, int A) {
-    CatRow q;
-    q.mx = z[0];
-    for (int c = 1; c < A; ++c) q.mx = fmaxf(q.mx, z[c]);
-    q.sum = 0.f;
-    for (int c = 0; c < A; ++c) q.sum += expf(z[c] - q.mx);
-    q.psum = 0.f;
-    for (int c = 0; c < A; ++c) q.psum += expf(z[c] - q.mx) / q.sum;
-    return q;
-}
-
-// CategoricalMasked (MAPPO_for_mask_action.py:191-215) of one row: logits' = where(mask, z, -1e8), Categorical(logits = logits').  The
-// normalised logit is l = logits' - (max + log sum exp(logits' - max)), in torch's order: in a row whose mask is all closed the
-// bracket rounds back to -1e8 and every l is exactly 0 (p = 1 / A, log-prob 0), where (z - max) - log sum would give -log A.
-// p = softmax(l); a closed column has p = 0 exactly next to an open one.  `mask` is the row's block in its ring record: nonzero = open.
-constexpr float kMaskedLogit = -1e8f;
-struct MaskedCatRow {
-    g_cf mask;
-    float lse, lmx, sum;
-    __device__ __forceinline__ bool open(int c) const { return mask[c] != 0.f; }
-    __device__ __forceinline__ float logit(float z, int c) const { return (open(c) ? z : kMaskedLogit) - lse; }      // l_c
-    __device__ __forceinline__ float prob(float l) const { return expf(l - lmx) / sum; }
-};
-__device__ __forceinline__ MaskedCatRow masked_cat_row(lds_cf z, g_cf mask, int A) {
-    MaskedCatRow q;
-    q.mask = mask;
-    auto sub = [&](int c) { return mask[c] != 0.f ? z[c] : kMaskedLogit; };
-    float mx = sub(0);
-    for (int c = 1; c < A; ++c) mx = fmaxf(mx, sub(c));
-    float s = 0.f;
-    for (int c = 0; c < A; ++c) s += expf(sub(c) - mx);
-    q.lse = mx + logf(s);
-    q.lmx = sub(0) - q.lse;
-    for (int c = 1; c < A; ++c) q.lmx = fmaxf(q.lmx, sub(c) - q.lse);
-    q.sum = 0.f;
-    for (int c = 0; c < A; ++c) q.sum += expf((sub(c) - q.lse) - q.lmx);
-    return q;
-}
-// entropy() of the same row: -sum over the open columns of p_c l_c
-__device__ __forceinline__ float masked_entropy(const MaskedCatRow& q, lds_cf z, int A) {
-    float h = 0.f;
-    for (int c = 0; c < A; ++c)
-        if (q.open(c)) { const float l = q.logit(z[c], c); h -= q.prob(l) * l; }
-    return h;
-}
-// the head delta of column c: coef (1[c = a] - p_c) + ent_m p_c (l_c + H) where open, 0 where closed (torch.where passes no gradient)
-__device__ __forceinline__ float masked_delta(const MaskedCatRow& q, float z, int c, int a, float coef, float ent_m, float H) {
-    if (!q.open(c)) return 0.f;
-    const float l = q.logit(z, c), pc = q.prob(l);
-    return coef * ((c == a ? 1.f : 0.f) - pc) + ent_m * pc * (l + H);
 }
 
 // the critic's input of agent i: its own observation block, or all blocks (they are contiguous in a record, in agent order)
@@ -270,7 +181,6 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
     int t_adam = steps[net];
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)u * a.k_epochs * n_mb * 2;
-    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;   // 0.5 + 0.5*log(2*pi)
     LearnArgs la = {};
     la.huber = a.huber;
     la.huber_delta = a.huber_delta;
@@ -299,7 +209,7 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
             if (do_actor) {
                 // ---------------- clipped surrogate - entropy_coefficient * mean entropy (MAPPO.py:399-412, IPPO.py:281-294)
                 float lossp = 0.f, entp = 0.f, gls = 0.f, ent = 0.f;
-                if (!discrete && threadIdx.x < A) ent = kHalfLog2PiPlusHalf + clamp_log_std(th[N.extra_off + threadIdx.x]);
+                if (!discrete && threadIdx.x < A) ent = kHalfLog2PiPlusHalf + clamp_range(th[N.extra_off + threadIdx.x], kLogStdMin, kLogStdMax);
                 const float ent_sum = block_sum(ent, S.red);          // Normal's entropy: the same for every row
                 for (int r0 = 0; r0 < m; r0 += rc) {
                     const int nv = min(rc, m - r0);
@@ -308,52 +218,19 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
                     __syncthreads();
                     mappo_fwd(D, N, th, S, X, O, discrete ? ACT_NONE : ACT_TANH);          // mean = tanh(mean_layer(.))
                     if (discrete) {
-                        // one thread per row
-                        if (threadIdx.x < rc) {
-                            const int r = threadIdx.x;
-                            if (r < nv) {
+                        // Categorical, or CategoricalMasked under the row's mask block: onpolicy.hpp's one-thread-per-row head
+                        cat_head_delta(S, nv, A, npad, a.ent_coef * invm,
+                            [&](int r, lds_cf z) {
+                                if constexpr (kMasked) return masked_cat_row(z, ring + (size_t)idx[r0 + r] * R.stride + mask_col, A);
+                                else return cat_row(z, A);
+                            },
+                            [&](int r) { return (int)ring[(size_t)idx[r0 + r] * R.stride + R.act_off[i]]; },
+                            [&](int r, float lp_now, float entr) {
                                 const int t = idx[r0 + r];
-                                g_cf rec = ring + (size_t)t * R.stride;
-                                const int ar = (int)rec[R.act_off[i]];
-                                if constexpr (kMasked) {
-                                    lds_cf z = S.outb + r * S.op;
-                                    const MaskedCatRow q = masked_cat_row(z, rec + mask_col, A);
-                                    const float entr = masked_entropy(q, z, A);
-                                    float lp_now = 0.f;
-                                    for (int c = 0; c < A; ++c)
-                                        if (c == ar) lp_now = q.logit(z[c], c);
-                                    const float ratio = expf(lp_now - rec[logp_col]);
-                                    const float coef = surrogate(ratio, t, invmn, lossp);
-                                    entp += entr;
-                                    for (int c = 0; c < npad; ++c)      // staged: outb is still being read by this row
-                                        S.abuf[r * S.ap + c] = c < A ? masked_delta(q, z[c], c, ar, coef, a.ent_coef * invm, entr) : 0.f;
-                                } else {
-                                    const CatRow q = cat_row(S.outb + r * S.op, A);
-                                    float entr = 0.f, lp_now = 0.f;
-                                    for (int c = 0; c < A; ++c) {
-                                        const float pc = q.prob(S.outb[r * S.op + c]);
-                                        const float lg = q.logp(pc);
-                                        entr -= lg * pc;
-                                        if (c == ar) lp_now = lg;
-                                    }
-                                    const float ratio = expf(lp_now - rec[logp_col]);
-                                    const float coef = surrogate(ratio, t, invmn, lossp);
-                                    entp += entr;
-                                    for (int c = 0; c < npad; ++c) {
-                                        float d = 0.f;
-                                        if (c < A) {
-                                            const float pc = q.prob(S.outb[r * S.op + c]);
-                                            d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_coef * invm) * pc * (q.logp(pc) + entr);
-                                        }
-                                        S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
-                                    }
-                                }
-                            } else {
-                                for (int c = 0; c < npad; ++c) S.abuf[r * S.ap + c] = 0.f;
-                            }
-                            for (int c = 0; c < npad; ++c) S.outb[r * S.op + c] = S.abuf[r * S.ap + c];
-                        }
-                        __syncthreads();
+                                const float coef = surrogate(expf(lp_now - ring[(size_t)t * R.stride + logp_col]), t, invmn, lossp);
+                                entp += entr;
+                                return coef;
+                            });
                     } else {
                         if (threadIdx.x < rc) {
                             const int r = threadIdx.x;
@@ -361,36 +238,19 @@ __device__ __forceinline__ void mappo_steps(const EngineDesc& D, const MappoArgs
                             if (r < nv) {
                                 const int t = idx[r0 + r];
                                 g_cf rec = ring + (size_t)t * R.stride;
-                                const float lp_now = normal_row_logp(rec + R.act_off[i], S.outb + r * S.op, th + N.extra_off, A);
+                                const float lp_now = normal_row_logp(rec + R.act_off[i], S.outb + r * S.op, th + N.extra_off, A, kLogStdMin, kLogStdMax);
                                 float lp_old = 0.f;
                                 for (int c = 0; c < A; ++c) lp_old += rec[logp_col + c];
                                 coef = surrogate(expf(lp_now - lp_old), t, invmn, lossp);
                             }
                             S.dabuf[r * S.ap] = coef;      // d loss / d sum_c logp_now
                         }
-                        __syncthreads();
-                        for (int e = threadIdx.x; e < rc * npad; e += kWG) {
-                            const int r = e / npad, c = e - r * npad;
-                            float d = 0.f, dl = 0.f;
-                            if (r < nv && c < A) {
-                                const float coef = S.dabuf[r * S.ap];
-                                const float mean = S.outb[r * S.op + c];
-                                const float var = expf(2.f * clamp_log_std(th[N.extra_off + c]));
-                                const float dm = ring[(size_t)idx[r0 + r] * R.stride + R.act_off[i] + c] - mean;
-                                d = coef * dm / var * (1.f - mean * mean);        // through mean = tanh(z)
-                                dl = coef * (dm * dm / var - 1.f);
-                            }
-                            S.outb[r * S.op + c] = d;
-                            if (c < A) S.abuf[r * S.ap + c] = dl;
-                        }
-                        __syncthreads();
-                        if (threadIdx.x < A)
-                            for (int r = 0; r < rc; ++r) gls += S.abuf[r * S.ap + threadIdx.x];
+                        normal_head_delta(S, nv, A, npad, idx + r0, ring, R.stride, R.act_off[i], th + N.extra_off, kLogStdMin, kLogStdMax, gls);
                     }
                     mappo_bwd(D, N, th, G, S, X, r0 == 0 ? GS_STORE : GS_ADD);
                 }
                 if (!discrete && threadIdx.x < A)
-                    G[N.extra_off + threadIdx.x] = log_std_grad_open(th[N.extra_off + threadIdx.x]) ? (gls - a.ent_coef) : 0.f;
+                    G[N.extra_off + threadIdx.x] = log_std_grad_open(th[N.extra_off + threadIdx.x], kLogStdMin, kLogStdMax) ? (gls - a.ent_coef) : 0.f;
                 const float surr = block_sum(lossp, S.red) * invmn;
                 const float entm = discrete ? block_sum(entp, S.red) * invm : ent_sum;
                 loss = surr - a.ent_coef * entm;

@@ -542,6 +542,15 @@ __device__ __forceinline__ void gather_cols(lds_f X, int ldx, int rc, int nvalid
             if (e0 + u * kWG < total) X[rr[u] * ldx + dst0 + cc[u]] = v[u];
     }
 }
+// The chunk of CONSECUTIVE rows: X[r][c] = src[(r0 + r) * stride + src0 + c] for r < nvalid, c < ncols; 0 in the rows behind them and
+// in columns ncols .. k_pad.  src is a learner's ring (the value passes, the horizon passes, REINFORCE's batch) or a dense [n_rows][K]
+// input whose pointer already stands at the chunk (the act kernels: r0 = 0, stride = K, src0 = 0)
+__device__ __forceinline__ void load_rows(lds_f X, int ldx, int rc, int nvalid, g_cf src, int r0, int stride, int src0, int ncols, int k_pad) {
+    for (int e = threadIdx.x; e < rc * k_pad; e += kWG) {
+        const int r = e / k_pad, c = e - r * k_pad;
+        X[r * ldx + c] = (r < nvalid && c < ncols) ? src[(size_t)(r0 + r) * stride + src0 + c] : 0.f;
+    }
+}
 // Batch_ObsNorm: X[r][c0 + c] = (X[r][c0 + c] - mean[c]) / (std[c] + 1e-8) for r < nvalid
 // (Normalization_batch_size.__call__, PPO_file/normalization.py:78-84); stats = {n, mean[O], S[O], std[O]}
 __device__ __forceinline__ void normalize_cols(lds_f X, int ldx, int nvalid, int c0, int ncols, g_cf stats, int O) {

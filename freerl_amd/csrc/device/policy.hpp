@@ -29,15 +29,18 @@ __device__ __forceinline__ void td_loss_row(const LearnArgs& a, float e, float& 
 }
 
 // log_std = clamp(log_std, -20, 2) (SAC.py:76, PPO_with_tricks.py:102): every kernel that reads a log_std — the SAC
-// sample and log_std gradient below, kernels_ppo / _ppo2, act_common.hpp
-__device__ __forceinline__ float clamp_log_std(float raw) { return fminf(fmaxf(raw, kLogStdMin), kLogStdMax); }
+// sample and log_std gradient below, kernels_ppo2, act_common.hpp; clamp_range is the same over a given range: onpolicy.hpp's Normal head
+// (kernels_ppo and mappo_steps with kLogStdMin / kLogStdMax, kernels_gail_ppo with the engine's)
+__device__ __forceinline__ float clamp_range(float raw, float lo, float hi) { return fminf(fmaxf(raw, lo), hi); }
+__device__ __forceinline__ float clamp_log_std(float raw) { return clamp_range(raw, kLogStdMin, kLogStdMax); }
 // torch.clamp passes no gradient outside its bounds: the log_std gradient of every SAC actor kernel (kernels_actor / _actor2 /
-// _actorw / _actorx / _solo / _solow) and of kernels_ppo / _ppo2
-__device__ __forceinline__ bool log_std_grad_open(float raw) { return raw >= kLogStdMin && raw <= kLogStdMax; }
+// _actorw / _actorx / _solo / _solow) and of kernels_ppo2; the ranged form gates the streaming on-policy kernels' log_std
+__device__ __forceinline__ bool log_std_grad_open(float raw, float lo, float hi) { return raw >= lo && raw <= hi; }      // (the CLOSED range)
+__device__ __forceinline__ bool log_std_grad_open(float raw) { return log_std_grad_open(raw, kLogStdMin, kLogStdMax); }
 
 // Normal(mean, sd).log_prob(x), d = x - mean, ls = log(sd) (SAC.py:86, torch.distributions.Normal): sac_sample below and its
-// written-out forms (kernels_criticw / _criticx / _actorx), kernels_ppo / _ppo2 (the stored action against the current mean),
-// act_common.hpp (ACT_PPO_SAMPLE)
+// written-out forms (kernels_criticw / _criticx / _actorx), onpolicy.hpp's normal_row_logp and kernels_ppo2 (the stored action
+// against the current mean), act_common.hpp and kernels_gail_ppo (ACT_PPO_SAMPLE)
 __device__ __forceinline__ float normal_logp(float d, float sd, float ls) { return -(d * d) / (2.f * sd * sd) - ls - kLogSqrt2Pi; }
 // log(1 - tanh(u)^2) in its stable form 2 (log 2 - u - softplus(-2u)) (SAC.py:87): sac_sample, kernels_criticw / _criticx / _actorx
 __device__ __forceinline__ float tanh_logp_correction(float u) { return 2.f * (kLog2 - u - softplus_t(-2.f * u)); }

@@ -25,10 +25,7 @@ __global__ __launch_bounds__(256) void act_kernel(const EngineDesc* __restrict__
     const int nl = N.n_layers / N.heads, l0 = a.head * nl;
     const int K = a.in_dim, kpad = N.L[l0].k_pad;
     g_cf in = as_global(a.in + ((size_t)p * a.n_rows + r0) * K);
-    for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-        const int r = e / kpad, c = e - r * kpad;
-        S.xin[r * S.xp + c] = (r < nv && c < K) ? in[(size_t)r * K + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, in, 0, K, 0, K, kpad);
     if (D.obs_norm_on && a.normalize) {          // select_action: norm(obs, update=False) (SAC.py:194-195, MADDPG.py:162-163)
         __syncthreads();
         const int nag = D.n_agents, j = nag > 1 ? a.net / 2 : 0;           // MADDPG: net 2j is agent j's actor

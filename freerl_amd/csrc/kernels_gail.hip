@@ -182,10 +182,7 @@ __global__ __launch_bounds__(256) void gail_forward_kernel(const EngineDesc* __r
     g_cf theta = as_global(D.theta + (size_t)p * D.learner_stride + D.net_off[0]);
     const int IN = N.L[0].k, k0pad = N.L[0].k_pad;
     g_cf x = as_global(in + ((size_t)p * n_rows + r0) * IN);
-    for (int e = threadIdx.x; e < rc * k0pad; e += kWG) {
-        const int r = e / k0pad, c = e - r * k0pad;
-        S.xin[r * S.xp + c] = (r < nv && c < IN) ? x[(size_t)r * IN + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, x, 0, IN, 0, IN, k0pad);
     FRL_PHASE(S);
     g_f y = as_global(out + (size_t)p * n_rows + r0);
     mlp_fwd_rows(N, 0, 3, theta, S, ACT_NONE, [&](int r) {

@@ -12,13 +12,11 @@
 #include "kernels.h"
 #include "device/act_common.hpp"
 #include "device/gae.hpp"
-#include "device/net.hpp"
+#include "device/onpolicy.hpp"
 
 namespace frl {
 
 namespace {
-
-__device__ __forceinline__ float clamp_range(float raw, float lo, float hi) { return fminf(fmaxf(raw, lo), hi); }
 
 // the forward of a 3-layer net whose hidden activation may be ACT_LEAKY_RELU; ends with a barrier
 __device__ __forceinline__ void fwd3(const NetDesc& N, g_cf theta, const Lds& S, int out_act) {
@@ -30,20 +28,10 @@ __device__ __forceinline__ void fwd3(const NetDesc& N, g_cf theta, const Lds& S,
 __device__ __forceinline__ float row_logp(const EngineDesc& D, const NetDesc& NA, g_cf thA, const Lds& S, int r, g_cf rec, bool discrete, int A) {
     const RecordDesc& R = D.rec;
     if (discrete) {
-        float mx = S.outb[r * S.op];
-        for (int c = 1; c < A; ++c) mx = fmaxf(mx, S.outb[r * S.op + c]);
-        float sum = 0.f;
-        for (int c = 0; c < A; ++c) sum += expf(S.outb[r * S.op + c] - mx);
-        const int ar = min(max((int)rec[R.act_off[0]], 0), A - 1);
-        return (S.outb[r * S.op + ar] - mx) - logf(sum);
+        lds_cf z = S.outb + r * S.op;
+        return cat_row(z, A, CAT_LOGITS_E).logit(z[min(max((int)rec[R.act_off[0]], 0), A - 1)]);
     }
-    float lp = 0.f;
-    for (int c = 0; c < A; ++c) {
-        const float ls = clamp_range(thA[NA.extra_off + c], D.log_std_min, D.log_std_max);
-        const float sd = expf(ls);
-        lp += normal_logp(rec[R.act_off[0] + c] - S.outb[r * S.op + c], sd, ls);
-    }
-    return lp;
+    return normal_row_logp(rec + R.act_off[0], S.outb + r * S.op, thA + NA.extra_off, A, D.log_std_min, D.log_std_max);
 }
 
 }  // namespace
@@ -63,10 +51,7 @@ __global__ __launch_bounds__(256) void gail_ppo_prepare_kernel(const EngineDesc*
     g_cf ring = as_global(D.replay + (size_t)p * D.capacity * R.stride);
     const bool discrete = D.n_discrete > 0;
     const int O = R.obs_dim[0], kpad = NA.L[0].k_pad, A = discrete ? D.n_discrete : R.act_dim[0];      // (both first layers: the same k_pad)
-    for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-        const int r = e / kpad, c = e - r * kpad;
-        S.xin[r * S.xp + c] = (r < nv && c < O) ? ring[(size_t)(r0 + r) * R.stride + R.obs_off[0] + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, ring, r0, R.stride, R.obs_off[0], O, kpad);
     __syncthreads();
     fwd3(NC, thC, S, ACT_NONE);
     const size_t o = (size_t)p * T + r0 + threadIdx.x;
@@ -105,14 +90,7 @@ __global__ __launch_bounds__(256) void gail_ppo_gae_kernel(const EngineDesc* __r
         ret[i] = x + vs[i];
         s1 += x;
     }
-    const float mean = block_sum(s1, lds + 8) / (float)T;
-    float s2 = 0.f;
-    for (int i = threadIdx.x; i < T; i += kWG) {
-        const float d = adv_raw[i] - mean;
-        s2 += d * d;
-    }
-    const float sd = sqrtf(block_sum(s2, lds + 8) / (float)(T - 1));
-    for (int i = threadIdx.x; i < T; i += kWG) adv[i] = (adv_raw[i] - mean) / (sd + 1e-8f);
+    normalize_adv(s1, T, adv_raw, adv, [](int i) { return i; }, lds + 8);
 }
 
 // ---- all K_epochs x ceil(T / mb) steps of one learner in one launch.  blockIdx.y: 0 = the actor's steps, 1 = the critic's: inside
@@ -141,7 +119,6 @@ __global__ __launch_bounds__(256) void gail_ppo_update_kernel(const EngineDesc* 
     int t = steps[do_actor ? 0 : 1];
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)p * a.k_epochs * n_mb * 2;
-    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;   // 0.5 + 0.5*log(2*pi): Normal.entropy() - log_std
     const int out_act = (do_actor && !discrete) ? ACT_TANH : ACT_NONE;
 
     for (int k = 0; k < a.k_epochs; ++k) {
@@ -161,56 +138,21 @@ __global__ __launch_bounds__(256) void gail_ppo_update_kernel(const EngineDesc* 
                 fwd3(N, th, S, out_act);
                 if (!do_actor) {
                     // ---------------- critic: value_loss_coef * mse(V(s[idx]), returns[idx]) (:295-298)
-                    for (int e = threadIdx.x; e < rc * npad; e += kWG) {
-                        const int r = e / npad, c = e - r * npad;
-                        float d = 0.f;
-                        if (c == 0 && r < nv) {
-                            const float diff = S.outb[r * S.op] - ret[idx[r0 + r]];
-                            d = a.value_loss_coef * (2.f * diff * invm);
-                            lossp += diff * diff;
-                        }
-                        S.outb[r * S.op + c] = d;
-                    }
-                    __syncthreads();
+                    critic_delta_rows(S, nv, npad, idx + r0, ret, a.value_loss_coef, invm, lossp);
                 } else if (discrete) {
-                    // ---------------- Categorical(logits=) (:277-280): one thread per row — log-softmax, entropy -sum p log p, ratio, the logits' delta
-                    if ((int)threadIdx.x < rc) {
-                        const int r = threadIdx.x;
-                        if (r < nv) {
+                    // ---------------- Categorical(logits=) (:277-280): log-softmax, entropy -sum p log p, ratio, the logits' delta — onpolicy.hpp's
+                    // one-thread-per-row head; the stored index is clamped to [0, A - 1] here and nowhere else
+                    cat_head_delta(S, nv, A, npad, a.ent_weight * invm,
+                        [&](int, lds_cf z) { return cat_row(z, A, CAT_LOGITS_E); },
+                        [&](int r) { return min(max((int)ring[(size_t)idx[r0 + r] * R.stride + R.act_off[0]], 0), A - 1); },
+                        [&](int r, float lp_now, float entr) {
                             const int row = idx[r0 + r];
-                            g_cf rec = ring + (size_t)row * R.stride;
-                            float mx = S.outb[r * S.op];
-                            for (int c = 1; c < A; ++c) mx = fmaxf(mx, S.outb[r * S.op + c]);
-                            float sum = 0.f;
-                            for (int c = 0; c < A; ++c) sum += expf(S.outb[r * S.op + c] - mx);
-                            const float lse = logf(sum);
-                            const int ar = min(max((int)rec[R.act_off[0]], 0), A - 1);
-                            float entr = 0.f, lp_now = 0.f;
-                            for (int c = 0; c < A; ++c) {
-                                const float lg = (S.outb[r * S.op + c] - mx) - lse;
-                                entr -= lg * expf(lg);
-                                if (c == ar) lp_now = lg;
-                            }
                             const float ratio = expf(lp_now - lp_old[row]);
-                            const float Ar = adv[row];
-                            const float s1 = ratio * Ar;
-                            const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                            lossp += -fminf(s1, s2) - a.ent_weight * entr;
-                            const float coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;
-                            for (int c = 0; c < npad; ++c) {
-                                float d = 0.f;
-                                if (c < A) {
-                                    const float lg = (S.outb[r * S.op + c] - mx) - lse, pc = expf(lg);
-                                    d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_weight * invm) * pc * (lg + entr);
-                                }
-                                S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
-                            }
-                        } else {
-                            for (int c = 0; c < npad; ++c) S.abuf[r * S.ap + c] = 0.f;
-                        }
-                        for (int c = 0; c < npad; ++c) S.outb[r * S.op + c] = S.abuf[r * S.ap + c];
-                    }
-                    __syncthreads();
+                            float surr = 0.f;
+                            const float open = surrogate_term(ratio, adv[row], a.clip, surr);
+                            lossp += surr - a.ent_weight * entr;
+                            return open * (-invm) * ratio;
+                        });
                 } else {
                     // ---------------- Normal (:282-292): the row's ratio and d loss / d sum_c logp, then the head's and log_std's deltas
                     if ((int)threadIdx.x < rc) {
@@ -220,32 +162,11 @@ __global__ __launch_bounds__(256) void gail_ppo_update_kernel(const EngineDesc* 
                             const int row = idx[r0 + r];
                             const float lp_now = row_logp(D, N, th, S, r, ring + (size_t)row * R.stride, false, A);
                             const float ratio = expf(lp_now - lp_old[row]);
-                            const float Ar = adv[row];
-                            const float s1 = ratio * Ar;
-                            const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                            lossp += -fminf(s1, s2);
-                            coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;
+                            coef = surrogate_term(ratio, adv[row], a.clip, lossp) * (-invm) * ratio;
                         }
                         S.dabuf[r * S.ap] = coef;
                     }
-                    __syncthreads();
-                    for (int e = threadIdx.x; e < rc * npad; e += kWG) {
-                        const int r = e / npad, c = e - r * npad;
-                        float d = 0.f, dl = 0.f;
-                        if (r < nv && c < A) {
-                            const float coef = S.dabuf[r * S.ap];
-                            const float mean = S.outb[r * S.op + c];
-                            const float var = expf(2.f * clamp_range(th[N.extra_off + c], lo, hi));
-                            const float dm = ring[(size_t)idx[r0 + r] * R.stride + R.act_off[0] + c] - mean;
-                            d = coef * dm / var * (1.f - mean * mean);        // through mean = tanh(z)
-                            dl = coef * (dm * dm / var - 1.f);
-                        }
-                        S.outb[r * S.op + c] = d;
-                        if (c < A) S.abuf[r * S.ap + c] = dl;
-                    }
-                    __syncthreads();
-                    if ((int)threadIdx.x < A)
-                        for (int r = 0; r < rc; ++r) gls += S.abuf[r * S.ap + threadIdx.x];
+                    normal_head_delta(S, nv, A, npad, idx + r0, ring, R.stride, R.act_off[0], th + N.extra_off, lo, hi, gls);
                 }
                 // one call site for both nets and both distributions: every inlined copy of the backward pass is ~20 k instructions of a
                 // kernel that walks its whole code once per minibatch step (kernels_ppo.hip)
@@ -254,7 +175,7 @@ __global__ __launch_bounds__(256) void gail_ppo_update_kernel(const EngineDesc* 
             if (do_actor && !discrete && (int)threadIdx.x < A) {
                 // torch.clamp passes the gradient on the CLOSED range [lo, hi] (:38)
                 const float raw = th[N.extra_off + threadIdx.x];
-                G[N.extra_off + threadIdx.x] = (raw >= lo && raw <= hi) ? (gls - a.ent_weight) : 0.f;
+                G[N.extra_off + threadIdx.x] = log_std_grad_open(raw, lo, hi) ? (gls - a.ent_weight) : 0.f;
             }
             float loss = block_sum(lossp, S.red) * invm;
             if (do_actor) loss -= discrete ? 0.f : a.ent_weight * ent_sum;
@@ -288,10 +209,7 @@ __global__ __launch_bounds__(256) void gail_ppo_act_kernel(const EngineDesc* __r
     g_cf theta = as_global(D.theta + (size_t)p * D.learner_stride + D.net_off[a.net]);
     const int K = a.in_dim, kpad = N.L[0].k_pad, nout = N.L[N.n_layers - 1].n;
     g_cf in = as_global(a.in + ((size_t)p * a.n_rows + r0) * K);
-    for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-        const int r = e / kpad, c = e - r * kpad;
-        S.xin[r * S.xp + c] = (r < nv && c < K) ? in[(size_t)r * K + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, in, 0, K, 0, K, kpad);
     __syncthreads();
     fwd3(N, theta, S, (a.mode == ACTM_TANH || a.mode == ACTM_PPO_SAMPLE) ? ACT_TANH : ACT_NONE);
     if (a.mode != ACTM_PPO_SAMPLE) {

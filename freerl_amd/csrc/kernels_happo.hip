@@ -25,24 +25,15 @@ __device__ __forceinline__ void happo_horizon_pass(const EngineDesc& D, const Ld
     const int rc = D.rc, O = R.obs_dim[i], A = N.L[2].n, kpad = N.L[0].k_pad;
     for (int r0 = 0; r0 < T; r0 += rc) {
         const int nv = min(rc, T - r0);
-        for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-            const int r = e / kpad, c = e - r * kpad;
-            S.xin[r * S.xp + c] = (r < nv && c < O) ? ring[(size_t)(r0 + r) * R.stride + R.obs_off[i] + c] : 0.f;
-        }
+        load_rows(S.xin, S.xp, rc, nv, ring, r0, R.stride, R.obs_off[i], O, kpad);
         __syncthreads();
         mappo_fwd(D, N, th, S, X, O, discrete ? ACT_NONE : ACT_TANH);
         if (threadIdx.x < nv) {
             const int r = threadIdx.x, t = r0 + r;
             g_cf rec = ring + (size_t)t * R.stride;
-            float lp = 0.f;
-            if (discrete) {
-                const CatRow q = cat_row(S.outb + r * S.op, A);
-                const int ar = (int)rec[R.act_off[i]];
-                for (int c = 0; c < A; ++c)
-                    if (c == ar) lp = q.logp(q.prob(S.outb[r * S.op + c]));
-            } else {
-                lp = normal_row_logp(rec + R.act_off[i], S.outb + r * S.op, th + N.extra_off, A);
-            }
+            lds_cf z = S.outb + r * S.op;
+            const float lp = discrete ? cat_row(z, A).logp_at(z, A, (int)rec[R.act_off[i]])
+                                      : normal_row_logp(rec + R.act_off[i], z, th + N.extra_off, A, kLogStdMin, kLogStdMax);
             if (first) old[t] = lp;
             else next[t] = (cur ? cur[t] : 1.f) * expf(lp - old[t]);
         }

@@ -30,10 +30,7 @@ __global__ __launch_bounds__(256) void mappo_values_kernel(const EngineDesc* __r
     float v0 = 0.f;
     for (int pass = 0; pass < 2; ++pass) {
         const int src = pass == 0 ? ci.obs : ci.nobs;
-        for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-            const int r = e / kpad, c = e - r * kpad;
-            S.xin[r * S.xp + c] = (r < nv && c < ci.width) ? ring[(size_t)(r0 + r) * R.stride + src + c] : 0.f;
-        }
+        load_rows(S.xin, S.xp, rc, nv, ring, r0, R.stride, src, ci.width, kpad);
         __syncthreads();
         mappo_fwd(D, N, theta, S, X, ci.width, ACT_NONE);
         if (threadIdx.x < nv) {
@@ -80,11 +77,7 @@ __global__ __launch_bounds__(256) void mappo_adv_kernel(const EngineDesc* __rest
         auto at = [&](int k) { return joint ? k : k * n + g; };
         float s1 = 0.f;
         for (int k = threadIdx.x; k < cnt; k += kWG) s1 += raw[at(k)];
-        const float mean = block_sum(s1, red) / (float)cnt;
-        float s2 = 0.f;
-        for (int k = threadIdx.x; k < cnt; k += kWG) { const float d = raw[at(k)] - mean; s2 += d * d; }
-        const float sd = sqrtf(block_sum(s2, red) / (float)(cnt - 1));
-        for (int k = threadIdx.x; k < cnt; k += kWG) adv[at(k)] = (raw[at(k)] - mean) / (sd + 1e-8f);
+        normalize_adv(s1, cnt, raw, adv, at, red);
     }
 }
 
@@ -110,10 +103,7 @@ __global__ __launch_bounds__(256) void mappo_act_kernel(const EngineDesc* __rest
     g_cf theta = as_global((a.use_target ? D.target : D.theta) + (size_t)p * D.learner_stride + D.net_off[a.net]);
     const int K = a.in_dim, kpad = N.L[0].k_pad;
     g_cf in = as_global(a.in + ((size_t)p * a.n_rows + r0) * K);
-    for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-        const int r = e / kpad, c = e - r * kpad;
-        S.xin[r * S.xp + c] = (r < nv && c < K) ? in[(size_t)r * K + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, in, 0, K, 0, K, kpad);
     __syncthreads();
     const int out_act = (a.mode == ACTM_TANH || a.mode == ACTM_PPO_SAMPLE) ? ACT_TANH : ACT_NONE;
     mappo_fwd(D, N, theta, S, X, K, out_act);

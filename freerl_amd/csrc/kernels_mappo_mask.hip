@@ -3,7 +3,7 @@
 //     mappo_values_kernel -> gae_dense_kernel -> mappo_adv_kernel -> mappo_mask_update_kernel
 // the first three as kernels_mappo.hip has them: the critic, the GAE scan and the advantages do not see the masks.  The update is
 // mappo_update_kernel's grid and step loop (device/mappo.hpp: mappo_steps) with the discrete actor's row read as CategoricalMasked
-// (device/mappo.hpp: masked_cat_row); select_action's draw is mappo_mask_act_kernel, on the same row arithmetic.
+// (device/onpolicy.hpp: masked_cat_row); select_action's draw is mappo_mask_act_kernel, on the same row arithmetic.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
@@ -36,10 +36,7 @@ __global__ __launch_bounds__(256) void mappo_mask_act_kernel(const EngineDesc* _
     g_cf theta = as_global(D.theta + (size_t)p * D.learner_stride + D.net_off[a.net]);
     const int K = a.in_dim, kpad = N.L[0].k_pad, A = N.L[2].n;
     g_cf in = as_global(a.in + ((size_t)p * a.n_rows + r0) * K);
-    for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-        const int r = e / kpad, c = e - r * kpad;
-        S.xin[r * S.xp + c] = (r < nv && c < K) ? in[(size_t)r * K + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, in, 0, K, 0, K, kpad);
     __syncthreads();
     mappo_fwd(D, N, theta, S, X, K, ACT_NONE);
     const unsigned long long key = D.seed + 0x9E3779B97F4A7C15ull * (p + 1);      // act_epilogue's key: (seed, learner), one counter per launch

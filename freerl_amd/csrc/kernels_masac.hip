@@ -226,10 +226,7 @@ __global__ __launch_bounds__(256) void masac_act_kernel(const EngineDesc* __rest
     const int K = a.in_dim, kp = N.L[0].k_pad, A = N.L[N.n_layers - 1].n / 2;
     g_cf theta = as_global((a.use_target ? D.target : D.theta) + (size_t)p * D.learner_stride + D.net_off[a.net]);
     g_cf in = as_global(a.in + ((size_t)p * a.n_rows + r0) * K);
-    for (int e = threadIdx.x; e < rc * kp; e += kWG) {
-        const int r = e / kp, c = e - r * kp;
-        S.xin[r * S.xp + c] = (r < nv && c < K) ? in[(size_t)r * K + c] : 0.f;
-    }
+    load_rows(S.xin, S.xp, rc, nv, in, 0, K, 0, K, kp);
     __syncthreads();
     mlp_fwd(N, 0, N.n_layers, theta, S, ACT_NONE);
     for (int e = threadIdx.x; e < nv * A; e += kWG) {

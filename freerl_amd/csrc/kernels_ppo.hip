@@ -6,7 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "device/net.hpp"
+#include "device/onpolicy.hpp"
 #include "device/gae.hpp"
 #include "device/special.hpp"
 #include "device/ppo_timing.hpp"
@@ -29,10 +29,7 @@ __global__ __launch_bounds__(256) void ppo_values_kernel(const EngineDesc* __res
     float v0 = 0.f;
     for (int pass = 0; pass < 2; ++pass) {
         const int src = pass == 0 ? R.obs_off[0] : R.nobs_off[0];
-        for (int e = threadIdx.x; e < rc * kpad; e += kWG) {
-            const int r = e / kpad, c = e - r * kpad;
-            S.xin[r * S.xp + c] = (r < nv && c < O) ? ring[(size_t)(r0 + r) * R.stride + src + c] : 0.f;
-        }
+        load_rows(S.xin, S.xp, rc, nv, ring, r0, R.stride, src, O, kpad);
         if (D.obs_norm_on) {
             __syncthreads();
             normalize_cols(S.xin, S.xp, nv, 0, O, as_global(D.obsnorm + (size_t)p * (1 + 3 * O)), O);
@@ -79,22 +76,12 @@ __global__ __launch_bounds__(256) void ppo_gae_kernel(const EngineDesc* __restri
         for (int i = threadIdx.x; i < T; i += kWG) adv[i] = adv_raw[i];
         return;
     }
-    const float mean = block_sum(s1, lds + 8) / (float)T;
-    float s2 = 0.f;
-    for (int i = threadIdx.x; i < T; i += kWG) {
-        const float d = adv_raw[i] - mean;
-        s2 += d * d;
-    }
-    const float sd = sqrtf(block_sum(s2, lds + 8) / (float)(T - 1));
-    for (int i = threadIdx.x; i < T; i += kWG) adv[i] = (adv_raw[i] - mean) / (sd + 1e-8f);
+    normalize_adv(s1, T, adv_raw, adv, [](int i) { return i; }, lds + 8);
 }
 
 // ---- PPO_advance/Buffer.py:480-507 `compute_returns_and_advantage` (stable-baselines3's form): the values were stored
 // at rollout time; float64 throughout (the reference scans float64 NumPy arrays with Python-float gamma / lambda), one
-// cast to float32 at the end (PPO_2.py:223-224).  Same affine suffix scan as gae_scan, in double.
-struct AffineD { double a, b; };
-__device__ __forceinline__ AffineD compose(AffineD f, AffineD g) { return AffineD{f.a * g.a, f.a * g.b + f.b}; }
-
+// cast to float32 at the end (PPO_2.py:223-224).  Same affine suffix scan as gae_scan, in double (gae.hpp's AffineD).
 __global__ __launch_bounds__(256) void ppo_gae_sb3_kernel(const EngineDesc* __restrict__ Dp, PpoArgs a) {
     __shared__ double lds_d[8];
     __shared__ float lds_s[16];
@@ -150,14 +137,7 @@ __global__ __launch_bounds__(256) void ppo_gae_sb3_kernel(const EngineDesc* __re
         for (int i = t; i < T; i += kWG) adv[i] = adv_raw[i];
         return;
     }
-    const float mean = block_sum(s1f, lds + 8) / (float)T;
-    float s2 = 0.f;
-    for (int i = t; i < T; i += kWG) {
-        const float d = adv_raw[i] - mean;
-        s2 += d * d;
-    }
-    const float sd = sqrtf(block_sum(s2, lds + 8) / (float)(T - 1));
-    for (int i = t; i < T; i += kWG) adv[i] = (adv_raw[i] - mean) / (sd + 1e-8f);
+    normalize_adv(s1f, T, adv_raw, adv, [](int i) { return i; }, lds + 8);
 }
 
 // ---- np.random.permutation(horizon) per (learner, epoch) (PPO_with_tricks.py:320) on the device when the caller does not
@@ -230,7 +210,6 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
     int tA = steps[0], tC = steps[1];
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)p * a.k_epochs * n_mb * 2;
-    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;   // 0.5 + 0.5*log(2*pi)
     PPO_T0();
 
     for (int k = 0; k < a.k_epochs; ++k) {
@@ -244,8 +223,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
             // ---------------- actor: clipped surrogate + entropy bonus (:324-346)
             float lossp = 0.f, gls = 0.f, ent = 0.f;
             if (!discrete && !beta && threadIdx.x < A) {
-                const float ls = clamp_log_std(thA[NA.extra_off + threadIdx.x]);
-                ent = kHalfLog2PiPlusHalf + ls;
+                ent = kHalfLog2PiPlusHalf + clamp_range(thA[NA.extra_off + threadIdx.x], kLogStdMin, kLogStdMax);
             }
             const float ent_sum = block_sum(ent, S.red);          // same for every row
             for (int r0 = 0; r0 < m; r0 += rc) {
@@ -277,11 +255,10 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                                 entr += lB - (al - 1.0) * digamma_d(al) - (be - 1.0) * digamma_d(be) + (al + be - 2.0) * digamma_d(al + be);
                             }
                             const float ratio = expf((float)(lp_now - lp_old));
-                            const float Ar = adv[idx[r0 + r]];
-                            const float s1 = ratio * Ar;
-                            const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                            lossp += -fminf(s1, s2) - a.ent_coef * (float)entr;
-                            const double coef = (double)((s1 <= s2 ? Ar : 0.f) * (-invm) * ratio), ce = (double)(a.ent_coef * invm);
+                            float surr = 0.f;
+                            const float open = surrogate_term(ratio, adv[idx[r0 + r]], a.clip, surr);
+                            lossp += surr - a.ent_coef * (float)entr;
+                            const double coef = (double)(open * (-invm) * ratio), ce = (double)(a.ent_coef * invm);
                             for (int c = 0; c < A; ++c) {
                                 const float za = S.outb[r * S.op + c], zb = S.outb[r * S.op + A + c];
                                 const double al = (double)(za > 20.f ? za : log1pf(expf(za))) + 1.0;
@@ -304,53 +281,18 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                     }
                     __syncthreads();
                 } else if (discrete) {
-                    // Categorical(probs = softmax(l3)) (:333-336): one thread per row does the softmax,
-                    // log-prob of the stored action, entropy, ratio and the logits' delta
-                    if (threadIdx.x < rc) {
-                        const int r = threadIdx.x;
-                        if (r < nv) {
-                            g_cf rec = ring + (size_t)idx[r0 + r] * R.stride;
-                            float mx = S.outb[r * S.op];
-                            for (int c = 1; c < A; ++c) mx = fmaxf(mx, S.outb[r * S.op + c]);
-                            float sum = 0.f;
-                            for (int c = 0; c < A; ++c) sum += expf(S.outb[r * S.op + c] - mx);
-                            float psum = 0.f;
-                            for (int c = 0; c < A; ++c) psum += expf(S.outb[r * S.op + c] - mx) / sum;
-                            const int ar = (int)rec[R.act_off[0]];
-                            const float lse = logf(sum);
-                            // log-prob of class c: clamped renormalised probability (probs=) or the log-softmax itself (logits=)
-                            auto logp_of = [&](int c, float pc) {
-                                return D.cat_logits ? (S.outb[r * S.op + c] - mx) - lse
-                                                    : logf(fminf(fmaxf(pc / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f));
-                            };
-                            float entr = 0.f, lp_now = 0.f;
-                            for (int c = 0; c < A; ++c) {
-                                const float pc = expf(S.outb[r * S.op + c] - mx) / sum;
-                                const float lg = logp_of(c, pc);
-                                entr -= lg * pc;
-                                if (c == ar) lp_now = lg;
-                            }
-                            const float ratio = expf(lp_now - rec[logp_col]);
-                            const float Ar = adv[idx[r0 + r]];
-                            const float s1 = ratio * Ar;
-                            const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                            lossp += -fminf(s1, s2) - a.ent_coef * entr;
-                            const float coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;
-                            for (int c = 0; c < napad; ++c) {
-                                float d = 0.f;
-                                if (c < A) {
-                                    const float pc = expf(S.outb[r * S.op + c] - mx) / sum;
-                                    const float lg = logp_of(c, pc);
-                                    d = coef * ((c == ar ? 1.f : 0.f) - pc) + (a.ent_coef * invm) * pc * (lg + entr);
-                                }
-                                S.abuf[r * S.ap + c] = d;      // staged: outb is still being read by this row
-                            }
-                        } else {
-                            for (int c = 0; c < napad; ++c) S.abuf[r * S.ap + c] = 0.f;
-                        }
-                        for (int c = 0; c < napad; ++c) S.outb[r * S.op + c] = S.abuf[r * S.ap + c];
-                    }
-                    __syncthreads();
+                    // Categorical(probs = softmax(l3)) (:333-336), or Categorical(logits = l3) on a cat_logits engine: the softmax,
+                    // log-prob of the stored action, entropy, ratio and the logits' delta are onpolicy.hpp's one-thread-per-row head
+                    cat_head_delta(S, nv, A, napad, a.ent_coef * invm,
+                        [&](int, lds_cf z) { return cat_row(z, A, D.cat_logits ? CAT_LOGITS_Q : CAT_PROBS); },
+                        [&](int r) { return (int)ring[(size_t)idx[r0 + r] * R.stride + R.act_off[0]]; },
+                        [&](int r, float lp_now, float entr) {
+                            const float ratio = expf(lp_now - ring[(size_t)idx[r0 + r] * R.stride + logp_col]);
+                            float surr = 0.f;
+                            const float open = surrogate_term(ratio, adv[idx[r0 + r]], a.clip, surr);
+                            lossp += surr - a.ent_coef * entr;
+                            return open * (-invm) * ratio;
+                        });
                 } else {
                 // per-row ratio and d loss / d sum(logp)
                 if (threadIdx.x < rc) {
@@ -358,43 +300,15 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                     float coef = 0.f;
                     if (r < nv) {
                         g_cf rec = ring + (size_t)idx[r0 + r] * R.stride;
-                        float lp_now = 0.f, lp_old = 0.f;
-                        for (int c = 0; c < A; ++c) {
-                            const float mean = S.outb[r * S.op + c];
-                            const float ls = clamp_log_std(thA[NA.extra_off + c]);
-                            const float sd = expf(ls);
-                            const float d = rec[R.act_off[0] + c] - mean;
-                            lp_now += normal_logp(d, sd, ls);
-                            lp_old += rec[logp_col + c];
-                        }
+                        const float lp_now = normal_row_logp(rec + R.act_off[0], S.outb + r * S.op, thA + NA.extra_off, A, kLogStdMin, kLogStdMax);
+                        float lp_old = 0.f;
+                        for (int c = 0; c < A; ++c) lp_old += rec[logp_col + c];
                         const float ratio = expf(lp_now - lp_old);
-                        const float Ar = adv[idx[r0 + r]];
-                        const float s1 = ratio * Ar;
-                        const float s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                        lossp += -fminf(s1, s2);
-                        coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;   // d loss / d sum_c logp_now
+                        coef = surrogate_term(ratio, adv[idx[r0 + r]], a.clip, lossp) * (-invm) * ratio;   // d loss / d sum_c logp_now
                     }
                     S.dabuf[r * S.ap] = coef;
                 }
-                __syncthreads();
-                for (int e = threadIdx.x; e < rc * napad; e += kWG) {
-                    const int r = e / napad, c = e - r * napad;
-                    float d = 0.f, dl = 0.f;
-                    if (r < nv && c < A) {
-                        const float coef = S.dabuf[r * S.ap];
-                        const float mean = S.outb[r * S.op + c];
-                        const float ls = clamp_log_std(thA[NA.extra_off + c]);
-                        const float var = expf(2.f * ls);
-                        const float dm = ring[(size_t)idx[r0 + r] * R.stride + R.act_off[0] + c] - mean;
-                        d = coef * dm / var * (1.f - mean * mean);        // through mean = tanh(z)
-                        dl = coef * (dm * dm / var - 1.f);
-                    }
-                    S.outb[r * S.op + c] = d;
-                    if (c < A) S.abuf[r * S.ap + c] = dl;
-                }
-                __syncthreads();
-                if (threadIdx.x < A)
-                    for (int r = 0; r < rc; ++r) gls += S.abuf[r * S.ap + threadIdx.x];
+                normal_head_delta(S, nv, A, napad, idx + r0, ring, R.stride, R.act_off[0], thA + NA.extra_off, kLogStdMin, kLogStdMax, gls);
                 }
                 // one call site for the three policy distributions (every inlined copy of the backward pass is ~20 k
                 // instructions of a kernel that walks its whole code once per minibatch step)
@@ -404,7 +318,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
             }
             if (!discrete && !beta && threadIdx.x < A) {
                 const float raw = thA[NA.extra_off + threadIdx.x];
-                gA[NA.extra_off + threadIdx.x] = log_std_grad_open(raw) ? (gls - a.ent_coef) : 0.f;
+                gA[NA.extra_off + threadIdx.x] = log_std_grad_open(raw, kLogStdMin, kLogStdMax) ? (gls - a.ent_coef) : 0.f;
             }
             const float aloss = block_sum(lossp, S.red) * invm - ((discrete || beta) ? 0.f : a.ent_coef * ent_sum);
             __syncthreads();
@@ -430,17 +344,7 @@ __global__ __launch_bounds__(256) void ppo_update_kernel(const EngineDesc* __res
                 PPO_T(0);
                 mlp_fwd(NC, 0, NC.n_layers, thC, S, ACT_NONE);
                 PPO_T(1);
-                for (int e = threadIdx.x; e < rc * ncpad; e += kWG) {
-                    const int r = e / ncpad, c = e - r * ncpad;
-                    float d = 0.f;
-                    if (c == 0 && r < nv) {
-                        const float diff = S.outb[r * S.op] - vt[idx[r0 + r]];
-                        d = 2.f * diff * invm;
-                        closs_p += diff * diff;
-                    }
-                    S.outb[r * S.op + c] = d;
-                }
-                __syncthreads();
+                critic_delta_rows(S, nv, ncpad, idx + r0, vt, 1.f, invm, closs_p);
                 PPO_T(2);
                 mlp_bwd(NC, 0, NC.n_layers, thC, gC, S, r0 == 0 ? GS_STORE : GS_ADD, false, 0, 0);
                 PPO_T(3);

@@ -24,6 +24,7 @@
 
 #include "kernels.h"
 #include "device/chain.hpp"
+#include "device/onpolicy.hpp"
 #include "device/ppo_timing.hpp"
 
 #ifndef FRL_PPO2_REFRESH
@@ -90,7 +91,6 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
     int t_step = steps[critic ? 1 : 0];
     const int n_mb = (T + mb - 1) / mb;
     float* trace = a.trace + (size_t)p * a.k_epochs * n_mb * 2;
-    constexpr float kHalfLog2PiPlusHalf = 1.41893853320467274178f;
     const float lr = critic ? a.critic_lr : a.actor_lr;
 
     // ---- parameters -> LDS (fragment order); engine layout: Wk[k][n] (n contiguous) then b[n_pad]
@@ -285,20 +285,25 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
                     lp_now = __shfl(lp_now, i16 + 48, 64); lp_old = __shfl(lp_old, i16 + 48, 64);
                     float coef = 0.f;
                     if (valid) {
-                        const float ratio = expf(lp_now - lp_old), Ar = cur.tgt;
-                        const float s1 = ratio * Ar, s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                        if (q == 0) lossp += -fminf(s1, s2);
-                        coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;      // d loss / d sum_c logp_now
+                        const float ratio = expf(lp_now - lp_old);
+                        float surr = 0.f;
+                        coef = surrogate_term(ratio, cur.tgt, a.clip, surr) * (-invm) * ratio;      // d loss / d sum_c logp_now
+                        if (q == 0) lossp += surr;
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (4 * q + r < A) {
+                            // (written out, not onpolicy.hpp's normal_head_delta / one_minus_sq: those are LDS block loops over a chunk, here
+                            // four columns of a row sit in one lane's registers and this kernel's own bits and register figures stay)
                             dz[r] = coef * dm[r] / var[r] * (1.f - mean[r] * mean[r]);      // through mean = tanh(z)
                             gls4[r] += coef * (dm[r] * dm[r] / var[r] - 1.f);
                         }
                     }
                 } else {
                     // Categorical over the A logits of the row, spread 4 per lane group (:333-336; PPO.py:257 for logits=)
+                    // (the softmax, entropy and delta stay written out: CatRow walks a row's classes in one thread and recomputes a column's
+                    // exp / log per use, here the classes are spread over four lane groups and pc / lg are kept; only the log-prob
+                    // expression and the constants are onpolicy.hpp's)
                     float mx = -3.0e38f;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) if (4 * q + r < A) mx = fmaxf(mx, z[r]);
@@ -325,10 +330,9 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
 #pragma unroll
                     for (int r = 0; r < 4; ++r) pc[r] = ex[r] / sum;
                     const float psum = seq_sum(pc);
-                    const float lse = logf(sum);
+                    const CatRow cq{mx, sum, psum, logf(sum), D.cat_logits ? CAT_LOGITS_Q : CAT_PROBS};
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        lg[r] = D.cat_logits ? (z[r] - mx) - lse : logf(fminf(fmaxf(pc[r] / psum, 1.1920929e-07f), 1.f - 1.1920929e-07f));
+                    for (int r = 0; r < 4; ++r) lg[r] = D.cat_logits ? cq.logit(z[r]) : cq.logp(pc[r]);
                     f32x4 et;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) et[r] = (4 * q + r < A) ? lg[r] * pc[r] : 0.f;
@@ -339,10 +343,10 @@ __device__ __forceinline__ void ppo_update_v2_body(const EngineDesc& D, const Pp
                     for (int r = 0; r < 4; ++r) if (4 * q + r == ar) lp_now = lg[r];
                     lp_now += lane_xor<16>(lp_now); lp_now += lane_xor<32>(lp_now);      // one group holds it, the others 0
                     if (valid) {
-                        const float ratio = expf(lp_now - cur.lpo[0]), Ar = cur.tgt;
-                        const float s1 = ratio * Ar, s2 = fminf(fmaxf(ratio, 1.f - a.clip), 1.f + a.clip) * Ar;
-                        if (q == 0) lossp += -fminf(s1, s2) - a.ent_coef * entr;
-                        const float coef = (s1 <= s2 ? Ar : 0.f) * (-invm) * ratio;
+                        const float ratio = expf(lp_now - cur.lpo[0]);
+                        float surr = 0.f;
+                        const float coef = surrogate_term(ratio, cur.tgt, a.clip, surr) * (-invm) * ratio;
+                        if (q == 0) lossp += surr - a.ent_coef * entr;
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
                             if (4 * q + r < A)

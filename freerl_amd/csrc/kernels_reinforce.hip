@@ -5,8 +5,9 @@
 // launches return before they read or write anything of it.
 #include <hip/hip_runtime.h>
 
+#include "device/gae.hpp"
 #include "device/lane.hpp"
-#include "device/net.hpp"
+#include "device/onpolicy.hpp"
 #include "device/update_common.hpp"
 #include "kernels.h"
 
@@ -14,10 +15,8 @@ namespace frl {
 
 // ------------------------------------------------------------------------------------ returns
 // G_t = r_t + gamma G_{t+1} (1 - done_t) is the affine map G -> b + a G with a = gamma (1 - done_t), b = r_t; a run of steps is the
-// composition of its maps.
-struct RetMap { double a, b; };
-// f after g: g belongs to the LATER steps (the scan runs backwards in time)
-__device__ __forceinline__ RetMap affine_after(const RetMap f, const RetMap g) { return RetMap{f.a * g.a, f.b + f.a * g.b}; }
+// composition of its maps: gae.hpp's AffineD, compose(f, g) = f after g, where g belongs to the LATER steps (the scan runs backwards
+// in time).
 
 template <int OFF>
 __device__ __forceinline__ double lane_xor_d(double v) {
@@ -28,13 +27,13 @@ __device__ __forceinline__ double lane_xor_d(double v) {
 // lanes and `tot` the whole block; afterwards the same for blocks of 2 OFF lanes.  Both halves form `tot` from the same two operands
 // in the same order, so every lane of a block holds the same bits.
 template <int OFF>
-__device__ __forceinline__ void rscan_step(RetMap& scan, RetMap& tot) {
-    const RetMap o{lane_xor_d<OFF>(tot.a), lane_xor_d<OFF>(tot.b)};
+__device__ __forceinline__ void rscan_step(AffineD& scan, AffineD& tot) {
+    const AffineD o{lane_xor_d<OFF>(tot.a), lane_xor_d<OFF>(tot.b)};
     if (threadIdx.x & OFF) {
-        tot = affine_after(o, tot);
+        tot = compose(o, tot);
     } else {
-        scan = affine_after(scan, o);
-        tot = affine_after(tot, o);
+        scan = compose(scan, o);
+        tot = compose(tot, o);
     }
 }
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -70,18 +69,18 @@ __global__ __launch_bounds__(256) void reinforce_returns_kernel(const EngineDesc
     const int tid = threadIdx.x, seg = (n + kWG - 1) / kWG;
     const int t0 = min(tid * seg, n), t1 = min(t0 + seg, n);
 
-    RetMap f{1.0, 0.0};
+    AffineD f{1.0, 0.0};
     for (int t = t1 - 1; t >= t0; --t) {
         const float* rec = ring + (size_t)t * R.stride;
         const double a = gamma * (1.0 - (double)rec[R.done_off]);
-        f = RetMap{a * f.a, (double)rec[R.rew_off] + a * f.b};
+        f = AffineD{a * f.a, (double)rec[R.rew_off] + a * f.b};
     }
-    RetMap scan = f, tot = f;
+    AffineD scan = f, tot = f;
     rscan_step<1>(scan, tot); rscan_step<2>(scan, tot); rscan_step<4>(scan, tot);
     rscan_step<8>(scan, tot); rscan_step<16>(scan, tot); rscan_step<32>(scan, tot);
     if ((tid & 63) == 0) { wave_a[tid >> 6] = tot.a; wave_b[tid >> 6] = tot.b; }
     __syncthreads();
-    for (int wv = (tid >> 6) + 1; wv < kWG / 64; ++wv) scan = affine_after(scan, RetMap{wave_a[wv], wave_b[wv]});
+    for (int wv = (tid >> 6) + 1; wv < kWG / 64; ++wv) scan = compose(scan, AffineD{wave_a[wv], wave_b[wv]});
     g_in[tid] = scan.b;                            // the return at the lane's first step: nothing follows the last step (G = 0)
     if (tid == 0) g_in[kWG] = 0.0;
     __syncthreads();
@@ -107,15 +106,6 @@ __global__ __launch_bounds__(256) void reinforce_returns_kernel(const EngineDesc
 }
 
 // --------------------------------------------------------------------------------------- grad
-// X[r][c] = ring row (first + r), column src0 + c, for r < nvalid; 0 for the rows past them
-__device__ __forceinline__ void load_rows(lds_f X, int ldx, int rc, int nvalid, g_cf rows, int stride, int src0, int ncols) {
-    const int total = rc * ncols;
-    for (int e = threadIdx.x; e < total; e += kWG) {
-        const int r = e / ncols, c = e - r * ncols;
-        X[r * ldx + c] = r < nvalid ? rows[(size_t)r * stride + src0 + c] : 0.f;
-    }
-}
-
 // loss = sum_t -log pi(a_t | s_t) g_t (:119-121, a sum) on the row-chunk skeleton: a workgroup's chunks are consecutive ring rows.
 // Categorical(probs = softmax(z)) (:82-85) renormalises the probabilities and takes log(clamp(q, eps, 1 - eps)), so the head delta
 // is g_t (q - onehot(a_t)), and zero for a row whose q[a_t] lies outside [eps, 1 - eps] (the clamp passes no gradient there).
@@ -137,32 +127,26 @@ __global__ __launch_bounds__(256, FRL_GRAD_WGS) void reinforce_grad_kernel(const
     g_cf ring = U.ring();
     g_cf gw = as_global(D.isw + (size_t)p * D.batch_max);
     const int O = R.obs_dim[0], A = D.n_discrete, npad = N.L[nl - 1].n_pad, k0pad = N.L[0].k_pad;
-    constexpr float kEps = 1.1920929e-07f;         // torch.finfo(float32).eps
 
     float lossp = 0.f;
     for (int ck = W.cr.c0; ck < W.cr.c1; ++ck) {
     const UnitChunk c = W.chunk(ck);
     const int gs = c.gs, r0 = c.r0, nv = c.nv;
     g_cf rows = ring + (size_t)r0 * R.stride;      // a workgroup's chunks are consecutive ring rows: no idx
-    load_rows(S.xin, S.xp, rc, nv, rows, R.stride, R.obs_off[0], O);
-    zero_cols(S.xin, S.xp, rc, O, k0pad);
+    load_rows(S.xin, S.xp, rc, nv, rows, 0, R.stride, R.obs_off[0], O, k0pad);
     lds_barrier();
     mlp_fwd_rows(N, 0, nl, theta, S, ACT_NONE, [&](int r) {
         lds_f o = S.outb + r * S.op;
         const int act = (r < nv) ? (int)rows[(size_t)r * R.stride + R.act_off[0]] : -1;
         if (act >= 0 && act < A) {
-            // F.softmax (max-subtracted, divided by the sum), then Categorical's probs / probs.sum(-1)
-            float mx = o[0];
-            for (int j = 1; j < A; ++j) mx = fmaxf(mx, o[j]);
-            float sum = 0.f;
-            for (int j = 0; j < A; ++j) { const float ex = expf(o[j] - mx); o[j] = ex; sum += ex; }
-            float psum = 0.f;
-            for (int j = 0; j < A; ++j) { const float pj = o[j] / sum; o[j] = pj; psum += pj; }
+            // F.softmax (max-subtracted, divided by the sum), then Categorical's probs / probs.sum(-1): onpolicy.hpp's CatRow
+            CatRow q = cat_softmax(o, A);
+            for (int j = 0; j < A; ++j) { o[j] = q.prob(o[j]); q.psum += o[j]; }
             const float g = gw[r0 + r];
-            const float qa = o[act] / psum;
-            const bool open = qa >= kEps && qa <= 1.f - kEps;
-            lossp -= (float)log((double)fminf(fmaxf(qa, kEps), 1.f - kEps)) * g;      // correctly rounded, as select_action records it
-            for (int c = 0; c < npad; ++c) o[c] = (open && c < A) ? g * (o[c] / psum - (c == act ? 1.f : 0.f)) : 0.f;
+            const float qa = o[act] / q.psum;
+            const bool open = qa >= kProbEps && qa <= 1.f - kProbEps;
+            lossp -= (float)log((double)q.clamped(o[act])) * g;      // correctly rounded, as select_action records it
+            for (int c = 0; c < npad; ++c) o[c] = (open && c < A) ? g * (o[c] / q.psum - (c == act ? 1.f : 0.f)) : 0.f;
         } else {
             for (int c = 0; c < npad; ++c) o[c] = 0.f;
         }

@@ -22,7 +22,7 @@ md = s[s.index("amdhsa.kernels:"):]
 BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8), ("solo_", 0), ("solow_", 0), ("dqn_fused_", 0), ("c51_grad_", 0), ("ac_critic_kernel", 0),
           ("ac_critic_wide_", 60), ("ac_actor_wide_", 16), ("ac_critic_x_", 700), ("ac_actor_x_", 460), ("ppo_update_v2_", 0),
           ("sacd_critic_", 9), ("sacd_actor_", 0),
-          # kernels_reinforce.hip: reinforce_returns_kernel 48 VGPRs, reinforce_grad_kernel 254 VGPRs; no spilled VGPR in either (the grad
+          # kernels_reinforce.hip: reinforce_returns_kernel 48 VGPRs, reinforce_grad_kernel 248 VGPRs; no spilled VGPR in either (the grad
           # kernel keeps 56 bytes of its row lambda's captures in scratch: stored at entry, three loads per row chunk, none in an MFMA loop)
           ("reinforce_returns_", 0), ("reinforce_grad_", 0),
           # kernels_envelope.hip: envelope_weights_kernel 38 VGPRs, none spilled; envelope_grad_kernel 256 VGPRs with 8 spilled and 88 bytes of
@@ -35,25 +35,25 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # (the per-row partial sums, the layers' offsets, the Lds carve, the row counts) are stored at entry (55 of the 62 scratch stores) and
           # reloaded at the start of a barrier phase or between two tile blocks of a dW phase (tools/asm_spills.py), none inside an MFMA k-loop;
           # gail_forward_kernel 188 VGPRs, gail_draw_kernel 28, gail_stats_kernel 19, none spilled
-          # kernels_gail_ppo.hip (the unit compiled on its own, profiles/gail_ppo/README.md): gail_ppo_update_kernel 296 VGPRs + 48 AGPRs (one
+          # kernels_gail_ppo.hip (the unit compiled on its own, profiles/gail_ppo/README.md): gail_ppo_update_kernel 300 VGPRs + 48 AGPRs (one
           # persistent workgroup per net, one wave per SIMD), gail_ppo_prepare_kernel 192 + 40, gail_ppo_act_kernel 188 + 40, gail_ppo_gae_kernel 16;
           # no spilled VGPR in any, 56 bytes of scratch in the three forward kernels (a lambda's captures, as in reinforce_grad_kernel)
           ("gail_ppo_", 0),
           ("gail_disc_", 70), ("gail_forward_", 0), ("gail_draw_", 0), ("gail_stats_", 0),
-          # kernels_mappo.hip: mappo_update_kernel 366 VGPRs + 110 AGPRs (one persistent workgroup per CU: one wave per SIMD, 512 registers),
-          # mappo_values_kernel 224 + 40, mappo_act_kernel 188 + 40, mappo_adv_kernel 19; no spilled VGPR in any, 56 bytes of scratch in the three
+          # kernels_mappo.hip: mappo_update_kernel 375 VGPRs + 119 AGPRs (one persistent workgroup per CU: one wave per SIMD, 512 registers),
+          # mappo_values_kernel 224 + 40, mappo_act_kernel 188 + 40, mappo_adv_kernel 17; no spilled VGPR in any, 56 bytes of scratch in the three
           # forward kernels (a lambda's captures, as in reinforce_grad_kernel: none in an MFMA loop)
           ("mappo_update_", 0), ("mappo_values_", 0), ("mappo_act_", 0), ("mappo_adv_", 0),
           # kernels_happo.hip: happo_update_kernel = mappo_update_kernel's steps (device/mappo.hpp: mappo_steps) between two forward-only
-          # horizon passes, one persistent workgroup per CU as well: 353 VGPRs + 97 AGPRs, no spilled VGPR, 56 bytes of scratch (with the step
-          # loop shared, mappo_update_kernel keeps its 366 + 110 and holds 72 bytes of scratch, the lambda's captures again)
+          # horizon passes, one persistent workgroup per CU as well: 355 VGPRs + 99 AGPRs, no spilled VGPR, 56 bytes of scratch (with the step
+          # loop shared, mappo_update_kernel keeps its 375 + 119 and holds 72 bytes of scratch, the lambda's captures again)
           ("happo_", 0),
-          # kernels_mappo_mask.hip: mappo_mask_update_kernel = mappo_steps with the masked categorical row in its discrete branch, 365 VGPRs +
-          # 109 AGPRs and 72 bytes of scratch; mappo_mask_act_kernel = mappo_act_kernel's forward with the masked draw behind it, 188 + 40 and
+          # kernels_mappo_mask.hip: mappo_mask_update_kernel = mappo_steps with the masked categorical row in its discrete branch, 369 VGPRs +
+          # 113 AGPRs and 72 bytes of scratch; mappo_mask_act_kernel = mappo_act_kernel's forward with the masked draw behind it, 188 + 40 and
           # 56 bytes; no spilled VGPR in either (mappo_update_kernel and happo_update_kernel keep their figures)
           ("mappo_mask_", 0),
           # kernels_mappo_state.hip: mappo_steps with the critic's row filled from two segments (kState): mappo_state_update_kernel and
-          # mappo_state_mask_update_kernel 366 VGPRs + 110 AGPRs and 72 bytes of scratch, mappo_state_values_kernel = mappo_values_kernel's
+          # mappo_state_mask_update_kernel 370 VGPRs + 114 AGPRs and 72 bytes of scratch, mappo_state_values_kernel = mappo_values_kernel's
           # 224 + 40 and 56 bytes; no spilled VGPR in any of the three (the other kernels of the family keep their figures)
           ("mappo_state_", 0),
           # kernels_att.hip (figures of the unit compiled on its own, profiles/att/README.md): the attention critic's forward and backward are
