@@ -224,22 +224,7 @@ struct ChainNetT {
     template <int T, bool VH>
     __device__ __forceinline__ void forward(const f32x4 (&xb)[T], f32x4 (&h1)[T][kHT], f32x4 (&h2)[T][kHT], f32x4 (&z)[T], int hn = 0) const {
         const LaneK K = lanes();
-        // first layer: all eight fragments and biases in flight before the first MFMA.  (All four k-steps are needed whatever the
-        // input width: k-step e of the fragment layout holds columns e, 4 + e, 8 + e, 12 + e, so the zero padding is spread
-        // over every step — a build that skipped "unused" steps dropped real columns and failed parity by 1 %.)
-        {
-            f32x4 w1f[kHT], b1f[kHT];
-#pragma unroll
-            for (int ot = 0; ot < kHT; ++ot) { w1f[ot] = ld4((lds_cf)(S.w1 + ot * 256 + K.fslot)); b1f[ot] = ld4((lds_cf)(S.b1 + ot * 16 + 4 * K.q)); }
-#pragma unroll
-            for (int ot = 0; ot < kHT; ++ot)
-#pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    const f32x4 acc = mfma4(b1f[ot], w1f[ot], xb[t]);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) h1[t][ot][r] = fmaxf(acc[r], 0.f);
-                }
-        }
+        first_layer<T>(K, xb, h1);
 #pragma unroll
         for (int ot = 0; ot < kHT; ++ot) {
             const f32x4 bb = ld4((lds_cf)(S.b2 + ot * 16 + 4 * K.q));
@@ -281,6 +266,24 @@ struct ChainNetT {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) h2[t][ot][r] = fmaxf(h2[t][ot][r], 0.f);
         if constexpr (VH) head_valu<T>(h2, z, hn); else head_mfma<T>(h2, z);
+    }
+    // first layer of forward(): all eight fragments and biases in flight before the first MFMA.  (All four k-steps are needed whatever
+    // the input width: k-step e of the fragment layout holds columns e, 4 + e, 8 + e, 12 + e, so the zero padding is spread
+    // over every step — a build that skipped "unused" steps dropped real columns and failed parity by 1 %.)
+    // Also called on its own (kernels_actor2.hip, pass C: h2 comes back from the park buffer, h1 is cheaper to form again than to park)
+    template <int T>
+    __device__ __forceinline__ void first_layer(const LaneK& K, const f32x4 (&xb)[T], f32x4 (&h1)[T][kHT]) const {
+        f32x4 w1f[kHT], b1f[kHT];
+#pragma unroll
+        for (int ot = 0; ot < kHT; ++ot) { w1f[ot] = ld4((lds_cf)(S.w1 + ot * 256 + K.fslot)); b1f[ot] = ld4((lds_cf)(S.b1 + ot * 16 + 4 * K.q)); }
+#pragma unroll
+        for (int ot = 0; ot < kHT; ++ot)
+#pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const f32x4 acc = mfma4(b1f[ot], w1f[ot], xb[t]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) h1[t][ot][r] = fmaxf(acc[r], 0.f);
+            }
     }
     // head layer as MFMA tiles: z[t][r] = output 4q + r of this lane's row (16 outputs)
     template <int T>

@@ -15,6 +15,7 @@
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
 #include "rowchunk_layout.h"
+#include "actor_park_layout.h"
 
 namespace frl {
 
@@ -98,6 +99,7 @@ struct PlanKnobs {
     int solow = -1;               // FRL_SOLOW (tri-state)
     bool solow_helpers = true;    // FRL_SOLOW_HELPERS=0: no helper workgroups
     int chain_waves = 8;          // FRL_CHAIN_WAVES: waves per workgroup of the register-chained actor-critic kernels (4: round 5's)
+    bool actor_park = true;       // FRL_ACTOR_PARK=0: the eight-wave chained actor stage recomputes its forward in pass C instead of parking pass A's activations
 };
 inline bool knob_flag(int tri, bool dflt) { return tri < 0 ? dflt : tri != 0; }
 
@@ -115,6 +117,8 @@ struct EngineFacts {
     int solow_wgs = 0;            // ... workgroups per unit in its grids (row-tile workgroups + helpers for the update)
     size_t act_wk_slot = 0;       // floats per slot of select_action's Wk-layout copies = P * largest net
     int chain_waves = 8;          // waves per workgroup of the register-chained actor-critic kernels
+    bool actor_park = true;       // the eight-wave chained actor stage reads pass A's activations back from EngineDesc::actor_park (false: it recomputes them)
+    size_t actor_park_count = 0;  // floats of EngineDesc::actor_park (actor_park_layout.h); 0 on every engine outside the chained family
     int n_cus = 256;              // compute units of the device the plan was made for (FRL_ASSUME_CUS applied)
     int lds_per_cu = 160 * 1024;  // LDS bytes of one compute unit
 };
@@ -638,6 +642,7 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     const int H = h.hidden;
     pl.family = choose_engine_family(pl, knobs);
     pl.chain_waves = knobs.chain_waves == 4 ? 4 : 8;
+    pl.actor_park = knobs.actor_park;
     h.act_max = 1;
     for (int j = 0; j < c.n_agents; ++j) h.act_max = std::max(h.act_max, R.act_dim[j]);
     // one hidden-activation buffer is enough when every head is input -> hidden -> output (DQN's Q-net): 17 KB less per 32-row
@@ -752,6 +757,8 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     pl.slab_count = slab_floats(h);
     pl.part_count = part_floats(h);
     pl.act_spill_count = T.act_spill ? act_spill_floats(h) : 0;
+    // the chained family's actor stage (chained_shape admits DDPG / TD3 / SAC only: each has one); allocated whatever FRL_ACTOR_PARK says
+    pl.actor_park_count = pl.family == FAM_CHAINED ? actor_park_floats(h.P) : 0;
     pl.idx_count = P * h.n_agents * h.batch_max;
     if (h.noisy) {
         const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];

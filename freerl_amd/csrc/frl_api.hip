@@ -276,7 +276,7 @@ extern "C" int frl_destroy(frl_engine* e) {
     return FRL_OK;
 }
 
-static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, const EngineDesc& h);
+static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, bool actor_park, const EngineDesc& h);
 static hipError_t set_family_lds_attributes(LearnFamily fam);
 
 extern "C" int frl_create(const frl_config* cfg, frl_engine** out) { return frl_create_ex(cfg, nullptr, out); }
@@ -295,6 +295,7 @@ static PlanKnobs create_knobs() {
     k.solow = tri("FRL_SOLOW");
     k.solow_helpers = env_flag("FRL_SOLOW_HELPERS", k.solow_helpers);
     k.chain_waves = env_int("FRL_CHAIN_WAVES", k.chain_waves);
+    k.actor_park = env_flag("FRL_ACTOR_PARK", k.actor_park);
     return k;
 }
 
@@ -397,6 +398,7 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
             *e->h_solo_err = 0;
             CREATE_TRY(hipHostGetDevicePointer((void**)&e->d_solo_err, e->h_solo_err, 0));
         }
+        if (e->actor_park_count) CREATE_TRY(e->mem.alloc_zero(&h.actor_park, e->actor_park_count, e->stream));
         if (h.wide) CREATE_TRY(e->mem.alloc_zero(&h.wide_scr, P * (size_t)h.n_agents * h.wide_unit, e->stream));
         if (h.wide || h.solow) {                                           // select_action's Wk-layout copies of the nets (launch_act)
             e->act_wk_version.assign(2 * (size_t)h.n_nets, 0ULL);
@@ -419,7 +421,7 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
     e->size.assign(P, 0);
     e->staged_per_learner.assign(P, 0);
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
-    if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, e->chain_waves, h);
+    if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, e->chain_waves, e->actor_park, h);
     // (a vector reward: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
     if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || T.vector_reward))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
         CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));

@@ -2,10 +2,11 @@
 // learns with is engine_plan.hpp's decision), a launcher per family, learn_impl and the work models.  Part of frl_api.hip.
 
 // --------------------------------------------------------------------------- the family table
-enum LearnKernelStage { LK_CRITIC, LK_CRITIC_NV, LK_ACTOR, LK_STEP };
+enum LearnKernelStage { LK_CRITIC, LK_CRITIC_NV, LK_ACTOR, LK_ACTOR_RECOMPUTE, LK_STEP };
 struct LearnKernelRow {
     LearnFamily fam;
-    int stage;          // LK_CRITIC_NV: the 8-wave chained critic with aligned next_obs / (reward, done) loads; LK_STEP: a whole policy step
+    int stage;          // LK_CRITIC_NV: the 8-wave chained critic with aligned next_obs / (reward, done) loads; LK_STEP: a whole policy step;
+                        // LK_ACTOR_RECOMPUTE: the 8-wave chained actor stage without the park buffer (FRL_ACTOR_PARK=0)
     int sub;            // FAM_CHAINED: waves per workgroup; FAM_SOLO: workgroups per learner; FAM_SOLOW: 1 single-agent, 2 (learner, agent) units
     int lds_bytes;      // dynamic LDS of the launch = the kernels' hipFuncAttributeMaxDynamicSharedMemorySize (engine_plan.hpp: family_lds_bytes)
     KernelPtr k[2][2];  // [critic heads - 1][16-column tiles of the actor head - 1]
@@ -16,6 +17,7 @@ static const LearnKernelRow kLearnKernels[] = {
     {FAM_CHAINED, LK_CRITIC, 8, kLdsChain8, {{ac_critic_v2_single_kernel, ac_critic_v2_single_kernel}, {ac_critic_v2_twin_kernel, ac_critic_v2_twin_kernel}}},
     {FAM_CHAINED, LK_CRITIC_NV, 8, kLdsChain8, {{ac_critic_v2_single_nv_kernel, ac_critic_v2_single_nv_kernel}, {ac_critic_v2_twin_nv_kernel, ac_critic_v2_twin_nv_kernel}}},
     {FAM_CHAINED, LK_ACTOR, 8, kLdsChain8, {{ac_actor_v2_kernel, ac_actor_v2_kernel}, {ac_actor_v2_kernel, ac_actor_v2_kernel}}},
+    {FAM_CHAINED, LK_ACTOR_RECOMPUTE, 8, kLdsChain8, {{ac_actor_v2_recompute_kernel, ac_actor_v2_recompute_kernel}, {ac_actor_v2_recompute_kernel, ac_actor_v2_recompute_kernel}}},
     {FAM_CHAINED, LK_CRITIC, 4, kLdsChain4, {{ac_critic_v2w4_single_kernel, ac_critic_v2w4_single_kernel}, {ac_critic_v2w4_twin_kernel, ac_critic_v2w4_twin_kernel}}},
     {FAM_CHAINED, LK_ACTOR, 4, kLdsChain4, {{ac_actor_v2w4_kernel, ac_actor_v2w4_kernel}, {ac_actor_v2w4_kernel, ac_actor_v2w4_kernel}}},
     {FAM_SOLO, LK_CRITIC, 16, kLdsSolo, {{solo_critic_single_kernel, solo_critic_single_kernel}, {solo_critic_twin_kernel, solo_critic_twin_kernel}}},
@@ -50,16 +52,20 @@ static hipError_t set_family_lds_attributes(LearnFamily fam) {
 }
 
 // the kernels `fam` runs on this engine: the twin / head-tile / waves / workgroups / multi-agent selections, made once at frl_create
-static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, const EngineDesc& h) {
+// actor_park: the engine's FRL_ACTOR_PARK (EngineFacts); false picks the family's LK_ACTOR_RECOMPUTE kernel where it has one (eight waves)
+static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, bool actor_park, const EngineDesc& h) {
     const int twin = h.net[1].heads == 2, a2 = h.net[0].L[2].n_pad > 16;
     const int sub = fam == FAM_CHAINED ? chain_waves : fam == FAM_SOLO ? h.solo : fam == FAM_SOLOW ? (h.n_agents > 1 ? 2 : 1) : 0;
     LearnKernels K;
+    KernelPtr recompute;
     K.block = (fam == FAM_CHAINED && sub == 8) ? 512 : 256;
     for (const LearnKernelRow& r : kLearnKernels) {
         if (r.fam != fam || r.sub != sub) continue;
-        (r.stage == LK_CRITIC ? K.critic : r.stage == LK_CRITIC_NV ? K.critic_nv : r.stage == LK_ACTOR ? K.actor : K.step) = r.k[twin][a2];
         K.lds_bytes = r.lds_bytes;
+        if (r.stage == LK_ACTOR_RECOMPUTE) { recompute = r.k[twin][a2]; continue; }
+        (r.stage == LK_CRITIC ? K.critic : r.stage == LK_CRITIC_NV ? K.critic_nv : r.stage == LK_ACTOR ? K.actor : K.step) = r.k[twin][a2];
     }
+    if (!actor_park && recompute.k) K.actor = recompute;
     return K;
 }
 
@@ -85,6 +91,12 @@ extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, 
     if (chained_out) *chained_out = path.chained;
     if (bytes_out) *bytes_out = path.bytes;
     if (rows_out) *rows_out = path.rows;
+    return FRL_OK;
+}
+
+extern "C" int frl_actor_park(const frl_engine* e, int* parked_out) {
+    if (!e || !parked_out) return fail(FRL_ERR_INVALID, "engine / parked_out is NULL");
+    *parked_out = e->family == FAM_CHAINED && e->kern.actor.k == (LearnKernel)ac_actor_v2_kernel;
     return FRL_OK;
 }
 

@@ -237,6 +237,10 @@ struct EngineDesc {
     // GAIL's policy side (kernels_gail_ppo.hip, ALGO_GAIL_PPO): the clamp range of the actor's log_std (GAIL_file/PPO2.py:38), engine state
     // set by frl_log_std_range_set.  No other algorithm's kernel reads it: theirs is device/policy.hpp's [-20, 2]
     float log_std_min, log_std_max;
+    // The eight-wave chained actor stage (kernels_actor2.hip): pass A's second hidden layer h2 of every batch row, parked for pass C
+    // — [P][2 chunks][8 tiles][8 waves][64 lanes] f32x4 (actor_park_layout.h), 128 KiB per learner; a lane reads back only what it wrote
+    // in the same launch.  Engines of the chained family (DDPG / TD3 / SAC) only; null everywhere else
+    float* actor_park;
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

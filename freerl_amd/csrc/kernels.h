@@ -331,6 +331,7 @@ __global__ void ac_actor_x_a2_kernel(const EngineDesc* __restrict__ Dp, LearnArg
 
 // kernels_actor2.hip: the actor stage of DDPG / TD3 likewise
 __global__ void ac_actor_v2_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);
+__global__ void ac_actor_v2_recompute_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);      // (FRL_ACTOR_PARK=0)
 __global__ void ac_actor_v2w4_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);
 
 // ---- kernels_solo.hip: a single learner's DDPG / TD3 / SAC update on kSoloWG workgroups (device/solo.hpp)

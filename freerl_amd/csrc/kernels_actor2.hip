@@ -5,26 +5,39 @@
 // launch, no gradient slabs.
 //
 // Three passes over the learner's batch, the net a pass needs staged once into the LDS images:
-//   A  actor forward (two row tiles per wave)                       -> a[row] in LDS
+//   A  actor forward (TA row tiles per wave: one at eight waves)    -> a[row] in LDS
 //   B  critic forward on [s | a] + the dX-only backward chain       -> dQ/da[row] in LDS, sum of Q for the loss
 //      (SAC: once per twin head, each staged in turn, the two dQ/da added)
-//   C  actor forward AGAIN (its activations are registers of pass A, long gone) + backward with the weight-gradient exchanges
-// Recomputing the forward costs 320 of the pass's 928 MFMAs per wave and chunk; keeping both nets' images resident instead
-// would leave no LDS for the exchange buffers.  Shape: as kernels_critic2.hip.  The update (adam_head) leaves the padded slots
-// of the first-layer tiles (input columns past obs_dim) and of the head tiles (outputs past act_dim) out of its stream.
+//   C  actor backward with the weight-gradient exchanges, on pass A's activations
+// Pass A's h1 / h2 are registers that are long gone by pass C, and keeping both nets' images resident would leave no LDS for the
+// exchange buffers.  The eight-wave kernel PARKS h2: passes A and C map rows to lanes alike (TA = 1) and call the same forward, so
+// every lane stores its eight f32x4 of a chunk's h2 to its own slots of EngineDesc::actor_park in pass A (actor_park_layout.h: 1 KB
+// per wave instruction, default cache policy — the lines stay in L2 / the Infinity Cache) and loads them back for pass C: chunk 0
+// next to the actor image's fetch behind pass B, a later chunk inside the previous chunk's backward, behind its dH1 chain, where h2
+// has just died.  A lane reads only what it wrote itself in this launch: program order is all the ordering there is to keep.  h1 is
+// the 32-MFMA first layer again (first_layer), the head's tanh comes from pass A (a[row], already in registers).  HBM idles during
+// the MFMA passes; the loads replace 256 of the 288 MFMAs of a second forward per wave and chunk (pass C: 928 -> 672).  Parking h1
+// as well was measured: 128 MiB per launch at 512 learners wash the other launches' parameters out of the Infinity Cache, the
+// critic launch pays more than the 32 MFMAs cost (profiles/park/).  PARK = false (ac_actor_v2_recompute_kernel, FRL_ACTOR_PARK=0; the four-wave kernel, whose pass
+// A maps two tiles per wave) runs the forward AGAIN in pass C instead: bit for bit the same update.
+// Shape: as kernels_critic2.hip.  The update (adam_head) leaves the padded slots of the first-layer tiles (input columns past
+// obs_dim) and of the head tiles (outputs past act_dim) out of its stream.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "actor_park_layout.h"
 #include "device/chain_net.hpp"
 #include "device/ppo_timing.hpp"
 
 namespace frl {
 
 // NW = waves per workgroup (device/chain_net.hpp; 8 since round 6, 4 = round 2-5's kernel for A/B runs), TA = 16-row tiles per wave
-// in passes A and B (nothing is accumulated there)
-template <int NW, int TA>
+// in passes A and B (nothing is accumulated there), PARK = pass C reads pass A's h2 back from EngineDesc::actor_park
+template <int NW, int TA, bool PARK>
 __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const LearnArgs& a, float* smem) {
     constexpr int kRC = 16 * NW, kRowsT = kRC * TA;                    // rows per chunk of pass C / of passes A and B
+    static_assert(!PARK || (NW == kParkWaves && TA == 1 && kRC == kParkChunkRows && kChainBatch == kParkRows && kHT == kParkTiles),
+                  "parking needs pass A's rows on pass C's lanes, in the layout of actor_park_layout.h");
     constexpr int kNC = kChainBatch / kRC, kNCT = kChainBatch / kRowsT;
     static_assert(kNCT >= 1, "a chunk of passes A / B is at most the whole batch");
     const int p = a.p0 + blockIdx.x;
@@ -54,6 +67,9 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
     const float dqv = sac ? -0.5f * invB : -invB;
     const int nchunks = (B + kRC - 1) / kRC, nch2 = (B + kRowsT - 1) / kRowsT;
     lds_f dab = S.eb;                                                  // dQ/da[row][4] at the start of eb: pass B has no exchanges
+    // this lane's slot of tile 0 of chunk 0 (PARK): wave base uniform, the lane and the (chunk, tile) steps 32-bit
+    FRL_GLB f32x4* const pkw = (FRL_GLB f32x4*)D.actor_park + actor_park_slot(p, 0, 0, w, 0);
+    auto park_at = [&](int c, int tile) { return pkw + (unsigned)(l + (c * kParkTiles + tile) * kParkTileStride); };
 
     // observation columns of this lane's rows: pass A / B in the TA-tile mapping (kRowsT c2 + 16 TA w + 16 t + i16), pass C in the
     // one-tile mapping (kRC c + 16 w + i16); ring addresses once, fields one chunk ahead of their use
@@ -109,6 +125,10 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
         if (c2 + 1 == nch2) pend = C.stage_fetch(thC, 0);
         f32x4 z[TA], h1[TA][kHT], h2[TA][kHT];
         C.template forward_vh<TA>(cur.x, h1, h2, z, A);
+        if constexpr (PARK) {                                          // every row, the ones past the batch too (x = 0: relu(bias), finite)
+#pragma unroll
+            for (int ft = 0; ft < kHT; ++ft) *park_at(c2, ft) = h2[0][ft];
+        }
 #pragma unroll
         for (int t = 0; t < TA; ++t) {
             const int row = c2 * kRowsT + 16 * TA * w + 16 * t + i16;
@@ -174,7 +194,14 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
         pend = hd + 1 < nq ? C.stage_fetch(thC, hd + 1) : C.stage_fetch((g_cf)thA, 0, NA.extra_n);
         PPO_T(2);
     }
-    // =========================================================== C: actor forward again, delta through tanh, backward into the accumulators
+    // =========================================================== C: [actor forward again,] delta through tanh, backward into the accumulators
+    // PARK: h2 of the chunk the loop works on next (ph1: its first layer, formed at the top of the chunk); every load unconditional (kernels_critic2.hip: a conditional one in these loops)
+    f32x4 ph1[1][kHT], ph2[kHT];
+    auto park_load = [&](int c) {
+#pragma unroll
+        for (int ft = 0; ft < kHT; ++ft) ph2[ft] = *park_at(c, ft);
+    };
+    if constexpr (PARK) park_load(0);                                  // (next to the actor image's fetch, which waits in the open anyway)
     typename Net::Grad g;
     PPO_T(2);
     C.grad_zero(g);
@@ -201,7 +228,10 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
         f32x4 xb[1] = {nxt}, z[1], h1[1][kHT], h2[1][kHT];
         nxt = load_obs(c + 1 < nchunks ? c + 1 : 0);
         PPO_T(5);
-        C.template forward_vh<1>(xb, h1, h2, z, A);
+        if constexpr (PARK) C.template first_layer<1>(C.lanes(), xb, ph1); else C.template forward_vh<1>(xb, h1, h2, z, A);
+#ifdef FRL_PPO_TIMING
+        if constexpr (PARK) __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): the stamp below is what the park loads still cost here
+#endif
         PPO_T(3);
         const f32x4 dq = pick(dqa, c);
         f32x4 dz = {0.f, 0.f, 0.f, 0.f};
@@ -219,13 +249,25 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
                         gls[r] += sac_log_std_grad(d, S.ls[r], ep[r], alpha, invB);
                     }
                 }
+            } else if constexpr (PARK) {                               // a[row] of pass A IS tanhf(z) of this row
+                const f32x4 av4 = pick(ava, c);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (r < A) dz[r] = tanh_delta(dq[r], av4[r]);
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (r < A) dz[r] = tanh_delta(dq[r], tanhf(z[0][r]));
             }
         }
-        C.backward(g, xb[0], h1[0], h2[0], dz, A);
+        if constexpr (PARK) {
+            // the late hook overwrites ph2 IN PLACE with the next chunk's (after the last chunk: chunk 0 again, unused): backward8
+            // does not read h2 behind the hook
+            const int cn = c + 1 < nchunks ? c + 1 : 0;
+            C.backward(g, xb[0], ph1[0], ph2, dz, A, [&] { park_load(cn); });
+        } else {
+            C.backward(g, xb[0], h1[0], h2[0], dz, A);
+        }
         PPO_T(4);
     }
     C.grad_finish(g);
@@ -292,11 +334,15 @@ __device__ __forceinline__ void ac_actor_v2_body(const EngineDesc& D, const Lear
 #endif
 __global__ __launch_bounds__(512) void ac_actor_v2_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    ac_actor_v2_body<8, FRL_ACTOR8_TA>(*Dp, a, smem);
+    ac_actor_v2_body<8, FRL_ACTOR8_TA, FRL_ACTOR8_TA == 1>(*Dp, a, smem);
+}
+__global__ __launch_bounds__(512) void ac_actor_v2_recompute_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    ac_actor_v2_body<8, FRL_ACTOR8_TA, false>(*Dp, a, smem);
 }
 __global__ __launch_bounds__(256) void ac_actor_v2w4_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    ac_actor_v2_body<4, 2>(*Dp, a, smem);
+    ac_actor_v2_body<4, 2, false>(*Dp, a, smem);
 }
 
 }  // namespace frl

@@ -105,6 +105,12 @@ class Engine:
         N.check(self._L.frl_learn_path(self._h, int(batch), C.byref(c), C.byref(b), C.byref(r)))
         return bool(c.value), b.value, r.value
 
+    def actor_park(self):
+        """Does the actor stage this engine launches read pass A's h2 back from the park buffer (frl_actor_park)?"""
+        v = C.c_int(0)
+        N.check(self._L.frl_actor_park(self._h, C.byref(v)))
+        return bool(v.value)
+
     # ------------------------------------------------------------------ replay
     def add(self, learner, record):
         rec = np.ascontiguousarray(record, dtype=F32)

@@ -267,6 +267,10 @@ int frl_lds_bytes(const frl_engine* e, int* bytes_out, int* row_chunk_out);
  * chained = 1: the sixteen-workgroups-per-learner families of small populations (kernels_solo.hip; kernels_solow.hip for wide first
  * layers and MADDPG: 160512 bytes of LDS). */
 int frl_learn_path(const frl_engine* e, int batch, int* chained_out, int* lds_bytes_out, int* rows_per_workgroup_out);
+/* 1: the actor stage this engine launches reads pass A's h2 back from its park buffer (the eight-wave chained kernel, unless the engine
+ * was created under FRL_ACTOR_PARK=0); 0: every other actor kernel, the recompute form of that one included.  Read off the kernel
+ * that frl_create resolved, not off the knob. */
+int frl_actor_park(const frl_engine* e, int* parked_out);
 
 /* ---------------------------------------------------------------- replay ring (Buffer.py)
  * Replaces class Buffer (TD3_file/Buffer.py:11-61 = DQN_file/Buffer.py:12-62) and

@@ -1,6 +1,7 @@
 """Developer instrument: shader-clock cycles per section of ac_actor_v2_kernel (kernels_actor2.hip), learner 0.
     python tools/actor2_timing.py [P]       (builds the `ppot` variant: -DFRL_PPO_TIMING, unity)
-The critic kernel of the same learn() call stamps the same clock array first; the actor stage runs last and its dump is what is read."""
+The critic kernel of the same learn() call stamps the same clock array first; the actor stage runs last and its dump is what is read.
+FRL_ACTOR_PARK=0 stamps the recompute kernel (pass C runs the actor's forward again) instead of the parked one."""
 import ctypes as C
 import os
 import sys
@@ -35,9 +36,9 @@ fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_longlong)]
 buf = (C.c_longlong * 16)()
 assert fn(buf) == 0
 clk = np.array(buf[:8], dtype=np.float64)
-names = ["weight staging (actor, critic head(s), actor again)", "pass A: actor forward (two tiles per wave)",
-         "pass B: critic forward + dX chain (two tiles per wave)", "pass C: actor forward again (4 chunks)",
-         "pass C: delta + exchanges + dW + dH (4 chunks)", "row prefetch issue + norm / reductions", "clip + Adam + soft update"]
+names = ["weight staging (actor, critic head(s), actor again)", "pass A: actor forward (+ the park stores)",
+         "pass B: critic forward + dX chain", "pass C: park loads + first layer (FRL_ACTOR_PARK=0: actor forward again)",
+         "pass C: delta + exchanges + dW + dH", "row prefetch issue + norm / reductions", "clip + Adam + soft update"]
 tot = clk[:7].sum()
 print("P=%d: %.0f cycles per learner (actor stage of %s)" % (P, tot, sys.argv[2] if len(sys.argv) > 2 else "td3"))
 for i, n in enumerate(names):
