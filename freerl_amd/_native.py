@@ -32,6 +32,7 @@ ALGO_HAPPO = 13
 ALGO_MADDPG_ATT = 14        # MADDPG_simple_with_tricks.py, trick['ATT']: a MADDPG engine whose critics are attention critics (frl_learn)
 ALGO_MASAC = 15             # MAAC_file/MASAC.py: MADDPG's records and net numbering, stacked [mean | log_std] actors, twin critics, one alpha per agent (frl_learn)
 ALGO_GAIL_PPO = 16          # GAIL_file/PPO2.py: GAIL's policy side — actor + critic with LeakyReLU / ReLU hidden layers (frl_gail_ppo_learn)
+ALGO_CEM_GD3PG = 18         # (17 is unassigned) CEM_GD3PG_file/CEM_GD3PG.py: two online actors, a frozen domain actor, one critic, two rings per learner (frl_cem_gd3pg_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL and GAIL_PPO engines only
@@ -131,6 +132,15 @@ class GailPpoArgs(C.Structure):         # frl_gail_ppo_args
                 ("last_value", C.POINTER(C.c_float)), ("rewards", C.POINTER(C.c_float)), ("perms", C.POINTER(C.c_int64)),
                 ("adv_out", C.POINTER(C.c_float)), ("returns_out", C.POINTER(C.c_float)), ("logp_old_out", C.POINTER(C.c_float)),
                 ("loss_trace_out", C.POINTER(C.c_float))]
+
+
+class CemGd3pgArgs(C.Structure):        # frl_cem_gd3pg_args
+    _fields_ = [("batch", C.c_int), ("gamma", C.c_float), ("tau", C.c_float), ("actor_lr", C.c_float), ("critic_lr", C.c_float),
+                ("lambda", C.c_float), ("f1_more", C.POINTER(C.c_int)), ("delta", C.POINTER(C.c_float)), ("idx", C.POINTER(C.c_int64)),
+                ("out", C.POINTER(C.c_float))]
+
+
+CEM_OUT = ("critic_loss", "critic_norm", "actor_1_loss", "actor_1_norm", "actor_2_loss", "actor_2_norm", "KL", "rows")      # frl_cem_gd3pg_args.out
 
 
 class MappoArgs(C.Structure):
@@ -242,6 +252,11 @@ SIGNATURES = {
     "frl_gail_ppo_learn": (_i, [_vp, _P(GailPpoArgs)]),
     "frl_log_std_range_set": (_i, [_vp, _f, _f]),
     "frl_log_std_range_get": (_i, [_vp, _fp, _fp]),
+    "frl_ring_add": (_i, [_vp, _i, _i, _fp]),
+    "frl_ring_add_batch": (_i, [_vp, _i, _i, _ip, _fp]),
+    "frl_ring_cursor_get": (_i, [_vp, _i, _i, _ip, _ip]),
+    "frl_ring_cursor_set": (_i, [_vp, _i, _i, _i, _i]),
+    "frl_cem_gd3pg_learn": (_i, [_vp, _P(CemGd3pgArgs)]),
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),

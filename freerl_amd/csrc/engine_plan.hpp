@@ -58,14 +58,17 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"ATT-MADDPG",     kFrlLearn,                 "",                                                                             false, false, false, false, false, true,  false},
     {"MASAC",          kFrlLearn,                 "FRL_ACT_SAC_SAMPLE / FRL_ACT_TANHHEAD on net 2i with agent i's observation",   false, false, false, false, false, true,  false},
     {"GAIL-PPO",       "frl_gail_ppo_learn",      "FRL_ACT_PPO_SAMPLE / FRL_ACT_TANHHEAD / FRL_ACT_CAT_SAMPLE on net 0, FRL_ACT_RAW on net 1: the value", false, false, false, false, false, false, false},
+    {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 17: refused as an unknown algo (check_create_args)
+    {"CEM-GD3PG",      "frl_cem_gd3pg_learn",     "FRL_ACT_TANHHEAD on net 0 / 1 / 3 (actor_1 / actor_2 / actor_domain), FRL_ACT_RAW on net 2 with [obs | act]", false, false, false, false, false, true,  false},
 };
+constexpr int kAlgoUnassigned = 17;      // a value no frl_algo has: its kAlgo row only keeps the table indexable by value
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 // (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
 //  policy noise and its own launch order — learn_impl and the launchers ask for it by name)
 inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_GAIL_PPO - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_CEM_GD3PG - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
@@ -121,6 +124,8 @@ struct EngineFacts {
     size_t actor_park_count = 0;  // floats of EngineDesc::actor_park (actor_park_layout.h); 0 on every engine outside the chained family
     int n_cus = 256;              // compute units of the device the plan was made for (FRL_ASSUME_CUS applied)
     int lds_per_cu = 160 * 1024;  // LDS bytes of one compute unit
+    int n_rings = 1;              // replay rings per learner (CEM_GD3PG: 2, `buffer` and `buffer_domain`), side by side in EngineDesc::replay
+    int ring_cap = 0;             // rows of one ring = frl_config.capacity; EngineDesc::capacity = n_rings * ring_cap rows per learner
 };
 // Everything the allocation step of frl_create needs: it makes no decisions of its own
 struct EnginePlan : EngineFacts {
@@ -415,7 +420,7 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
     if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_GAIL_PPO) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_CEM_GD3PG || c.algo == kAlgoUnassigned) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -487,6 +492,17 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
             if (c.discrete && c.act_dim[0] > kSacdMaxActions) return plan_refuse(message, "%s: %d actions > %d head columns", T.name, c.act_dim[0], kSacdMaxActions);
             if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0)
                 return plan_refuse(message, "%s: twin_critic, dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
+            return FRL_OK;
+        case FRL_ALGO_CEM_GD3PG:
+            // what kernels_cem_gd3pg.hip handles (CEM_GD3PG.py:30-92: tanh actors, a LeakyReLU critic with one Q head, continuous actions)
+            if (c.discrete)
+                return plan_refuse(message, "%s: discrete is refused (the reference builds a one-column action buffer that its critic cannot read, CEM_GD3PG.py:134)", T.name);
+            if (c.twin_critic) return plan_refuse(message, "%s: twin_critic is refused (one critic serves both actors; the minimum is over the two target actors)", T.name);
+            if (c.hidden_act != FRL_ACT_TANH)
+                return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_TANH, the actors' activation; the critic is always LeakyReLU)", T.name, c.hidden_act);
+            if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0 || c.extra_cols != 0)
+                return plan_refuse(message, "%s: dueling, noisy, c51_atoms, actor_dist and extra_cols must be 0", T.name);
+            if (c.capacity > (1 << 30)) return plan_refuse(message, "%s: capacity %d > 2^30 (a learner's two rings are indexed as one)", T.name, c.capacity);
             return FRL_OK;
         case FRL_ALGO_DQN:
             if (const int rc = no_leaky_relu()) return rc;
@@ -576,6 +592,14 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
             build_net(h.net[0], {{H, c.obs_dim[0]}, {H, H}, {c.act_dim[0], H}}, 1, lact, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[0]);
             build_net(h.net[1], {{H, c.obs_dim[0]}, {H, H}, {1, H}}, 1, lact, ACT_NONE, 0);
             h.log_std_min = -10.f; h.log_std_max = 2.f;      // PPO2's shipped range; frl_log_std_range_set
+            break;
+        }
+        case FRL_ALGO_CEM_GD3PG: {
+            // Actor (CEM_GD3PG.py:30-49) three times: actor_1, actor_2 and, behind the critic, the frozen actor_domain; Critic (:74-92)
+            h.n_nets = 4;
+            const int O = c.obs_dim[0], A = c.act_dim[0];
+            for (int i : {0, 1, 3}) build_net(h.net[i], {{H, O}, {H, H}, {A, H}}, 1, ACT_TANH, ACT_TANH, 0);
+            build_net(h.net[2], {{H, O + A}, {H, H}, {1, H}}, 1, ACT_LEAKY_RELU, ACT_NONE, 0);
             break;
         }
         case FRL_ALGO_MADDPG_ATT:
@@ -756,7 +780,7 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
     pl.slab_count = slab_floats(h);
     pl.part_count = part_floats(h);
-    pl.act_spill_count = T.act_spill ? act_spill_floats(h) : 0;
+    pl.act_spill_count = c.algo == FRL_ALGO_CEM_GD3PG ? cem_spill_floats(h) : T.act_spill ? act_spill_floats(h) : 0;      // (CEM_GD3PG: a block per (learner, actor, slice))
     // the chained family's actor stage (chained_shape admits DDPG / TD3 / SAC only: each has one); allocated whatever FRL_ACTOR_PARK says
     pl.actor_park_count = pl.family == FAM_CHAINED ? actor_park_floats(h.P) : 0;
     pl.idx_count = P * h.n_agents * h.batch_max;
@@ -804,7 +828,9 @@ inline int plan_engine(const frl_config& c, const frl_config_ext* ext, const Pla
     h.P = c.n_learners;
     h.n_agents = c.n_agents;
     h.hidden = c.hidden > 0 ? c.hidden : 128;
-    h.capacity = c.capacity;
+    pl.ring_cap = c.capacity;
+    pl.n_rings = c.algo == FRL_ALGO_CEM_GD3PG ? 2 : 1;
+    h.capacity = c.algo == FRL_ALGO_CEM_GD3PG ? (c.capacity <= (1 << 30) ? 2 * c.capacity : c.capacity) : c.capacity;      // (plan_refusals refuses the larger ones)
     h.batch_max = c.batch_max > 0 ? c.batch_max : 256;
     if (c.algo == FRL_ALGO_REINFORCE) h.batch_max = c.capacity;      // a call's batch is everything stored since the last one
     h.seed = c.seed;

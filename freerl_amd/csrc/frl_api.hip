@@ -52,6 +52,7 @@
 #include "kernels_att.hip"
 #include "kernels_masac.hip"
 #include "kernels_her.hip"
+#include "kernels_cem_gd3pg.hip"
 #endif
 
 using namespace frl;
@@ -133,7 +134,7 @@ struct frl_engine : frl::EngineFacts {      // (what the plan fixed: family, lds
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_stage = nullptr;
     LearnKernels kern;                    // the kernels of the engine's family (a DQN engine: the one-launch update's)
-    // replay cursors (host authoritative, reference semantics Buffer.py:23-24,36-38)
+    // replay cursors (host authoritative, reference semantics Buffer.py:23-24,36-38): [n_rings][P], ring 0's first
     std::vector<int> index, size;
     // pinned staging of not-yet-flushed adds
     float* stage_rows = nullptr;          // [stage_cap][width] pinned
@@ -198,6 +199,7 @@ struct frl_engine : frl::EngineFacts {      // (what the plan fixed: family, lds
     hipEvent_t ev_ep[2] = {nullptr, nullptr};
     unsigned ep_seq = 0;
     float* h_gail_rows = nullptr;         // frl_gail_learn: pinned staging of the uploaded policy rows [P][batch_max][obs_dim + act_dim]
+    float* h_cem_ctl = nullptr;           // frl_cem_gd3pg_learn: pinned staging of EngineDesc::cem_ctl, two alternating slots [2][2][P] (ev_ep, ep_seq: as h_ep_n)
     float* h_env_w = nullptr;             // frl_envelope_learn / frl_envelope_ddpg_learn: pinned staging of uploaded preference vectors [P][batch_max][reward_dim]
     // frl_her_relabel: the call's small arrays in one pinned block and its device copy (both grow on demand), the event behind the copy
     unsigned char* h_her = nullptr;
@@ -252,7 +254,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 113; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get
+extern "C" int frl_version(void) { return 114; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -373,6 +375,12 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
             CREATE_TRY(e->mem.alloc(&e->h_ep_n, 2 * P, MEM_PINNED));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
+        if (c.algo == FRL_ALGO_CEM_GD3PG) {
+            CREATE_TRY(e->mem.alloc_zero(&h.cem_ctl, 2 * P, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.cem_out, 8 * P, e->stream));
+            CREATE_TRY(e->mem.alloc(&e->h_cem_ctl, 4 * P, MEM_PINNED));
+            for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
         if (c.algo == FRL_ALGO_GAIL) {
             const size_t rows_n = P * (size_t)h.batch_max * (c.obs_dim[0] + c.act_dim[0]);
             CREATE_TRY(e->mem.alloc_zero(&h.gail_rows, rows_n, e->stream));
@@ -417,8 +425,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
     CREATE_TRY(e->mem.alloc(&e->d_idx64, (size_t)h.batch_max * 16, MEM_DEVICE));
     CREATE_TRY(e->mem.alloc(&e->d, 1, MEM_DEVICE));
     CREATE_TRY(hipMemcpyAsync(e->d, &h, sizeof h, hipMemcpyHostToDevice, e->stream));
-    e->index.assign(P, 0);
-    e->size.assign(P, 0);
+    e->index.assign(P * e->n_rings, 0);
+    e->size.assign(P * e->n_rings, 0);
     e->staged_per_learner.assign(P, 0);
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
     if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, e->chain_waves, e->actor_park, h);
@@ -436,7 +444,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)happo_update_kernel, (const void*)mappo_mask_update_kernel, (const void*)mappo_mask_act_kernel,
                               (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
                               (const void*)att_q_kernel, (const void*)masac_act_kernel, (const void*)gail_ppo_prepare_kernel,
-                              (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel})
+                              (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel, (const void*)cem_critic_kernel, (const void*)cem_actor_kernel,
+                              (const void*)cem_act_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -533,22 +542,25 @@ static int flush_stage(frl_engine* e) {
     return FRL_OK;
 }
 
-static int stage_one(frl_engine* e, int learner, const float* record) {
+// ring: which of the learner's rings (0 everywhere but on a CEM_GD3PG engine; ring r's rows are the learner's rows [r ring_cap, (r + 1) ring_cap))
+static int stage_one(frl_engine* e, int learner, const float* record, int ring = 0) {
     if (learner < 0 || learner >= e->h.P) return fail(FRL_ERR_INVALID, "learner %d out of range", learner);
+    if (ring < 0 || ring >= e->n_rings) return fail(FRL_ERR_INVALID, "ring %d out of range (the engine has %d per learner)", ring, e->n_rings);
     // one scatter launch writes its rows in no particular order: never stage the same ring row twice
-    if (e->stage_n == e->stage_cap || e->staged_per_learner[learner] >= e->h.capacity) { int rc = flush_stage(e); if (rc) return rc; }
+    if (e->stage_n == e->stage_cap || e->staged_per_learner[learner] >= e->ring_cap) { int rc = flush_stage(e); if (rc) return rc; }
     if (e->stage_inflight) {     // the pinned area may still be read by the previous flush's copy
         HIP_TRY(hipEventSynchronize(e->ev_stage));
         e->stage_inflight = false;
     }
     const RecordDesc& R = e->h.rec;
     memcpy(e->stage_rows + (size_t)e->stage_n * R.width, record, (size_t)R.width * sizeof(float));
-    int& ix = e->index[learner];
-    e->stage_slots[e->stage_n] = (long long)learner * e->h.capacity + ix;
+    const size_t cur = (size_t)ring * e->h.P + learner;
+    int& ix = e->index[cur];
+    e->stage_slots[e->stage_n] = (long long)learner * e->h.capacity + (long long)ring * e->ring_cap + ix;
     e->stage_n++;
     e->staged_per_learner[learner]++;
-    ix = (ix + 1) % e->h.capacity;                        // Buffer.py:36
-    if (e->size[learner] < e->h.capacity) e->size[learner]++;   // Buffer.py:37-38
+    ix = (ix + 1) % e->ring_cap;                          // Buffer.py:36
+    if (e->size[cur] < e->ring_cap) e->size[cur]++;       // Buffer.py:37-38
     return FRL_OK;
 }
 
@@ -585,8 +597,8 @@ extern "C" int frl_buffer_cursor_get(const frl_engine* e, int learner, int* inde
 extern "C" int frl_buffer_cursor_set(frl_engine* e, int learner, int index, int size) {
     ENG(e);
     if (learner < 0 || learner >= e->h.P) return fail(FRL_ERR_INVALID, "learner out of range");
-    if (index < 0 || index >= e->h.capacity || size < 0 || size > e->h.capacity)
-        return fail(FRL_ERR_INVALID, "cursor (%d,%d) outside capacity %d", index, size, e->h.capacity);
+    if (index < 0 || index >= e->ring_cap || size < 0 || size > e->ring_cap)
+        return fail(FRL_ERR_INVALID, "cursor (%d,%d) outside capacity %d", index, size, e->ring_cap);
     // rows staged before the cursor moves are committed first: afterwards the same ring slot may be staged again, and one
     // scatter launch must never hold a slot twice (it writes its rows in no particular order)
     int rc = flush_stage(e);
@@ -649,7 +661,7 @@ extern "C" int frl_buffer_read(frl_engine* e, int learner, int row0, int n, floa
 
 extern "C" int frl_buffer_fill_synthetic(frl_engine* e, int rows, uint64_t seed) {
     ENG(e);
-    if (rows < 0 || rows > e->h.capacity) return fail(FRL_ERR_INVALID, "rows out of range");
+    if (rows < 0 || rows > e->ring_cap) return fail(FRL_ERR_INVALID, "rows out of range");
     if (e->per_on)       // priorities are assigned by add (PER_Buffer.add, Buffer.py:92-98): a bulk fill would leave the trees empty
         return fail(FRL_ERR_STATE, "frl_buffer_fill_synthetic bypasses the priority trees: fill a PER engine through frl_buffer_add_batch");
     int rc = flush_stage(e);
@@ -659,7 +671,7 @@ extern "C" int frl_buffer_fill_synthetic(frl_engine* e, int rows, uint64_t seed)
         float* ring = e->h.replay + (size_t)p * e->h.capacity * R.stride;
         hipLaunchKernelGGL(replay_fill_kernel, dim3(std::min((rows + 255) / 256, 2048)), dim3(256), 0, e->stream, ring,
                            (long long)rows, R, e->h.n_discrete, seed + 0x632BE59BD9B4E019ull * (p + 1));
-        e->index[p] = rows % e->h.capacity;
+        e->index[p] = rows % e->ring_cap;
         e->size[p] = rows;
     }
     HIP_TRY(hipGetLastError());
@@ -900,6 +912,15 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
         if ((mode != FRL_ACT_SAC_SAMPLE && mode != FRL_ACT_TANHHEAD) || ex) return fail(FRL_ERR_INVALID, "a MASAC actor acts through FRL_ACT_SAC_SAMPLE, FRL_ACT_TANHHEAD or FRL_ACT_RAW");
         if (mode == FRL_ACT_SAC_SAMPLE && !eps_dev) return fail(FRL_ERR_INVALID, "FRL_ACT_SAC_SAMPLE on a MASAC actor needs the N(0,1) draws in eps");
         hipLaunchKernelGGL(masac_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
+    if (e->h.algo == ALGO_CEM_GD3PG) {      // tanh actors and a LeakyReLU critic in one engine: kernels_cem_gd3pg.hip's forward
+        const bool critic = net == 2;
+        const bool ok = critic ? mode == FRL_ACT_RAW : (mode == FRL_ACT_TANHHEAD || mode == FRL_ACT_RAW);
+        if (!ok || ex || (net == 3 && use_target))
+            return fail(FRL_ERR_INVALID, "a CEM-GD3PG engine acts through FRL_ACT_TANHHEAD (nets 0, 1 and 3; use_target on 0 and 1) and FRL_ACT_RAW (net 2: Q of [obs | act])");
+        hipLaunchKernelGGL(cem_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
         return FRL_OK;
     }
@@ -1192,6 +1213,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (e->h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MASAC.py has no Batch_ObsNorm and kernels_masac.hip does not normalise");
+    if (e->h.algo == ALGO_CEM_GD3PG) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: CEM_GD3PG.py has no Batch_ObsNorm and kernels_cem_gd3pg.hip does not normalise");
     if (e->h.algo == ALGO_GAIL_PPO) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: PPO2.py has no Batch_ObsNorm (its env wrapper scales observations) and kernels_gail_ppo.hip does not normalise");
     if (e->h.algo == ALGO_MADDPG_ATT) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MADDPG_simple_with_tricks.py has no Batch_ObsNorm and the attention critic's kernels do not normalise");
     if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
@@ -1256,6 +1278,7 @@ extern "C" int frl_per_enable(frl_engine* e, double alpha, double beta, double b
     ENG(e);
     if (e->h.n_agents != 1) return fail(FRL_ERR_INVALID, "PER is a single-agent buffer (DQN_file/Buffer.py:66)");
     if (e->per_on) return fail(FRL_ERR_STATE, "PER already enabled");
+    if (e->n_rings != 1) return fail(FRL_ERR_STATE, "frl_per_enable: a %s engine samples its two rings uniformly (CEM_GD3PG.py:160-176)", algo_traits(e->h.algo).name);
     int rc = flush_stage(e);
     if (rc) return rc;
     for (int p = 0; p < e->h.P; ++p)
@@ -1394,3 +1417,4 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_rollout.inc"
 #include "frl_api_her.inc"
 #include "frl_api_comm.inc"
+#include "frl_api_cem_gd3pg.inc"

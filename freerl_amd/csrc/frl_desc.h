@@ -12,7 +12,7 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
-                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16 };
+                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16, ALGO_CEM_GD3PG = 18 /* 17: unassigned */ };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -241,6 +241,10 @@ struct EngineDesc {
     // — [P][2 chunks][8 tiles][8 waves][64 lanes] f32x4 (actor_park_layout.h), 128 KiB per learner; a lane reads back only what it wrote
     // in the same launch.  Engines of the chained family (DDPG / TD3 / SAC) only; null everywhere else
     float* actor_park;
+    // CEM_GD3PG (kernels_cem_gd3pg.hip, ALGO_CEM_GD3PG): net 0 actor_1, net 1 actor_2, net 2 the critic, net 3 actor_domain (frozen).  A learner's
+    // `capacity` ring rows are TWO rings of capacity / 2 rows, `buffer` then `buffer_domain`; idx holds absolute rows of the pair
+    float* cem_ctl;       // [2][P] of the current frl_cem_gd3pg_learn call: is_F1_more (0 / 1) of every learner, then its delta
+    float* cem_out;       // [P][8] what frl_cem_gd3pg_args::out returns, written by cem_step_kernel
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

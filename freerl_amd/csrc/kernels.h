@@ -200,6 +200,24 @@ __global__ void gail_ppo_gae_kernel(const EngineDesc* __restrict__ Dp, GailPpoAr
 __global__ void gail_ppo_update_kernel(const EngineDesc* __restrict__ Dp, GailPpoArgs a);
 __global__ void gail_ppo_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
+// kernels_cem_gd3pg.hip: CEM_GD3PG (CEM_GD3PG_file/CEM_GD3PG.py) on an ALGO_CEM_GD3PG engine: net 0 actor_1, net 1 actor_2, net 2 the critic,
+// net 3 actor_domain.  The batch is rows = 2 x half absolute ring rows in EngineDesc::idx: `half` of ring 0, then `half` of ring 1
+struct CemArgs {
+    int rows, half;               // B = 2 half rows of a call
+    int size1;                    // cem_draw_kernel: both halves are drawn below this (rows valid in every learner's ring 1)
+    int ring_cap;                 // rows of one ring: ring 1's row r is absolute row ring_cap + r
+    float gamma, lambda;
+    float tau, actor_lr, critic_lr;
+    int stage;                    // cem_step_kernel: 0 the critic (units = learners), 1 both actors (units = (learner, actor))
+    unsigned long long rng_counter;
+    int p0, p_count;
+};
+__global__ void cem_draw_kernel(const EngineDesc* __restrict__ Dp, CemArgs a);
+__global__ void cem_critic_kernel(const EngineDesc* __restrict__ Dp, CemArgs a, int ns);
+__global__ void cem_actor_kernel(const EngineDesc* __restrict__ Dp, CemArgs a, int ns);
+__global__ void cem_step_kernel(const EngineDesc* __restrict__ Dp, CemArgs a, int ns);
+__global__ void cem_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_mappo.hip: MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py): a unit = (learner, agent); nets 2i / 2i+1 = agent i's actor / critic
 struct MappoArgs {
     int horizon, minibatch, k_epochs, adv_norm;

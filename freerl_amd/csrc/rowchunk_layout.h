@@ -62,6 +62,22 @@ FRL_LAYOUT_FN int hidden_pitch(int hidden) { return hidden + 4; }
 FRL_LAYOUT_FN int act_spill_pitch(const EngineDesc& D) { return 2 * D.rc * hidden_pitch(D.hidden); }
 FRL_LAYOUT_FN size_t act_spill_offset(const EngineDesc& D, int p, int ag, int sl) { return unit_slice_index(D, p, ag, sl) * act_spill_pitch(D); }
 
+// ------------------------------------------------------------------------------ CEM_GD3PG (kernels_cem_gd3pg.hip)
+// The actor launch's units are (learner, actor) pairs of a single-agent engine: both actors of a learner share its idx and its part
+// slots (the floats below), each has its net's region of the slice's slab and a spill block of its own.
+constexpr int kCemActors = 2;
+// a (learner, slice)'s part slot: the critic launch writes the first two floats, actor j of the actor launch float CEM_PART_ACTOR + j
+enum CemPart : int { CEM_PART_CRITIC = 0, CEM_PART_C2 = 1, CEM_PART_ACTOR = 2 };      // squared TD errors | sum c^2 of the guided actor | -Q sums
+static_assert(CEM_PART_ACTOR + kCemActors <= kPartFloats, "a part slot holds the critic's two sums and one per actor");
+// act_spill [P][2 actors][S][2][rc][hidden + 4]
+FRL_LAYOUT_FN size_t cem_spill_offset(const EngineDesc& D, int p, int actor, int sl) {
+    return (((size_t)p * kCemActors + actor) * D.S + sl) * act_spill_pitch(D);
+}
+FRL_LAYOUT_FN size_t cem_spill_floats(const EngineDesc& D) { return cem_spill_offset(D, D.P, 0, 0); }
+// the domain actor's output of row r0 .., parked by the critic launch for the guided actor's head delta: set 0 of the unit's noise block
+// (no kernel of this algorithm draws noise)
+FRL_LAYOUT_FN size_t cem_domain_offset(const EngineDesc& D, int p, int r0) { return noise_offset(D, p, 0, 0, r0); }
+
 // ------------------------------------------------------------------------------ what the plan allocates
 FRL_LAYOUT_FN size_t slab_floats(const EngineDesc& D) { return (size_t)D.P * D.S * D.learner_stride; }
 FRL_LAYOUT_FN size_t part_floats(const EngineDesc& D) { return part_offset(D, D.P, 0, 0); }

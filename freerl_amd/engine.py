@@ -532,6 +532,58 @@ class Engine:
             a.critic_loss_out, a.actor_loss_out = _fp(out["critic_loss"]), _fp(out["actor_loss"])
         return self._envelope_call(self._L.frl_envelope_ddpg_learn, a, batch, weight_num, idx, weights, want_weights, out)
 
+    # ------------------------------------------------------------------ CEM_GD3PG: two rings per learner, one learn entry point
+    def ring_add(self, ring, record, learner=0):
+        rec = np.ascontiguousarray(record, dtype=F32)
+        assert rec.size == self.width, (rec.size, self.width)
+        N.check(self._L.frl_ring_add(self._h, int(learner), int(ring), _fp(rec)))
+
+    def ring_add_batch(self, ring, records, learners=None):
+        recs = np.ascontiguousarray(records, dtype=F32).reshape(-1, self.width)
+        lp = None
+        if learners is not None:
+            ln = np.ascontiguousarray(learners, dtype=np.int32)
+            assert ln.size == recs.shape[0]
+            lp = ln.ctypes.data_as(C.POINTER(C.c_int))
+        N.check(self._L.frl_ring_add_batch(self._h, int(ring), recs.shape[0], lp, _fp(recs)))
+
+    def ring_cursor(self, ring, learner=0):
+        i, s = C.c_int(0), C.c_int(0)
+        N.check(self._L.frl_ring_cursor_get(self._h, int(learner), int(ring), C.byref(i), C.byref(s)))
+        return i.value, s.value
+
+    def set_ring_cursor(self, ring, index, size, learner=0):
+        N.check(self._L.frl_ring_cursor_set(self._h, int(learner), int(ring), int(index), int(size)))
+
+    def ring_rows(self, ring, row0, n, learner=0):
+        """Rows [row0, row0 + n) of ring `ring` (a learner's rings lie side by side: frl_buffer_read's rows [ring capacity, ..))."""
+        return self.read_rows(learner, int(ring) * self.capacity + int(row0), n)
+
+    def cem_gd3pg_learn(self, batch, *, gamma, tau, actor_lr, critic_lr, f1_more, delta, lam=10.0, idx=None, want_out=True):
+        """CEM_GD3PG.learn for every learner (frl_cem_gd3pg_learn) on 2 x half rows, half = min(len(ring 1), batch) // 2: f1_more and delta
+        one per learner (scalars broadcast), idx [P][2][half] ring-relative rows (ring 0's first) or None: drawn on the device.
+        -> float32 [P][8] in the order of _native.CEM_OUT, or None (asynchronous) when want_out is false."""
+        a = N.CemGd3pgArgs()
+        a.batch, a.gamma, a.tau, a.actor_lr, a.critic_lr = int(batch), float(gamma), float(tau), float(actor_lr), float(critic_lr)
+        setattr(a, "lambda", float(lam))
+        f1 = np.ascontiguousarray(np.broadcast_to(np.asarray(f1_more).astype(np.int32).reshape(-1), (self.P,)))
+        dl = np.ascontiguousarray(np.broadcast_to(np.asarray(delta, dtype=F32).reshape(-1), (self.P,)))
+        a.f1_more, a.delta = f1.ctypes.data_as(C.POINTER(C.c_int)), _fp(dl)
+        keep = [f1, dl]
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, 2, -1)
+            half = min(min(self.ring_cursor(1, p)[1] for p in range(self.P)), int(batch)) // 2      # what the library will read
+            if ix.shape[2] != half:
+                raise ValueError("idx holds %d rows per ring, the call uses %d" % (ix.shape[2], half))
+            keep.append(ix)
+            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
+        out = None
+        if want_out:
+            out = np.full((self.P, 8), np.nan, dtype=F32)
+            a.out = _fp(out)
+        N.check(self._L.frl_cem_gd3pg_learn(self._h, C.byref(a)))
+        return out
+
     def gail_learn(self, policy_rows, *, gp, lr, beta1, beta2, n_expert=None, gp_weight=5.0, adam_eps=1e-8, idx=None, want_out=True,
                    want_idx=False):
         """GAIL.trian_D for every learner (frl_gail_learn): policy_rows [P][n_policy][obs_dim + act_dim] against expert ring rows

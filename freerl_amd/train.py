@@ -117,6 +117,13 @@ FLAGS = {
                   flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=120000, save_freq=5000 // 4, start_steps=0,
                                                                learn_steps_interval=0, gamma=0.95, actor_lr=1e-4, critic_lr=1e-4),
                   trick=dict(_MAPPO_TRICK)),
+    # CEM_GD3PG_file/CEM_GD3PG.py:300-337: the script's own defaults (no --save_freq: the loop saves once, at the end; --elitism and --mult_noise
+    # are its store_true flags, --n_grad is parsed and unused there too)
+    "cem_gd3pg": dict(env_name="BipedalWalker-v3", policy_name="CEM_GD3PG", device="cpu", is_dis_to_con=False,
+                      flags=[f for f in _COMMON if f[0] != "save_freq"] + _AC + _REPLAY + [("gauss_sigma", float, 0.1), ("max_action", float, None),
+                             ("pop_size", int, 10), ("n_grad", int, 5), ("sigma_init", float, 1e-3), ("damp", float, 1e-3), ("damp_limit", float, 1e-5)],
+                      overrides=dict(start_steps=1000),
+                      trick={"Double": False, "Dueling": False, "PER": False, "HER": False, "Noisy": False, "n_step": False}),
 }
 
 
@@ -134,6 +141,9 @@ def build_parser(algo):
         p.add_argument("--realize", type=dict, default={"clip_double": True, "policy_noise": True, "twin_delay": True})
     if algo == "ppo":
         p.add_argument("--beta", type=bool, default=False)
+    if algo == "cem_gd3pg":
+        p.add_argument("--elitism", dest="elitism", action="store_true")
+        p.add_argument("--mult_noise", dest="mult_noise", action="store_true")
     if algo in _MA_PPO:                    # (type=bool as in the scripts: any non-empty string is True)
         p.add_argument("--continuous_actions", type=bool, default=(algo == "mappo"))
     p.add_argument("--device", type=str, default=spec["device"])
@@ -643,6 +653,85 @@ def _run_masac(args, env, policy, dim_info, max_action, model_dir, writer, log=p
     return dict(returns=arr, steps=step, seconds=time.time() - t0)
 
 
+def _run_cem_gd3pg(args, env, policy, dim_info, max_action, model_dir, writer, log=print):
+    """CEM_GD3PG.py:364-486: the population's first evaluations into `buffer`; then per episode — every pop_size episodes a generation
+    step (tell, ask, evaluate the new half into `buffer`, mix the best into the poorer actor with weight 0.5) —, the two fitness
+    episodes, the running fitness averages and delta, the noisy domain episode into `buffer_domain`, and one learn() per step of it."""
+    from .CEM_GD3PG import sepCEM
+    action_dim, n = dim_info[1], args.pop_size
+    t0 = time.time()
+
+    def eval_actor(actor, buffer=None, noise=False):
+        """one episode (:370-396) -> (return, steps); stores into `buffer`, explores with Gaussian noise when `noise`"""
+        episode_reward, steps = 0, 0
+        obs, _ = env.reset(seed=args.seed)
+        done = False
+        while not done:
+            action = policy.select_action(obs, actor)
+            if noise:
+                action_ = np.clip(action * max_action + np.random.normal(scale=args.gauss_sigma * max_action, size=action_dim), -max_action, max_action)
+            else:
+                action_ = action * max_action
+            next_obs, reward, terminated, truncated, _ = env.step(action_)
+            done = terminated or truncated
+            if buffer is not None:
+                policy.add(buffer, obs, action, reward, next_obs, done if not truncated else False)
+            episode_reward += reward
+            steps += 1
+            obs = next_obs
+        return episode_reward, steps
+
+    ag = policy.agent
+    actor_1, actor_2, actor_domain = ag.actor_1, ag.actor_2, ag.actor_domain
+    es = sepCEM(actor_1.get_size(), mu_init=actor_1.get_params(), sigma_init=args.sigma_init, damp=args.damp, damp_limit=args.damp_limit,
+                pop_size=n, antithetic=not n % 2, parents=n // 2, elitism=args.elitism)
+    f1_total = f2_total = 0
+    cnt_es, episode_num, step, train_return = 0, 0, 0, []
+    env.reset(seed=args.seed)
+    es_params = es.ask(n * 2)
+    fitness = []
+    for i in range(n):                                   # `buffer` starts pop_size episodes ahead of `buffer_domain` (:415-418)
+        actor_domain.set_params(es_params[i])
+        fitness.append(eval_actor(actor_domain, policy.buffer)[0])
+    while episode_num < args.max_episodes:
+        if cnt_es == n:
+            es.tell(es_params, fitness)
+            half = es.ask(n)
+            fitness, cnt_es = [], 0
+            for params in half:
+                actor_domain.set_params(params)
+                fitness.append(eval_actor(actor_domain, policy.buffer)[0])
+            best = int(np.argsort(fitness)[-1])
+            log("select best actor : Actor%d ,fitness :%s" % (best, fitness[best]))
+            poorer = actor_2 if f1_total >= f2_total else actor_1
+            poorer.set_params((half[best] + poorer.get_params()) / 2)          # pi_poor = (1 - beta) pi_best + beta pi_poor, beta = 0.5 (:436)
+            es_params[:n] = half
+        f1, f2 = eval_actor(actor_1)[0], eval_actor(actor_2)[0]
+        f1_total = 0.8 * f1_total + 0.2 * f1                                   # alpha = 0.2 (:445)
+        f2_total = 0.8 * f2_total + 0.2 * f2
+        hi, lo, better = (f1_total, f2_total, actor_1) if f1_total >= f2_total else (f2_total, f1_total, actor_2)
+        actor_domain.set_params(better.get_params())
+        delta = min(1, 1 - lo / hi) if hi > 0 else 1 - hi / lo                 # (:447-460)
+        es_params[cnt_es + n] = actor_domain.get_params()
+        fitness.append(max(f1, f2))
+        cnt_es += 1
+        episode_reward, steps = eval_actor(actor_domain, policy.buffer_domain, noise=True)
+        args.gauss_sigma = max(0.05, args.gauss_sigma * 0.999)
+        if (episode_num + 1) % 100 == 0:
+            log("episode: {}, reward: {}".format(episode_num + 1, episode_reward))
+        writer.add_scalar("reward_domain", episode_reward, episode_num + 1)
+        train_return.append(episode_reward)
+        episode_num += 1
+        step += steps
+        if step > args.start_steps:
+            for _ in range(steps):
+                policy.learn(args.batch_size, args.gamma, args.tau, f1_total >= f2_total, delta, actor_domain)
+    log("total_time:", time.time() - t0)
+    policy.save(model_dir, actor_domain)
+    np.save(os.path.join(model_dir, "%s_seed_%d.npy" % (args.policy_name, args.seed)), np.array(train_return))
+    return dict(returns=[float(r) for r in train_return], steps=step, seconds=time.time() - t0)
+
+
 def _mappo_policy_name(args, base):
     """MAPPO.py:573-588 / IPPO.py:451-465 / HAPPO.py:586-601: the policy name decides the tricks — `MAPPO` switches all on but reward_norm and lr_decay,
     `MAPPO_simple` all off"""
@@ -837,6 +926,14 @@ def run(algo, argv=None, env=None, log=print):
         from .MASAC import MASAC
         policy = MASAC(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, **kw)
         out = _run_masac(args, env, policy, dim_info, max_action, model_dir, writer, log)
+        writer.close()
+        return dict(out, model_dir=model_dir, policy=policy, args=args)
+    elif algo == "cem_gd3pg":
+        from .CEM_GD3PG import CEM_GD3PG
+        if not is_continue:
+            raise ValueError("cem_gd3pg trains on continuous action spaces (CEM_GD3PG.py:296-298); %s is discrete" % args.env_name)
+        policy = CEM_GD3PG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, args.trick, batch_max=max(args.batch_size, 2), **kw)
+        out = _run_cem_gd3pg(args, env, policy, dim_info, max_action if max_action is not None else args.max_action, model_dir, writer, log)
         writer.close()
         return dict(out, model_dir=model_dir, policy=policy, args=args)
     elif algo in _MA_PPO:

@@ -99,7 +99,7 @@ enum frl_algo {
                                   Refused at create: discrete, twin_critic = 0, hidden_act != FRL_ACT_RELU, a row chunk that does not
                                   fit a CU's LDS.  Refused at the call (FRL_ERR_STATE): frl_obsnorm_enable, use_policy_noise,
                                   frl_rollout, frl_act_explore.  frl_version() 111 */
-    FRL_ALGO_GAIL_PPO = 16     /* GAIL_file/PPO2.py:20-307, the policy side of GAIL (and PPO2.py's own loop): net 0 the actor obs_dim ->
+    FRL_ALGO_GAIL_PPO = 16,    /* GAIL_file/PPO2.py:20-307, the policy side of GAIL (and PPO2.py's own loop): net 0 the actor obs_dim ->
                                   hidden -> hidden -> act_dim with tanh on the mean and a state-independent log_std [act_dim] (zeros at
                                   create) clamped to the ENGINE's range (frl_log_std_range_set; [-10, 2] at create, PPO2's shipped
                                   config), or, with discrete, the logits of Categorical(logits=); net 1 the critic obs_dim -> hidden ->
@@ -108,6 +108,17 @@ enum frl_algo {
                                   Updated by frl_gail_ppo_learn only.  frl_act: FRL_ACT_RAW (net 1: value; net 0: the head),
                                   FRL_ACT_TANHHEAD (pi(return_mean=True)), FRL_ACT_PPO_SAMPLE (mean + std eps under the engine's
                                   range, eps given or drawn), FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX (discrete).  frl_version() 113 */
+    FRL_ALGO_CEM_GD3PG = 18    /* (17 is unassigned: frl_create refuses it as an unknown algo, which callers and the suite have relied on since
+                                  frl_version 113.)  CEM_GD3PG_file/CEM_GD3PG.py:30-231, guided dual-actor DDPG: net 0 actor_1, net 1 actor_2 and net 3
+                                  actor_domain obs_dim -> hidden (tanh) -> hidden (tanh) -> act_dim (tanh), net 2 the critic [obs | act] ->
+                                  hidden (LeakyReLU 0.01) -> hidden (LeakyReLU 0.01) -> 1.  Nets 0-2 have a target net and Adam state;
+                                  net 3 is frozen (no kernel writes it; its target and Adam blocks are never touched).  hidden_act must
+                                  be FRL_ACT_TANH (the actors'; the critic is always LeakyReLU); discrete, twin_critic and n_agents != 1
+                                  are refused.  TWO rings of `capacity` rows per learner, ring 0 `buffer` and ring 1 `buffer_domain`
+                                  (frl_ring_add / frl_ring_cursor_get; the frl_buffer_* calls serve ring 0, and frl_buffer_read's rows
+                                  [r capacity, (r + 1) capacity) are ring r), zero-filled at create.  Updated by frl_cem_gd3pg_learn
+                                  only.  frl_act: FRL_ACT_TANHHEAD on nets 0, 1 and 3 (use_target on 0 and 1), FRL_ACT_RAW on net 2.
+                                  frl_version() 114 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -564,6 +575,44 @@ int frl_gail_ppo_learn(frl_engine* e, const frl_gail_ppo_args* args);
  * both are finite; FRL_ERR_STATE on engines of any other algorithm (theirs is compiled in: [-20, 2]). */
 int frl_log_std_range_set(frl_engine* e, float lo, float hi);
 int frl_log_std_range_get(const frl_engine* e, float* lo_out, float* hi_out);
+
+/* ---------------------------------------------------------------- CEM_GD3PG (CEM_GD3PG_file/CEM_GD3PG.py) on a FRL_ALGO_CEM_GD3PG engine
+ * The two rings of a learner.  Ring 0 is `buffer`, ring 1 `buffer_domain` (:134-135); each has `capacity` rows, its own cursor and size,
+ * and Buffer.add's arithmetic (index = (index + 1) % capacity, size = min(size + 1, capacity)).  Engines of every other algorithm have
+ * ring 0 only, where these are frl_buffer_add / _add_batch / _cursor_get / _cursor_set; FRL_ERR_INVALID for a ring the engine lacks. */
+int frl_ring_add(frl_engine* e, int learner, int ring, const float* record);
+int frl_ring_add_batch(frl_engine* e, int ring, int n, const int* learners /* [n] or NULL: learner 0 */, const float* records /* [n][width] */);
+int frl_ring_cursor_get(const frl_engine* e, int learner, int ring, int* index_out, int* size_out);
+int frl_ring_cursor_set(frl_engine* e, int learner, int ring, int index, int size);
+/* `CEM_GD3PG.learn(batch_size, gamma, tau, is_F1_more, delta, actor_domain)` (:180-231) for every learner in one launch chain over
+ * B = 2 half rows, half = min(len(buffer_domain), batch) / 2 (:160-176; the smallest ring 1 of the population decides): `half` rows of
+ * ring 0, then `half` rows of ring 1, BOTH drawn below ring 1's size — rows of ring 0 that were never written read as zeros, as the
+ * reference's do.
+ *   Critic step: T = r + gamma (1 - done) min(critic_target(s', actor_1_target(s')), critic_target(s', actor_2_target(s'))), MSE against
+ *     critic(s, a), clip_grad_norm_ 0.5, Adam(critic_lr).
+ *   Actor steps, through the critic just stepped: the unguided actor u (actor_1 if f1_more, else actor_2) has loss -mean Q(s, actor_u(s));
+ *     the guided actor g, the other one, has -mean Q(s, actor_g(s)) + lambda delta KL with c = actor_g(s) - actor_domain(s) and
+ *     KL = sqrt(sum c^2 / B).  Each has its own clip at 0.5 and Adam(actor_lr).  sum c^2 == 0 (torch: NaN gradients): the penalty's gradient
+ *     is taken as 0 and KL is reported as 0.
+ *   Soft update of the three targets with tau.  Net 3 (actor_domain) is read only.
+ * Refused before any launch with FRL_ERR_INVALID: batch < 2, 2 half > batch_max, NaN scalars or a NaN delta, f1_more / delta NULL, an idx
+ * entry outside [0, capacity) (ring 0: what was never written is zeros) or outside [0, size of ring 1) (ring 1); with FRL_ERR_STATE: a
+ * ring 1 that holds fewer than 2 rows, and engines of any other algorithm.  Every other learn, rollout or explore entry point returns
+ * FRL_ERR_STATE for a FRL_ALGO_CEM_GD3PG engine and names this one. */
+struct frl_cem_gd3pg_args {
+    int batch;              /* batch_size */
+    float gamma, tau, actor_lr, critic_lr;
+    float lambda;           /* Actor.lambda_ (:42): 10 */
+    const int* f1_more;     /* host [P]: is_F1_more of every learner (nonzero: actor_1 is unguided, actor_2 guided) */
+    const float* delta;     /* host [P] */
+    const int64_t* idx;     /* host [P][2][half] ring-relative rows, ring 0's first (the two np.random.choice draws, :165-166), or NULL:
+                               drawn on the device without replacement, both halves below ring 1's size */
+    float* out;             /* host [P][8] = {critic loss, critic pre-clip norm, actor_1 loss, actor_1 norm, actor_2 loss, actor_2 norm,
+                               KL, rows used} or NULL: the call is asynchronous.  FRL_STAT_CRITIC_LOSS / _CRITIC_GNORM / _ACTOR_LOSS /
+                               _ACTOR_GNORM (actor_1's) carry the same values */
+};
+typedef struct frl_cem_gd3pg_args frl_cem_gd3pg_args;
+int frl_cem_gd3pg_learn(frl_engine* e, const frl_cem_gd3pg_args* args);
 
 /* ---------------------------------------------------------------- MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py)
  * `MAPPO.learn / IPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner in

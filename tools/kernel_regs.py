@@ -68,7 +68,12 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # start of a barrier phase or between two tile blocks, none inside an innermost MFMA k-loop (some outer layer / tile-block loops hold them)
           ("masac_critic_", 0), ("masac_actor_", 52), ("masac_act_", 0),
           # kernels_her.hip (the unit compiled on its own): her_relabel_kernel 29 VGPRs, 60 SGPRs, no spilled VGPR, no scratch (byte work)
-          ("her_", 0), ("", 20)]
+          ("her_", 0),
+          # kernels_cem_gd3pg.hip (the unit compiled on its own, profiles/cem_gd3pg/kernel_regs.txt): cem_critic_kernel 256 VGPRs with 44 spilled and
+          # 204 bytes of scratch — seven forward passes and a backward over three nets' layer offsets, the Lds carve, the chunk loop's bounds and two
+          # per-row sums: stored at entry, reloaded at the start of a pass, none of its 102 scratch accesses inside an innermost MFMA k-loop;
+          # cem_actor_kernel 255 VGPRs, none spilled, 56 bytes (a row lambda's captures); cem_act_kernel 188 + 40 AGPRs; cem_draw_kernel 106; cem_step_kernel 61
+          ("cem_critic_", 44), ("cem_actor_", 0), ("cem_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
