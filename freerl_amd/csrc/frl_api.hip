@@ -481,6 +481,13 @@ extern "C" int frl_sync(frl_engine* e) {
     return solo_err_check(e);
 }
 
+// The host's descriptor to the device after a setter changed it: no launch may be reading it while it changes
+static int push_desc(frl_engine* e) {
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
+    return FRL_OK;
+}
+
 extern "C" int frl_lds_bytes(const frl_engine* e, int* bytes_out, int* rc_out) {
     if (!e) return fail(FRL_ERR_INVALID, "engine is NULL");
     if (bytes_out) *bytes_out = e->lds_bytes;
@@ -1234,9 +1241,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
         e->h.solow = 0;
     }
     e->h.obs_norm_on = on ? 1 : 0;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
-    return FRL_OK;
+    return push_desc(e);
 }
 // stats of one learner: n_agents blocks of (1 + 3*max obs_dim) floats, block j = {n, mean[O_j], S[O_j], std[O_j]} of agent j
 // (the version the next select_action / learn starts from); single agent: one block of 1 + 3*O floats
@@ -1301,7 +1306,7 @@ extern "C" int frl_per_enable(frl_engine* e, double alpha, double beta, double b
             e->idx_count = P * e->h.n_agents * bm;
             HIP_TRY(e->mem.alloc(&e->h.idx, e->idx_count, MEM_DEVICE));
             HIP_TRY(e->mem.alloc(&e->h_idx, e->idx_count, MEM_PINNED));
-            HIP_TRY(hipMemcpy(e->d, &e->h, sizeof(EngineDesc), hipMemcpyHostToDevice));
+            if (const int prc = push_desc(e)) return prc;
         }
         return FRL_OK;
     };

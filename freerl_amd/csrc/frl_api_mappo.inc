@@ -5,9 +5,7 @@ extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm)
     if (!is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_net_norm_set");
     e->h.feature_norm = feature_norm ? 1 : 0;
     e->h.layer_norm = layer_norm ? 1 : 0;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
-    return FRL_OK;
+    return push_desc(e);
 }
 
 // MAPPO_for_mask_action.py on a FRL_ALGO_MAPPO engine: the record column of the first mask block (behind the log-prob and adv_done
@@ -26,9 +24,7 @@ extern "C" int frl_action_mask_set(frl_engine* e, int on) {
         return fail(FRL_ERR_INVALID, "frl_action_mask_set: extra_cols %d < %d log-prob and adv_done columns + %d mask columns + %d state columns", R.extra, first,
                     blocks, e->h.state_dim);
     e->h.mask_off = on ? R.extra_off + first : 0;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipMemcpy(e->d, &e->h, sizeof e->h, hipMemcpyHostToDevice));
-    return FRL_OK;
+    return push_desc(e);
 }
 
 // select_action of a masked engine: one synchronous categorical draw per row of an actor, host in / host out
@@ -72,10 +68,13 @@ struct HappoCall {
 // then mappo_update_kernel once or happo_update_kernel once per visiting position, all on the engine's one stream
 static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const HappoCall* hc) {
     const EngineDesc& h = e->h;
-    const int T = args->horizon, mb = args->minibatch, K = args->k_epochs, n = h.n_agents;
-    if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
-    if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
-    if (K < 1) return fail(FRL_ERR_INVALID, "k_epochs must be >= 1");
+    const int n = h.n_agents;
+    const size_t P = h.P, U = P * n;
+    OnpolicyCall c;
+    std::string why;
+    if (const int rc = plan_onpolicy(ONP_MAPPO, h.capacity, h.batch_max, U, args->horizon, args->minibatch, args->k_epochs, args->perms != nullptr, &c, &why))
+        return fail(rc, "%s", why.c_str());
+    const int T = c.T, mb = c.mb;
     // a state engine with the reference's pairing (MAPPO_for_mask_action_state.py:371-373): torch.cat of obs_[index] with the unindexed
     // `state` raises unless the minibatch is the whole horizon
     if (h.state_dim > 0 && h.state_rows == FRL_STATE_ROWS_POSITION && mb != T)
@@ -83,17 +82,10 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
                                      "minibatch; FRL_STATE_ROWS_SAMPLE takes any minibatch)", mb, T);
     if (args->loss_kind != FRL_LOSS_MSE && args->loss_kind != FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "loss_kind %d (FRL_LOSS_MSE or FRL_LOSS_HUBER)", args->loss_kind);
     if (args->loss_kind == FRL_LOSS_HUBER && !(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "FRL_LOSS_HUBER needs huber_delta > 0");
-    const int n_mb = (T + mb - 1) / mb;
-    const size_t P = h.P, U = P * n;
+    // permutations: the caller's np.random.permutation draws, one per (agent, epoch) in agent-major order (MAPPO.py:391-395,
+    // IPPO.py:254,275-277), else drawn with a unit = (learner, agent) (onpolicy_perms)
     std::vector<int> perm;
-    if (args->perms) {
-        perm.resize(U * (size_t)K * T);
-        for (size_t i = 0; i < perm.size(); ++i) {
-            const int64_t v = args->perms[i];
-            if (v < 0 || v >= T) return fail(FRL_ERR_INVALID, "permutation entry %lld outside [0,%d)", (long long)v, T);
-            perm[i] = (int)v;
-        }
-    }
+    if (args->perms && narrow_perms(args->perms, c.perm_n(), T, &perm, &why)) return fail(FRL_ERR_INVALID, "%s", why.c_str());
     std::vector<int> order;
     if (hc && hc->agent_order) {
         order.assign(hc->agent_order, hc->agent_order + U);
@@ -106,35 +98,12 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
             }
         }
     }
-    int rc = flush_stage(e);
-    if (rc) return rc;
-    const size_t trace_n = U * (size_t)K * n_mb * 2;
-    // (HAPPO: old [P][T] and factor [P][n][T] behind the trace, the visiting order [P][n] behind the permutations)
-    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, 7 * U * T + trace_n + (hc ? (P + U) * T : 0), MEM_DEVICE));
-    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, U * (size_t)K * T + (hc ? U : 0), MEM_DEVICE));
-    // permutations: the caller's np.random.permutation draws, one per (agent, epoch) in agent-major order (MAPPO.py:391-395,
-    // IPPO.py:254,275-277), else ppo_perm_kernel's with a unit = (learner, agent); horizons beyond 8192 rows: a host Fisher-Yates
-    int Tpad = 2;
-    while (Tpad < T) Tpad <<= 1;
-    const bool dev_perm = !args->perms && Tpad <= 8192;
-    if (dev_perm) {
-        hipLaunchKernelGGL(ppo_perm_kernel, dim3(K, (unsigned)U), dim3(256), (size_t)Tpad * sizeof(unsigned long long), e->stream,
-                           e->d_perm, T, Tpad, (unsigned long long)(++e->rng_counter), (unsigned long long)h.seed);
-    } else {
-        if (!args->perms) {
-            perm.resize(U * (size_t)K * T);
-            unsigned long long s = h.seed ^ (0xD1B54A32D192ED03ull * (++e->rng_counter));
-            for (size_t blk = 0; blk < U * (size_t)K; ++blk) {
-                int* q = perm.data() + blk * T;
-                for (int i = 0; i < T; ++i) q[i] = i;
-                for (int i = T - 1; i > 0; --i) std::swap(q[i], q[(int)(splitmix64(s) % (unsigned long long)(i + 1))]);
-            }
-        }
-        HIP_TRY(hipMemcpyAsync(e->d_perm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    }
+    const MappoLayout L = mappo_layout(c, P, hc != nullptr);
+    if (const int rc = onpolicy_scratch(e, L.floats, L.ints)) return rc;
+    if (const int rc = onpolicy_perms(e, c, &perm)) return rc;
     MappoArgs a;
     memset(&a, 0, sizeof a);
-    a.horizon = T; a.minibatch = mb; a.k_epochs = K; a.adv_norm = args->adv_norm ? 1 : 0;
+    a.horizon = T; a.minibatch = mb; a.k_epochs = c.K; a.adv_norm = args->adv_norm ? 1 : 0;
     a.huber = args->loss_kind == FRL_LOSS_HUBER ? 1 : 0;
     a.huber_delta = args->huber_delta;
     a.gamma = args->gamma; a.lmbda = args->lmbda; a.clip = args->clip; a.ent_coef = args->ent_coef;
@@ -142,15 +111,8 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     a.adam_eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f;
     a.beta1 = 0.9f; a.beta2 = 0.999f;
     a.clip_norm = args->clip_norm;
-    float* q = e->d_ppo;
-    a.td = q; q += U * T;
-    a.advd = q; q += U * T;
-    a.vs = q; q += U * T;
-    a.adv_seq = q; q += U * T;
-    a.adv_raw = q; q += U * T;
-    a.adv = q; q += U * T;
-    a.vtarget = q; q += U * T;
-    a.trace = q;
+    a.td = e->d_ppo + L.td; a.advd = e->d_ppo + L.advd; a.vs = e->d_ppo + L.vs; a.adv_seq = e->d_ppo + L.adv_seq; a.adv_raw = e->d_ppo + L.adv_raw;
+    a.adv = e->d_ppo + L.adv; a.vtarget = e->d_ppo + L.vtarget; a.trace = e->d_ppo + L.trace;
     a.perm = e->d_perm;
     if (h.state_dim > 0)      // the critic's row from two segments (kernels_mappo_state.hip)
         hipLaunchKernelGGL(mappo_state_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
@@ -161,20 +123,11 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     HappoArgs x = {};
     if (hc) {
         // the visiting order (HAPPO.py:375: torch.randperm(n)): the caller's, else a host Fisher-Yates per learner from the seed and counter
-        if (order.empty()) {
-            order.resize(U);
-            unsigned long long s = h.seed ^ (0xD1B54A32D192ED03ull * (++e->rng_counter));
-            for (size_t p = 0; p < P; ++p) {
-                int* q = order.data() + p * n;
-                for (int i = 0; i < n; ++i) q[i] = i;
-                for (int i = n - 1; i > 0; --i) std::swap(q[i], q[(int)(splitmix64(s) % (unsigned long long)(i + 1))]);
-            }
-        }
-        int* d_order = e->d_perm + U * (size_t)K * T;
-        HIP_TRY(hipMemcpyAsync(d_order, order.data(), U * sizeof(int), hipMemcpyHostToDevice, e->stream));
-        x.order = d_order;
-        x.old = a.trace + trace_n;
-        x.factor = x.old + P * T;
+        if (order.empty()) host_shuffle(h.seed, ++e->rng_counter, P, n, &order);
+        HIP_TRY(hipMemcpyAsync(e->d_perm + L.order, order.data(), U * sizeof(int), hipMemcpyHostToDevice, e->stream));
+        x.order = e->d_perm + L.order;
+        x.old = e->d_ppo + L.old;
+        x.factor = e->d_ppo + L.factor;
         for (x.k = 0; x.k < n; ++x.k)
             hipLaunchKernelGGL(happo_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, x);
     } else if (h.state_dim > 0) {      // the critics' rows with the state block behind the observations (kernels_mappo_state.hip)
@@ -188,10 +141,10 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->stream));      // `perm` and `order` (pageable) must outlive their copies
     ++e->param_version;
-    if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, U * T * sizeof(float), hipMemcpyDeviceToHost));
-    if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, U * T * sizeof(float), hipMemcpyDeviceToHost));
-    if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, trace_n * sizeof(float), hipMemcpyDeviceToHost));
-    if (hc && hc->factor_out) HIP_TRY(hipMemcpy(hc->factor_out, x.factor, U * T * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, c.trace_n() * sizeof(float), hipMemcpyDeviceToHost));
+    if (hc && hc->factor_out) HIP_TRY(hipMemcpy(hc->factor_out, x.factor, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
     // Buffer_for_PPO.clear() (MAPPO.py:481-482, IPPO.py:321-322, HAPPO.py:456-458): counters only
     for (int p = 0; p < h.P; ++p) { e->index[p] = 0; e->size[p] = 0; }
     return FRL_OK;

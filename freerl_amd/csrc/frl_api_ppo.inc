@@ -1,17 +1,27 @@
 // PPO entry points (included at the end of frl_api.hip).
 
-static int ppo_scratch(frl_engine* e, int T, int k_epochs, int n_mb) {
-    const size_t P = e->h.P;
-    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, P * ((size_t)5 * T + (size_t)k_epochs * n_mb * 2), MEM_DEVICE));
-    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, P * (size_t)k_epochs * T, MEM_DEVICE));
+#include "onpolicy_plan.hpp"
+
+// The call's permutations into d_perm on the engine's stream: the caller's (`host`, narrowed by narrow_perms), ppo_perm_kernel's, or past
+// 8192 rows the host shuffle's.  One rng_counter value per drawn call.  `host` is pageable: it must outlive the copy (the callers synchronise)
+static int onpolicy_perms(frl_engine* e, const OnpolicyCall& c, std::vector<int>* host) {
+    if (c.perms == PERM_DEVICE) {
+        hipLaunchKernelGGL(ppo_perm_kernel, dim3(c.K, (unsigned)c.units), dim3(256), (size_t)c.Tpad * sizeof(unsigned long long), e->stream,
+                           e->d_perm, c.T, c.Tpad, (unsigned long long)(++e->rng_counter), (unsigned long long)e->h.seed);
+        return FRL_OK;
+    }
+    if (c.perms == PERM_HOST) host_shuffle(e->h.seed, ++e->rng_counter, c.units * c.K, c.T, host);
+    HIP_TRY(hipMemcpyAsync(e->d_perm, host->data(), host->size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
     return FRL_OK;
 }
 
-static inline unsigned long long splitmix64(unsigned long long& s) {
-    unsigned long long z = (s += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
+// flush_stage (which takes no rng_counter value), then d_ppo and d_perm grown to the layout's totals
+static int onpolicy_scratch(frl_engine* e, size_t floats, size_t ints) {
+    const int rc = flush_stage(e);
+    if (rc) return rc;
+    HIP_TRY(e->mem.grow(&e->d_ppo, e->ppo_cap, floats, MEM_DEVICE));
+    HIP_TRY(e->mem.grow(&e->d_perm, e->perm_cap, ints, MEM_DEVICE));
+    return FRL_OK;
 }
 
 extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
@@ -19,64 +29,34 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
     if (h.algo != ALGO_PPO) return wrong_engine(h, "frl_ppo_learn");
-    const int T = args->horizon, mb = args->minibatch, K = args->k_epochs;
-    if (T < 2 || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d outside [2, capacity %d]", T, h.capacity);
-    if (mb < 1 || mb > h.batch_max) return fail(FRL_ERR_INVALID, "minibatch %d outside [1,%d]", mb, h.batch_max);
-    if (K < 1) return fail(FRL_ERR_INVALID, "k_epochs must be >= 1");
+    // everything that can refuse the call comes before anything is flushed, grown, uploaded or launched
+    OnpolicyCall c;
+    std::string why;
+    std::vector<int> perm;      // permutations: the caller's np.random.permutation draws (PPO_with_tricks.py:320), else drawn (onpolicy_perms)
+    if (const int rc = plan_onpolicy(ONP_PPO, h.capacity, h.batch_max, h.P, args->horizon, args->minibatch, args->k_epochs, args->perms != nullptr, &c, &why))
+        return fail(rc, "%s", why.c_str());
     if (args->gae_mode != 0 && args->gae_mode != 1) return fail(FRL_ERR_INVALID, "gae_mode %d (0 or 1)", args->gae_mode);
     if (args->gae_mode == 1) {
         if (!args->last_value) return fail(FRL_ERR_INVALID, "gae_mode 1 needs last_value");
         if (h.rec.extra < 3) return fail(FRL_ERR_STATE, "gae_mode 1 needs the value column: extra_cols = log-probs + value + adv_done");
     }
-    const int n_mb = (T + mb - 1) / mb;
-    int rc = flush_stage(e);
-    if (rc) return rc;
-    rc = ppo_scratch(e, T, K, n_mb);
-    if (rc) return rc;
+    if (args->perms && narrow_perms(args->perms, c.perm_n(), c.T, &perm, &why)) return fail(FRL_ERR_INVALID, "%s", why.c_str());
+    const int T = c.T;
     const size_t P = h.P;
-    // permutations: caller's np.random.permutation draws (PPO_with_tricks.py:320), else drawn on the device (a sort of random
-    // keys per learner and epoch; horizons beyond 8192 rows: a host Fisher-Yates)
-    int Tpad = 2;
-    while (Tpad < T) Tpad <<= 1;
-    const bool dev_perm = !args->perms && Tpad <= 8192;
-    std::vector<int> perm(dev_perm ? 0 : P * (size_t)K * T);
-    if (dev_perm) {
-        hipLaunchKernelGGL(ppo_perm_kernel, dim3(K, h.P), dim3(256), (size_t)Tpad * sizeof(unsigned long long), e->stream,
-                           e->d_perm, T, Tpad, (unsigned long long)(++e->rng_counter), (unsigned long long)h.seed);
-    } else if (args->perms) {
-        for (size_t i = 0; i < perm.size(); ++i) {
-            const int64_t v = args->perms[i];
-            if (v < 0 || v >= T) return fail(FRL_ERR_INVALID, "permutation entry %lld outside [0,%d)", (long long)v, T);
-            perm[i] = (int)v;
-        }
-    } else {
-        unsigned long long s = h.seed ^ (0xD1B54A32D192ED03ull * (++e->rng_counter));
-        for (size_t blk = 0; blk < P * (size_t)K; ++blk) {
-            int* q = perm.data() + blk * T;
-            for (int i = 0; i < T; ++i) q[i] = i;
-            for (int i = T - 1; i > 0; --i) {
-                const int j = (int)(splitmix64(s) % (unsigned long long)(i + 1));
-                std::swap(q[i], q[j]);
-            }
-        }
-    }
-    if (!dev_perm) HIP_TRY(hipMemcpyAsync(e->d_perm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    const PpoLayout L = ppo_layout(c);
+    if (const int rc = onpolicy_scratch(e, L.floats, L.ints)) return rc;
+    if (const int rc = onpolicy_perms(e, c, &perm)) return rc;
     PpoArgs a;
     memset(&a, 0, sizeof a);
-    a.horizon = T; a.minibatch = mb; a.k_epochs = K; a.adv_norm = args->adv_norm;
+    a.horizon = T; a.minibatch = c.mb; a.k_epochs = c.K; a.adv_norm = args->adv_norm;
     a.gamma = args->gamma; a.lmbda = args->lmbda; a.clip = args->clip; a.ent_coef = args->ent_coef;
     a.actor_lr = args->actor_lr; a.critic_lr = args->critic_lr;
     a.adam_eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f;
     a.beta1 = 0.9f; a.beta2 = 0.999f;
     a.clip_norm = args->clip_norm;
     a.optimizer = args->optimizer;
-    float* q = e->d_ppo;
-    a.td = q; q += P * T;
-    a.vs = q; q += P * T;
-    a.adv_raw = q; q += P * T;
-    a.adv = q; q += P * T;
-    a.vtarget = q; q += P * T;
-    a.trace = q;
+    a.td = e->d_ppo + L.td; a.vs = e->d_ppo + L.vs; a.adv_raw = e->d_ppo + L.adv_raw; a.adv = e->d_ppo + L.adv;
+    a.vtarget = e->d_ppo + L.vtarget; a.trace = e->d_ppo + L.trace;
     a.perm = e->d_perm;
     if (h.obs_norm_on)      // learn(): obs = norm(obs) over the whole horizon updates the statistics (PPO_with_tricks.py:297-299)
         hipLaunchKernelGGL(obsnorm_kernel, dim3(h.P), dim3(256), 0, e->stream, e->d, T, 1, 0);
@@ -107,10 +87,11 @@ extern "C" int frl_ppo_learn(frl_engine* e, const frl_ppo_args* args) {
         hipLaunchKernelGGL(ppo_update_kernel, dim3(h.P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
     }
     HIP_TRY(hipGetLastError());
+    ++e->param_version;      // as its siblings do; read only on wide and solow engines, which a PPO engine never is: nothing observable changes
     HIP_TRY(hipStreamSynchronize(e->stream));      // `perm` (pageable) must outlive the copy
-    if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, P * T * sizeof(float), hipMemcpyDeviceToHost));
-    if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, P * T * sizeof(float), hipMemcpyDeviceToHost));
-    if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, P * (size_t)K * n_mb * 2 * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
+    if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, c.trace_n() * sizeof(float), hipMemcpyDeviceToHost));
     // Buffer_for_PPO.clear() (PPO_with_tricks.py:354): counters only
     for (int p = 0; p < h.P; ++p) { e->index[p] = 0; e->size[p] = 0; }
     return FRL_OK;

@@ -16,6 +16,27 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _trace_steps(horizon, minibatch, k_epochs):
+    """minibatch steps of an on-policy learn call: k_epochs * ceil(horizon / minibatch).  (An argument < 1: the library refuses the call;
+    the guards only let it get there.)"""
+    return max(int(k_epochs), 0) * max((int(horizon) + int(minibatch) - 1) // max(int(minibatch), 1), 0)
+
+
+def _perm_arg(a, keep, perms, shape):
+    """a caller's minibatch permutations into `a.perms` (int64 of `shape`); None: the library draws them"""
+    if perms is not None:
+        pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(shape)
+        keep.append(pm)
+        a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def _want_outputs(a, out, wanted):
+    """allocates the outputs a caller asked for: (key of `out`, field of the args struct, shape) each"""
+    for key, field, shape in wanted:
+        out[key] = np.zeros(shape, dtype=F32)
+        setattr(a, field, _fp(out[key]))
+
+
 def make_config(algo, obs_dim, act_dim, capacity, *, n_learners=1, discrete=False, hidden=128,
                 hidden_act=N.ACT_RELU, twin_critic=False, batch_max=256, extra_cols=0, device_id=0, seed=0, actor_dist=0, dueling=False, noisy=False, c51=None, reward_dim=0,
                 state_dim=0, state_rows=N.STATE_ROWS_POSITION):
@@ -402,24 +423,16 @@ class Engine:
         a.gamma, a.lmbda, a.clip, a.ent_coef = gamma, lmbda, clip, ent_coef
         a.actor_lr, a.critic_lr, a.adam_eps, a.clip_norm = actor_lr, critic_lr, adam_eps, clip_norm
         a.optimizer = int(optimizer)
-        keep = []
-        if perms is not None:
-            pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, int(k_epochs), int(horizon))
-            keep.append(pm)
-            a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
+        keep, out = [], {}
+        _perm_arg(a, keep, perms, (self.P, int(k_epochs), int(horizon)))
         if last_value is not None:
             lv = np.ascontiguousarray(np.broadcast_to(np.asarray(last_value, dtype=F32).reshape(-1), (self.P,)))
             keep.append(lv)
             a.gae_mode, a.last_value, a.gae_gamma, a.gae_lmbda = 1, _fp(lv), float(gamma), float(lmbda)
-        n_mb = (int(horizon) + int(minibatch) - 1) // int(minibatch)
-        out = {}
         if want_trace:
-            out["trace"] = np.zeros((self.P, int(k_epochs) * n_mb, 2), dtype=F32)
-            a.loss_trace_out = _fp(out["trace"])
+            _want_outputs(a, out, [("trace", "loss_trace_out", (self.P, _trace_steps(horizon, minibatch, k_epochs), 2))])
         if want_adv:
-            out["adv"] = np.zeros((self.P, int(horizon)), dtype=F32)
-            out["v_target"] = np.zeros((self.P, int(horizon)), dtype=F32)
-            a.adv_out, a.vtarget_out = _fp(out["adv"]), _fp(out["v_target"])
+            _want_outputs(a, out, [("adv", "adv_out", (self.P, int(horizon))), ("v_target", "vtarget_out", (self.P, int(horizon)))])
         N.check(self._L.frl_ppo_learn(self._h, C.byref(a)))
         return out
 
@@ -442,17 +455,10 @@ class Engine:
             rw = np.ascontiguousarray(rewards, dtype=F32).reshape(self.P, T)
             keep.append(rw)
             a.rewards = _fp(rw)
-        if perms is not None:
-            pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, K, T)
-            keep.append(pm)
-            a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
-        n_mb = (T + int(minibatch) - 1) // max(int(minibatch), 1)
+        _perm_arg(a, keep, perms, (self.P, K, T))
         out = {}
-        for name, field, shape in (("adv", "adv_out", (self.P, T)), ("returns", "returns_out", (self.P, T)),
-                                   ("logp_old", "logp_old_out", (self.P, T)), ("trace", "loss_trace_out", (self.P, max(K, 0) * n_mb, 2))):
-            if name in want:
-                out[name] = np.zeros(shape, dtype=F32)
-                setattr(a, field, _fp(out[name]))
+        _want_outputs(a, out, [w for w in (("adv", "adv_out", (self.P, T)), ("returns", "returns_out", (self.P, T)), ("logp_old", "logp_old_out", (self.P, T)),
+                                           ("trace", "loss_trace_out", (self.P, _trace_steps(T, minibatch, K), 2))) if w[0] in want])
         N.check(self._L.frl_gail_ppo_learn(self._h, C.byref(a)))
         return out
 
@@ -659,18 +665,12 @@ class Engine:
         a.adv_norm, a.value_clip = int(bool(adv_norm)), int(bool(value_clip))
         if huber_delta is not None:
             a.loss_kind, a.huber_delta = N.LOSS_HUBER, float(huber_delta)
-        if perms is not None:
-            pm = np.ascontiguousarray(perms, dtype=np.int64).reshape(self.P, self.n_agents, int(k_epochs), int(horizon))
-            keep.append(pm)
-            a.perms = pm.ctypes.data_as(C.POINTER(C.c_int64))
-        n_mb = (int(horizon) + int(minibatch) - 1) // max(int(minibatch), 1)      # (minibatch < 1: the library refuses the call)
+        _perm_arg(a, keep, perms, (self.P, self.n_agents, int(k_epochs), int(horizon)))
         if want_trace:
-            out["trace"] = np.zeros((self.P, self.n_agents, int(k_epochs) * n_mb, 2), dtype=F32)
-            a.loss_trace_out = _fp(out["trace"])
+            _want_outputs(a, out, [("trace", "loss_trace_out", (self.P, self.n_agents, _trace_steps(horizon, minibatch, k_epochs), 2))])
         if want_adv:
-            out["adv"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
-            out["v_target"] = np.zeros((self.P, int(horizon), self.n_agents), dtype=F32)
-            a.adv_out, a.vtarget_out = _fp(out["adv"]), _fp(out["v_target"])
+            shape = (self.P, int(horizon), self.n_agents)
+            _want_outputs(a, out, [("adv", "adv_out", shape), ("v_target", "vtarget_out", shape)])
 
     def mappo_learn(self, horizon, minibatch, k_epochs, **kw):
         """MAPPO.learn / IPPO.learn for every learner (frl_mappo_learn): gamma, lmbda, clip, ent_coef, actor_lr, critic_lr, adam_eps=1e-8,
@@ -693,8 +693,7 @@ class Engine:
             keep.append(od)
             a.agent_order = od.ctypes.data_as(C.POINTER(C.c_int32))
         if want_factor:
-            out["factor"] = np.zeros((self.P, self.n_agents, int(horizon)), dtype=F32)
-            a.factor_out = _fp(out["factor"])
+            _want_outputs(a, out, [("factor", "factor_out", (self.P, self.n_agents, int(horizon)))])
         N.check(self._L.frl_happo_learn(self._h, C.byref(a)))
         return out
 
