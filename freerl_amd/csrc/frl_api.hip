@@ -14,6 +14,7 @@
 #include "../../include/freerl_hip.h"
 #include "frl_desc.h"
 #include "engine_plan.hpp"
+#include "learn_plan.hpp"
 #include "her_plan.h"
 #include "host_mem.hpp"
 
@@ -168,6 +169,8 @@ struct frl_engine : frl::EngineFacts {      // (what the plan fixed: family, lds
     bool ma_pre_valid = false;
     unsigned long long ma_pre_counter = 0;
     int ma_pre_size = 0, ma_pre_batch = 0;
+    frl::LearnKnobs knobs;                // the per-call knobs of the off-policy learn call in progress (frl_api_learn.inc: learn_knobs)
+    std::vector<int> idx_narrow;          // ... and its caller's idx, narrowed by the plan (kept for its capacity)
     int* h_solo_err = nullptr;            // pinned: a solo workgroup that waited 2 s for its learner's others sets it (checked after syncs: solo_err_check)
     int* d_solo_ticket = nullptr;         // the rollout tail's learner ticket
     unsigned solo_bar_base = 0;           // arrivals every counter has seen (one counting barrier per launch: kSoloWG)
@@ -430,9 +433,10 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
     e->staged_per_learner.assign(P, 0);
     if (h.algo == ALGO_DQN) CREATE_TRY(set_family_lds_attributes(FAM_DQN_FUSED));
     if (h.algo == ALGO_DQN || e->family != FAM_ROWCHUNK) e->kern = resolve_learn_kernels(h.algo == ALGO_DQN ? FAM_DQN_FUSED : e->family, e->chain_waves, e->actor_park, h);
-    // (a vector reward: batch_max counts rows = batch x weight_num; the draw is for `batch` of them)
-    if (h.batch_max > 256 && (4 * h.batch_max <= kDrawTableHost || T.vector_reward))     // draw_kernel's duplicate table for batches of 257 .. 2048 rows (device/net.hpp)
-        CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 2048 + 2 * kDrawTableHost) * (int)sizeof(int)));
+    // the most LDS a draw of any batch up to batch_max asks for (learn_plan.hpp: the duplicate table of batches of 257 .. 2048 rows; a vector
+    // reward's batch_max counts rows = batch x weight_num and still bounds the batch)
+    if (draw_lds_max(h.batch_max) > 64 * 1024)
+        CREATE_TRY(hipFuncSetAttribute((const void*)draw_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)draw_lds_max(h.batch_max)));
     if (e->family != FAM_ROWCHUNK) CREATE_TRY(set_family_lds_attributes(e->family));
     if (e->family == FAM_SOLO || e->family == FAM_CHAINED)         // select_action on fragment-image nets, the solo rollout tail's act_frag_body
         CREATE_TRY(hipFuncSetAttribute((const void*)act_frag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, critic2_lds_floats() * (int)sizeof(float)));
@@ -1067,32 +1071,16 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
 }
 
 // ------------------------------------------------------------------------------------ learn
-static int upload_idx_noise(frl_engine* e, const int64_t* idx, const float* noise, int batch, int n_sets_per_learner) {
+// a caller's smoothing / exploration noise (a caller's idx: frl_api_learn.inc, upload_idx, behind the plan's range check)
+static int upload_noise(frl_engine* e, const float* noise, int batch) {
+    if (!noise) return FRL_OK;
     const EngineDesc& h = e->h;
-    if (idx || noise) HIP_TRY(hipStreamSynchronize(e->stream));    // pinned scratch reuse
-    if (idx) {
-        for (int p = 0; p < h.P; ++p)
-            for (int a = 0; a < n_sets_per_learner; ++a) {
-                const int64_t* src = idx + ((size_t)p * n_sets_per_learner + a) * batch;
-                int* dst = e->h_idx + ((size_t)p * h.n_agents + a) * h.batch_max;
-                const int sz = e->size[p];
-                for (int i = 0; i < batch; ++i) {
-                    int64_t v = src[i];
-                    if (v < 0) v += h.capacity;
-                    if (v < 0 || v >= h.capacity) return fail(FRL_ERR_INVALID, "sample index %lld out of range", (long long)src[i]);
-                    (void)sz;
-                    dst[i] = (int)v;
-                }
-            }
-        HIP_TRY(hipMemcpyAsync(h.idx, e->h_idx, e->idx_count * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    }
-    if (noise) {
-        // host [P][n_agents][noise_sets][batch][act_max] -> device [P][n_agents][noise_sets][batch_max][act_max]
-        const int am = h.act_max;
-        for (size_t s = 0; s < (size_t)h.P * h.n_agents * h.noise_sets; ++s)
-            memcpy(e->h_noise + s * h.batch_max * am, noise + s * batch * am, (size_t)batch * am * sizeof(float));
-        HIP_TRY(hipMemcpyAsync(h.noise, e->h_noise, e->noise_count * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    }
+    HIP_TRY(hipStreamSynchronize(e->stream));    // pinned scratch reuse
+    // host [P][n_agents][noise_sets][batch][act_max] -> device [P][n_agents][noise_sets][batch_max][act_max]
+    const int am = h.act_max;
+    for (size_t s = 0; s < (size_t)h.P * h.n_agents * h.noise_sets; ++s)
+        memcpy(e->h_noise + s * h.batch_max * am, noise + s * batch * am, (size_t)batch * am * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(h.noise, e->h_noise, e->noise_count * sizeof(float), hipMemcpyHostToDevice, e->stream));
     return FRL_OK;
 }
 

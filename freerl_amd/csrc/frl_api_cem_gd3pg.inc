@@ -57,44 +57,14 @@ extern "C" int frl_cem_gd3pg_learn(frl_engine* e, const frl_cem_gd3pg_args* args
     const EngineDesc& h = e->h;
     if (h.algo != ALGO_CEM_GD3PG) return wrong_engine(h, "frl_cem_gd3pg_learn");
     const int P = h.P, C = e->ring_cap;
-    if (args->batch < 2) return fail(FRL_ERR_INVALID, "batch %d must be >= 2 (half of it comes from each ring)", args->batch);
-    for (const float v : {args->gamma, args->tau, args->actor_lr, args->critic_lr, args->lambda})
-        if (!(v == v)) return fail(FRL_ERR_INVALID, "gamma / tau / actor_lr / critic_lr / lambda is NaN");
-    if (!args->f1_more || !args->delta) return fail(FRL_ERR_INVALID, "f1_more / delta is NULL (one entry per learner)");
-    for (int p = 0; p < P; ++p)
-        if (!(args->delta[p] == args->delta[p])) return fail(FRL_ERR_INVALID, "delta of learner %d is NaN", p);
-    // sample() (:160-164): total = len(buffer_domain) bounds the batch AND both draws; the population shares one launch shape, so its
-    // smallest ring 1 decides
-    const int* size1 = e->size.data() + P;
-    int min1 = C;
-    for (int p = 0; p < P; ++p) min1 = std::min(min1, size1[p]);
-    if (min1 < 2) {
-        int who = 0;
-        for (int p = 0; p < P; ++p) if (size1[p] == min1) { who = p; break; }
-        return fail(FRL_ERR_STATE, "ring 1 (buffer_domain) of learner %d holds %d rows < 2: no half batch can be drawn from it", who, min1);
-    }
-    const int half = std::min(min1, args->batch) / 2, rows = 2 * half;
-    if (rows > h.batch_max) return fail(FRL_ERR_INVALID, "2 x half = %d rows > batch_max %d", rows, h.batch_max);
-    const size_t draw_lds = (size_t)2 * ((half + 3) & ~3) * sizeof(int);
-    if (!args->idx && draw_lds > 64 * 1024) return fail(FRL_ERR_INVALID, "device index draw of 2 x %d rows does not fit the draw kernel's LDS; pass idx", half);
-    if (args->idx) {
-        HIP_TRY(hipStreamSynchronize(e->stream));                       // pinned scratch reuse
-        for (int p = 0; p < P; ++p)
-            for (int r = 0; r < 2; ++r) {
-                const int64_t* src = args->idx + ((size_t)p * 2 + r) * half;
-                int* dst = e->h_idx + idx_offset(h, p, 0, r * half);
-                const int bound = r == 0 ? C : size1[p];      // ring 0: rows never written are zeros, as the reference's (:165-167)
-                for (int i = 0; i < half; ++i) {
-                    if (src[i] < 0 || src[i] >= bound)
-                        return fail(FRL_ERR_INVALID, "learner %d: idx entry %lld of ring %d outside [0, %d) (%s)", p, (long long)src[i], r, bound,
-                                    r == 0 ? "its capacity" : "the rows it holds");
-                    dst[i] = (int)src[i] + r * C;
-                }
-            }
-    }
+    e->knobs = learn_knobs();
+    CemPlan pl;
+    std::string why;
+    if (const int prc = plan_cem_gd3pg(h, e->size.data() + P, C, *args, &pl, &e->idx_narrow, &why)) return fail(prc, "%s", why.c_str());
+    const int half = pl.half, rows = pl.rows, min1 = pl.min1;
     int rc = flush_stage(e);
     if (rc) return rc;
-    if (args->idx) HIP_TRY(hipMemcpyAsync(h.idx, e->h_idx, e->idx_count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    if (args->idx) { rc = upload_idx(e, e->idx_narrow, 1, rows); if (rc) return rc; }      // (a learner's two halves side by side)
     // is_F1_more and delta of every learner, staged in two alternating pinned slots (the call does not wait for the stream)
     const unsigned slot = e->ep_seq++ & 1u;
     float* hc = e->h_cem_ctl + (size_t)slot * 2 * P;
@@ -109,11 +79,11 @@ extern "C" int frl_cem_gd3pg_learn(frl_engine* e, const frl_cem_gd3pg_args* args
     a.rows = rows; a.half = half; a.size1 = min1; a.ring_cap = C;
     a.gamma = args->gamma; a.lambda = args->lambda; a.tau = args->tau; a.actor_lr = args->actor_lr; a.critic_lr = args->critic_lr;
     a.p0 = 0; a.p_count = P;
-    const int ns = rowchunk_ns(h, rows);
+    const int ns = pl.ns;
     if (!args->idx) {
         a.rng_counter = e->rng_counter++;
         prof_begin(e, PK_DRAW);
-        hipLaunchKernelGGL(cem_draw_kernel, dim3(P), dim3(256), draw_lds, e->stream, e->d, a);
+        hipLaunchKernelGGL(cem_draw_kernel, dim3(P), dim3(256), pl.draw_lds, e->stream, e->d, a);
         prof_end(e);
     }
     const dim3 blk(256);

@@ -6,14 +6,8 @@
 // envelope_grad_kernel (row chunks over the batch x weight_num rows) -> reduce + Adam + soft update (launch_adam: net 0, statistics
 // in the actor slots, no clipping — the reference's clip_grad_norm_ runs between zero_grad() and backward(), on gradients that are None).
 
-// Both envelope entry points up to and including envelope_weights_kernel: validation, the staged rows, idx and the preference vectors
-// on the device, the draw.  `scalars` (named in `scalar_names`) are refused when NaN.
-struct EnvelopeCall {
-    int batch, weight_num;
-    float gamma, beta;
-    const int64_t* idx;
-    const float* weights;
-};
+// Both envelope entry points up to and including envelope_weights_kernel: the plan (learn_plan.hpp: plan_envelope — `scalars`, named in
+// `scalar_names`, are refused when NaN), then the staged rows, idx and the preference vectors on the device, the draw.
 struct EnvelopeLaunch {
     EnvelopeArgs a;
     int rows, ns;                   // batch x weight_num; workgroups (= slabs) per learner
@@ -21,25 +15,13 @@ struct EnvelopeLaunch {
 static int envelope_prelude(frl_engine* e, const EnvelopeCall& c, std::initializer_list<float> scalars, const char* scalar_names, EnvelopeLaunch* out) {
     const EngineDesc& h = e->h;
     const int B = c.batch, W = c.weight_num, RD = h.reward_dim, P = h.P;
-    if (B < 1) return fail(FRL_ERR_INVALID, "batch %d must be >= 1", B);
-    if (W < 1) return fail(FRL_ERR_INVALID, "weight_num %d must be >= 1", W);
-    if ((long long)B * W > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d x weight_num %d = %lld rows > batch_max %d", B, W, (long long)B * W, h.batch_max);
-    for (const float v : scalars)
-        if (!(v == v)) return fail(FRL_ERR_INVALID, "%s is NaN", scalar_names);
-    if (c.beta < 0.f || c.beta > 1.f) return fail(FRL_ERR_INVALID, "beta %g outside [0, 1]", (double)c.beta);
-    int min_size = h.capacity;
-    for (int p = 0; p < P; ++p) min_size = std::min(min_size, e->size[p]);
-    if (min_size < B) return fail(FRL_ERR_STATE, "a ring holds %d rows < batch %d", min_size, B);
-    const bool dev_idx = c.idx == nullptr;
-    const bool table = B > 256 && 4 * B <= kDrawTableHost;
-    const size_t draw_lds = ((size_t)2 * ((B + 3) & ~3) + (table ? 2 * kDrawTableHost : 0)) * sizeof(int);
-    if (dev_idx && min_size < 2 * B) return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
-    if (dev_idx && draw_lds > (size_t)(2 * 2048 + 2 * kDrawTableHost) * sizeof(int))
-        return fail(FRL_ERR_INVALID, "device index draw of %d rows does not fit the draw kernel's LDS; pass idx", B);
+    e->knobs = learn_knobs();
+    EnvelopePlan pl;
+    std::string why;
+    if (const int rc = plan_envelope(h, e->size.data(), c, scalars, scalar_names, &pl, &e->idx_narrow, &why)) return fail(rc, "%s", why.c_str());
     int rc = flush_stage(e);
     if (rc) return rc;
-    rc = upload_idx_noise(e, c.idx, nullptr, B, 1);
-    if (rc) return rc;
+    if (c.idx) { rc = upload_idx(e, e->idx_narrow, 1, B); if (rc) return rc; }
     const size_t wpitch = (size_t)h.batch_max * RD, wn = (size_t)W * RD;
     if (c.weights) {
         HIP_TRY(hipStreamSynchronize(e->stream));                       // pinned staging reuse
@@ -54,14 +36,14 @@ static int envelope_prelude(frl_engine* e, const EnvelopeCall& c, std::initializ
     a.gamma = c.gamma; a.beta = c.beta;
     a.p0 = 0; a.p_count = P;
     ++e->param_version;
-    out->rows = B * W;
-    out->ns = rowchunk_ns(h, out->rows);
-    if (dev_idx) {
+    out->rows = pl.rows;
+    out->ns = pl.ns;
+    if (pl.dev_idx) {
         LearnArgs la;
         memset(&la, 0, sizeof la);
-        la.batch = B; la.size = min_size; la.device_rng = 1; la.rng_counter = e->rng_counter++; la.p0 = 0; la.p_count = P;
+        la.batch = B; la.size = pl.min_size; la.device_rng = 1; la.rng_counter = e->rng_counter++; la.p0 = 0; la.p_count = P;
         prof_begin(e, PK_DRAW);
-        hipLaunchKernelGGL(draw_kernel, dim3(P), dim3(256), draw_lds, e->stream, e->d, la, table ? 0 : 2);
+        hipLaunchKernelGGL(draw_kernel, dim3(P), dim3(256), pl.draw.lds_bytes, e->stream, e->d, la, pl.draw.flag);
         prof_end(e);
     }
     a.rng_counter = e->rng_counter++;

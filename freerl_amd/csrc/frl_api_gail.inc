@@ -12,28 +12,13 @@ extern "C" int frl_gail_learn(frl_engine* e, const frl_gail_args* args) {
     if (h.algo != ALGO_GAIL) return wrong_engine(h, "frl_gail_learn");
     const int E = args->n_expert, NP = args->n_policy, P = h.P;
     const int IN = h.rec.obs_dim[0] + h.rec.act_dim[0];
-    if (E < 1 || E > h.batch_max) return fail(FRL_ERR_INVALID, "n_expert %d outside [1, batch_max %d]", E, h.batch_max);
-    if (NP < 1 || NP > h.batch_max) return fail(FRL_ERR_INVALID, "n_policy %d outside [1, batch_max %d]", NP, h.batch_max);
-    if (args->gp != 0 && args->gp != 1) return fail(FRL_ERR_INVALID, "gp %d must be 0 or 1", args->gp);
-    for (const float v : {args->gp_weight, args->lr, args->beta1, args->beta2, args->adam_eps})
-        if (!(v == v)) return fail(FRL_ERR_INVALID, "gp_weight / lr / beta1 / beta2 / adam_eps is NaN");
-    if (args->gp_weight < 0.f) return fail(FRL_ERR_INVALID, "gp_weight %g must be >= 0", (double)args->gp_weight);
-    if (args->beta1 < 0.f || args->beta1 >= 1.f || args->beta2 < 0.f || args->beta2 >= 1.f)
-        return fail(FRL_ERR_INVALID, "betas (%g, %g) outside [0, 1)", (double)args->beta1, (double)args->beta2);
-    if (!args->policy_rows) return fail(FRL_ERR_INVALID, "policy_rows is NULL");
-    int min_size = h.capacity;
-    for (int p = 0; p < P; ++p) min_size = std::min(min_size, e->size[p]);
-    if (min_size < 1) return fail(FRL_ERR_STATE, "a learner's ring is empty: store the expert rows first");
-    if (args->idx)
-        for (int p = 0; p < P; ++p)
-            for (int i = 0; i < E; ++i) {
-                const int64_t v = args->idx[(size_t)p * E + i];
-                if (v < 0 || v >= e->size[p]) return fail(FRL_ERR_STATE, "idx entry %lld of learner %d is not one of its %d stored rows", (long long)v, p, e->size[p]);
-            }
+    e->knobs = learn_knobs();
+    GailPlan pl;
+    std::string why;
+    if (const int prc = plan_gail(h, e->size.data(), *args, &pl, &e->idx_narrow, &why)) return fail(prc, "%s", why.c_str());
     int rc = flush_stage(e);
     if (rc) return rc;
-    rc = upload_idx_noise(e, args->idx, nullptr, E, 1);
-    if (rc) return rc;
+    if (args->idx) { rc = upload_idx(e, e->idx_narrow, 1, E); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(e->stream));                           // pinned staging reuse
     const size_t pitch = (size_t)h.batch_max * IN, rn = (size_t)NP * IN;
     for (int p = 0; p < P; ++p) {
@@ -43,9 +28,9 @@ extern "C" int frl_gail_learn(frl_engine* e, const frl_gail_args* args) {
     GailArgs a;
     memset(&a, 0, sizeof a);
     a.n_expert = E; a.n_policy = NP; a.gp = args->gp; a.gp_weight = args->gp_weight;
-    a.size = min_size; a.p0 = 0; a.p_count = P;
+    a.size = pl.min_size; a.p0 = 0; a.p_count = P;
     ++e->param_version;
-    const int ns = rowchunk_ns(h, E + NP);
+    const int ns = pl.ns;
     if (!args->idx) {
         a.rng_counter = e->rng_counter++;
         prof_begin(e, PK_DRAW);

@@ -1,5 +1,7 @@
 // frl_learn(): the ONE table of the kernel families' kernels and LDS bytes (a new family is registered there; which family an engine
-// learns with is engine_plan.hpp's decision), a launcher per family, learn_impl and the work models.  Part of frl_api.hip.
+// learns with is engine_plan.hpp's decision), a launcher per family, learn_impl and the work models.  What a call decides — refusals,
+// defaults, who draws, which launches in which order — is learn_plan.hpp's plan_learn; the launchers here hold the launch lines and the
+// profile brackets.  Part of frl_api.hip.
 
 // --------------------------------------------------------------------------- the family table
 enum LearnKernelStage { LK_CRITIC, LK_CRITIC_NV, LK_ACTOR, LK_ACTOR_RECOMPUTE, LK_STEP };
@@ -69,10 +71,36 @@ static LearnKernels resolve_learn_kernels(LearnFamily fam, int chain_waves, bool
     return K;
 }
 
-// The family THIS call runs and the workgroups per learner of its one-launch DQN update (engine_plan.hpp), under the per-call knobs
-// FRL_DQN_FUSED=0/1 and FRL_DQN_SPLIT
-static LearnFamily learn_family(const frl_engine* e, int batch) { return learn_family(e->h, e->family, batch, env_flag("FRL_DQN_FUSED", true)); }
-static int dqn_split_for(const EngineDesc& h, int batch, int pc) { return dqn_split_for(h, batch, pc, env_set("FRL_DQN_SPLIT") ? env_int("FRL_DQN_SPLIT", 0) : -1); }
+// The per-call knobs of every off-policy learn entry point (learn_plan.hpp: LearnKnobs), read here and nowhere else: each entry point
+// leaves them in e->knobs at its head, the launchers take them from there.  ONE walk over the environment instead of a getenv per knob
+// (each of which is such a walk): this runs in front of every learn call of the 53 us single-learner step
+extern char** environ;
+static LearnKnobs learn_knobs() {
+    LearnKnobs k;
+    for (char** ev = environ; ev && *ev; ++ev) {
+        const char* s = *ev;
+        if (strncmp(s, "FRL_", 4) != 0) continue;
+        auto is = [s](const char* name, const char** value) {
+            const size_t n = strlen(name);
+            if (strncmp(s + 4, name, n) != 0 || s[4 + n] != '=') return false;
+            *value = s + 4 + n + 1;
+            return true;
+        };
+        const char* v = nullptr;
+        if (is("DQN_FUSED", &v)) k.dqn_fused = atoi(v) != 0;
+        else if (is("DQN_SPLIT", &v)) k.dqn_split = atoi(v);
+        else if (is("DRAW_SCAN", &v)) k.draw_scan = atoi(v) != 0;
+        else if (is("ADAM_TWO_PASS", &v)) k.adam_two_pass = true;
+        else if (is("STAGGER", &v)) k.stagger = atoi(v);
+        else if (is("STAGGER_GROUPS", &v)) k.stagger_groups = clamp_stagger_groups(atoi(v));
+        else if (is("CRITIC2_NOVEC", &v)) k.critic2_novec = true;
+        else if (is("SOLO_PREDRAW", &v)) k.solo_predraw = atoi(v) != 0;
+        else if (is("SOLOW_FUSE", &v)) k.solow_fuse = atoi(v) != 0;
+    }
+    return k;
+}
+// The family a call made NOW would run and the workgroups per learner of its one-launch DQN update (engine_plan.hpp)
+static LearnFamily learn_family(const frl_engine* e, int batch) { return learn_family(e->h, e->family, batch, knob_flag(learn_knobs().dqn_fused, true)); }
 
 // frl_learn_path / frl_learn_work / frl_learn_work_executed describe frl_learn(): not the engines that learn through another entry point
 // (a PPO engine: frl_learn_path has always said FRL_ERR_INVALID, the work models report no work; a replay-only engine is let through)
@@ -87,7 +115,8 @@ extern "C" int frl_learn_path(const frl_engine* e, int batch, int* chained_out, 
     const EngineDesc& h = e->h;
     if (const int rc = describes_learn_guard(h, "frl_learn_path", true)) return rc;
     if (batch <= 0 || batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch out of range");
-    const LearnPath path = learn_path(h, *e, learn_family(e, batch), batch, dqn_split_for(h, batch, h.P));
+    const LearnKnobs k = learn_knobs();
+    const LearnPath path = learn_path(h, *e, learn_family(h, e->family, batch, knob_flag(k.dqn_fused, true)), batch, dqn_split_for(h, batch, h.P, k.dqn_split));
     if (chained_out) *chained_out = path.chained;
     if (bytes_out) *bytes_out = path.bytes;
     if (rows_out) *rows_out = path.rows;
@@ -110,7 +139,7 @@ static void launch_adam(frl_engine* e, hipStream_t st, const AdamArgs& ad, int u
         const int net = (h.algo == ALGO_DQN) ? 0 : (ad.which == 0 ? 2 * ag + 1 : 2 * ag);
         max_n4 = std::max(max_n4, h.net[net].size / 4);
     }
-    const bool two_pass = env_set("FRL_ADAM_TWO_PASS");
+    const bool two_pass = e->knobs.adam_two_pass;
     if (max_n4 <= kFusedThreads * kFusedVec && !h.noisy && !two_pass) {
         hipLaunchKernelGGL(adam_fused_kernel, dim3(units), dim3(kFusedThreads), 0, st, e->d, ad);
     } else if (max_n4 <= kFusedThreads * kFusedVecWide && !two_pass) {       // (also every NoisyLinear head: the sigma gradients)
@@ -126,29 +155,23 @@ static void launch_adam(frl_engine* e, hipStream_t st, const AdamArgs& ad, int u
 struct LearnStage {
     hipStream_t st;
     int stage, p0, pc, units;       // units = (learner, agent) pairs
-    bool dev_rng, needs_noise;
 };
 
-// the head of stage 0 of every family but the one-launch DQN update
-static void launch_draw_and_prologue(frl_engine* e, const LearnStage& s, const LearnArgs& a, bool draw) {
-    const EngineDesc& h = e->h;
+// what the plan puts in front of a launch
+static void launch_prologue(frl_engine* e, const LearnStage& s, const LearnPlan& pl, const LearnLaunch& l) {
     const dim3 blk(256);
-    if (draw) {
+    if (l.draw) {
         prof_begin(e, PK_DRAW);
-        const bool table = a.batch > 256 && 4 * a.batch <= kDrawTableHost && !env_flag("FRL_DRAW_SCAN", false);     // (developer / test knob: no duplicate table)
-        const size_t draw_lds = ((size_t)2 * ((a.batch + 3) & ~3) + (table ? 2 * kDrawTableHost : 0)) * sizeof(int);
-        hipLaunchKernelGGL(draw_kernel, dim3(s.units), blk, draw_lds, s.st, e->d, a, (s.needs_noise ? 1 : 0) | (table ? 0 : 2));
+        hipLaunchKernelGGL(draw_kernel, dim3(s.units), blk, pl.draw.lds_bytes, s.st, e->d, pl.a, (pl.needs_noise ? 1 : 0) | pl.draw.flag);
         prof_end(e);
     }
-    if (h.obs_norm_on && h.algo != ALGO_DQN)                         // sample(): norm(obs) updates the statistics first
-        hipLaunchKernelGGL(obsnorm_kernel, dim3(s.pc), blk, 0, s.st, e->d, a.batch, 0, s.p0);
-    if (h.noisy)      // sets: 0 online on s' (Double only), 1 target on s', 2 online on s
-        hipLaunchKernelGGL(noisy_materialise_kernel, dim3(h.P), blk, 0, s.st, e->d, 0, 3, 0x2);
+    if (l.obsnorm) hipLaunchKernelGGL(obsnorm_kernel, dim3(s.pc), blk, 0, s.st, e->d, pl.a.batch, 0, s.p0);
+    if (l.noisy_materialise)      // sets: 0 online on s' (Double only), 1 target on s', 2 online on s
+        hipLaunchKernelGGL(noisy_materialise_kernel, dim3(e->h.P), blk, 0, s.st, e->d, 0, 3, 0x2);
 }
 
 // kernels_dqn2.hip: draw + update + Adam + soft update in one launch (`step`, frl_rollout: add() and the next select_action too)
-static void launch_dqn_fused(frl_engine* e, const LearnStage& s, LearnArgs a, const DqnStepArgs* step) {
-    a.dqn_split = dqn_split_for(e->h, a.batch, s.pc);
+static void launch_dqn_fused(frl_engine* e, const LearnStage& s, const LearnArgs& a, const DqnStepArgs* step) {
     prof_begin(e, PK_GRAD_CRITIC);
     const DqnStepArgs sa = step ? *step : DqnStepArgs{};
     hipLaunchKernelGGL(e->kern.critic.kd, dim3(s.pc * a.dqn_split), dim3(256), (size_t)e->kern.lds_bytes, s.st, e->d, a, sa);
@@ -197,17 +220,11 @@ static void launch_rowchunk(frl_engine* e, const LearnStage& s, const LearnArgs&
 }
 
 // kernels_critic2.hip / kernels_actor2.hip: a whole stage of DDPG / TD3 / SAC in one launch, one workgroup per learner
-static void launch_chained(frl_engine* e, const LearnStage& s, LearnArgs a) {
+static void launch_chained(frl_engine* e, const LearnStage& s, LearnArgs a, bool critic_nv) {
     const LearnKernels& K = e->kern;
     LearnKernel k = K.actor.k;
-    if (s.stage == 0) {
-        a.stagger = env_int("FRL_STAGGER", 0);         // developer knob: spread the Adam bursts of the first round
-        a.stagger_groups = env_int("FRL_STAGGER_GROUPS", 4); a.stagger_wgs = e->n_cus;
-        // (_nv: next_obs 16-byte aligned with its 16 columns inside the row, (reward, done) an aligned pair)
-        const RecordDesc& R = e->h.rec;
-        const bool nv = R.nobs_off[0] % 4 == 0 && R.nobs_off[0] + 16 <= R.stride && R.rew_off % 2 == 0 && R.done_off == R.rew_off + 1 && !env_set("FRL_CRITIC2_NOVEC");
-        k = (nv && K.critic_nv.k) ? K.critic_nv.k : K.critic.k;
-    }
+    if (s.stage == 0) k = (critic_nv && K.critic_nv.k) ? K.critic_nv.k : K.critic.k;
+    else a.stagger = a.stagger_groups = a.stagger_wgs = 0;      // (the critic stage's alone)
     prof_begin(e, s.stage == 0 ? PK_GRAD_CRITIC : PK_GRAD_ACTOR);
     hipLaunchKernelGGL(k, dim3(s.pc), dim3(K.block), (size_t)K.lds_bytes, s.st, e->d, a);
     prof_end(e);
@@ -229,58 +246,48 @@ static SoloArgs solo_args(frl_engine* e) {
     return sa;
 }
 
-// The next call's rows drawn by spare workgroups of this critic launch: two alternating slots of `slot_stride` ints, a tag the reader
-// checks (stale or foreign tags fail the kernel's check, and it draws for itself).  The launch reads slot seq & 1 and, where it may,
-// writes the other one for the counter the next frl_learn takes, unless something else draws first.  -> whether it writes
-static bool predraw_slots(frl_engine* e, SoloArgs& sa, size_t slot_stride, bool read, bool may_write) {
-    if (read) sa.pre_read = e->d_solo_pre + (size_t)(e->solo_pre_seq & 1) * slot_stride;
-    if (may_write) {
+// The next call's rows drawn by spare workgroups of this critic launch: two alternating slots of ints, a tag the reader checks (stale
+// or foreign tags fail the kernel's check, and it draws for itself).  Where the plan says so the launch reads slot seq & 1 and writes the
+// other one for the counter the next frl_learn takes, unless something else draws first.  The bookkeeping of the slots lives here.
+static void predraw_slots(frl_engine* e, SoloArgs& sa, const LearnPlan& pl, const LearnArgs& a) {
+    if (!pl.pre_touch) return;
+    const EngineDesc& h = e->h;
+    const size_t slot_stride = pl.pre_multi ? (size_t)h.P * h.n_agents * (8 + h.batch_max) : (size_t)h.P * kSoloPre;
+    if (pl.pre_read) sa.pre_read = e->d_solo_pre + (size_t)(e->solo_pre_seq & 1) * slot_stride;
+    if (pl.pre_write) {
         sa.pre_write = e->d_solo_pre + (size_t)((e->solo_pre_seq + 1) & 1) * slot_stride;
         sa.pre_counter = e->rng_counter;
     }
     ++e->solo_pre_seq;
-    return may_write;
+    if (pl.pre_multi) {
+        e->ma_pre_valid = pl.pre_write;
+        if (pl.pre_write) { e->ma_pre_counter = sa.pre_counter; e->ma_pre_size = a.size; e->ma_pre_batch = a.batch; }
+    }
 }
 
 // kernels_solo.hip: sixteen (eight) workgroups per learner, reduce + Adam behind grid barriers (`sstep`, frl_rollout: the vector step folded in)
-static void launch_solo(frl_engine* e, const LearnStage& s, const LearnArgs& a, const SoloStepArgs* sstep) {
+// (stage 0: the next call's rows drawn by pc spare workgroups of the launch, where the plan found them a CU of their own — 117 KB of LDS)
+static void launch_solo(frl_engine* e, const LearnStage& s, const LearnPlan& pl, const LearnArgs& a, const SoloStepArgs* sstep) {
     const LearnKernels& K = e->kern;
-    const int P = e->h.P, W = e->h.solo;
     prof_begin(e, s.stage == 0 ? PK_GRAD_CRITIC : PK_GRAD_ACTOR);
     SoloArgs sa = solo_args(e);
     const SoloStepArgs ss = sstep ? *sstep : SoloStepArgs{};
-    int extra = 0;
-    if (s.stage == 0) {
-        // the next call's rows drawn by pc spare workgroups of this launch (plain frl_learn calls with device draws; the spare ones
-        // need a CU of their own — 117 KB of LDS — next to the learners' pc x 16: FRL_SOLO_PREDRAW=0/1 overrides)
-        const bool predraw_on = env_flag("FRL_SOLO_PREDRAW", true);
-        if (s.dev_rng && !sstep && e->d_solo_pre && s.pc == P && predraw_slots(e, sa, (size_t)P * kSoloPre, true, s.pc * (W + 1) <= e->n_cus && predraw_on))
-            extra = s.pc;
-    }
-    hipLaunchKernelGGL(s.stage == 0 ? K.critic.ks : K.actor.ks, dim3(s.pc * W + extra), dim3(K.block), (size_t)K.lds_bytes, s.st, e->d, a, sa, ss);
+    if (s.stage == 0) predraw_slots(e, sa, pl, a);
+    const int extra = s.stage == 0 ? pl.pre_extra : 0;
+    hipLaunchKernelGGL(s.stage == 0 ? K.critic.ks : K.actor.ks, dim3(s.pc * e->h.solo + extra), dim3(K.block), (size_t)K.lds_bytes, s.st, e->d, a, sa, ss);
     prof_end(e);
 }
 
-// kernels_solow.hip: sixteen workgroups (+ helpers) per unit, W1 streamed from the block.  ma_predraw: a multi-agent call whose rows
-// spare workgroups may draw a launch ahead; ma_use_pre: ... and the previous launch did, for exactly this call (the dispatcher skipped draw_kernel)
-static void launch_solow(frl_engine* e, const LearnStage& s, const LearnArgs& a, bool ma_predraw, bool ma_use_pre) {
-    const EngineDesc& h = e->h;
+// kernels_solow.hip: sixteen workgroups (+ helpers) per unit, W1 streamed from the block.  Stage 0 of a single-agent engine: the learners'
+// first helper workgroups draw the next call's rows; of a multi-agent one: one spare workgroup per unit does, the duplicate table in its
+// own LDS, and the call those rows are for finds draw_kernel left out of its plan
+static void launch_solow(frl_engine* e, const LearnStage& s, const LearnPlan& pl, const LearnArgs& a) {
     const LearnKernels& K = e->kern;
     prof_begin(e, s.stage == 0 ? PK_GRAD_CRITIC : PK_GRAD_ACTOR);
     SoloArgs sa = solo_args(e);
-    SolowKernel k = K.actor.kw;
-    int extra = 0;
-    if (s.stage == 0) {
-        const bool predraw_on = env_flag("FRL_SOLO_PREDRAW", true);
-        if (h.n_agents == 1) {      // the learners' first helper workgroups draw
-            if (s.dev_rng && e->d_solo_pre && s.pc == h.P) predraw_slots(e, sa, (size_t)h.P * kSoloPre, true, e->solow_wgs > e->solow_row_wgs && predraw_on);
-        } else {                    // one spare workgroup per unit draws, the duplicate table in its own LDS
-            e->ma_pre_valid = predraw_slots(e, sa, (size_t)h.P * h.n_agents * (8 + h.batch_max), ma_use_pre,
-                                            ma_predraw && s.units * (e->solow_wgs + 1) <= e->n_cus && predraw_on);
-            if (e->ma_pre_valid) { extra = s.units; e->ma_pre_counter = sa.pre_counter; e->ma_pre_size = a.size; e->ma_pre_batch = a.batch; }
-        }
-        k = a.fuse_actor ? K.step.kw : K.critic.kw;
-    }
+    if (s.stage == 0) predraw_slots(e, sa, pl, a);
+    const SolowKernel k = s.stage != 0 ? K.actor.kw : a.fuse_actor ? K.step.kw : K.critic.kw;
+    const int extra = s.stage == 0 ? pl.pre_extra : 0;
     hipLaunchKernelGGL(k, dim3(s.units * e->solow_wgs + extra), dim3(K.block), (size_t)K.lds_bytes, s.st, e->d, a, sa);
     prof_end(e);
 }
@@ -295,38 +302,53 @@ static void launch_masac(frl_engine* e, const LearnStage& s, const LearnArgs& a)
     launch_rowchunk_update(e, s.st, actor ? s.pc : s.units, s.p0, rowchunk_ns(e->h, a.batch), ad, actor ? e->kern.actor.kr : e->kern.critic.kr, a);
 }
 
-static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, LearnArgs a, int stage, int p0, int pc, bool dev_rng, bool needs_noise,
-                               const DqnStepArgs* step = nullptr, const SoloStepArgs* sstep = nullptr) {
+// one entry of the plan's list
+static void launch_learn_stage(frl_engine* e, hipStream_t st, const LearnPlan& pl, const LearnLaunch& l, const DqnStepArgs* step, const SoloStepArgs* sstep) {
     const EngineDesc& h = e->h;
-    a.p0 = p0; a.p_count = pc;
-    const LearnStage s{st, stage, p0, pc, pc * h.n_agents, dev_rng, needs_noise};
-    if (stage == 2) {                                 // MATD3_simple.py:245-246: targets move with the delayed policy step
+    LearnArgs a = pl.a;
+    a.agent = l.agent;
+    const LearnStage s{st, l.stage, a.p0, a.p_count, l.units};
+    if (l.stage == 2) {                               // MATD3_simple.py:245-246: targets move with the delayed policy step
         prof_begin(e, PK_SOFT);
         int biggest = 0;
         for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);
-        const int per = std::max(1, std::min((biggest + 4095) / 4096, 4 * e->n_cus / std::max(1, pc * h.n_nets)));
-        hipLaunchKernelGGL(soft_update_kernel, dim3(pc * h.n_nets, per), dim3(256), 0, st, e->d, a.tau, p0);
+        const int per = std::max(1, std::min((biggest + 4095) / 4096, 4 * e->n_cus / std::max(1, s.pc * h.n_nets)));
+        hipLaunchKernelGGL(soft_update_kernel, dim3(s.pc * h.n_nets, per), dim3(256), 0, st, e->d, a.tau, s.p0);
         prof_end(e);
         return;
     }
-    if (fam == FAM_DQN_FUSED) { launch_dqn_fused(e, s, a, step); return; }
-    // kernels_solow.hip, MADDPG without smoothing noise: the rows may have been drawn by the previous launch's spare workgroups (one per
-    // unit) — for exactly this counter, ring size and batch, or draw_kernel runs as ever
-    const bool ma_predraw = fam == FAM_SOLOW && h.n_agents > 1 && stage == 0 && dev_rng && !needs_noise && pc == h.P;
-    const bool ma_use_pre = ma_predraw && e->ma_pre_valid && e->ma_pre_counter == a.rng_counter && e->ma_pre_size == a.size && e->ma_pre_batch == a.batch;
-    if (stage == 0) {
-        const bool draws_in_critic = fam == FAM_SOLO || (fam == FAM_SOLOW && h.n_agents == 1);      // (kernels_solo.hip / single-agent kernels_solow.hip)
-        launch_draw_and_prologue(e, s, a, dev_rng && !ma_use_pre && !draws_in_critic);
-    }
+    launch_prologue(e, s, pl, l);
+    const LearnFamily fam = pl.fam;
     switch (fam) {
+        case FAM_DQN_FUSED: launch_dqn_fused(e, s, a, step); break;
         case FAM_ROWCHUNK: case FAM_ATT: launch_rowchunk(e, s, a, fam); break;
-        case FAM_CHAINED: launch_chained(e, s, a); break;
-        case FAM_SOLO: launch_solo(e, s, a, sstep); break;
-        case FAM_SOLOW: launch_solow(e, s, a, ma_predraw, ma_use_pre); break;
+        case FAM_CHAINED: launch_chained(e, s, a, pl.critic_nv); break;
+        case FAM_SOLO: launch_solo(e, s, pl, a, sstep); break;
+        case FAM_SOLOW: launch_solow(e, s, pl, a); break;
         case FAM_WIDE: case FAM_WIDE16: launch_wide(e, s, a); break;
         case FAM_MASAC: launch_masac(e, s, a); break;
-        case FAM_DQN_FUSED: break;
     }
+}
+
+static LearnFacts learn_facts(const frl_engine* e, int min_size) {
+    LearnFacts F;
+    F.h = &e->h; F.f = e;
+    F.min_size = min_size;
+    F.per_on = e->per_on; F.predraw_bufs = e->d_solo_pre != nullptr;
+    F.ma_pre_valid = e->ma_pre_valid; F.ma_pre_counter = e->ma_pre_counter; F.ma_pre_size = e->ma_pre_size; F.ma_pre_batch = e->ma_pre_batch;
+    F.rng_counter = e->rng_counter;
+    return F;
+}
+
+// a caller's rows, narrowed by the plan: [P][sets][n] into the pinned scratch's pitch of batch_max per (learner, agent), and up
+static int upload_idx(frl_engine* e, const std::vector<int>& idx, int sets, int n) {
+    const EngineDesc& h = e->h;
+    HIP_TRY(hipStreamSynchronize(e->stream));                           // pinned scratch reuse
+    for (int p = 0; p < h.P; ++p)
+        for (int a = 0; a < sets; ++a)
+            memcpy(e->h_idx + idx_offset(h, p, a, 0), idx.data() + ((size_t)p * sets + a) * n, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(h.idx, e->h_idx, e->idx_count * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    return FRL_OK;
 }
 
 // What frl_rollout folds into a learn step (nullptr: a plain frl_learn).  dqn (DQN engines on the fused path) / solo (kernels_solo.hip): the
@@ -334,95 +356,41 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, LearnFamily fam, L
 // pre-armed launch is enqueued before the step's rows are counted in e->size).  stream: non-null for the pool's second stream
 struct StepFold { const DqnStepArgs* dqn; const SoloStepArgs* solo; int size_at_launch; hipStream_t stream; };
 static int learn_impl(frl_engine* e, const frl_learn_args* args, const StepFold* fold) {
-    const DqnStepArgs* step = fold ? fold->dqn : nullptr;
-    const SoloStepArgs* sstep = fold ? fold->solo : nullptr;
-    const int size_override = fold ? fold->size_at_launch : -1;
-    hipStream_t stream_override = fold ? fold->stream : nullptr;
     ENG(e);
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
     if (algo_traits(h.algo).learn != kFrlLearn) return wrong_engine(h, "frl_learn");
-    if (args->batch < 1 || args->batch > h.batch_max) return fail(FRL_ERR_INVALID, "batch %d outside [1,%d]", args->batch, h.batch_max);
-    int min_size = h.capacity;
-    for (int p = 0; p < h.P; ++p) min_size = std::min(min_size, e->size[p]);
-    if (size_override >= 0) min_size = size_override;
-    if (min_size < args->batch) return fail(FRL_ERR_STATE, "a ring holds %d rows < batch %d", min_size, args->batch);
-    if (args->per && (h.algo != ALGO_DQN || !e->per_on)) return fail(FRL_ERR_STATE, "per = 1 needs a DQN engine with frl_per_enable");
-    if (args->per && args->idx) return fail(FRL_ERR_INVALID, "per = 1 uses the rows of the last frl_per_sample; idx must be NULL");
-    const bool dev_rng = (args->idx == nullptr) && !args->per;
-    if (dev_rng && min_size < 2 * args->batch)
-        return fail(FRL_ERR_STATE, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
-    const bool td3_like = (h.algo == ALGO_TD3 || is_maddpg(h.algo));           // MADDPG + noise/delay = MATD3_simple.py (ATT-MADDPG: do_actor only)
-    const bool needs_noise = (h.algo == ALGO_SAC) || h.algo == ALGO_MASAC || (td3_like && args->use_policy_noise);
-    if (h.algo == ALGO_MASAC && args->use_policy_noise) return fail(FRL_ERR_STATE, "frl_learn: MASAC has no target policy smoothing (MATD3's): use_policy_noise must be 0");
-    if (h.algo == ALGO_MASAC && args->loss_kind == FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "MASAC's critic loss is F.mse_loss (MASAC.py:241): no Huber variant");
-    if (h.algo == ALGO_MADDPG_ATT && args->use_policy_noise) return fail(FRL_ERR_INVALID, "ATT-MADDPG has no target policy smoothing: use_policy_noise must be 0");
-    if (!dev_rng && needs_noise && !args->noise) return fail(FRL_ERR_INVALID, "idx given without noise: both or neither");
+    const DqnStepArgs* step = fold ? fold->dqn : nullptr;
+    const SoloStepArgs* sstep = fold ? fold->solo : nullptr;
+    e->knobs = learn_knobs();
+    LearnPlan pl;
+    std::string why;
+    const int min_size = fold && fold->size_at_launch >= 0 ? fold->size_at_launch : min_ring_size(e->size.data(), h.P, h.capacity).size;
+    if (const int rc = plan_learn(learn_facts(e, min_size), e->knobs, *args, sstep ? LEARN_FOLD_SOLO : step ? LEARN_FOLD_DQN : LEARN_PLAIN, &pl, &e->idx_narrow, &why))
+        return fail(rc, "%s", why.c_str());
+    // from here on nothing refuses: the staged rows, the caller's arrays, the call's counter values, the launches
     int rc = flush_stage(e);
     if (rc) return rc;
-    rc = upload_idx_noise(e, args->idx, needs_noise ? args->noise : nullptr, args->batch, h.n_agents);
+    if (args->idx) { rc = upload_idx(e, e->idx_narrow, h.n_agents, pl.a.batch); if (rc) return rc; }
+    rc = upload_noise(e, pl.needs_noise ? args->noise : nullptr, pl.a.batch);
     if (rc) return rc;
-    LearnArgs a;
-    memset(&a, 0, sizeof a);
-    a.batch = args->batch;
-    a.size = min_size;
-    a.device_rng = dev_rng ? 1 : 0;
-    a.do_actor = td3_like ? (args->do_actor ? 1 : 0) : 1;
-    a.gamma = args->gamma; a.tau = args->tau;
-    a.actor_lr = args->actor_lr; a.critic_lr = args->critic_lr; a.alpha_lr = args->alpha_lr;
-    a.adam_eps = args->adam_eps > 0 ? args->adam_eps : 1e-8f;
-    a.beta1 = 0.9f; a.beta2 = 0.999f;
-    a.critic_wd = args->critic_weight_decay;
-    a.clip_norm = args->clip_norm;
-    a.policy_noise = args->policy_noise; a.noise_clip = args->noise_clip;
-    a.max_action = args->max_action != 0.f ? args->max_action : 1.f;
-    a.policy_noise_scale = args->policy_noise_scale;
-    a.use_policy_noise = (td3_like && args->use_policy_noise) ? 1 : 0;
-    a.target_entropy = args->target_entropy;
-    a.double_dqn = (h.algo == ALGO_DQN && args->double_dqn) ? 1 : 0;
-    a.use_isw = (h.algo == ALGO_DQN && args->per) ? (args->per == 2 ? 2 : 1) : 0;
-    if (args->loss_kind != FRL_LOSS_MSE && args->loss_kind != FRL_LOSS_HUBER) return fail(FRL_ERR_INVALID, "unknown loss_kind %d", args->loss_kind);
-    if (args->loss_kind == FRL_LOSS_HUBER) {
-        if (!(args->huber_delta > 0.f)) return fail(FRL_ERR_INVALID, "Huber loss needs huber_delta > 0");
-        if (h.c51_atoms) return fail(FRL_ERR_STATE, "the Categorical head's loss is a cross-entropy: no Huber variant");
-        if (h.algo == ALGO_SAC_DISCRETE) return fail(FRL_ERR_INVALID, "discrete SAC's critic loss is F.mse_loss (SAC_add_discrete.py:313-314): no Huber variant");
-        a.huber = 1; a.huber_delta = args->huber_delta;
-    }
-    a.rng_counter = e->rng_counter++;
+    e->rng_counter += pl.counters;
     ++e->param_version;                       // (select_action's re-laid-out copies of the nets are stale from here on)
     // One chain for the whole population.  Measured and rejected (profiles/README.md): two halves of the population on two
     // streams so that one half's HBM-bound reduce/Adam runs under the other half's MFMA-bound gradient kernel — unchained
     // +2.7 %, with the gradient kernels chained across the streams -8 %: the Adam workgroups do not get co-resident with
     // the gradient kernel's (2 x 80 KB of LDS and 448 of 512 VGPRs per SIMD are taken).
-    const LearnFamily fam = learn_family(e, a.batch);
-    // (kernels_solow.hip moves MADDPG's targets at the end of its actor launch)
-    const bool actor_stage = (h.algo != ALGO_DQN && a.do_actor), soft_stage = (is_maddpg(h.algo) && a.do_actor && fam != FAM_SOLOW);
-    if (h.noisy) {
-        // the reference draws noise per forward in program order: [online(s') if Double,] target(s'), online(s)
-        const int first = a.double_dqn ? 0 : 1;
-        if (args->noisy_eps) { rc = noisy_upload(e, args->noisy_eps, first, 3 - first); if (rc) return rc; }
-        else hipLaunchKernelGGL(noisy_draw_kernel, dim3(h.P, 3), dim3(256), 0, e->stream, e->d, 0, 3, e->rng_counter++);
+    if (pl.noisy) {
+        if (!pl.noisy_device_draw) { rc = noisy_upload(e, args->noisy_eps, pl.noisy_first, 3 - pl.noisy_first); if (rc) return rc; }
+        else hipLaunchKernelGGL(noisy_draw_kernel, dim3(h.P, 3), dim3(256), 0, e->stream, e->d, 0, 3, pl.a.rng_counter + 1);
     }
-    // kernels_solow.hip, single agent, helper workgroups present: a policy step is ONE launch — the critic's update runs on the helpers
-    // under the policy's forward (FRL_SOLOW_FUSE=0: two launches)
-    if (actor_stage && fam == FAM_SOLOW && h.n_agents == 1 && e->solow_wgs > e->solow_row_wgs) a.fuse_actor = env_flag("FRL_SOLOW_FUSE", true) ? 1 : 0;
-    hipStream_t lst = stream_override ? stream_override : e->stream;      // (frl_rollout's pre-armed launches: the pool's second stream)
-    // frl_rollout on a solo engine (`sstep`): the step's add() rides at the head of the critic launch, its tail (obs advance + the next
-    // select_action + hand-over) at the end of the step's LAST launch
-    SoloStepArgs s0, s1;
-    if (sstep) {
-        if (fam != FAM_SOLO || !dev_rng) return fail(FRL_ERR_STATE, "step fusion needs a solo engine with device draws");
-        s0 = s1 = *sstep;
-        s0.head = 1; s0.tail = actor_stage ? 0 : 1;
-        s1.head = 0; s1.tail = 1;
+    hipStream_t lst = fold && fold->stream ? fold->stream : e->stream;      // (frl_rollout's pre-armed launches: the pool's second stream)
+    SoloStepArgs ss[2];
+    for (int i = 0; sstep && i < 2; ++i) { ss[i] = *sstep; ss[i].head = pl.head[i]; ss[i].tail = pl.tail[i]; }
+    for (int i = 0; i < pl.n_launches; ++i) {
+        const LearnLaunch& l = pl.launches[i];
+        launch_learn_stage(e, lst, pl, l, step, sstep && l.stage < 2 ? &ss[l.stage] : nullptr);
     }
-    launch_learn_stage(e, lst, fam, a, 0, 0, h.P, dev_rng, needs_noise, step, sstep ? &s0 : nullptr);
-    if (fam == FAM_MASAC) {      // DESIGN.md "MASAC": behind all the critics the agents' actor + alpha steps one after the other, then every target
-        for (int ag = 0; ag < h.n_agents; ++ag) { a.agent = ag; launch_learn_stage(e, lst, fam, a, 1, 0, h.P, dev_rng, needs_noise); }
-    } else if (actor_stage && !a.fuse_actor) {
-        launch_learn_stage(e, lst, fam, a, 1, 0, h.P, dev_rng, needs_noise, nullptr, sstep ? &s1 : nullptr);
-    }
-    if (soft_stage || fam == FAM_MASAC) launch_learn_stage(e, lst, fam, a, 2, 0, h.P, dev_rng, needs_noise);
     HIP_TRY(hipGetLastError());
     if (sstep) return FRL_OK;
     if (args->stats_out) return frl_stats_get(e, args->stats_out);

@@ -10,32 +10,23 @@ extern "C" int frl_reinforce_learn(frl_engine* e, const frl_reinforce_args* args
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     const EngineDesc& h = e->h;
     if (h.algo != ALGO_REINFORCE) return wrong_engine(h, "frl_reinforce_learn");
-    if (!(args->gamma == args->gamma) || !(args->lr == args->lr)) return fail(FRL_ERR_INVALID, "gamma / lr is NaN");
     const int P = h.P;
-    int n_max = 0;
-    for (int p = 0; p < P; ++p) {
-        const int n = args->n_steps ? args->n_steps[p] : e->size[p];
-        if (n < 0 || n > h.capacity) return fail(FRL_ERR_INVALID, "learner %d: %d steps outside [0, capacity = %d]", p, n, h.capacity);
-        if (n == 1)
-            return fail(FRL_ERR_INVALID, "learner %d has exactly one stored step: the std of one return is NaN "
-                                         "(the reference turns every parameter into NaN here)", p);
-        if (n > e->size[p]) return fail(FRL_ERR_STATE, "learner %d: %d steps asked for, its ring holds %d", p, n, e->size[p]);
-        if (n > 0 && e->index[p] != e->size[p] % h.capacity)      // rows 0..n-1 are in time order only in a ring filled from an empty cursor
-            return fail(FRL_ERR_STATE, "learner %d: ring cursor (%d, %d) was not filled from empty: its rows are not in time order", p, e->index[p], e->size[p]);
-        n_max = std::max(n_max, n);
-    }
-    if (n_max == 0) return FRL_OK;                 // every learner sits out
+    e->knobs = learn_knobs();
+    ReinforcePlan pl;
+    std::string why;
+    if (const int prc = plan_reinforce(h, e->size.data(), e->index.data(), *args, &pl, &why)) return fail(prc, "%s", why.c_str());
+    if (pl.n_max == 0) return FRL_OK;              // every learner sits out
     int rc = flush_stage(e);
     if (rc) return rc;
     const unsigned slot = e->ep_seq++ & 1u;
     int* hn = e->h_ep_n + (size_t)slot * P;
     if (e->ep_seq > 2) HIP_TRY(hipEventSynchronize(e->ev_ep[slot]));     // the copy out of this slot two calls ago
-    for (int p = 0; p < P; ++p) hn[p] = args->n_steps ? args->n_steps[p] : e->size[p];
+    for (int p = 0; p < P; ++p) hn[p] = pl.n[p];
     HIP_TRY(hipMemcpyAsync(h.ep_n, hn, (size_t)P * sizeof(int), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(e->ev_ep[slot], e->stream));
     ++e->param_version;
 
-    const int ns = rowchunk_ns(h, n_max);          // workgroups (= slabs) of the longest episode
+    const int ns = pl.ns;                          // workgroups (= slabs) of the longest episode
     prof_begin(e, PK_DRAW);
     hipLaunchKernelGGL(reinforce_returns_kernel, dim3(P), dim3(256), 0, e->stream, e->d, args->gamma);
     prof_end(e);

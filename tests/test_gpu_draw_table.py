@@ -15,14 +15,14 @@ def N():
     return _native
 
 
-def _rows(N, monkeypatch, scan, B, size, P, family):
+def _rows(N, monkeypatch, scan, B, size, P, family, batch_max=None):
     from freerl_amd.engine import Engine
     monkeypatch.setenv("FRL_DRAW_SCAN", "1" if scan else "0")
     if family is None:
         monkeypatch.delenv("FRL_CRITIC_V2", raising=False)
     else:
         monkeypatch.setenv("FRL_CRITIC_V2", str(family))
-    e = Engine(N.ALGO_MADDPG, [6, 5, 7], [2, 3, 2], 4096, n_learners=P, batch_max=B, seed=23)
+    e = Engine(N.ALGO_MADDPG, [6, 5, 7], [2, 3, 2], 4096, n_learners=P, batch_max=batch_max or B, seed=23)
     e.fill_synthetic(size, seed=2)
     out = []
     for k in range(6):
@@ -32,10 +32,14 @@ def _rows(N, monkeypatch, scan, B, size, P, family):
     return np.stack(out)                       # [calls][P][agents][B]
 
 
-@pytest.mark.parametrize("B,size,P,family", [(1024, 4096, 1, None), (1000, 2003, 2, 0), (300, 4096, 3, 0), (2048, 4096, 1, 0)])
-def test_table_and_scan_draw_the_same_rows(N, monkeypatch, B, size, P, family):
-    a = _rows(N, monkeypatch, False, B, size, P, family)
-    b = _rows(N, monkeypatch, True, B, size, P, family)
+# (the last case: an engine created for batches of up to 4096 rows, past the table's range, that learns at 1024 — the table's 80 KB of
+# LDS must have been allowed for at create, whatever batch_max says)
+@pytest.mark.parametrize("B,size,P,family,batch_max", [(1024, 4096, 1, None, None), (1000, 2003, 2, 0, None), (300, 4096, 3, 0, None), (2048, 4096, 1, 0, None),
+                                                       (1024, 4096, 1, 0, 4096)],
+                         ids=["1024-4096-1-None", "1000-2003-2-0", "300-4096-3-0", "2048-4096-1-0", "1024-4096-1-0-batch_max4096"])
+def test_table_and_scan_draw_the_same_rows(N, monkeypatch, B, size, P, family, batch_max):
+    a = _rows(N, monkeypatch, False, B, size, P, family, batch_max)
+    b = _rows(N, monkeypatch, True, B, size, P, family, batch_max)
     np.testing.assert_array_equal(a, b)
     assert a.min() >= 0 and a.max() < size
     for k in range(a.shape[0]):
