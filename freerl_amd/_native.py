@@ -33,6 +33,7 @@ ALGO_MADDPG_ATT = 14        # MADDPG_simple_with_tricks.py, trick['ATT']: a MADD
 ALGO_MASAC = 15             # MAAC_file/MASAC.py: MADDPG's records and net numbering, stacked [mean | log_std] actors, twin critics, one alpha per agent (frl_learn)
 ALGO_GAIL_PPO = 16          # GAIL_file/PPO2.py: GAIL's policy side — actor + critic with LeakyReLU / ReLU hidden layers (frl_gail_ppo_learn)
 ALGO_CEM_GD3PG = 18         # (17 is unassigned) CEM_GD3PG_file/CEM_GD3PG.py: two online actors, a frozen domain actor, one critic, two rings per learner (frl_cem_gd3pg_learn)
+ALGO_DDPG_POPART = 20       # (19 is unassigned) DDPG_file/DDPG_simple_with_tricks.py, trick['popart']: DDPG's nets + an upper layer and running target statistics per learner (frl_popart_ddpg_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL and GAIL_PPO engines only
@@ -141,6 +142,15 @@ class CemGd3pgArgs(C.Structure):        # frl_cem_gd3pg_args
 
 
 CEM_OUT = ("critic_loss", "critic_norm", "actor_1_loss", "actor_1_norm", "actor_2_loss", "actor_2_norm", "KL", "rows")      # frl_cem_gd3pg_args.out
+
+
+class PopartDdpgArgs(C.Structure):      # frl_popart_ddpg_args
+    _fields_ = [("batch", C.c_int), ("gamma", C.c_float), ("tau", C.c_float), ("actor_lr", C.c_float), ("critic_lr", C.c_float),
+                ("upper_lr", C.c_float), ("beta", C.c_float), ("idx", C.POINTER(C.c_int64)), ("out", C.POINTER(C.c_float))]
+
+
+POPART_OUT = ("critic_loss", "lower_norm", "upper_norm", "actor_loss", "actor_norm", "sigma", "mu", "rows")      # frl_popart_ddpg_args.out
+POPART_STATE = ("W", "b", "sigma", "mu", "nu")                                                                   # frl_popart_get / _set
 
 
 class MappoArgs(C.Structure):
@@ -257,6 +267,9 @@ SIGNATURES = {
     "frl_ring_cursor_get": (_i, [_vp, _i, _i, _ip, _ip]),
     "frl_ring_cursor_set": (_i, [_vp, _i, _i, _i, _i]),
     "frl_cem_gd3pg_learn": (_i, [_vp, _P(CemGd3pgArgs)]),
+    "frl_popart_ddpg_learn": (_i, [_vp, _P(PopartDdpgArgs)]),
+    "frl_popart_get": (_i, [_vp, _i, _fp]),
+    "frl_popart_set": (_i, [_vp, _i, _fp]),
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),

@@ -60,15 +60,18 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"GAIL-PPO",       "frl_gail_ppo_learn",      "FRL_ACT_PPO_SAMPLE / FRL_ACT_TANHHEAD / FRL_ACT_CAT_SAMPLE on net 0, FRL_ACT_RAW on net 1: the value", false, false, false, false, false, false, false},
     {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 17: refused as an unknown algo (check_create_args)
     {"CEM-GD3PG",      "frl_cem_gd3pg_learn",     "FRL_ACT_TANHHEAD on net 0 / 1 / 3 (actor_1 / actor_2 / actor_domain), FRL_ACT_RAW on net 2 with [obs | act]", false, false, false, false, false, true,  false},
+    {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 19: refused like 17
+    {"PopArt-DDPG",    "frl_popart_ddpg_learn",   "FRL_ACT_TANHHEAD on net 0, FRL_ACT_RAW on net 1 with [obs | act]: the lower critic's output h, Q = sigma (W h + b) + mu (frl_popart_get)", false, false, false, false, false, true,  false},
 };
-constexpr int kAlgoUnassigned = 17;      // a value no frl_algo has: its kAlgo row only keeps the table indexable by value
+constexpr int kAlgoUnassigned[] = {17, 19};      // values no frl_algo has: their kAlgo rows only keep the table indexable by value
+inline bool algo_unassigned(int algo) { return algo == kAlgoUnassigned[0] || algo == kAlgoUnassigned[1]; }
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 // (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
 //  policy noise and its own launch order — learn_impl and the launchers ask for it by name)
 inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_CEM_GD3PG - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_DDPG_POPART - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo value, the two unassigned ones included");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
@@ -126,6 +129,7 @@ struct EngineFacts {
     int lds_per_cu = 160 * 1024;  // LDS bytes of one compute unit
     int n_rings = 1;              // replay rings per learner (CEM_GD3PG: 2, `buffer` and `buffer_domain`), side by side in EngineDesc::replay
     int ring_cap = 0;             // rows of one ring = frl_config.capacity; EngineDesc::capacity = n_rings * ring_cap rows per learner
+    size_t popart_count = 0;      // floats of EngineDesc::popart (rowchunk_layout.h); 0 on every engine but FRL_ALGO_DDPG_POPART's
 };
 // Everything the allocation step of frl_create needs: it makes no decisions of its own
 struct EnginePlan : EngineFacts {
@@ -420,7 +424,7 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
     if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_CEM_GD3PG || c.algo == kAlgoUnassigned) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_DDPG_POPART || algo_unassigned(c.algo)) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -503,6 +507,15 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
             if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0 || c.extra_cols != 0)
                 return plan_refuse(message, "%s: dueling, noisy, c51_atoms, actor_dist and extra_cols must be 0", T.name);
             if (c.capacity > (1 << 30)) return plan_refuse(message, "%s: capacity %d > 2^30 (a learner's two rings are indexed as one)", T.name, c.capacity);
+            return FRL_OK;
+        case FRL_ALGO_DDPG_POPART:
+            // what kernels_popart.hip handles (DDPG_simple_with_tricks.py:44-74: ReLU nets, one critic head, continuous actions)
+            if (c.discrete)
+                return plan_refuse(message, "%s: discrete is refused (the reference's discrete branch calls Agent.argmax, which does not exist, DDPG_simple_with_tricks.py:233)", T.name);
+            if (c.twin_critic) return plan_refuse(message, "%s: twin_critic is refused (PopArt's lower layers are one critic with one output)", T.name);
+            if (c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
+            if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0 || c.extra_cols != 0)
+                return plan_refuse(message, "%s: dueling, noisy, c51_atoms, actor_dist and extra_cols must be 0", T.name);
             return FRL_OK;
         case FRL_ALGO_DQN:
             if (const int rc = no_leaky_relu()) return rc;
@@ -783,6 +796,10 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     pl.act_spill_count = c.algo == FRL_ALGO_CEM_GD3PG ? cem_spill_floats(h) : T.act_spill ? act_spill_floats(h) : 0;      // (CEM_GD3PG: a block per (learner, actor, slice))
     // the chained family's actor stage (chained_shape admits DDPG / TD3 / SAC only: each has one); allocated whatever FRL_ACTOR_PARK says
     pl.actor_park_count = pl.family == FAM_CHAINED ? actor_park_floats(h.P) : 0;
+    if (c.algo == FRL_ALGO_DDPG_POPART) {      // the per-learner block: upper layer, statistics, its Adam state, S part slots, batch_max parked targets
+        h.popart_stride = popart_block_floats(h.S, h.batch_max);
+        pl.popart_count = popart_floats(h);
+    }
     pl.idx_count = P * h.n_agents * h.batch_max;
     if (h.noisy) {
         const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];

@@ -54,6 +54,7 @@
 #include "kernels_masac.hip"
 #include "kernels_her.hip"
 #include "kernels_cem_gd3pg.hip"
+#include "kernels_popart.hip"
 #endif
 
 using namespace frl;
@@ -257,7 +258,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 114; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set
+extern "C" int frl_version(void) { return 115; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set; 115: FRL_ALGO_DDPG_POPART, frl_popart_ddpg_args, frl_popart_ddpg_learn, frl_popart_get / _set
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -384,6 +385,14 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
             CREATE_TRY(e->mem.alloc(&e->h_cem_ctl, 4 * P, MEM_PINNED));
             for (hipEvent_t& ev : e->ev_ep) CREATE_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         }
+        if (c.algo == FRL_ALGO_DDPG_POPART) {      // W = 1, b = 0, sigma = 1, mu = 0, nu = sigma^2 + mu^2 = 1 (DDPG_simple_with_tricks.py:100-118)
+            CREATE_TRY(e->mem.alloc_zero(&h.popart, e->popart_count, e->stream));
+            CREATE_TRY(e->mem.alloc_zero(&h.popart_out, 8 * P, e->stream));
+            std::vector<float> head(P * 5, 1.f);
+            for (size_t p = 0; p < P; ++p) head[p * 5 + POP_B] = head[p * 5 + POP_MU] = 0.f;
+            CREATE_TRY(hipStreamSynchronize(e->stream));      // (the block's zeroing is on the stream)
+            CREATE_TRY(hipMemcpy2D(h.popart, (size_t)h.popart_stride * sizeof(float), head.data(), 5 * sizeof(float), 5 * sizeof(float), P, hipMemcpyHostToDevice));
+        }
         if (c.algo == FRL_ALGO_GAIL) {
             const size_t rows_n = P * (size_t)h.batch_max * (c.obs_dim[0] + c.act_dim[0]);
             CREATE_TRY(e->mem.alloc_zero(&h.gail_rows, rows_n, e->stream));
@@ -449,7 +458,7 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
                               (const void*)att_q_kernel, (const void*)masac_act_kernel, (const void*)gail_ppo_prepare_kernel,
                               (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel, (const void*)cem_critic_kernel, (const void*)cem_actor_kernel,
-                              (const void*)cem_act_kernel})
+                              (const void*)cem_act_kernel, (const void*)popart_target_kernel, (const void*)popart_critic_kernel, (const void*)popart_actor_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -1209,6 +1218,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (e->h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MASAC.py has no Batch_ObsNorm and kernels_masac.hip does not normalise");
     if (e->h.algo == ALGO_CEM_GD3PG) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: CEM_GD3PG.py has no Batch_ObsNorm and kernels_cem_gd3pg.hip does not normalise");
+    if (e->h.algo == ALGO_DDPG_POPART) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: DDPG_simple_with_tricks.py has no Batch_ObsNorm and kernels_popart.hip does not normalise");
     if (e->h.algo == ALGO_GAIL_PPO) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: PPO2.py has no Batch_ObsNorm (its env wrapper scales observations) and kernels_gail_ppo.hip does not normalise");
     if (e->h.algo == ALGO_MADDPG_ATT) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MADDPG_simple_with_tricks.py has no Batch_ObsNorm and the attention critic's kernels do not normalise");
     if (is_mappo_family(e->h.algo)) return wrong_engine(e->h, "frl_obsnorm_enable");      // (ObsNorm belongs to these algorithms' loop: freerl_amd/normalization.py)
@@ -1411,3 +1421,4 @@ extern "C" int frl_debug_phase_clocks(int* out, int stride) {
 #include "frl_api_her.inc"
 #include "frl_api_comm.inc"
 #include "frl_api_cem_gd3pg.inc"
+#include "frl_api_popart.inc"

@@ -12,7 +12,8 @@ enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LEAKY_RELU = 3 };
 constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slope
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
-                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16, ALGO_CEM_GD3PG = 18 /* 17: unassigned */ };
+                  ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16, ALGO_CEM_GD3PG = 18 /* 17: unassigned */,
+                  ALGO_DDPG_POPART = 20 /* 19: unassigned */ };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -245,6 +246,12 @@ struct EngineDesc {
     // `capacity` ring rows are TWO rings of capacity / 2 rows, `buffer` then `buffer_domain`; idx holds absolute rows of the pair
     float* cem_ctl;       // [2][P] of the current frl_cem_gd3pg_learn call: is_F1_more (0 / 1) of every learner, then its delta
     float* cem_out;       // [P][8] what frl_cem_gd3pg_args::out returns, written by cem_step_kernel
+    // PopArt DDPG (kernels_popart.hip, ALGO_DDPG_POPART): net 0 the actor, net 1 PopArt's lower layers.  One block per learner
+    // (rowchunk_layout.h: PopartSlot ...): the upper layer {W, b}, the statistics {sigma, mu, nu}, the upper layer's Adam moments and
+    // step, the workgroups' partial sums of a call and the call's TD targets y, parked between the target and the critic launch
+    float* popart;        // [P][popart_stride]
+    int popart_stride;    // floats per learner: popart_block_floats()
+    float* popart_out;    // [P][8] what frl_popart_ddpg_args::out returns, written by popart_step_kernel
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).

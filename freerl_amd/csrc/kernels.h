@@ -218,6 +218,22 @@ __global__ void cem_actor_kernel(const EngineDesc* __restrict__ Dp, CemArgs a, i
 __global__ void cem_step_kernel(const EngineDesc* __restrict__ Dp, CemArgs a, int ns);
 __global__ void cem_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
+// kernels_popart.hip: PopArt DDPG (DDPG_file/DDPG_simple_with_tricks.py, trick['popart']) on an ALGO_DDPG_POPART engine: net 0 the actor,
+// net 1 PopArt's lower layers; the upper layer and the statistics in EngineDesc::popart.  The batch is `rows` ring rows in EngineDesc::idx
+constexpr int kPopartOut = 8;      // floats per learner of EngineDesc::popart_out (frl_popart_ddpg_args::out)
+struct PopartArgs {
+    int rows;                    // B = min(len(buffer), batch_size)
+    float gamma, tau;
+    float actor_lr, critic_lr, upper_lr;
+    float beta;                   // the weight of the new batch in mu and nu
+    int stage;                    // popart_step_kernel: 0 the lower critic and the upper layer, 1 the actor
+    int p0, p_count;
+};
+__global__ void popart_target_kernel(const EngineDesc* __restrict__ Dp, PopartArgs a, int ns);
+__global__ void popart_critic_kernel(const EngineDesc* __restrict__ Dp, PopartArgs a, int ns);
+__global__ void popart_actor_kernel(const EngineDesc* __restrict__ Dp, PopartArgs a, int ns);
+__global__ void popart_step_kernel(const EngineDesc* __restrict__ Dp, PopartArgs a, int ns);
+
 // kernels_mappo.hip: MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py): a unit = (learner, agent); nets 2i / 2i+1 = agent i's actor / critic
 struct MappoArgs {
     int horizon, minibatch, k_epochs, adv_norm;

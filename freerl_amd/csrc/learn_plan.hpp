@@ -347,6 +347,33 @@ inline int plan_cem_gd3pg(const EngineDesc& h, const int* size1, int ring_cap, c
     return FRL_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- frl_popart_ddpg_learn
+// sample() (DDPG_simple_with_tricks.py:244-250): rows = min(len(buffer), batch_size); the population shares one launch shape, so its
+// smallest ring decides.  The device draw is draw_kernel's, with its rule (a ring of at least 2 x rows rows)
+struct PopartPlan { int min_size = 0, rows = 0, ns = 0; bool dev_idx = false; DrawPlan draw{false, 0, 2}; };
+inline int plan_popart_ddpg(const EngineDesc& h, const int* sizes, const frl_popart_ddpg_args& args, PopartPlan* out, std::vector<int>* idx_out,
+                            std::string* message) {
+    if (args.batch < 1) return plan_refuse(message, "batch %d must be >= 1", args.batch);
+    if (const int rc = refuse_nan({args.gamma, args.tau, args.actor_lr, args.critic_lr, args.upper_lr, args.beta},
+                                  "gamma / tau / actor_lr / critic_lr / upper_lr / beta", message)) return rc;
+    if (args.beta < 0.f || args.beta > 1.f) return plan_refuse(message, "beta %g outside [0, 1]", (double)args.beta);
+    const MinRing m = min_ring_size(sizes, h.P, h.capacity);
+    if (m.size < 1) return FRL_REFUSE_STATE(message, "the ring of learner %d is empty: no batch can be drawn from it", m.who);
+    PopartPlan pl;
+    pl.min_size = m.size;
+    pl.rows = std::min(m.size, args.batch);
+    if (pl.rows > h.batch_max) return plan_refuse(message, "min(len(buffer), batch) = %d rows > batch_max %d", pl.rows, h.batch_max);
+    pl.dev_idx = args.idx == nullptr;
+    pl.draw = plan_draw(pl.rows, false);
+    if (pl.dev_idx && m.size < 2 * pl.rows) return FRL_REFUSE_STATE(message, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", m.size);
+    if (pl.dev_idx && pl.draw.lds_bytes > kDrawLdsLimit) return refuse_draw(pl.rows, message);
+    if (args.idx)
+        if (const int rc = narrow_idx(IDX_CAPACITY_WRAP, args.idx, h.P, 1, pl.rows, h.capacity, nullptr, idx_out, message)) return rc;
+    pl.ns = rowchunk_ns(h, pl.rows);
+    *out = pl;
+    return FRL_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- frl_reinforce_learn
 // n[p]: the rows learner p trains on (0: it sits the call out); n_max == 0: every learner sits out and the call launches nothing
 struct ReinforcePlan { int n_max = 0, ns = 0; std::vector<int> n; };

@@ -78,6 +78,21 @@ FRL_LAYOUT_FN size_t cem_spill_floats(const EngineDesc& D) { return cem_spill_of
 // (no kernel of this algorithm draws noise)
 FRL_LAYOUT_FN size_t cem_domain_offset(const EngineDesc& D, int p, int r0) { return noise_offset(D, p, 0, 0, r0); }
 
+// ------------------------------------------------------------------------------ PopArt DDPG (kernels_popart.hip)
+// EngineDesc::popart, one block per learner: [kPopartHead floats: PopartSlot] [S part slots of kPopartPart floats] [batch_max floats: y].
+// The head: the upper layer, the statistics, the upper layer's Adam moments and (as an int's bits) its step count.
+enum PopartSlot : int { POP_W = 0, POP_B = 1, POP_SIGMA = 2, POP_MU = 3, POP_NU = 4, POP_MW = 5, POP_MB = 6, POP_VW = 7, POP_VB = 8, POP_STEP = 9 };
+constexpr int kPopartHead = 16;
+// a (learner, slice)'s part slot.  popart_target_kernel writes the two doubles (floats 0 .. 3), popart_critic_kernel the next three
+// floats — while other workgroups of its launch still read the doubles — and popart_actor_kernel the last
+enum PopartPart : int { POP_PART_SY = 0, POP_PART_SY2 = 2, POP_PART_LOSS = 4, POP_PART_DW = 5, POP_PART_DB = 6, POP_PART_ACTOR = 7 };
+constexpr int kPopartPart = 8;      // (a multiple of 2 floats behind an even head: the doubles are 8-byte aligned when the stride is even)
+FRL_LAYOUT_FN int popart_block_floats(int S, int batch_max) { return (kPopartHead + kPopartPart * S + batch_max + 3) / 4 * 4; }
+FRL_LAYOUT_FN size_t popart_offset(const EngineDesc& D, int p) { return (size_t)p * D.popart_stride; }
+FRL_LAYOUT_FN size_t popart_part_offset(const EngineDesc& D, int p, int sl) { return popart_offset(D, p) + kPopartHead + (size_t)kPopartPart * sl; }
+FRL_LAYOUT_FN size_t popart_y_offset(const EngineDesc& D, int p, int r0) { return popart_offset(D, p) + kPopartHead + (size_t)kPopartPart * D.S + r0; }
+FRL_LAYOUT_FN size_t popart_floats(const EngineDesc& D) { return popart_offset(D, D.P); }
+
 // ------------------------------------------------------------------------------ what the plan allocates
 FRL_LAYOUT_FN size_t slab_floats(const EngineDesc& D) { return (size_t)D.P * D.S * D.learner_stride; }
 FRL_LAYOUT_FN size_t part_floats(const EngineDesc& D) { return part_offset(D, D.P, 0, 0); }

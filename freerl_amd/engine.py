@@ -590,6 +590,39 @@ class Engine:
         N.check(self._L.frl_cem_gd3pg_learn(self._h, C.byref(a)))
         return out
 
+    def popart_ddpg_learn(self, batch, *, gamma, tau, actor_lr, critic_lr, upper_lr=1e-3, beta=0.99999, idx=None, want_out=True):
+        """DDPG.learn with trick['popart'] for every learner (frl_popart_ddpg_learn) on rows = min(len(buffer), batch) rows: idx [P][rows]
+        ring rows or None: drawn on the device.  upper_lr and beta default to PopArt's literals.
+        -> float32 [P][8] in the order of _native.POPART_OUT (rows negated where the variance guard fired), or None (asynchronous) when
+        want_out is false."""
+        a = N.PopartDdpgArgs()
+        a.batch, a.gamma, a.tau, a.actor_lr, a.critic_lr = int(batch), float(gamma), float(tau), float(actor_lr), float(critic_lr)
+        a.upper_lr, a.beta = float(upper_lr), float(beta)
+        keep = []
+        if idx is not None:
+            ix = np.ascontiguousarray(idx, dtype=np.int64).reshape(self.P, -1)
+            rows = min(min(self.cursor(p)[1] for p in range(self.P)), int(batch))      # what the library will read
+            if ix.shape[1] != rows:
+                raise ValueError("idx holds %d rows per learner, the call uses %d" % (ix.shape[1], rows))
+            keep.append(ix)
+            a.idx = ix.ctypes.data_as(C.POINTER(C.c_int64))
+        out = None
+        if want_out:
+            out = np.full((self.P, 8), np.nan, dtype=F32)
+            a.out = _fp(out)
+        N.check(self._L.frl_popart_ddpg_learn(self._h, C.byref(a)))
+        return out
+
+    def popart_get(self, learner=0):
+        """-> float32 [5] = {W, b, sigma, mu, nu} of one learner (_native.POPART_STATE)."""
+        out = np.zeros(5, dtype=F32)
+        N.check(self._L.frl_popart_get(self._h, int(learner), _fp(out)))
+        return out
+
+    def popart_set(self, vals5, learner=0):
+        v = np.ascontiguousarray(vals5, dtype=F32).reshape(5)
+        N.check(self._L.frl_popart_set(self._h, int(learner), _fp(v)))
+
     def gail_learn(self, policy_rows, *, gp, lr, beta1, beta2, n_expert=None, gp_weight=5.0, adam_eps=1e-8, idx=None, want_out=True,
                    want_idx=False):
         """GAIL.trian_D for every learner (frl_gail_learn): policy_rows [P][n_policy][obs_dim + act_dim] against expert ring rows

@@ -53,6 +53,10 @@ FLAGS = {
                 trick={"Double": False, "Dueling": False, "PER": False, "Noisy": False, "N_Step": False, "Categorical": False}),
     "ddpg": dict(env_name="Pendulum-v1", policy_name="DDPG_simple", device="cuda", is_dis_to_con=False,
                  flags=_COMMON + _AC + _REPLAY + _GAUSS, trick=None),
+    # DDPG_simple_with_tricks.py:361-392: DDPG_simple's flags with batch 64, gauss_sigma 1 and trick {'popart': True}.  The script's own
+    # MountainCarContinuous-v0 is not among envs.py's environments: Pendulum-v1 stands in as the default
+    "ddpg_popart": dict(env_name="Pendulum-v1", policy_name="DDPG_simple", device="cpu", is_dis_to_con=False,
+                        flags=_COMMON + _AC + _REPLAY + _GAUSS, overrides=dict(batch_size=64, gauss_sigma=1), trick={"popart": True}),
     # DDPG_simple_try_HER.py:298-326: DDPG_simple's flags, tau 0.01, both lrs 1e-3, start_steps 500, device cpu
     "her": dict(env_name="Pendulum-v1", policy_name="DDPG_simple_HER", device="cpu", is_dis_to_con=False,
                 flags=_COMMON + _AC + _REPLAY + _GAUSS, trick=None),
@@ -873,6 +877,11 @@ def run(algo, argv=None, env=None, log=print):
     elif algo == "ddpg":
         from .DDPG import DDPG
         policy = DDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick, **kw)
+        hooks = _GaussHooks(args, env, policy, dim_info, max_action)
+    elif algo == "ddpg_popart":
+        from .DDPG_simple_with_tricks import DDPG
+        policy = DDPG(dim_info, is_continue, args.actor_lr, args.critic_lr, args.buffer_size, device, trick=args.trick,
+                      batch_max=max(args.batch_size, 1), **kw)
         hooks = _GaussHooks(args, env, policy, dim_info, max_action)
     elif algo == "her":
         import random

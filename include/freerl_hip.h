@@ -108,7 +108,7 @@ enum frl_algo {
                                   Updated by frl_gail_ppo_learn only.  frl_act: FRL_ACT_RAW (net 1: value; net 0: the head),
                                   FRL_ACT_TANHHEAD (pi(return_mean=True)), FRL_ACT_PPO_SAMPLE (mean + std eps under the engine's
                                   range, eps given or drawn), FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX (discrete).  frl_version() 113 */
-    FRL_ALGO_CEM_GD3PG = 18    /* (17 is unassigned: frl_create refuses it as an unknown algo, which callers and the suite have relied on since
+    FRL_ALGO_CEM_GD3PG = 18,   /* (17 is unassigned: frl_create refuses it as an unknown algo, which callers and the suite have relied on since
                                   frl_version 113.)  CEM_GD3PG_file/CEM_GD3PG.py:30-231, guided dual-actor DDPG: net 0 actor_1, net 1 actor_2 and net 3
                                   actor_domain obs_dim -> hidden (tanh) -> hidden (tanh) -> act_dim (tanh), net 2 the critic [obs | act] ->
                                   hidden (LeakyReLU 0.01) -> hidden (LeakyReLU 0.01) -> 1.  Nets 0-2 have a target net and Adam state;
@@ -119,6 +119,14 @@ enum frl_algo {
                                   [r capacity, (r + 1) capacity) are ring r), zero-filled at create.  Updated by frl_cem_gd3pg_learn
                                   only.  frl_act: FRL_ACT_TANHHEAD on nets 0, 1 and 3 (use_target on 0 and 1), FRL_ACT_RAW on net 2.
                                   frl_version() 114 */
+    FRL_ALGO_DDPG_POPART = 20  /* (19 is unassigned, as 17 is.)  DDPG_file/DDPG_simple_with_tricks.py:44-292 with trick['popart']: net 0 the actor
+                                  obs_dim -> hidden (ReLU) -> hidden (ReLU) -> act_dim (tanh), net 1 PopArt's lower layers, the critic
+                                  [obs | act] -> hidden (ReLU) -> hidden (ReLU) -> 1, each with a target net.  Per learner, outside the nets:
+                                  the upper layer Linear(1, 1) {W, b} (1, 0 at create) with its own Adam state and no target copy, and the
+                                  statistics {sigma, mu, nu} (1, 0, 1 at create): frl_popart_get / frl_popart_set.  hidden_act must be
+                                  FRL_ACT_RELU; discrete, twin_critic, dueling, noisy, c51_atoms and n_agents != 1 are refused.  Updated by
+                                  frl_popart_ddpg_learn only.  frl_act as on a FRL_ALGO_DDPG engine: FRL_ACT_TANHHEAD on net 0,
+                                  FRL_ACT_RAW on net 1 = the LOWER critic's raw output h (Q = sigma (W h + b) + mu).  frl_version() 115 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -613,6 +621,39 @@ struct frl_cem_gd3pg_args {
 };
 typedef struct frl_cem_gd3pg_args frl_cem_gd3pg_args;
 int frl_cem_gd3pg_learn(frl_engine* e, const frl_cem_gd3pg_args* args);
+
+/* ---------------------------------------------------------------- PopArt DDPG (DDPG_file/DDPG_simple_with_tricks.py) on a FRL_ALGO_DDPG_POPART engine
+ * `DDPG.learn(batch_size, gamma, tau)` (:253-292) with trick['popart'] for every learner in one launch chain over
+ * rows = min(len(buffer), batch) rows (:244-250; the smallest ring of the population decides):
+ *   y = r + gamma (1 - done) (sigma (W critic_target(s', actor_target(s')) + b) + mu), with the statistics and the online upper layer as
+ *     they stand before the call.
+ *   art + pop (:128-146): mu' = (1 - beta) mu + beta mean(y), nu' = (1 - beta) nu + beta mean(y^2), sigma' = sqrt(nu' - mu'^2);
+ *     W <- W sigma / sigma', b <- (b sigma + mu - mu') / sigma', so that sigma' (W h + b) + mu' is what sigma (W h + b) + mu was.
+ *     nu' - mu'^2 <= 0 (a constant y, a batch of one; the reference divides by zero or takes a NaN root and never recovers): that call keeps
+ *     sigma' = sigma, still moves mu and nu, and reports it by negating out[7].
+ *   Critic step: loss = mean (W h + b - (y - mu') / sigma')^2, h = critic(s, a); clip_grad_norm_ 0.5 and Adam(critic_lr) on the lower
+ *     layers, then clip_grad_norm_ 0.5 over {dW, db} alone and Adam(upper_lr) on the upper layer (torch's default betas and eps).
+ *   Actor step: loss = -mean (sigma' (W critic(s, actor(s)) + b) + mu') through the lower critic and the upper layer just stepped; clip 0.5,
+ *     Adam(actor_lr).  Soft update of critic_target (lower layers) and actor_target with tau.
+ * Refused before any launch with FRL_ERR_INVALID: batch < 1, more rows than batch_max, NaN scalars, beta outside [0, 1], an idx entry
+ * outside [-capacity, capacity); with FRL_ERR_STATE: an empty ring, a device draw (idx NULL) from a ring of fewer than 2 x rows rows, and
+ * engines of any other algorithm.  Every other learn, rollout or explore entry point returns FRL_ERR_STATE for a FRL_ALGO_DDPG_POPART
+ * engine and names this one. */
+struct frl_popart_ddpg_args {
+    int batch;              /* batch_size */
+    float gamma, tau, actor_lr, critic_lr;
+    float upper_lr;         /* PopArt.lr (:120): the literal 1e-3, whatever critic_lr is */
+    float beta;             /* PopArt.beta (:119): 0.99999, the weight of the NEW batch */
+    const int64_t* idx;     /* host [P][rows] ring rows (np.random.choice(len(buffer), rows, replace=False), :247), or NULL: drawn on the device */
+    float* out;             /* host [P][8] = {critic loss, lower pre-clip norm, upper pre-clip norm, actor loss, actor pre-clip norm, sigma, mu,
+                               rows used — negated when the variance guard fired} or NULL: the call is asynchronous.  FRL_STAT_CRITIC_LOSS /
+                               _CRITIC_GNORM (the lower layers') / _ACTOR_LOSS / _ACTOR_GNORM carry the same values */
+};
+typedef struct frl_popart_ddpg_args frl_popart_ddpg_args;
+int frl_popart_ddpg_learn(frl_engine* e, const frl_popart_ddpg_args* args);
+/* {W, b, sigma, mu, nu} of one learner.  _set keeps the upper layer's Adam state; sigma must be > 0 and every value finite. */
+int frl_popart_get(frl_engine* e, int learner, float* out5);
+int frl_popart_set(frl_engine* e, int learner, const float* in5);
 
 /* ---------------------------------------------------------------- MAPPO / IPPO (MAPPO_file/MAPPO.py, IPPO.py)
  * `MAPPO.learn / IPPO.learn(minibatch_size, gamma, lmbda, clip_param, K_epochs, entropy_coefficient, huber_delta)` for every learner in

@@ -73,7 +73,12 @@ BOUNDS = [("ac_critic_v2_", 8), ("ac_actor_v2_", 0), ("solo_critic_twin_w8_", 8)
           # 204 bytes of scratch — seven forward passes and a backward over three nets' layer offsets, the Lds carve, the chunk loop's bounds and two
           # per-row sums: stored at entry, reloaded at the start of a pass, none of its 102 scratch accesses inside an innermost MFMA k-loop;
           # cem_actor_kernel 255 VGPRs, none spilled, 56 bytes (a row lambda's captures); cem_act_kernel 188 + 40 AGPRs; cem_draw_kernel 106; cem_step_kernel 61
-          ("cem_critic_", 44), ("cem_actor_", 0), ("cem_", 0), ("", 20)]
+          ("cem_critic_", 44), ("cem_actor_", 0), ("cem_", 0),
+          # kernels_popart.hip (the unit compiled on its own, profiles/popart/kernel_regs.txt): popart_target_kernel 235 VGPRs and popart_critic_kernel
+          # 250, none spilled, 56 bytes of scratch each (a row lambda's captures); popart_actor_kernel 256 with 20 spilled and 116 bytes — two
+          # NetDescs' layer offsets and the chunk loop's bounds, reloaded at the start of a pass, none of its 41 scratch accesses inside an
+          # innermost MFMA k-loop; popart_step_kernel 62
+          ("popart_actor_", 20), ("popart_", 0), ("", 20)]
 bad = []
 for blk in md.split("  - .agpr_count:")[1:]:
     g = lambda k: re.search(r"\.%s:\s+(\S+)" % k, blk).group(1)
