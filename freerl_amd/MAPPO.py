@@ -78,7 +78,7 @@ class MultiAgentPPO:
         self._e.net_norm_set(self.trick["feature_norm"], self.trick["LayerNorm"])
         self.agents, self.buffers = {}, {}
         for j, aid in enumerate(self.agent_ids):
-            self.agents[aid] = Agent(self._e, j, self._od[j], self._ad[j], self._critic_in(j), is_continue, self.trick, hidden)
+            self.agents[aid] = self._agent(j, hidden)
             self._optimizers(self.agents[aid], j, actor_lr, critic_lr)
             self.buffers[aid] = AgentBuffer(self._e, j, self.device, self.horizon)
         if self.trick["lr_decay"]:
@@ -86,6 +86,9 @@ class MultiAgentPPO:
         self._rng = rng
         self._rec = np.zeros(self._e.width, dtype=F32)
         self.last_trace = None
+
+    def _agent(self, j, hidden):
+        return Agent(self._e, j, self._od[j], self._ad[j], self._critic_in(j), self.is_continue, self.trick, hidden)
 
     def select_action(self, obs):
         actions, log_pis = {}, {}

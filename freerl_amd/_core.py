@@ -52,6 +52,19 @@ class OptimizerView:
                     exp_avg_sq=self._e.get_params(self._net, N.PARAM_ADAM_V), param_groups=self.param_groups)
 
 
+def split_layers(layers, flat, extra=None):
+    """a flat parameter vector -> {name.weight, name.bias, [extra]} views, `layers` = [(name, out, in)], `extra` = (name, shape)"""
+    out, o = {}, 0
+    for n, od, idim in layers:
+        out[n + ".weight"] = flat[o:o + od * idim].reshape(od, idim); o += od * idim
+        out[n + ".bias"] = flat[o:o + od]; o += od
+    if extra:
+        sz = int(np.prod(extra[1]))
+        out[extra[0]] = flat[o:o + sz].reshape(extra[1]); o += sz
+    assert o == flat.size
+    return out
+
+
 class DeviceNet:
     """Stands where the reference has an `nn.Module` (`agent.Qnet`, `agent.actor`, ...): the
     parameters live in the engine; `state_dict()/load_state_dict()` keep the reference's
@@ -71,16 +84,7 @@ class DeviceNet:
         return ks
 
     def _split(self, flat):
-        out, o = {}, 0
-        for n, od, idim in self._layers:
-            out[n + ".weight"] = flat[o:o + od * idim].reshape(od, idim); o += od * idim
-            out[n + ".bias"] = flat[o:o + od]; o += od
-        if self._extra:
-            shp = self._extra[1]
-            sz = int(np.prod(shp))
-            out[self._extra[0]] = flat[o:o + sz].reshape(shp); o += sz
-        assert o == flat.size
-        return out
+        return split_layers(self._layers, flat, self._extra)
 
     def state_dict(self):
         parts = self._split(self._e.get_params(self._net, self._kind, self._learner))

@@ -34,6 +34,7 @@ ALGO_MASAC = 15             # MAAC_file/MASAC.py: MADDPG's records and net numbe
 ALGO_GAIL_PPO = 16          # GAIL_file/PPO2.py: GAIL's policy side — actor + critic with LeakyReLU / ReLU hidden layers (frl_gail_ppo_learn)
 ALGO_CEM_GD3PG = 18         # (17 is unassigned) CEM_GD3PG_file/CEM_GD3PG.py: two online actors, a frozen domain actor, one critic, two rings per learner (frl_cem_gd3pg_learn)
 ALGO_DDPG_POPART = 20       # (19 is unassigned) DDPG_file/DDPG_simple_with_tricks.py, trick['popart']: DDPG's nets + an upper layer and running target statistics per learner (frl_popart_ddpg_learn)
+ALGO_MAPPO_ATT = 22         # (21 is unassigned) MAPPO_file/MAPPO_attention.py: MAPPO's record and actors, attention critics over one shared block, agents as the outer loop (frl_mappo_att_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL and GAIL_PPO engines only
@@ -166,6 +167,10 @@ class HappoArgs(C.Structure):           # frl_mappo_args' fields, then HAPPO's t
     _fields_ = MappoArgs._fields_ + [("agent_order", C.POINTER(C.c_int32)), ("factor_out", C.POINTER(C.c_float))]
 
 
+class MappoAttArgs(C.Structure):        # frl_mappo_args' fields, then the norm trace
+    _fields_ = MappoArgs._fields_ + [("norm_trace_out", C.POINTER(C.c_float))]
+
+
 class ExploreArgs(C.Structure):
     _fields_ = [("kind", C.c_int), ("epsilon", C.c_float), ("sigma", C.c_float), ("scale", C.c_float), ("max_action", C.c_float),
                 ("ou_theta", C.c_float), ("ou_sigma", C.c_float), ("ou_dt", C.c_float)]
@@ -273,6 +278,7 @@ SIGNATURES = {
     "frl_mappo_learn": (_i, [_vp, _P(MappoArgs)]),
     "frl_net_norm_set": (_i, [_vp, _i, _i]),
     "frl_happo_learn": (_i, [_vp, _P(HappoArgs)]),
+    "frl_mappo_att_learn": (_i, [_vp, _P(MappoAttArgs)]),
     "frl_action_mask_set": (_i, [_vp, _i]),
     "frl_act_masked": (_i, [_vp, _i, _i, _i, _fp, _fp, _fp, _fp, _fp]),
     "frl_ppo_work": (_i, [_vp, _i, _i, _P(C.c_double), _P(C.c_double)]),

@@ -62,16 +62,18 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"CEM-GD3PG",      "frl_cem_gd3pg_learn",     "FRL_ACT_TANHHEAD on net 0 / 1 / 3 (actor_1 / actor_2 / actor_domain), FRL_ACT_RAW on net 2 with [obs | act]", false, false, false, false, false, true,  false},
     {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 19: refused like 17
     {"PopArt-DDPG",    "frl_popart_ddpg_learn",   "FRL_ACT_TANHHEAD on net 0, FRL_ACT_RAW on net 1 with [obs | act]: the lower critic's output h, Q = sigma (W h + b) + mu (frl_popart_get)", false, false, false, false, false, true,  false},
+    {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 21: refused like 17
+    {"MAPPO-attention", "frl_mappo_att_learn",    "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
 };
-constexpr int kAlgoUnassigned[] = {17, 19};      // values no frl_algo has: their kAlgo rows only keep the table indexable by value
-inline bool algo_unassigned(int algo) { return algo == kAlgoUnassigned[0] || algo == kAlgoUnassigned[1]; }
+constexpr int kAlgoUnassigned[] = {17, 19, 21};      // values no frl_algo has: their kAlgo rows only keep the table indexable by value
+inline bool algo_unassigned(int algo) { return algo == kAlgoUnassigned[0] || algo == kAlgoUnassigned[1] || algo == kAlgoUnassigned[2]; }
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 // (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
 //  policy noise and its own launch order — learn_impl and the launchers ask for it by name)
 inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
-inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO; }              // ... and what is built, and acts, like them
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_DDPG_POPART - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo value, the two unassigned ones included");
+inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO || algo == FRL_ALGO_MAPPO_ATT; }      // ... and what is built, and acts, like them (FRL_ALGO_MAPPO_ATT: its actors; its critics have their own forward)
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MAPPO_ATT - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo value, the unassigned ones included");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
@@ -424,7 +426,7 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
     if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_DDPG_POPART || algo_unassigned(c.algo)) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MAPPO_ATT || algo_unassigned(c.algo)) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -445,7 +447,17 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
                : plan_refuse(message, "FRL_ACT_LEAKY_RELU is the GAIL discriminator's hidden activation; %s engines do not take it", T.name);
     };
     switch (c.algo) {
-        case FRL_ALGO_MAPPO: case FRL_ALGO_IPPO: case FRL_ALGO_HAPPO: {
+        case FRL_ALGO_MAPPO: case FRL_ALGO_IPPO: case FRL_ALGO_HAPPO: case FRL_ALGO_MAPPO_ATT: {
+            // what kernels_mappo_att.hip handles beyond that (attention.py:135-205: torch.cat of no others raises; every e_j goes through
+            // agent i's own encoder_fc_s; Attention() is built at 128 / 128 / 4 whatever the script's hidden is)
+            if (c.algo == FRL_ALGO_MAPPO_ATT) {
+                if (c.n_agents < 2) return plan_refuse(message, "%s: n_agents %d < 2: the attention runs over the OTHER agents' encodings and would have none", T.name, c.n_agents);
+                for (int j = 1; j < c.n_agents; ++j)
+                    if (c.obs_dim[j] != c.obs_dim[0])
+                        return plan_refuse(message, "%s: obs_dim[%d] = %d != obs_dim[0] = %d: every agent's observation goes through agent i's own encoder, so the widths must be equal",
+                                           T.name, j, c.obs_dim[j], c.obs_dim[0]);
+                if (h.hidden != kMattHidden) return plan_refuse(message, "%s: hidden %d is refused (128: the attention block is built at 128 wide with 4 heads of 32)", T.name, h.hidden);
+            }
             // what kernels_mappo.hip handles (the LayerNorm mask is 256 bits per row; one thread per row walks a discrete head)
             int amax = 0, lp_cols = 0;
             for (int j = 0; j < c.n_agents; ++j) { amax = std::max(amax, c.act_dim[j]); lp_cols += c.discrete ? 1 : c.act_dim[j]; }
@@ -584,6 +596,15 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
                 if (c.discrete) h.n_discrete = std::max(h.n_discrete, c.act_dim[j]);      // (a flag to these kernels: an agent's action count is its actor's head width)
             }
             break;
+        case FRL_ALGO_MAPPO_ATT:
+            // Actor / Actor_discrete as MAPPO's (MAPPO_attention.py:116-186); Attention_Critic (attention.py:135-205) as the six layers of MattLayer
+            h.n_nets = 2 * c.n_agents;
+            for (int j = 0; j < c.n_agents; ++j) {
+                build_net(h.net[2 * j], {{H, c.obs_dim[j]}, {H, H}, {c.act_dim[j], H}}, 1, ACT_RELU, c.discrete ? ACT_NONE : ACT_TANH, c.discrete ? 0 : c.act_dim[j]);
+                build_net(h.net[2 * j + 1], {{H, c.obs_dim[j]}, {H, 2 * H}, {1, H}, {H, H}, {2 * H, H}, {H, H}}, 1, ACT_RELU, ACT_NONE, 0);
+                if (c.discrete) h.n_discrete = std::max(h.n_discrete, c.act_dim[j]);
+            }
+            break;
         case FRL_ALGO_PPO:
             h.n_nets = 2;
             if (c.discrete) h.n_discrete = c.act_dim[0];
@@ -660,6 +681,10 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
             kin = std::max(kin, h.net[i].L[ATT_E].k_pad);
             continue;
         }
+        if (c.algo == FRL_ALGO_MAPPO_ATT && (i & 1)) {       // no chain either: xin holds one agent's observation segment, outb the value column
+            kin = std::max(kin, h.net[i].L[MATT_ENC].k_pad);
+            continue;
+        }
         for (int hd = 0; hd < h.net[i].heads; ++hd) {
             kin = std::max(kin, h.net[i].L[hd * nl].k_pad);
             outp = std::max(outp, h.net[i].L[hd * nl + nl - 1].n_pad);
@@ -717,6 +742,11 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
             h.lds_row_extra = mappo_row_extra(H);                               // reserved for the LayerNorm case: frl_net_norm_set cannot fail for space
             one_wg_per_net = whole_cu = true;
             break;
+        case FRL_ALGO_MAPPO_ATT:         // one persistent workgroup per net of the launch's agent; device/mappo_att.hpp: carve_matt behind carve_mappo
+            if (c.discrete) h.lds_act_pad = std::max(h.lds_act_pad, h.lds_out_pad);
+            h.lds_row_extra = matt_row_extra(H, c.n_agents);
+            one_wg_per_net = true;
+            break;
         case FRL_ALGO_MASAC:             // device/masac.hpp: the updating actor's head row behind the common carve
             h.lds_row_extra = masac_row_extra(h.act_max);
             break;
@@ -749,6 +779,12 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         if (lds_bytes_for(h, h.rc) > kLdsAtt)
             return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB (encoder input %d columns, decoder input at most %d)", T.name, lds_bytes_for(h, h.rc),
                                h.lds_kin_pad, h.lds_row_extra - 4 - 4 * (H + 4) - (kAttHeads * H + 4));
+    }
+    if (c.algo == FRL_ALGO_MAPPO_ATT) {       // the critic's chunk is one MFMA M tile: a constant, like the ATT-MADDPG family's
+        h.rc = kMattRc;
+        if (lds_bytes_for(h, h.rc) > 160 * 1024)
+            return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB (an observation segment of %d columns, %d action columns)", T.name, lds_bytes_for(h, h.rc),
+                               h.lds_kin_pad, h.lds_act_pad);
     }
     if (c.algo == FRL_ALGO_MASAC && lds_bytes_for(h, h.rc) > kLdsMasac)
         return plan_refuse(message, "%s: hidden %d is refused: %d B of LDS per %d-row chunk > 160 KB (the joint critic input is %d columns wide)", T.name, H,

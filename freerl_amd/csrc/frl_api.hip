@@ -55,6 +55,7 @@
 #include "kernels_her.hip"
 #include "kernels_cem_gd3pg.hip"
 #include "kernels_popart.hip"
+#include "kernels_mappo_att.hip"
 #endif
 
 using namespace frl;
@@ -258,7 +259,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 115; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set; 115: FRL_ALGO_DDPG_POPART, frl_popart_ddpg_args, frl_popart_ddpg_learn, frl_popart_get / _set
+extern "C" int frl_version(void) { return 116; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set; 115: FRL_ALGO_DDPG_POPART, frl_popart_ddpg_args, frl_popart_ddpg_learn, frl_popart_get / _set; 116: FRL_ALGO_MAPPO_ATT, frl_mappo_att_args, frl_mappo_att_learn
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -458,7 +459,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)mappo_state_values_kernel, (const void*)mappo_state_update_kernel, (const void*)mappo_state_mask_update_kernel,
                               (const void*)att_q_kernel, (const void*)masac_act_kernel, (const void*)gail_ppo_prepare_kernel,
                               (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel, (const void*)cem_critic_kernel, (const void*)cem_actor_kernel,
-                              (const void*)cem_act_kernel, (const void*)popart_target_kernel, (const void*)popart_critic_kernel, (const void*)popart_actor_kernel})
+                              (const void*)cem_act_kernel, (const void*)popart_target_kernel, (const void*)popart_critic_kernel, (const void*)popart_actor_kernel,
+                              (const void*)mappo_att_values_kernel, (const void*)mappo_att_update_kernel, (const void*)mappo_att_v_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -886,7 +888,8 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (head < 0 || head >= N.heads) return fail(FRL_ERR_INVALID, "head out of range");
     const int nl = N.n_layers / N.heads;
     // (an attention critic's rows are [all obs | all actions]: x_e and x_d are cut from them in the kernel)
-    const int want_in = (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total : N.L[head * nl].k;
+    const int want_in = (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total
+                        : (e->h.algo == ALGO_MAPPO_ATT && (net & 1)) ? e->h.rec.obs_total : N.L[head * nl].k;      // (an attention critic of either kind cuts its segments from the joint row)
     if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
     const bool masac_actor = e->h.algo == ALGO_MASAC && !(net & 1);      // its log_std is the head's second half, not an extra vector
     if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0 && !(masac_actor && mode == FRL_ACT_SAC_SAMPLE)) return fail(FRL_ERR_INVALID, "net has no log_std");
@@ -916,6 +919,12 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     a.normalize = (!no_norm && e->h.obs_norm_on && (e->h.n_agents == 1 || net % 2 == 0) && in_dim == e->h.rec.obs_dim[agent]) ? 1 : 0;
     a.in = in_dev; a.eps = eps_dev; a.out = out_dev; a.out_logp = logp_dev;
     if (build_only) { *build_only = a; return FRL_OK; }
+    if (e->h.algo == ALGO_MAPPO_ATT && (net & 1)) {      // the attention critic is no chain: its own forward (kernels_mappo_att.hip), V_i of the joint observation
+        if (mode != FRL_ACT_RAW || ex) return fail(FRL_ERR_INVALID, "a MAPPO-attention critic acts through FRL_ACT_RAW on rows [obs_0 | .. | obs_{n-1}] (its value)");
+        hipLaunchKernelGGL(mappo_att_v_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
     if (is_mappo_family(e->h.algo)) {        // the normalised forward (kernels_mappo.hip) in front of act_kernel's epilogue
         if (mode == FRL_ACT_SAC_SAMPLE || ex) return fail(FRL_ERR_INVALID, "a %s engine acts through FRL_ACT_RAW, _TANHHEAD, _ARGMAX, _PPO_SAMPLE or _CAT_SAMPLE", algo_traits(e->h.algo).name);
         hipLaunchKernelGGL(mappo_act_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);

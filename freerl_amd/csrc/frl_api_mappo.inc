@@ -1,4 +1,4 @@
-// MAPPO / IPPO entry points (included at the end of frl_api.hip); mappo_learn_chain is frl_happo_learn's too (frl_api_happo.inc).
+// MAPPO / IPPO / MAPPO_attention entry points (included at the end of frl_api.hip); mappo_learn_chain is frl_happo_learn's too (frl_api_happo.inc).
 
 extern "C" int frl_net_norm_set(frl_engine* e, int feature_norm, int layer_norm) {
     ENG(e);
@@ -64,9 +64,15 @@ struct HappoCall {
     float* factor_out;
 };
 
-// the whole of frl_mappo_learn, and of frl_happo_learn with `hc`: the argument refusals, the permutations, the three advantage launches,
-// then mappo_update_kernel once or happo_update_kernel once per visiting position, all on the engine's one stream
-static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const HappoCall* hc) {
+// MAPPO_attention's part of a call (frl_mappo_att_learn): nullptr for the other two
+struct MattCall {
+    float* norm_trace_out;
+};
+
+// the whole of frl_mappo_learn, of frl_happo_learn with `hc` and of frl_mappo_att_learn with `mc`: the argument refusals, the permutations,
+// the three advantage launches, then mappo_update_kernel once, happo_update_kernel once per visiting position or mappo_att_update_kernel
+// once per agent, all on the engine's one stream
+static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const HappoCall* hc, const MattCall* mc = nullptr) {
     const EngineDesc& h = e->h;
     const int n = h.n_agents;
     const size_t P = h.P, U = P * n;
@@ -99,7 +105,7 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
         }
     }
     const MappoLayout L = mappo_layout(c, P, hc != nullptr);
-    if (const int rc = onpolicy_scratch(e, L.floats, L.ints)) return rc;
+    if (const int rc = onpolicy_scratch(e, L.floats + (mc ? c.trace_n() / 2 : 0), L.ints)) return rc;      // (the critics' norm trace rides behind the layout)
     if (const int rc = onpolicy_perms(e, c, &perm)) return rc;
     MappoArgs a;
     memset(&a, 0, sizeof a);
@@ -114,7 +120,10 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     a.td = e->d_ppo + L.td; a.advd = e->d_ppo + L.advd; a.vs = e->d_ppo + L.vs; a.adv_seq = e->d_ppo + L.adv_seq; a.adv_raw = e->d_ppo + L.adv_raw;
     a.adv = e->d_ppo + L.adv; a.vtarget = e->d_ppo + L.vtarget; a.trace = e->d_ppo + L.trace;
     a.perm = e->d_perm;
-    if (h.state_dim > 0)      // the critic's row from two segments (kernels_mappo_state.hip)
+    float* norm_trace = mc ? e->d_ppo + L.floats : nullptr;
+    if (mc)                   // the attention critics' forward, the others streamed (kernels_mappo_att.hip)
+        hipLaunchKernelGGL(mappo_att_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
+    else if (h.state_dim > 0)      // the critic's row from two segments (kernels_mappo_state.hip)
         hipLaunchKernelGGL(mappo_state_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
     else
         hipLaunchKernelGGL(mappo_values_kernel, dim3((T + h.rc - 1) / h.rc, (unsigned)U), dim3(256), e->lds_bytes, e->stream, e->d, a);
@@ -130,6 +139,9 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
         x.factor = e->d_ppo + L.factor;
         for (x.k = 0; x.k < n; ++x.k)
             hipLaunchKernelGGL(happo_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, x);
+    } else if (mc) {                   // the agents are the outer loop: launch i + 1 starts from the attention block as launch i left it
+        for (int i = 0; i < n; ++i)
+            hipLaunchKernelGGL(mappo_att_update_kernel, dim3((unsigned)P, 2), dim3(256), e->lds_bytes, e->stream, e->d, a, i, norm_trace);
     } else if (h.state_dim > 0) {      // the critics' rows with the state block behind the observations (kernels_mappo_state.hip)
         if (h.mask_off) hipLaunchKernelGGL(mappo_state_mask_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
         else hipLaunchKernelGGL(mappo_state_update_kernel, dim3((unsigned)U, 2), dim3(256), e->lds_bytes, e->stream, e->d, a);
@@ -144,6 +156,7 @@ static int mappo_learn_chain(frl_engine* e, const frl_mappo_args* args, const Ha
     if (args->adv_out) HIP_TRY(hipMemcpy(args->adv_out, a.adv_raw, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
     if (args->vtarget_out) HIP_TRY(hipMemcpy(args->vtarget_out, a.vtarget, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
     if (args->loss_trace_out) HIP_TRY(hipMemcpy(args->loss_trace_out, a.trace, c.trace_n() * sizeof(float), hipMemcpyDeviceToHost));
+    if (mc && mc->norm_trace_out) HIP_TRY(hipMemcpy(mc->norm_trace_out, norm_trace, c.trace_n() / 2 * sizeof(float), hipMemcpyDeviceToHost));
     if (hc && hc->factor_out) HIP_TRY(hipMemcpy(hc->factor_out, x.factor, c.rows() * sizeof(float), hipMemcpyDeviceToHost));
     // Buffer_for_PPO.clear() (MAPPO.py:481-482, IPPO.py:321-322, HAPPO.py:456-458): counters only
     for (int p = 0; p < h.P; ++p) { e->index[p] = 0; e->size[p] = 0; }
@@ -155,4 +168,16 @@ extern "C" int frl_mappo_learn(frl_engine* e, const frl_mappo_args* args) {
     if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
     if (!is_mappo(e->h.algo)) return wrong_engine(e->h, "frl_mappo_learn");
     return mappo_learn_chain(e, args, nullptr);
+}
+
+extern "C" int frl_mappo_att_learn(frl_engine* e, const frl_mappo_att_args* args) {
+    ENG(e);
+    if (!args) return fail(FRL_ERR_INVALID, "args is NULL");
+    if (e->h.algo != ALGO_MAPPO_ATT) return wrong_engine(e->h, "frl_mappo_att_learn");
+    // frl_mappo_att_args is frl_mappo_args' fields, in order, and one more behind them
+    static_assert(offsetof(frl_mappo_att_args, norm_trace_out) == sizeof(frl_mappo_args), "frl_mappo_att_args begins with frl_mappo_args' fields");
+    frl_mappo_args m;
+    memcpy(&m, args, sizeof m);
+    const MattCall mc = {args->norm_trace_out};
+    return mappo_learn_chain(e, &m, nullptr, &mc);
 }

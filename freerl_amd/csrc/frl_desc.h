@@ -13,7 +13,7 @@ constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slop
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
                   ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16, ALGO_CEM_GD3PG = 18 /* 17: unassigned */,
-                  ALGO_DDPG_POPART = 20 /* 19: unassigned */ };
+                  ALGO_DDPG_POPART = 20 /* 19: unassigned */, ALGO_MAPPO_ATT = 22 /* 21: unassigned */ };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -89,7 +89,20 @@ constexpr int kMappoMaskWords = 8;       // 32-bit words of ReLU mask bits per r
 constexpr int mappo_row_extra(int hidden) { return (hidden + 4) + 2 + 2 * kMappoMaskWords + 2; }
 // MAPPO and HAPPO engines (not IPPO): every critic reads the concatenated observation, actor and critic use all n advantage / target
 // columns of a row, adv_norm runs over the whole [T][n] matrix (host and device)
-constexpr bool mappo_joint(int algo) { return algo == ALGO_MAPPO || algo == ALGO_HAPPO; }
+constexpr bool mappo_joint(int algo) { return algo == ALGO_MAPPO || algo == ALGO_HAPPO || algo == ALGO_MAPPO_ATT; }
+
+// MAPPO_attention's critic (device/mappo_att.hpp, kernels_mappo_att.hip; MAPPO_file/attention.py:85-205): the layers of net 2i+1 of an
+// ALGO_MAPPO_ATT engine.  The first three are critic i's own; the last three are the shared attention block, whose parameters live in
+// net 1's copy (the same layers of nets 3, 5, .. hold that agent's Adam moments and gradient only).  Like AttLayer's net it is no chain.
+constexpr int kMattHeads = 4, kMattHidden = 128, kMattHeadDim = kMattHidden / kMattHeads;      // Attention(in_dim=128, hidden_dim=128, num_heads=4)
+enum MattLayer : int { MATT_ENC = 0, MATT_L1 = 1, MATT_L3 = 2, MATT_Q = 3, MATT_KV = 4, MATT_O = 5, MATT_LAYERS = 6 };
+constexpr int kMattRc = 16;              // rows per chunk: the 16 rows are one MFMA M tile, and a (row, head) pair is 16 lanes' work
+// floats per chunk row behind carve_mappo()'s region (device/mappo_att.hpp: carve_matt): three [2 hidden] rows (x = [e_i | att], [K | V],
+// d x), five [hidden] rows (Q, attn, d attn, d Q, d e), the raw scores of the n_agents - 1 others x 4 heads, then 16 floats: m, l, D per
+// head and the joint feature norm's mean and rstd.  Nothing in it is sized by kMaxAgents
+constexpr int matt_row_extra(int hidden, int n_agents) {
+    return mappo_row_extra(hidden) + 3 * (2 * hidden + 4) + 5 * (hidden + 4) + kMattHeads * (n_agents - 1) + 16;
+}
 
 // The attention critic of ATT-MADDPG (device/att.hpp, kernels_att.hip; MADDPG_file/ATT.py:181-229): the layers of net 2i+1 of an
 // ALGO_MADDPG_ATT engine in the reference's state_dict order, the four fc_encoder_heads stacked into ONE layer of 4 x hidden outputs

@@ -287,6 +287,12 @@ struct HappoArgs {
 };
 __global__ void happo_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a, HappoArgs x);
 
+// kernels_mappo_att.hip: MAPPO_attention (MAPPO_file/MAPPO_attention.py) on an ALGO_MAPPO_ATT engine: the attention critics' value pass in
+// front of MAPPO's scan and advantage launches, one update launch per agent (`agent`) behind them, and the critic's forward for frl_act
+__global__ void mappo_att_values_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a);
+__global__ void mappo_att_update_kernel(const EngineDesc* __restrict__ Dp, MappoArgs a, int agent, float* norm_trace);      // norm_trace [P][n][k_epochs * n_mb]: the critic's gradient norm of every step before clipping, or nullptr
+__global__ void mappo_att_v_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_dqn.hip
 __global__ void dqn_grad_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 

@@ -730,6 +730,16 @@ class Engine:
         N.check(self._L.frl_happo_learn(self._h, C.byref(a)))
         return out
 
+    def mappo_att_learn(self, horizon, minibatch, k_epochs, *, want_norms=False, **kw):
+        """MAPPO_attention's learn for every learner (frl_mappo_att_learn): mappo_learn's arguments; want_norms adds `norms`
+        [P][n_agents][k_epochs * n_mb], the critic's gradient norm of every step before clipping."""
+        a, keep, out = N.MappoAttArgs(), [], {}
+        self._mappo_args(a, keep, out, horizon, minibatch, k_epochs, **kw)
+        if want_norms:
+            _want_outputs(a, out, [("norms", "norm_trace_out", (self.P, self.n_agents, _trace_steps(horizon, minibatch, k_epochs)))])
+        N.check(self._L.frl_mappo_att_learn(self._h, C.byref(a)))
+        return out
+
     # ------------------------------------------------------------------ timing
     def ppo_work(self, horizon, k_epochs):
         fl, by = C.c_double(0), C.c_double(0)

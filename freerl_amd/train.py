@@ -38,7 +38,7 @@ _MAPPO = [("N", int, None), ("horizon", int, 256), ("clip_param", float, 0.2), (
 _MAPPO_TRICK = {"adv_norm": False, "ObsNorm": False, "reward_norm": False, "reward_scaling": False, "orthogonal_init": False,
                 "adam_eps": False, "lr_decay": False, "ValueClip": False, "huber_loss": False, "LayerNorm": False, "feature_norm": False}
 
-_MA_PPO = ("mappo", "ippo", "happo")      # the multi-agent PPO scripts: one loop (_run_mappo)
+_MA_PPO = ("mappo", "ippo", "happo", "mappo_attention")      # the multi-agent PPO scripts: one loop (_run_mappo)
 _MADDPG = ("maddpg", "maddpg_att")        # MADDPG_simple.py and MADDPG_simple_with_tricks.py: one loop (_run_maddpg)
 _MA_REPLAY = _MADDPG + ("masac",)         # ... and MAAC_file/MASAC.py (_run_masac): continuous parallel envs, dict in / dict out
 
@@ -116,6 +116,11 @@ FLAGS = {
     "ippo": dict(env_name="simple_adversary_v3", policy_name="IPPO", device="cuda", is_dis_to_con=False,
                  flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=5000, save_freq=5000 // 4, start_steps=0,
                                                               learn_steps_interval=0), trick=dict(_MAPPO_TRICK)),
+    # MAPPO_file/MAPPO_attention.py:491-532.  --N: the script's 30 agents cannot be built (FRL_MAX_AGENTS is 8 in the ABI's structs); 3 is
+    # simple_spread's own count, what `train mappo` runs on
+    "mappo_attention": dict(env_name="simple_spread_v3", policy_name="MAPPO_attention", device="cpu", is_dis_to_con=False,
+                            flags=_COMMON + _AC + _MAPPO, overrides=dict(N=3, seed=0, max_episodes=5000, save_freq=5000 // 4, start_steps=0,
+                                                                         learn_steps_interval=0, gamma=0.95), trick=dict(_MAPPO_TRICK)),
     # MAPPO_file/HAPPO.py:547-583
     "happo": dict(env_name="simple_spread_v3", policy_name="HAPPO", device="cuda", is_dis_to_con=False,
                   flags=_COMMON + _AC + _MAPPO, overrides=dict(seed=100, max_episodes=120000, save_freq=5000 // 4, start_steps=0,
@@ -149,7 +154,9 @@ def build_parser(algo):
         p.add_argument("--elitism", dest="elitism", action="store_true")
         p.add_argument("--mult_noise", dest="mult_noise", action="store_true")
     if algo in _MA_PPO:                    # (type=bool as in the scripts: any non-empty string is True)
-        p.add_argument("--continuous_actions", type=bool, default=(algo == "mappo"))
+        p.add_argument("--continuous_actions", type=bool, default=algo in ("mappo", "mappo_attention"))
+    if algo == "mappo_attention":          # (the script's spelling of the flag; the class's argument is `improment`)
+        p.add_argument("--improvement", type=dict, default={"attention": True})
     p.add_argument("--device", type=str, default=spec["device"])
     # additions of this build (not in the reference)
     p.add_argument("--results_root", type=str, default=os.path.join(os.getcwd(), "results"))
@@ -841,7 +848,17 @@ def run(algo, argv=None, env=None, log=print):
     log("-" * 50)
     log("Algorithm:", args.policy_name)
     device = torch.device(args.device) if torch.cuda.is_available() else torch.device("cpu")
-    if algo in _MA_PPO:
+    if algo == "mappo_attention":          # MAPPO_attention.py:539-562: `MAPPO_attention` switches on what `MAPPO` does, and the attention critic
+        if args.policy_name != "MAPPO_attention":
+            _mappo_policy_name(args, "MAPPO")
+        t = args.trick
+        if args.policy_name == "MAPPO_attention" or (t["lr_decay"] is False and args.improvement["attention"] and
+                                                     all(v for k, v in t.items() if k not in ("reward_norm", "lr_decay"))):
+            args.policy_name = "MAPPO_attention"
+            for k in t:
+                t[k] = k not in ("reward_norm", "lr_decay")
+            args.improvement["attention"] = True
+    elif algo in _MA_PPO:
         _mappo_policy_name(args, algo.upper())
     if algo in _MA_REPLAY or algo in _MA_PPO:
         if algo not in _MA_REPLAY and not args.continuous_actions and env is None:
@@ -949,9 +966,11 @@ def run(algo, argv=None, env=None, log=print):
         from .HAPPO import HAPPO
         from .IPPO import IPPO
         from .MAPPO import MAPPO
-        cls = dict(mappo=MAPPO, ippo=IPPO, happo=HAPPO)[algo]
+        from .MAPPO_attention import MAPPO as MAPPO_attention
+        cls = dict(mappo=MAPPO, ippo=IPPO, happo=HAPPO, mappo_attention=MAPPO_attention)[algo]
+        extra = (args.improvement,) if algo == "mappo_attention" else ()
         # (these classes draw their permutations from np.random like the scripts unless --rng device is asked for)
-        policy = cls(dim_info, is_continue, args.actor_lr, args.critic_lr, args.horizon, device, args.trick,
+        policy = cls(dim_info, is_continue, args.actor_lr, args.critic_lr, args.horizon, device, args.trick, *extra,
                      rng="device" if args.rng == "device" else "host", seed=args.seed, minibatch_max=max(args.minibatch_size, 1))
         out = _run_mappo(args, env, policy, dim_info, max_action, is_continue, model_dir, writer, log)
         writer.close()

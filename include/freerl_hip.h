@@ -119,7 +119,7 @@ enum frl_algo {
                                   [r capacity, (r + 1) capacity) are ring r), zero-filled at create.  Updated by frl_cem_gd3pg_learn
                                   only.  frl_act: FRL_ACT_TANHHEAD on nets 0, 1 and 3 (use_target on 0 and 1), FRL_ACT_RAW on net 2.
                                   frl_version() 114 */
-    FRL_ALGO_DDPG_POPART = 20  /* (19 is unassigned, as 17 is.)  DDPG_file/DDPG_simple_with_tricks.py:44-292 with trick['popart']: net 0 the actor
+    FRL_ALGO_DDPG_POPART = 20, /* (19 is unassigned, as 17 is.)  DDPG_file/DDPG_simple_with_tricks.py:44-292 with trick['popart']: net 0 the actor
                                   obs_dim -> hidden (ReLU) -> hidden (ReLU) -> act_dim (tanh), net 1 PopArt's lower layers, the critic
                                   [obs | act] -> hidden (ReLU) -> hidden (ReLU) -> 1, each with a target net.  Per learner, outside the nets:
                                   the upper layer Linear(1, 1) {W, b} (1, 0 at create) with its own Adam state and no target copy, and the
@@ -127,6 +127,17 @@ enum frl_algo {
                                   FRL_ACT_RELU; discrete, twin_critic, dueling, noisy, c51_atoms and n_agents != 1 are refused.  Updated by
                                   frl_popart_ddpg_learn only.  frl_act as on a FRL_ALGO_DDPG engine: FRL_ACT_TANHHEAD on net 0,
                                   FRL_ACT_RAW on net 1 = the LOWER critic's raw output h (Q = sigma (W h + b) + mu).  frl_version() 115 */
+    FRL_ALGO_MAPPO_ATT = 22    /* (21 is unassigned, as 17 and 19 are.)  MAPPO_file/MAPPO_attention.py with improvement['attention'] (attention.py:85-205):
+                                  a FRL_ALGO_MAPPO engine's record, actors (net 2i) and learn arguments, but net 2i+1 is agent i's
+                                  Attention_Critic, six layers in this order: encoder_fc_s obs_dim -> 128, l1 256 -> 128, l3 128 -> 1, then
+                                  the attention block query 128 -> 128, [key ; value.0] 128 -> 256 (rows [0, 128) the key) and fc_out
+                                  128 -> 128.  query and key have no bias: their bias slots are zero and stay zero.  ONE attention block
+                                  serves every critic of a learner (MAPPO.__init__ builds one Attention()): its parameters are the three
+                                  attention layers of net 1; the same layers of nets 3, 5, .. hold only THAT agent's Adam moments
+                                  (FRL_PARAM_ADAM_M / _V) and gradient, their FRL_PARAM_ONLINE slot is never read.  2 <= n_agents <=
+                                  FRL_MAX_AGENTS, every obs_dim equal, hidden 128; extra_cols as FRL_ALGO_MAPPO without masks or state.
+                                  Updated by frl_mappo_att_learn only.  frl_act: the actors as on FRL_ALGO_MAPPO; FRL_ACT_RAW on net 2i+1
+                                  with rows [obs_0 | .. | obs_{n-1}] is V_i.  frl_net_norm_set serves it.  frl_version() 116 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
@@ -767,6 +778,38 @@ struct frl_happo_args {
 };
 typedef struct frl_happo_args frl_happo_args;
 int frl_happo_learn(frl_engine* e, const frl_happo_args* args);
+
+/* ---------------------------------------------------------------- MAPPO_attention (MAPPO_file/MAPPO_attention.py) on a FRL_ALGO_MAPPO_ATT engine
+ * `MAPPO.learn(...)` with improvement['attention'] for every learner.  V(s) and V(s') of all n attention critics as they stand, the GAE
+ * scan, v_target and adv_norm over the whole matrix, the n-column surrogate and critic regression and the ValueClip that changes nothing
+ * are FRL_ALGO_MAPPO's.  Then the AGENTS are the outer loop (MAPPO_attention.py:354-400): agent i takes all k_epochs x ceil(horizon /
+ * minibatch) steps, actor and critic, before agent i+1 starts, so critic i+1 begins from the shared attention block as critic i's last
+ * step left it.  A critic step is clip_grad_norm_(clip_norm) over its 12 tensors (its own 6 and the block's 6) and Adam with agent i's
+ * own moments and step count for all 12.  One launch per agent follows the three advantage launches on the engine's one stream; stream
+ * order alone carries the dependency.  The caller passes IPPO's two Adams' settings (two lrs, adam_eps, clip_norm 0.5).
+ * Refusals are frl_mappo_learn's; FRL_ERR_STATE on engines of any other algorithm, and frl_mappo_learn / frl_happo_learn return it for
+ * FRL_ALGO_MAPPO_ATT engines.  Afterwards every ring cursor is (0, 0). */
+struct frl_mappo_att_args {
+    /* frl_mappo_args' fields, in its order and with its meaning */
+    int horizon;
+    int minibatch, k_epochs;
+    float gamma, lmbda, clip, ent_coef;
+    float actor_lr, critic_lr;
+    float adam_eps;
+    float clip_norm;
+    int adv_norm;
+    int value_clip;
+    int loss_kind;
+    float huber_delta;
+    const int64_t* perms;
+    float* adv_out;
+    float* vtarget_out;
+    float* loss_trace_out;
+    /* this entry point's own */
+    float* norm_trace_out;     /* host [P][n_agents][k_epochs * n_mb]: the critic's gradient norm (over its 12 tensors) of every step before clipping, or NULL */
+};
+typedef struct frl_mappo_att_args frl_mappo_att_args;
+int frl_mappo_att_learn(frl_engine* e, const frl_mappo_att_args* args);
 
 /* stand-alone GAE scan (K3) on device arrays [n_seq][horizon]: replaces the host loop at
  * PPO_with_tricks.py:308-311 / PPO.py:229-231 */
