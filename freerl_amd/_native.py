@@ -35,6 +35,7 @@ ALGO_GAIL_PPO = 16          # GAIL_file/PPO2.py: GAIL's policy side — actor + 
 ALGO_CEM_GD3PG = 18         # (17 is unassigned) CEM_GD3PG_file/CEM_GD3PG.py: two online actors, a frozen domain actor, one critic, two rings per learner (frl_cem_gd3pg_learn)
 ALGO_DDPG_POPART = 20       # (19 is unassigned) DDPG_file/DDPG_simple_with_tricks.py, trick['popart']: DDPG's nets + an upper layer and running target statistics per learner (frl_popart_ddpg_learn)
 ALGO_MAPPO_ATT = 22         # (21 is unassigned) MAPPO_file/MAPPO_attention.py: MAPPO's record and actors, attention critics over one shared block, agents as the outer loop (frl_mappo_att_learn)
+ALGO_MAAC = 24              # (23 is unassigned) MAAC_file/MAAC_discrete.py: MADDPG's records with one-hot actions, Categorical actors, attention critics over ONE shared block (nets 2 n + i of the per-net calls), a constant alpha per agent (frl_learn)
 LOSS_MSE, LOSS_HUBER = 0, 1
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 ACT_LEAKY_RELU = 3          # enum frl_activation: GAIL and GAIL_PPO engines only

@@ -64,23 +64,31 @@ inline constexpr AlgoTraits kAlgo[] = {
     {"PopArt-DDPG",    "frl_popart_ddpg_learn",   "FRL_ACT_TANHHEAD on net 0, FRL_ACT_RAW on net 1 with [obs | act]: the lower critic's output h, Q = sigma (W h + b) + mu (frl_popart_get)", false, false, false, false, false, true,  false},
     {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 21: refused like 17
     {"MAPPO-attention", "frl_mappo_att_learn",    "FRL_ACT_PPO_SAMPLE / FRL_ACT_CAT_SAMPLE on net 2i with agent i's observation",  false, false, false, false, false, false, false},
+    {"(unassigned)",   "",                        "",                                                                             false, false, false, false, false, false, false},      // 23: refused like 17
+    {"MAAC",           kFrlLearn,                 "FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX on net 2i with agent i's observation, FRL_ACT_RAW on net 2i+1 with [all obs | all one-hot actions]", false, false, false, false, false, false, false},
 };
-constexpr int kAlgoUnassigned[] = {17, 19, 21};      // values no frl_algo has: their kAlgo rows only keep the table indexable by value
-inline bool algo_unassigned(int algo) { return algo == kAlgoUnassigned[0] || algo == kAlgoUnassigned[1] || algo == kAlgoUnassigned[2]; }
+constexpr int kAlgoUnassigned[] = {17, 19, 21, 23};      // values no frl_algo has: their kAlgo rows only keep the table indexable by value
+inline bool algo_unassigned(int algo) {
+    for (const int u : kAlgoUnassigned)
+        if (algo == u) return true;
+    return false;
+}
 inline bool is_maddpg(int algo) { return algo == FRL_ALGO_MADDPG || algo == FRL_ALGO_MADDPG_ATT; }       // what frl_learn steps as MADDPG_simple.learn does
 // (FRL_ALGO_MASAC shares MADDPG's record, its nets 2i / 2i+1 and the frl_learn entry, but is NOT is_maddpg: it has no delayed policy step, no
 //  policy noise and its own launch order — learn_impl and the launchers ask for it by name)
-inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
+inline bool is_multi_agent_replay(int algo) { return is_maddpg(algo) || algo == FRL_ALGO_MASAC || algo == FRL_ALGO_MAAC; }      // n_agents > 1 on a replay ring, learnt by frl_learn
+inline bool per_agent_alpha(int algo) { return algo == FRL_ALGO_MASAC || algo == FRL_ALGO_MAAC; }      // EngineDesc::alpha is [P][n_agents][4], 2 n + 1 noise sets per updating agent
 inline bool is_mappo(int algo) { return algo == FRL_ALGO_MAPPO || algo == FRL_ALGO_IPPO; }                 // what frl_mappo_learn updates
 inline bool is_mappo_family(int algo) { return is_mappo(algo) || algo == FRL_ALGO_HAPPO || algo == FRL_ALGO_MAPPO_ATT; }      // ... and what is built, and acts, like them (FRL_ALGO_MAPPO_ATT: its actors; its critics have their own forward)
-static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MAPPO_ATT - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo value, the unassigned ones included");
+static_assert(sizeof kAlgo / sizeof kAlgo[0] == FRL_ALGO_MAAC - FRL_ALGO_REPLAY_ONLY + 1, "one kAlgo row per frl_algo value, the unassigned ones included");
 inline const AlgoTraits& algo_traits(int algo) { return kAlgo[algo - FRL_ALGO_REPLAY_ONLY]; }
 
 // The kernel family an engine's frl_learn() runs on (frl_api_learn.inc: kLearnKernels registers each family's kernels).
 // plan_engine fixes the engine's chained family — or none: FAM_ROWCHUNK — with its parameter layout; learn_family() says what one call takes.
 // FAM_ATT: the attention critic's row-chunk kernels (kernels_att.hip) — what every FRL_ALGO_MADDPG_ATT engine learns with, and nothing else does
 // FAM_MASAC: MASAC's row-chunk kernels (kernels_masac.hip): one critic launch, then one actor launch per agent — every FRL_ALGO_MASAC engine, nothing else
-enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16, FAM_ATT, FAM_MASAC };
+// FAM_MAAC: MAAC's row-chunk kernels (kernels_maac.hip): per agent a critic launch, its own reduce + step, an actor launch — every FRL_ALGO_MAAC engine, nothing else
+enum LearnFamily { FAM_ROWCHUNK, FAM_DQN_FUSED, FAM_CHAINED, FAM_SOLO, FAM_SOLOW, FAM_WIDE, FAM_WIDE16, FAM_ATT, FAM_MASAC, FAM_MAAC };
 // dynamic LDS of a family's launches = its kernels' hipFuncAttributeMaxDynamicSharedMemorySize
 constexpr int kLdsDqnFused = dqn2_lds_floats() * (int)sizeof(float);
 constexpr int kLdsChain4 = critic2_lds_floats() * (int)sizeof(float), kLdsChain8 = critic8_lds_floats() * (int)sizeof(float);
@@ -88,6 +96,7 @@ constexpr int kLdsSolo = std::max(solo_lds_floats(), critic2_lds_floats()) * (in
 constexpr int kLdsSolow = solow_lds_floats() * (int)sizeof(float);
 constexpr int kLdsWide = wide_lds_floats() * (int)sizeof(float), kLdsWide16 = wide16_lds_floats_host() * (int)sizeof(float);
 constexpr int kLdsMasac = 160 * 1024;     // ... and a FAM_MASAC launch (the row chunk is chosen for two workgroups per CU where the nets allow it)
+constexpr int kLdsMaac = 160 * 1024;      // the most a FAM_MAAC launch may carve: one workgroup per CU at 16 rows (plan_sizes refuses more)
 constexpr int kLdsAtt = 160 * 1024;       // the most a FAM_ATT launch may carve; a launch carves its engine's own row-chunk bytes (plan_sizes refuses more)
 
 struct PlanLimits {               // of the device
@@ -195,7 +204,7 @@ inline void build_record(RecordDesc& R, const frl_config& c) {
     R.obs_total = off;
     for (int j = 0; j < c.n_agents; ++j) {
         R.act_off[j] = off;
-        R.act_dim[j] = (c.discrete || T.index_action) ? 1 : c.act_dim[j];
+        R.act_dim[j] = ((c.discrete && c.algo != FRL_ALGO_MAAC) || T.index_action) ? 1 : c.act_dim[j];      // (MAAC stores the one-hot action)
         off += R.act_dim[j];
     }
     R.act_total = off - R.obs_total;
@@ -299,6 +308,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
     const int n_cus = pl.n_cus, lds_per_cu = pl.lds_per_cu;
     if (!pl.has_nets) return FAM_ROWCHUNK;
     if (h.algo == ALGO_MASAC) return FAM_MASAC;         // (nor the stacked [mean | log_std] head, the all-actors actor loss or the per-agent launches)
+    if (h.algo == ALGO_MAAC) return FAM_MAAC;           // (its critics are no chains and its launches go agent by agent)
     if (h.algo == ALGO_MADDPG_ATT) return FAM_ATT;      // (no chained, solo, solow or wide kernel knows the attention critic: the shapes below never see it)
     const bool named = knobs.critic_v2 >= 0;
     if (chained_shape(h) && !knobs.solow_narrow) {
@@ -363,7 +373,7 @@ inline LearnFamily choose_engine_family(EnginePlan& pl, const PlanKnobs& knobs) 
 // (super-chunks of 256 rows / a 16-row tile per workgroup).
 inline LearnFamily learn_family(const EngineDesc& h, LearnFamily family, int batch, bool dqn_fused_on) {
     if (dqn_fused_shape(h, batch) && dqn_fused_on) return FAM_DQN_FUSED;
-    if (family == FAM_ATT || family == FAM_MASAC) return family;
+    if (family == FAM_ATT || family == FAM_MASAC || family == FAM_MAAC) return family;
     const bool narrow = family == FAM_CHAINED || family == FAM_SOLO;
     return (h.obs_norm_on || (narrow && batch > 256)) ? FAM_ROWCHUNK : family;
 }
@@ -389,6 +399,7 @@ inline int family_lds_bytes(LearnFamily fam, int chain_waves) {
         case FAM_WIDE16: return kLdsWide16;
         case FAM_ATT: return kLdsAtt;
         case FAM_MASAC: return kLdsMasac;
+        case FAM_MAAC: return kLdsMaac;
         case FAM_ROWCHUNK: break;
     }
     return 0;
@@ -404,9 +415,11 @@ inline LearnPath learn_path(const EngineDesc& h, const EngineFacts& f, LearnFami
         // kernels_solo.hip: 16-row tiles, 16 / h.solo of them per workgroup (its own carve; the launch carries the rollout tail's on top)
         case FAM_SOLO: bytes = solo_lds_floats() * (int)sizeof(float); rows = 16 * (kSoloWG / h.solo); break;
         case FAM_SOLOW: rows = 16 * (h.solow / std::max(1, f.solow_row_wgs)); break;      // one 16-row tile per workgroup
+        // row chunks, and the rows are those of ALL the chunks a workgroup walks: cps chunks of rc rows, or as many as the batch has
+        case FAM_MAAC: bytes = f.lds_bytes; rows = h.rc * std::min(h.cps, rowchunk_chunks(h, batch)); break;
         default: break;                                                                 // one workgroup per unit walks the batch
     }
-    return {fam != FAM_ROWCHUNK && fam != FAM_ATT && fam != FAM_MASAC, bytes, rows};
+    return {fam != FAM_ROWCHUNK && fam != FAM_ATT && fam != FAM_MASAC && fam != FAM_MAAC, bytes, rows};
 }
 
 // ------------------------------------------------------------------------------- the plan
@@ -426,7 +439,7 @@ inline int check_create_args(const frl_config& c, const frl_config_ext* ext, std
     if (c.n_agents < 1 || c.n_agents > FRL_MAX_AGENTS) return plan_refuse(message, "n_agents out of range");
     if (!is_multi_agent_replay(c.algo) && !is_mappo_family(c.algo) && c.n_agents != 1) return plan_refuse(message, "n_agents > 1 needs FRL_ALGO_MADDPG");
     if (c.capacity < 1) return plan_refuse(message, "capacity must be >= 1");
-    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MAPPO_ATT || algo_unassigned(c.algo)) return plan_refuse(message, "unknown algo %d", c.algo);
+    if (c.algo < FRL_ALGO_REPLAY_ONLY || c.algo > FRL_ALGO_MAAC || algo_unassigned(c.algo)) return plan_refuse(message, "unknown algo %d", c.algo);
     for (int j = 0; j < c.n_agents; ++j)
         if (c.obs_dim[j] < 1 || c.act_dim[j] < 1) return plan_refuse(message, "obs_dim/act_dim must be >= 1");
     return FRL_OK;
@@ -494,6 +507,20 @@ inline int plan_refusals(const frl_config& c, int state_dim, const EngineDesc& h
             if (!c.twin_critic) return plan_refuse(message, "%s: twin_critic = 0 is refused (Critic holds Q1 and Q2 in one net and the update takes their minimum, MASAC.py:72-97)", T.name);
             if (c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0) return plan_refuse(message, "%s: dueling, noisy, c51_atoms and actor_dist must be 0", T.name);
             if (c.hidden_act != FRL_ACT_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_RELU: the reference's nets have no other)", T.name, c.hidden_act);
+            return FRL_OK;
+        case FRL_ALGO_MAAC:
+            // what kernels_maac.hip handles (MAAC_discrete.py:44-75, Attention.py:63-231: Categorical actors, LeakyReLU nets, 4 heads over the others)
+            if (!c.discrete)
+                return plan_refuse(message, "%s: continuous actions are refused (discrete = 1: MAAC_discrete.py's Categorical actors; MAAC.py's critic never encodes the agent's own action)", T.name);
+            if (c.n_agents < 2) return plan_refuse(message, "%s: n_agents %d < 2: the attention runs over the OTHER agents' encodings and would have none", T.name, c.n_agents);
+            if (h.hidden % (8 * kMaacHeads) || h.hidden > kMaacMaxHidden)
+                return plan_refuse(message, "%s: hidden %d is refused (a multiple of 32 up to %d: %d heads whose columns two lanes share)", T.name, h.hidden, kMaacMaxHidden, kMaacHeads);
+            if (c.hidden_act != FRL_ACT_LEAKY_RELU) return plan_refuse(message, "%s: hidden_act %d is refused (FRL_ACT_LEAKY_RELU: the reference's nets have no other)", T.name, c.hidden_act);
+            if (c.twin_critic || c.dueling || c.noisy || c.c51_atoms || c.actor_dist != 0 || c.extra_cols != 0)
+                return plan_refuse(message, "%s: twin_critic, dueling, noisy, c51_atoms, actor_dist and extra_cols must be 0", T.name);
+            for (int j = 0; j < c.n_agents; ++j)
+                if (c.act_dim[j] < 2 || c.act_dim[j] > kSacdMaxActions)
+                    return plan_refuse(message, "%s: act_dim[%d] = %d outside [2, %d] (one thread per row walks an agent's logits)", T.name, j, c.act_dim[j], kSacdMaxActions);
             return FRL_OK;
         case FRL_ALGO_GAIL:     // (the gradient penalty's closed form needs a piecewise-linear activation: csrc/device/gail.hpp)
             if (c.hidden_act == FRL_ACT_TANH) return plan_refuse(message, "GAIL: hidden_act FRL_ACT_TANH is refused (FRL_ACT_LEAKY_RELU or FRL_ACT_RELU)");
@@ -657,6 +684,17 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
             }
             break;
         }
+        case FRL_ALGO_MAAC:
+            // Actor_discrete (MAAC_discrete.py:44-75): l1, l2, l3 with LeakyReLU, logits; Attention_Critic's own seven layers in state_dict order
+            // (MaacLayer); the attention block (Attention.py:63-110) as query, [key | value] and fc_out: EngineDesc::maac_att
+            h.n_nets = 2 * c.n_agents;
+            for (int j = 0; j < c.n_agents; ++j) {
+                const int O = c.obs_dim[j], A = c.act_dim[j];
+                build_net(h.net[2 * j], {{H, O}, {H, H}, {A, H}}, 1, ACT_LEAKY_RELU, ACT_NONE, 0);
+                build_net(h.net[2 * j + 1], {{H, O}, {H, O + A}, {H, A}, {H, 2 * H}, {A, H}, {H, H}, {1, H}}, 1, ACT_LEAKY_RELU, ACT_NONE, 0);
+            }
+            build_net(h.maac_att, {{H, H}, {2 * H, H}, {H, H}}, 1, ACT_NONE, ACT_NONE, 0);
+            break;
         default: {      // DDPG, TD3, SAC, MADDPG: an actor and a (twin) critic on the joint [obs | act] per agent
             h.n_nets = 2 * c.n_agents;
             const int cin = R.obs_total + R.act_total;
@@ -685,12 +723,21 @@ inline void plan_nets(const frl_config& c, int state_dim, EnginePlan& pl) {
             kin = std::max(kin, h.net[i].L[MATT_ENC].k_pad);
             continue;
         }
+        if (c.algo == FRL_ALGO_MAAC && (i & 1)) {            // no chain: xin holds one [o_j | a_j] segment, outb the all_q row
+            kin = std::max(kin, h.net[i].L[MAAC_ENC_SA].k_pad);
+            outp = std::max(outp, h.net[i].L[MAAC_FC2].n_pad);
+            continue;
+        }
         for (int hd = 0; hd < h.net[i].heads; ++hd) {
             kin = std::max(kin, h.net[i].L[hd * nl].k_pad);
             outp = std::max(outp, h.net[i].L[hd * nl + nl - 1].n_pad);
         }
     }
     h.learner_stride = pad32(off);
+    if (c.algo == FRL_ALGO_MAAC) {      // the attention block's n_agents slots behind the nets (frl_desc.h: EngineDesc::maac_off)
+        h.maac_off = h.learner_stride;
+        h.learner_stride += c.n_agents * h.maac_att.size;
+    }
     h.lds_kin_pad = kin;
     h.lds_out_pad = outp;
 }
@@ -750,6 +797,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         case FRL_ALGO_MASAC:             // device/masac.hpp: the updating actor's head row behind the common carve
             h.lds_row_extra = masac_row_extra(h.act_max);
             break;
+        case FRL_ALGO_MAAC:              // device/maac.hpp: carve_maac behind the common carve
+            h.lds_row_extra = maac_row_extra(H, c.n_agents);
+            break;
         case FRL_ALGO_MADDPG_ATT: {      // device/att.hpp: carve_att behind the common carve
             int xd = 16;
             for (int j = 0; j < c.n_agents; ++j) xd = std::max(xd, h.net[2 * j + 1].L[ATT_D].k_pad);
@@ -785,6 +835,13 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         if (lds_bytes_for(h, h.rc) > 160 * 1024)
             return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB (an observation segment of %d columns, %d action columns)", T.name, lds_bytes_for(h, h.rc),
                                h.lds_kin_pad, h.lds_act_pad);
+    }
+    if (c.algo == FRL_ALGO_MAAC) {            // the critic's chunk is one MFMA M tile, a (row, head) pair 16 lanes' work: a constant
+        h.rc = kMaacRc;
+        if (lds_bytes_for(h, h.rc) > kLdsMaac)
+            return plan_refuse(message, "%s: %d B of LDS per 16-row chunk > 160 KB: the action width does not fit the carve (an [o_j | a_j] segment of %d columns, a head of %d, "
+                                        "%d joint action columns twice; at 8 agents and hidden 128 the widest action that fits is 43)", T.name, lds_bytes_for(h, h.rc),
+                               h.lds_kin_pad, h.lds_out_pad, h.lds_act_pad);
     }
     if (c.algo == FRL_ALGO_MASAC && lds_bytes_for(h, h.rc) > kLdsMasac)
         return plan_refuse(message, "%s: hidden %d is refused: %d B of LDS per %d-row chunk > 160 KB (the joint critic input is %d columns wide)", T.name, H,
@@ -827,6 +884,8 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
     const size_t P = h.P;
     h.Gmax = 1;
     for (int i = 0; i < h.n_nets; ++i) h.Gmax = std::max(h.Gmax, (h.net[i].size / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
+    if (c.algo == FRL_ALGO_MAAC)      // (a critic's reduce / step walk its own net and an attention slot as one index space: kernels_maac.hip)
+        for (int j = 0; j < c.n_agents; ++j) h.Gmax = std::max(h.Gmax, ((h.net[2 * j + 1].size + h.maac_att.size) / 4 + 256 * kAdamVec - 1) / (256 * kAdamVec));
     pl.slab_count = slab_floats(h);
     pl.part_count = part_floats(h);
     pl.act_spill_count = c.algo == FRL_ALGO_CEM_GD3PG ? cem_spill_floats(h) : T.act_spill ? act_spill_floats(h) : 0;      // (CEM_GD3PG: a block per (learner, actor, slice))
@@ -841,9 +900,9 @@ inline int plan_sizes(const frl_config& c, const PlanKnobs& knobs, EnginePlan& p
         const LayerDesc& HL = h.net[0].L[h.net[0].n_layers - 1];
         pl.noisy_per_set = 2 * (HL.k_pad + HL.n_pad);
     }
-    h.noise_sets = c.algo == FRL_ALGO_MASAC ? 2 * h.n_agents + 1 : std::max(2, h.n_agents);      // (MASAC: frl_desc.h, EngineDesc::noise_sets)
-    pl.alpha_count = P * (c.algo == FRL_ALGO_MASAC ? (size_t)h.n_agents : 1) * 4;
-    pl.steps_count = P * (kMaxNets + 1) + (c.algo == FRL_ALGO_MASAC ? P * (size_t)h.n_agents : 0);
+    h.noise_sets = per_agent_alpha(c.algo) ? 2 * h.n_agents + 1 : std::max(2, h.n_agents);      // (MASAC, MAAC: frl_desc.h, EngineDesc::noise_sets)
+    pl.alpha_count = P * (per_agent_alpha(c.algo) ? (size_t)h.n_agents : 1) * 4;
+    pl.steps_count = P * (kMaxNets + 1) + (per_agent_alpha(c.algo) ? P * (size_t)h.n_agents : 0);
     pl.noise_count = P * h.n_agents * h.noise_sets * (size_t)h.batch_max * h.act_max;
     int biggest = 0;
     for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);

@@ -56,6 +56,7 @@
 #include "kernels_cem_gd3pg.hip"
 #include "kernels_popart.hip"
 #include "kernels_mappo_att.hip"
+#include "kernels_maac.hip"
 #endif
 
 using namespace frl;
@@ -259,7 +260,7 @@ static void prof_collect(frl_engine* e) {
 
 // --------------------------------------------------------------------------------- lifetime
 extern "C" const char* frl_last_error(void) { return g_err.c_str(); }
-extern "C" int frl_version(void) { return 116; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set; 115: FRL_ALGO_DDPG_POPART, frl_popart_ddpg_args, frl_popart_ddpg_learn, frl_popart_get / _set; 116: FRL_ALGO_MAPPO_ATT, frl_mappo_att_args, frl_mappo_att_learn
+extern "C" int frl_version(void) { return 117; }      // 101: frl_rollout_args.explore_kind 0 = FRL_EXPLORE_DEFAULT; 102: frl_learn_work_executed; 103: frl_config.reward_dim (appended), frl_envelope_learn; 104: FRL_ALGO_ENVELOPE_DDPG, frl_envelope_ddpg_learn; 105: FRL_ALGO_GAIL, FRL_ACT_LEAKY_RELU, frl_gail_learn, frl_gail_reward; 106: FRL_ALGO_MAPPO, FRL_ALGO_IPPO, frl_mappo_learn, frl_net_norm_set; 107: FRL_ALGO_HAPPO, frl_happo_args, frl_happo_learn; 108: frl_action_mask_set, frl_act_masked; 109: frl_config_ext, frl_create_ex, frl_state_info (the level whose body read `return 109;`: tests/test_mappo_state_abi.py looks for that text in this file); 110: FRL_ALGO_MADDPG_ATT (likewise `return 110;`: tests/test_att_abi.py); 111: FRL_ALGO_MASAC, frl_alpha_get_agent, frl_alpha_set_agent; 112: frl_her_args, frl_her_relabel; 113: FRL_ALGO_GAIL_PPO, frl_gail_ppo_args, frl_gail_ppo_learn, frl_log_std_range_set / _get; 114: FRL_ALGO_CEM_GD3PG, frl_cem_gd3pg_args, frl_cem_gd3pg_learn, frl_ring_add / _add_batch / _cursor_get / _cursor_set; 115: FRL_ALGO_DDPG_POPART, frl_popart_ddpg_args, frl_popart_ddpg_learn, frl_popart_get / _set; 116: FRL_ALGO_MAPPO_ATT, frl_mappo_att_args, frl_mappo_att_learn; 117: FRL_ALGO_MAAC (the attention block as nets 2 n + i of the per-net calls)
 
 extern "C" int frl_device_count(int* n_out) {
     if (!n_out) return fail(FRL_ERR_INVALID, "n_out is NULL");
@@ -460,7 +461,8 @@ extern "C" int frl_create_ex(const frl_config* cfg, const frl_config_ext* ext, f
                               (const void*)att_q_kernel, (const void*)masac_act_kernel, (const void*)gail_ppo_prepare_kernel,
                               (const void*)gail_ppo_update_kernel, (const void*)gail_ppo_act_kernel, (const void*)cem_critic_kernel, (const void*)cem_actor_kernel,
                               (const void*)cem_act_kernel, (const void*)popart_target_kernel, (const void*)popart_critic_kernel, (const void*)popart_actor_kernel,
-                              (const void*)mappo_att_values_kernel, (const void*)mappo_att_update_kernel, (const void*)mappo_att_v_kernel})
+                              (const void*)mappo_att_values_kernel, (const void*)mappo_att_update_kernel, (const void*)mappo_att_v_kernel,
+                              (const void*)maac_act_kernel, (const void*)maac_q_kernel})
             CREATE_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, e->lds_bytes));
         if (h.algo == ALGO_DDPG || h.algo == ALGO_TD3 || h.algo == ALGO_SAC) CREATE_TRY(set_family_lds_attributes(FAM_CHAINED));
         if (h.algo == ALGO_PPO)
@@ -707,8 +709,51 @@ extern "C" int frl_net_count(const frl_engine* e, int* n_out) {
     return FRL_OK;
 }
 
+static float* kind_ptr(frl_engine* e, int kind);
+// MAAC: the attention block is addressed as nets 2 n + i of the per-net calls (include/freerl_hip.h: FRL_ALGO_MAAC); -1: `net` is none of them
+static int maac_att_agent(const EngineDesc& h, int net) {
+    return (h.algo == ALGO_MAAC && net >= h.n_nets && net < h.n_nets + h.n_agents) ? net - h.n_nets : -1;
+}
+
+// the block of attention net 2 n + i: host order query.weight, key.weight, value.0.weight, value.0.bias, fc_out.weight, fc_out.bias; on the
+// device [key | value] is one layer (rows [0, H) the key) and the query's and the key's bias slots stay zero.  FRL_PARAM_ONLINE: slot 0,
+// the one block every online critic shares; every other kind: slot i
+static int maac_att_xfer(frl_engine* e, int learner, int agent, int kind, float* host, bool to_device) {
+    const EngineDesc& h = e->h;
+    const NetDesc& N = h.maac_att;
+    float* base = kind_ptr(e, kind);
+    if (!base || !host) return fail(FRL_ERR_INVALID, "bad kind / NULL buffer");
+    float* dev = base + (size_t)learner * h.learner_stride + maac_att_offset(h, kind == FRL_PARAM_ONLINE ? 0 : agent);
+    std::vector<float> blk(N.size, 0.f);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (!to_device) HIP_TRY(hipMemcpy(blk.data(), dev, (size_t)N.size * sizeof(float), hipMemcpyDeviceToHost));
+    const int H = N.L[MAAC_Q].n;
+    size_t o = 0;
+    auto move = [&](float& d) { if (to_device) d = host[o]; else host[o] = d; ++o; };
+    auto weight = [&](const LayerDesc& L, int row0) {
+        for (int r = 0; r < H; ++r)
+            for (int c = 0; c < H; ++c) move(blk[L.w_off + weight_index(N, L, row0 + r, c)]);
+    };
+    weight(N.L[MAAC_Q], 0);
+    weight(N.L[MAAC_KV], 0);
+    weight(N.L[MAAC_KV], H);
+    for (int r = 0; r < H; ++r) move(blk[N.L[MAAC_KV].b_off + H + r]);
+    weight(N.L[MAAC_O], 0);
+    for (int r = 0; r < H; ++r) move(blk[N.L[MAAC_O].b_off + r]);
+    if (to_device) {
+        HIP_TRY(hipMemcpy(dev, blk.data(), (size_t)N.size * sizeof(float), hipMemcpyHostToDevice));
+        ++e->param_version;
+    }
+    return FRL_OK;
+}
+
 extern "C" int frl_net_num_params(const frl_engine* e, int net, int* n_out) {
     if (!e || !n_out) return fail(FRL_ERR_INVALID, "NULL argument");
+    if (maac_att_agent(e->h, net) >= 0) {
+        const int H = e->h.hidden;
+        *n_out = 4 * H * H + 2 * H;
+        return FRL_OK;
+    }
     if (net < 0 || net >= e->h.n_nets) return fail(FRL_ERR_INVALID, "net %d out of range", net);
     *n_out = e->h.net[net].n_params;
     return FRL_OK;
@@ -729,6 +774,7 @@ static int params_xfer(frl_engine* e, int learner, int net, int kind, float* hos
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (learner < 0 || learner >= e->h.P) return fail(FRL_ERR_INVALID, "learner out of range");
+    if (maac_att_agent(e->h, net) >= 0) return maac_att_xfer(e, learner, maac_att_agent(e->h, net), kind, host, to_device);
     if (net < 0 || net >= e->h.n_nets) return fail(FRL_ERR_INVALID, "net %d out of range", net);
     float* base = kind_ptr(e, kind);
     if (!base || !host) return fail(FRL_ERR_INVALID, "bad kind / NULL buffer");
@@ -809,6 +855,7 @@ extern "C" int frl_params_pad_max(frl_engine* e, int learner, int net, int kind,
 
 extern "C" int frl_opt_step_get(frl_engine* e, int learner, int net, int* t_out) {
     ENG(e);
+    if (maac_att_agent(e->h, net) >= 0) net = 2 * maac_att_agent(e->h, net) + 1;      // (agent i's one critic optimiser steps both)
     if (!e->has_nets || learner < 0 || learner >= e->h.P || net < 0 || net > kMaxNets || !t_out) return fail(FRL_ERR_INVALID, "bad argument");
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(t_out, e->h.steps + (size_t)learner * (kMaxNets + 1) + net, sizeof(int), hipMemcpyDeviceToHost));
@@ -816,6 +863,7 @@ extern "C" int frl_opt_step_get(frl_engine* e, int learner, int net, int* t_out)
 }
 extern "C" int frl_opt_step_set(frl_engine* e, int learner, int net, int t) {
     ENG(e);
+    if (maac_att_agent(e->h, net) >= 0) net = 2 * maac_att_agent(e->h, net) + 1;
     if (!e->has_nets || learner < 0 || learner >= e->h.P || net < 0 || net > kMaxNets) return fail(FRL_ERR_INVALID, "bad argument");
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->h.steps + (size_t)learner * (kMaxNets + 1) + net, &t, sizeof(int), hipMemcpyHostToDevice));
@@ -835,21 +883,21 @@ static int masac_alpha_xfer(frl_engine* e, int learner, int agent, float* vals4,
 extern "C" int frl_alpha_get_agent(frl_engine* e, int learner, int agent, float* vals4_out, int* step_out) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || agent < 0 || agent >= e->h.n_agents || !vals4_out) return fail(FRL_ERR_INVALID, "bad argument");
-    if (e->h.algo != ALGO_MASAC) return agent == 0 ? frl_alpha_get(e, learner, vals4_out, step_out) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
+    if (!per_agent_alpha(e->h.algo)) return agent == 0 ? frl_alpha_get(e, learner, vals4_out, step_out) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
     return masac_alpha_xfer(e, learner, agent, vals4_out, step_out, false);
 }
 extern "C" int frl_alpha_set_agent(frl_engine* e, int learner, int agent, const float* vals4, int step) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || agent < 0 || agent >= e->h.n_agents || !vals4) return fail(FRL_ERR_INVALID, "bad argument");
-    if (e->h.algo != ALGO_MASAC) return agent == 0 ? frl_alpha_set(e, learner, vals4, step) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
+    if (!per_agent_alpha(e->h.algo)) return agent == 0 ? frl_alpha_set(e, learner, vals4, step) : fail(FRL_ERR_INVALID, "agent %d: a %s engine has one alpha per learner", agent, algo_traits(e->h.algo).name);
     return masac_alpha_xfer(e, learner, agent, const_cast<float*>(vals4), &step, true);
 }
 
 extern "C" int frl_alpha_get(frl_engine* e, int learner, float* vals4_out, int* step_out) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || !vals4_out) return fail(FRL_ERR_INVALID, "bad argument");
-    if (e->h.algo == ALGO_MASAC)
-        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_get: a MASAC engine has one alpha per agent: frl_alpha_get_agent") : masac_alpha_xfer(e, learner, 0, vals4_out, step_out, false);
+    if (per_agent_alpha(e->h.algo))
+        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_get: a MASAC / MAAC engine has one alpha per agent: frl_alpha_get_agent") : masac_alpha_xfer(e, learner, 0, vals4_out, step_out, false);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(vals4_out, e->h.alpha + (size_t)learner * 4, 4 * sizeof(float), hipMemcpyDeviceToHost));
     if (step_out) return frl_opt_step_get(e, learner, kMaxNets, step_out);
@@ -858,8 +906,8 @@ extern "C" int frl_alpha_get(frl_engine* e, int learner, float* vals4_out, int* 
 extern "C" int frl_alpha_set(frl_engine* e, int learner, const float* vals4, int step) {
     ENG(e);
     if (!e->has_nets || learner < 0 || learner >= e->h.P || !vals4) return fail(FRL_ERR_INVALID, "bad argument");
-    if (e->h.algo == ALGO_MASAC)
-        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_set: a MASAC engine has one alpha per agent: frl_alpha_set_agent") : masac_alpha_xfer(e, learner, 0, const_cast<float*>(vals4), &step, true);
+    if (per_agent_alpha(e->h.algo))
+        return e->h.n_agents > 1 ? fail(FRL_ERR_STATE, "frl_alpha_set: a MASAC / MAAC engine has one alpha per agent: frl_alpha_set_agent") : masac_alpha_xfer(e, learner, 0, const_cast<float*>(vals4), &step, true);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(e->h.alpha + (size_t)learner * 4, vals4, 4 * sizeof(float), hipMemcpyHostToDevice));
     return frl_opt_step_set(e, learner, kMaxNets, step);
@@ -888,7 +936,7 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (head < 0 || head >= N.heads) return fail(FRL_ERR_INVALID, "head out of range");
     const int nl = N.n_layers / N.heads;
     // (an attention critic's rows are [all obs | all actions]: x_e and x_d are cut from them in the kernel)
-    const int want_in = (e->h.algo == ALGO_MADDPG_ATT && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total
+    const int want_in = ((e->h.algo == ALGO_MADDPG_ATT || e->h.algo == ALGO_MAAC) && (net & 1)) ? e->h.rec.obs_total + e->h.rec.act_total
                         : (e->h.algo == ALGO_MAPPO_ATT && (net & 1)) ? e->h.rec.obs_total : N.L[head * nl].k;      // (an attention critic of either kind cuts its segments from the joint row)
     if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
     const bool masac_actor = e->h.algo == ALGO_MASAC && !(net & 1);      // its log_std is the head's second half, not an extra vector
@@ -922,6 +970,19 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
     if (e->h.algo == ALGO_MAPPO_ATT && (net & 1)) {      // the attention critic is no chain: its own forward (kernels_mappo_att.hip), V_i of the joint observation
         if (mode != FRL_ACT_RAW || ex) return fail(FRL_ERR_INVALID, "a MAPPO-attention critic acts through FRL_ACT_RAW on rows [obs_0 | .. | obs_{n-1}] (its value)");
         hipLaunchKernelGGL(mappo_att_v_kernel, dim3((n_rows + e->h.rc - 1) / e->h.rc, e->h.P), dim3(256), e->lds_bytes, e->stream, e->d, a);
+        HIP_TRY(hipGetLastError());
+        return FRL_OK;
+    }
+    if (e->h.algo == ALGO_MAAC) {      // LeakyReLU actors with a Categorical head, attention critics that are no chains: kernels_maac.hip's forwards
+        const bool critic = net & 1;
+        const bool ok = critic ? mode == FRL_ACT_RAW : (mode == FRL_ACT_CAT_SAMPLE || mode == FRL_ACT_ARGMAX || mode == FRL_ACT_RAW);
+        if (!ok || ex)
+            return fail(FRL_ERR_INVALID, "a MAAC engine acts through FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX / FRL_ACT_RAW (net 2i, agent i's observation) and FRL_ACT_RAW "
+                                         "(net 2i+1, rows [all obs | all one-hot actions]: all_q)");
+        if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE on a MAAC actor needs the Exp(1) draws in eps");
+        const dim3 grid((n_rows + e->h.rc - 1) / e->h.rc, e->h.P);
+        if (critic) hipLaunchKernelGGL(maac_q_kernel, grid, dim3(256), e->lds_bytes, e->stream, e->d, a);
+        else hipLaunchKernelGGL(maac_act_kernel, grid, dim3(256), e->lds_bytes, e->stream, e->d, a);
         HIP_TRY(hipGetLastError());
         return FRL_OK;
     }
@@ -1027,6 +1088,7 @@ extern "C" int frl_act(frl_engine* e, int net, int mode, int head, int use_targe
     if (head < 0 || head >= N.heads) return fail(FRL_ERR_INVALID, "head out of range");
     int nout = N.L[head * nl + nl - 1].n;
     if (e->h.algo == ALGO_MASAC && !(net & 1) && (mode & ~FRL_ACT_NO_OBSNORM) != FRL_ACT_RAW) nout /= 2;      // an action, not the [mean | log_std] head row
+    if (e->h.algo == ALGO_MAAC && (net & 1)) nout = e->h.rec.act_dim[net / 2];      // all_q (the net's last layer is bias_fc2, not the head)
     const size_t rows = (size_t)e->h.P * n_rows;
     const size_t in_n = rows * in_dim, out_n = rows * nout;
     int rc = act_scratch(e, in_n, out_n);
@@ -1055,7 +1117,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (!obs_host || !x || !store_act_out || !env_act_out || n_rows < 1) return fail(FRL_ERR_INVALID, "bad argument");
     const EngineDesc& h = e->h;
     if (is_mappo_family(h.algo)) return wrong_engine(h, "frl_act_explore");
-    if (h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_act_explore does not serve a MASAC engine: %s", algo_traits(h.algo).act_hint);
+    if (per_agent_alpha(h.algo)) return fail(FRL_ERR_STATE, "frl_act_explore does not serve a %s engine: %s", algo_traits(h.algo).name, algo_traits(h.algo).act_hint);
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
@@ -1226,6 +1288,7 @@ extern "C" int frl_obsnorm_enable(frl_engine* e, int on) {
     ENG(e);
     if (!e->has_nets) return fail(FRL_ERR_STATE, "replay-only engine has no networks");
     if (e->h.algo == ALGO_MASAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MASAC.py has no Batch_ObsNorm and kernels_masac.hip does not normalise");
+    if (e->h.algo == ALGO_MAAC) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: MAAC_discrete.py has no Batch_ObsNorm and kernels_maac.hip does not normalise");
     if (e->h.algo == ALGO_CEM_GD3PG) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: CEM_GD3PG.py has no Batch_ObsNorm and kernels_cem_gd3pg.hip does not normalise");
     if (e->h.algo == ALGO_DDPG_POPART) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: DDPG_simple_with_tricks.py has no Batch_ObsNorm and kernels_popart.hip does not normalise");
     if (e->h.algo == ALGO_GAIL_PPO) return fail(FRL_ERR_STATE, "frl_obsnorm_enable: PPO2.py has no Batch_ObsNorm (its env wrapper scales observations) and kernels_gail_ppo.hip does not normalise");

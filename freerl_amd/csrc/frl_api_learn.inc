@@ -41,6 +41,9 @@ static const LearnKernelRow kLearnKernels[] = {
     // MASAC on the row-chunk skeleton (kernels_masac.hip): the critic launch over (learner, agent) units, the actor launch over learners for one agent
     {FAM_MASAC, LK_CRITIC, 0, kLdsMasac, {{masac_critic_kernel, masac_critic_kernel}, {masac_critic_kernel, masac_critic_kernel}}},
     {FAM_MASAC, LK_ACTOR, 0, kLdsMasac, {{masac_actor_kernel, masac_actor_kernel}, {masac_actor_kernel, masac_actor_kernel}}},
+    // MAAC on the row-chunk skeleton (kernels_maac.hip): both launches over learners for one agent
+    {FAM_MAAC, LK_CRITIC, 0, kLdsMaac, {{maac_critic_kernel, maac_critic_kernel}, {maac_critic_kernel, maac_critic_kernel}}},
+    {FAM_MAAC, LK_ACTOR, 0, kLdsMaac, {{maac_actor_kernel, maac_actor_kernel}, {maac_actor_kernel, maac_actor_kernel}}},
 };
 
 // every kernel of the family may carve its row's LDS bytes, whichever of them the engine's shape resolves to
@@ -162,7 +165,9 @@ static void launch_prologue(frl_engine* e, const LearnStage& s, const LearnPlan&
     const dim3 blk(256);
     if (l.draw) {
         prof_begin(e, PK_DRAW);
-        hipLaunchKernelGGL(draw_kernel, dim3(s.units), blk, pl.draw.lds_bytes, s.st, e->d, pl.a, (pl.needs_noise ? 1 : 0) | pl.draw.flag);
+        const bool maac = pl.fam == FAM_MAAC;      // (its draws are Exp(1), not draw_kernel's normal ones: maac_noise_kernel)
+        hipLaunchKernelGGL(draw_kernel, dim3(s.units), blk, pl.draw.lds_bytes, s.st, e->d, pl.a, (pl.needs_noise && !maac ? 1 : 0) | pl.draw.flag);
+        if (maac) hipLaunchKernelGGL(maac_noise_kernel, dim3(s.units), blk, 0, s.st, e->d, pl.a);
         prof_end(e);
     }
     if (l.obsnorm) hipLaunchKernelGGL(obsnorm_kernel, dim3(s.pc), blk, 0, s.st, e->d, pl.a.batch, 0, s.p0);
@@ -302,6 +307,30 @@ static void launch_masac(frl_engine* e, const LearnStage& s, const LearnArgs& a)
     launch_rowchunk_update(e, s.st, actor ? s.pc : s.units, s.p0, rowchunk_ns(e->h, a.batch), ad, actor ? e->kern.actor.kr : e->kern.critic.kr, a);
 }
 
+// kernels_maac.hip, for the ONE agent a.agent over the learners.  Stage 0: critic i's gradient launch, then its own reduce and clip + Adam
+// over the two storage regions of its 12 trained tensors (targets untouched: the soft stage moves them).  Stage 1: actor i's gradient
+// launch and the common reduce + clip + Adam of its net.  Stream order makes critic i + 1 read the shared attention block, and actor i
+// the actors j < i, as stepped (MAAC_discrete.py:208-280)
+static void launch_maac(frl_engine* e, const LearnStage& s, const LearnArgs& a) {
+    const EngineDesc& h = e->h;
+    const bool actor = s.stage == 1;
+    const int ns = rowchunk_ns(h, a.batch);
+    AdamArgs ad = learn_adam_args(a, actor);
+    ad.agent1 = a.agent + 1;
+    if (actor) {
+        launch_rowchunk_update(e, s.st, s.pc, s.p0, ns, ad, e->kern.actor.kr, a);
+        return;
+    }
+    prof_begin(e, PK_GRAD_CRITIC);
+    hipLaunchKernelGGL(e->kern.critic.kr, dim3(((s.pc + 7) / 8) * 8 * ns), dim3(256), e->lds_bytes, s.st, e->d, a, ns);
+    prof_end(e);
+    ad.ns = ns; ad.p0 = s.p0; ad.G = h.Gmax;
+    prof_begin(e, PK_ADAM_CRITIC);
+    hipLaunchKernelGGL(maac_reduce_kernel, dim3(s.pc * h.Gmax), dim3(256), 0, s.st, e->d, ad);
+    hipLaunchKernelGGL(maac_step_kernel, dim3(s.pc * h.Gmax), dim3(256), 0, s.st, e->d, ad);
+    prof_end(e);
+}
+
 // one entry of the plan's list
 static void launch_learn_stage(frl_engine* e, hipStream_t st, const LearnPlan& pl, const LearnLaunch& l, const DqnStepArgs* step, const SoloStepArgs* sstep) {
     const EngineDesc& h = e->h;
@@ -314,6 +343,8 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, const LearnPlan& p
         for (int i = 0; i < h.n_nets; ++i) biggest = std::max(biggest, h.net[i].size);
         const int per = std::max(1, std::min((biggest + 4095) / 4096, 4 * e->n_cus / std::max(1, s.pc * h.n_nets)));
         hipLaunchKernelGGL(soft_update_kernel, dim3(s.pc * h.n_nets, per), dim3(256), 0, st, e->d, a.tau, s.p0);
+        if (pl.fam == FAM_MAAC)      // ... and the n target attention blocks, which are no nets of the learner's
+            hipLaunchKernelGGL(maac_soft_kernel, dim3(s.pc * h.n_agents, std::max(1, std::min((h.maac_att.size + 4095) / 4096, 16))), dim3(256), 0, st, e->d, a.tau, s.p0);
         prof_end(e);
         return;
     }
@@ -327,6 +358,7 @@ static void launch_learn_stage(frl_engine* e, hipStream_t st, const LearnPlan& p
         case FAM_SOLOW: launch_solow(e, s, pl, a); break;
         case FAM_WIDE: case FAM_WIDE16: launch_wide(e, s, a); break;
         case FAM_MASAC: launch_masac(e, s, a); break;
+        case FAM_MAAC: launch_maac(e, s, a); break;
     }
 }
 

@@ -13,7 +13,7 @@ constexpr float kLeakySlope = 0.01f;     // nn.LeakyReLU's default negative_slop
 enum Algo : int { ALGO_DQN = 0, ALGO_DDPG = 1, ALGO_TD3 = 2, ALGO_SAC = 3, ALGO_MADDPG = 4, ALGO_PPO = 5, ALGO_SAC_DISCRETE = 6,
                   ALGO_REINFORCE = 7, ALGO_ENVELOPE_DQN = 8, ALGO_ENVELOPE_DDPG = 9, ALGO_GAIL = 10, ALGO_MAPPO = 11, ALGO_IPPO = 12, ALGO_HAPPO = 13,
                   ALGO_MADDPG_ATT = 14, ALGO_MASAC = 15, ALGO_GAIL_PPO = 16, ALGO_CEM_GD3PG = 18 /* 17: unassigned */,
-                  ALGO_DDPG_POPART = 20 /* 19: unassigned */, ALGO_MAPPO_ATT = 22 /* 21: unassigned */ };
+                  ALGO_DDPG_POPART = 20 /* 19: unassigned */, ALGO_MAPPO_ATT = 22 /* 21: unassigned */, ALGO_MAAC = 24 /* 23: unassigned */ };
 
 // One nn.Linear in the engine-internal layout: Wk[k_pad][n_pad] (CONTRACTION-major for the forward pass: row =
 // input feature, n contiguous), zero padded, then b[n_pad].  theta / target / m / v / grad / slab all use it;
@@ -117,6 +117,18 @@ constexpr int kAttRc = 16;               // rows per chunk of this family: 16 ro
 // MASAC (kernels_masac.hip, device/masac.hpp; MAAC_file/MASAC.py): floats per chunk row behind carve_lds()'s region — the updating actor's
 // head row [mean | log_std] (2 x act_dim columns), kept from its forward until its head delta is formed behind the two critic passes
 constexpr int masac_row_extra(int act_max) { return (2 * act_max + 3) / 4 * 4; }
+
+// MAAC (device/maac.hpp, kernels_maac.hip; MAAC_file/MAAC_discrete.py with Attention.py:63-231): net 2i+1 of an ALGO_MAAC engine is critic
+// i's own seven layers in the reference's state_dict order; the attention block (query, [key | value] stacked, fc_out) is the NetDesc
+// EngineDesc::maac_att, kept in n slots behind the nets of a learner's stride (EngineDesc::maac_off; rowchunk_layout.h: maac_att_offset).
+// Neither is a chain.  A head is hidden / 4 columns wide (hidden a multiple of 32, at most 128).
+constexpr int kMaacHeads = 4, kMaacMaxHidden = 128;
+enum MaacLayer : int { MAAC_ENC_S = 0, MAAC_ENC_SA = 1, MAAC_ENC_A = 2, MAAC_FC1 = 3, MAAC_FC2 = 4, MAAC_BIAS1 = 5, MAAC_BIAS2 = 6, MAAC_LAYERS = 7 };
+enum MaacAttLayer : int { MAAC_Q = 0, MAAC_KV = 1, MAAC_O = 2, MAAC_ATT_LAYERS = 3 };
+constexpr int kMaacRc = 16;              // rows per chunk: one MFMA M tile; a (row, head) pair is 16 lanes' work
+// floats per chunk row behind carve_lds()'s region (device/maac.hpp: carve_maac): three [2 hidden] rows (x = [s_i | other], [K_j | Vpre_j],
+// d x), five [hidden] rows (Q, attn, d attn, d Q, d s), the raw scores of the n_agents - 1 others x 4 heads, then m, l and D per head
+constexpr int maac_row_extra(int hidden, int n_agents) { return 3 * (2 * hidden + 4) + 5 * (hidden + 4) + kMaacHeads * (n_agents - 1) + 12; }
 
 // float index of W[out n][in k] inside a layer's weight block (host and device)
 #if defined(__HIPCC__)
@@ -265,6 +277,11 @@ struct EngineDesc {
     float* popart;        // [P][popart_stride]
     int popart_stride;    // floats per learner: popart_block_floats()
     float* popart_out;    // [P][8] what frl_popart_ddpg_args::out returns, written by popart_step_kernel
+    // MAAC (kernels_maac.hip, ALGO_MAAC): the attention block's region of a learner's stride in theta / target / m / v / grad / slab: n_agents
+    // slots of maac_att.size floats from float maac_off.  theta: slot 0 is the ONE online block every critic reads and every agent's Adam
+    // steps (the other slots are unused); target: slot i is target critic i's copy; m, v, grad, slab: slot i is agent i's
+    int maac_off;
+    NetDesc maac_att;     // query [H, H], [key | value] [2 H, H], fc_out [H, H]; query's and key's bias slots stay zero
 };
 
 // Hyper-parameters of one learn() call (passed by value to the kernels).
@@ -292,7 +309,7 @@ struct LearnArgs {
     int fuse_actor;       // kernels_solow.hip: this call's critic AND actor stage run in one launch (solow_step_*); frl_learn skips the actor launch
     int huber;            // TD loss: 0 F.mse_loss (every hot-path loss of the reference), 1 Huber with `huber_delta`
     float huber_delta;    // (the reference's huber_loss, MAPPO_file/MAPPO.py:273-276: e^2/2 if |e| <= d else d(|e| - d/2), mean)
-    int agent;            // masac_actor_kernel: the ONE agent whose actor this launch differentiates (units = learners); unused elsewhere
+    int agent;            // masac_actor_kernel, the maac kernels: the ONE agent this launch works for (units = learners); unused elsewhere
 };
 
 }  // namespace frl

@@ -278,6 +278,18 @@ __global__ void masac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs
 __global__ void masac_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
 __global__ void masac_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
 
+// kernels_maac.hip: MAAC (MAAC_file/MAAC_discrete.py, Attention.py): the gradient kernels of an ALGO_MAAC engine in the row-chunk launch
+// shape, both over learners for the ONE agent LearnArgs::agent; one critic's reduce and clip + Adam over its own net and the shared attention
+// block (AdamArgs::agent1); the target attention blocks' soft update; Exp(1) draws for a device-drawn call; the forwards for frl_act
+__global__ void maac_critic_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void maac_actor_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a, int ns);
+__global__ void maac_reduce_kernel(const EngineDesc* __restrict__ Dp, AdamArgs a);
+__global__ void maac_step_kernel(const EngineDesc* __restrict__ Dp, AdamArgs a);
+__global__ void maac_soft_kernel(const EngineDesc* __restrict__ Dp, float tau, int p0);
+__global__ void maac_noise_kernel(const EngineDesc* __restrict__ Dp, LearnArgs a);
+__global__ void maac_act_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+__global__ void maac_q_kernel(const EngineDesc* __restrict__ Dp, ActArgs a);
+
 // kernels_happo.hip: HAPPO (MAPPO_file/HAPPO.py): one launch per visiting position, after MAPPO's three advantage launches
 struct HappoArgs {
     const int* order;     // [P][n] the agent visited at each position

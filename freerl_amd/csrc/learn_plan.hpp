@@ -120,7 +120,7 @@ struct LearnFacts {
 // what frl_rollout folds into the step (FOLD_NONE: a plain frl_learn)
 enum LearnFold { LEARN_PLAIN, LEARN_FOLD_DQN, LEARN_FOLD_SOLO };
 
-// One launch_learn_stage: stage 0 critic | Q, 1 actor (agent: MASAC's one agent per launch), 2 the soft update; units = (learner, agent)
+// One launch_learn_stage: stage 0 critic | Q, 1 actor (agent: MASAC's and MAAC's one agent per launch), 2 the soft update; units = (learner, agent)
 // pairs.  draw / obsnorm / noisy_materialise: draw_kernel, obsnorm_kernel, noisy_materialise_kernel run in front of it
 struct LearnLaunch { int stage = 0, agent = 0, units = 0; bool draw = false, obsnorm = false, noisy_materialise = false; };
 struct LearnPlan {
@@ -141,7 +141,7 @@ struct LearnPlan {
     int pre_extra = 0;
     int head[2] = {0, 0}, tail[2] = {0, 0};      // a folded solo step: SoloStepArgs::head / tail of the critic and the actor launch
     int n_launches = 0;
-    LearnLaunch launches[FRL_MAX_AGENTS + 2];
+    LearnLaunch launches[2 * FRL_MAX_AGENTS + 2];      // (the most: MAAC's critic and actor launch per agent, then the soft stage)
 };
 
 // FRL_OK and *out, or the refusal's code and *message: everything that can refuse a frl_learn, in one order, before anything is flushed,
@@ -158,11 +158,13 @@ inline int plan_learn(const LearnFacts& F, const LearnKnobs& k, const frl_learn_
     LearnPlan pl;
     pl.dev_rng = args.idx == nullptr && !args.per;
     if (pl.dev_rng && min_size < 2 * B) return FRL_REFUSE_STATE(message, "device index draw needs len(buffer) >= 2*batch (have %d); pass idx", min_size);
-    const bool maddpg = is_maddpg(h.algo), masac = h.algo == FRL_ALGO_MASAC, dqn = h.algo == FRL_ALGO_DQN;
+    const bool maddpg = is_maddpg(h.algo), masac = h.algo == FRL_ALGO_MASAC, maac = h.algo == FRL_ALGO_MAAC, dqn = h.algo == FRL_ALGO_DQN;
     const bool td3_like = h.algo == FRL_ALGO_TD3 || maddpg;            // MADDPG + noise/delay = MATD3_simple.py (ATT-MADDPG: do_actor only)
-    pl.needs_noise = h.algo == FRL_ALGO_SAC || masac || (td3_like && args.use_policy_noise);
+    pl.needs_noise = h.algo == FRL_ALGO_SAC || masac || maac || (td3_like && args.use_policy_noise);      // (MAAC: Exp(1) draws, not normal ones)
     if (masac && args.use_policy_noise) return FRL_REFUSE_STATE(message, "frl_learn: MASAC has no target policy smoothing (MATD3's): use_policy_noise must be 0");
     if (masac && args.loss_kind == FRL_LOSS_HUBER) return plan_refuse(message, "MASAC's critic loss is F.mse_loss (MASAC.py:241): no Huber variant");
+    if (maac && args.use_policy_noise) return FRL_REFUSE_STATE(message, "frl_learn: MAAC has no target policy smoothing (MATD3's): use_policy_noise must be 0");
+    if (maac && args.loss_kind == FRL_LOSS_HUBER) return plan_refuse(message, "MAAC's critic loss is MSELoss (MAAC_discrete.py:236): no Huber variant");
     if (h.algo == FRL_ALGO_MADDPG_ATT && args.use_policy_noise) return plan_refuse(message, "ATT-MADDPG has no target policy smoothing: use_policy_noise must be 0");
     if (!pl.dev_rng && pl.needs_noise && !args.noise) return plan_refuse(message, "idx given without noise: both or neither");
     if (args.idx)
@@ -250,6 +252,15 @@ inline int plan_learn(const LearnFacts& F, const LearnKnobs& k, const frl_learn_
         l.stage = stage; l.agent = agent; l.units = units;
         return l;
     };
+    if (fam == FAM_MAAC) {      // DESIGN.md "MAAC": per agent, in agent order, critic i (+ its reduce and step) then actor i (+ its); then every target
+        for (int ag = 0; ag < h.n_agents; ++ag) {
+            push(0, ag).draw = ag == 0 && draw_kernel_runs;
+            push(1, ag);
+        }
+        push(2, 0);
+        *out = pl;
+        return FRL_OK;
+    }
     LearnLaunch& c = push(0, 0);
     if (fam != FAM_DQN_FUSED) {      // (the one-launch DQN update draws, normalises and materialises for itself)
         c.draw = draw_kernel_runs;

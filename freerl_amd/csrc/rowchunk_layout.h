@@ -93,6 +93,13 @@ FRL_LAYOUT_FN size_t popart_part_offset(const EngineDesc& D, int p, int sl) { re
 FRL_LAYOUT_FN size_t popart_y_offset(const EngineDesc& D, int p, int r0) { return popart_offset(D, p) + kPopartHead + (size_t)kPopartPart * D.S + r0; }
 FRL_LAYOUT_FN size_t popart_floats(const EngineDesc& D) { return popart_offset(D, D.P); }
 
+// ------------------------------------------------------------------------------ MAAC (kernels_maac.hip)
+// The attention block's slots behind the nets of a learner's stride (frl_desc.h: EngineDesc::maac_off), and slot `slot` of slice sl's slab
+FRL_LAYOUT_FN size_t maac_att_offset(const EngineDesc& D, int slot) { return (size_t)D.maac_off + (size_t)slot * D.maac_att.size; }
+FRL_LAYOUT_FN size_t maac_att_slab_offset(const EngineDesc& D, int p, int sl, int slot) {
+    return ((size_t)p * D.S + sl) * D.learner_stride + maac_att_offset(D, slot);
+}
+
 // ------------------------------------------------------------------------------ what the plan allocates
 FRL_LAYOUT_FN size_t slab_floats(const EngineDesc& D) { return (size_t)D.P * D.S * D.learner_stride; }
 FRL_LAYOUT_FN size_t part_floats(const EngineDesc& D) { return part_offset(D, D.P, 0, 0); }

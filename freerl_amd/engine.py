@@ -87,7 +87,7 @@ class Engine:
         self.width = lay.width
         self.act_max = max(lay.act_dim[j] for j in range(self.n_agents))
         # draw sets per (learner, updating agent) of learn()'s `noise` (include/freerl_hip.h: frl_learn_args.noise)
-        self.noise_sets = 2 * self.n_agents + 1 if self.algo == N.ALGO_MASAC else max(2, self.n_agents)
+        self.noise_sets = 2 * self.n_agents + 1 if self.algo in (N.ALGO_MASAC, N.ALGO_MAAC) else max(2, self.n_agents)
         self.reward_dim = lay.done_off - lay.rew_off if self.n_agents == 1 else 1      # (envelope DQN / DDPG: the reward vector's columns)
         n = C.c_int(0)
         N.check(self._L.frl_net_count(self._h, C.byref(n)))

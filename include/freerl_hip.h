@@ -127,7 +127,7 @@ enum frl_algo {
                                   FRL_ACT_RELU; discrete, twin_critic, dueling, noisy, c51_atoms and n_agents != 1 are refused.  Updated by
                                   frl_popart_ddpg_learn only.  frl_act as on a FRL_ALGO_DDPG engine: FRL_ACT_TANHHEAD on net 0,
                                   FRL_ACT_RAW on net 1 = the LOWER critic's raw output h (Q = sigma (W h + b) + mu).  frl_version() 115 */
-    FRL_ALGO_MAPPO_ATT = 22    /* (21 is unassigned, as 17 and 19 are.)  MAPPO_file/MAPPO_attention.py with improvement['attention'] (attention.py:85-205):
+    FRL_ALGO_MAPPO_ATT = 22,   /* (21 is unassigned, as 17 and 19 are.)  MAPPO_file/MAPPO_attention.py with improvement['attention'] (attention.py:85-205):
                                   a FRL_ALGO_MAPPO engine's record, actors (net 2i) and learn arguments, but net 2i+1 is agent i's
                                   Attention_Critic, six layers in this order: encoder_fc_s obs_dim -> 128, l1 256 -> 128, l3 128 -> 1, then
                                   the attention block query 128 -> 128, [key ; value.0] 128 -> 256 (rows [0, 128) the key) and fc_out
@@ -138,6 +138,21 @@ enum frl_algo {
                                   FRL_MAX_AGENTS, every obs_dim equal, hidden 128; extra_cols as FRL_ALGO_MAPPO without masks or state.
                                   Updated by frl_mappo_att_learn only.  frl_act: the actors as on FRL_ALGO_MAPPO; FRL_ACT_RAW on net 2i+1
                                   with rows [obs_0 | .. | obs_{n-1}] is V_i.  frl_net_norm_set serves it.  frl_version() 116 */
+    FRL_ALGO_MAAC = 24         /* (23 is unassigned, as 17, 19 and 21 are.)  MAAC_file/MAAC_discrete.py with Attention.py: MADDPG's joint record
+                                  with the ONE-HOT action in the action block (frl_config.discrete must be 1; act_dim[j] = agent j's action
+                                  count), learnt by frl_learn with 2 n + 1 sets of Exp(1) draws per updating agent (target actors, online
+                                  actors, the updating actor again), as FRL_ALGO_MASAC lays out its noise.  Net 2i: actor i, obs_dim ->
+                                  hidden -> hidden -> act_dim logits, LeakyReLU(0.01).  Net 2i+1: critic i's own seven layers in state_dict
+                                  order: encoder_fc_s, encoder_fc_sa, encoder_fc_a, fc1, fc2, bias_fc1, bias_fc2 (encoder_fc_sa, encoder_fc_a,
+                                  bias_fc1 and bias_fc2 are stored, copied to the target and never trained).  The attention block is addressed as nets 2 n + i
+                                  (frl_params_get / _set, frl_net_num_params, frl_opt_step_get / _set; frl_net_count stays 2 n): host order
+                                  query.weight, key.weight, value.0.weight, value.0.bias, fc_out.weight, fc_out.bias; FRL_PARAM_ONLINE of every
+                                  i is the ONE block all online critics share, FRL_PARAM_TARGET target critic i's copy, FRL_PARAM_ADAM_M / _V
+                                  agent i's moments, the step count critic i's (net 2i+1).  Alpha (a constant): frl_alpha_set_agent.
+                                  2 <= n_agents <= FRL_MAX_AGENTS, hidden a multiple of 32 up to 128, hidden_act FRL_ACT_LEAKY_RELU.
+                                  frl_act: FRL_ACT_CAT_SAMPLE / FRL_ACT_ARGMAX / FRL_ACT_RAW on net 2i with agent i's observation;
+                                  FRL_ACT_RAW on net 2i+1 with rows [all obs | all one-hot actions]: all_q, act_dim[i] columns.
+                                  frl_version() 117 */
 };
 
 enum frl_activation { FRL_ACT_NONE = 0, FRL_ACT_RELU = 1, FRL_ACT_TANH = 2,
