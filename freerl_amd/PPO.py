@@ -143,9 +143,14 @@ class PPO:
             a, lp = self._e.act(0, N.ACT_CAT_SAMPLE, np.asarray(obs, dtype=np.float32).reshape(1, 1, -1), eps=q,
                                 want_logp=True)
             return np.int64(a[0, 0, 0]), np.float32(lp[0, 0, 0])
+        if self.actor_dist["Beta"] and self._rng == "device":
+            # forward, Beta draw (Marsaglia-Tsang gammas on the engine's Philox stream) and log-prob in one launch
+            a, lp = self._e.act(0, N.ACT_PPO_SAMPLE, np.asarray(obs, dtype=np.float32).reshape(1, 1, -1),
+                                out_dim=self._act_dim, want_logp=True)
+            return a[0, 0], lp[0, 0]                                          # action in (0,1) (:243-247)
         if self.actor_dist["Beta"]:
-            # alpha, beta come from the GPU forward; the Beta variate itself is torch's own sampler on the host (its gamma
-            # rejection sampler consumes the generator in C++ and cannot be fed injected draws): one [1, A] draw per env step
+            # rng="host": alpha, beta come from the GPU forward; the Beta variate itself is torch's own sampler on the host (its
+            # gamma rejection sampler consumes the generator in C++ and cannot be fed injected draws): one [1, A] draw per env step
             al, be = self.agent.actor.alpha_beta(np.asarray(obs, dtype=np.float32).reshape(1, -1))
             dist = torch.distributions.Beta(al, be)
             act = dist.sample()

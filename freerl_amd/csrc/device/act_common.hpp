@@ -5,16 +5,64 @@
 #include "c51.hpp"
 #include "onpolicy.hpp"
 #include "chain_net.hpp"
+#include "special.hpp"
 
 namespace frl {
 
+// ---- The Beta actor's draw (Actor_Beta, PPO_with_tricks.py:120-151,243-247): act_epilogue<true>, ACTM_PPO_SAMPLE on a beta_actor engine.
+constexpr int kBetaTries = 16;                                                  // attempts per gamma variate, a bound and the draws' address pitch
+constexpr unsigned kStreamGammaA = 0x9400u, kStreamGammaB = 0x9500u;      // Philox streams of Ga and Gb, next to 0x9100 / 0x9200 / 0x9300 below
+
+// G ~ Gamma(shape, 1) by Marsaglia-Tsang (2000): d = shape - 1/3, c = 1 / sqrt(9 d); with n ~ N(0,1), u ~ U(0,1] and v = (1 + c n)^3
+// accept d v when v > 0 and ln u < n^2 / 2 + d - d v + d ln v.  shape = softplus(.) + 1 >= 1 here, so the method's boost for shapes
+// below 1 (Gamma(shape + 1) u^(1/shape)) has no branch.  One Philox call per attempt gives n (z, w) and u (x); attempt t of element e
+// reads counter word e0 + t, so a draw depends on (launch, learner, row, dimension) only.  Acceptance is >= 0.95 at shapes >= 1:
+// all kBetaTries attempts fail with probability < 1e-20, and then the variate is d (the mode of d v), never a loop without end.
+__device__ __forceinline__ float gamma_draw(float shape, unsigned long long counter, unsigned stream, unsigned e0, unsigned long long key) {
+    const float d = shape - (1.f / 3.f), c = rsqrtf(9.f * d);
+    float g = d;
+    for (int t = 0; t < kBetaTries; ++t) {
+        const Philox4 r = philox4x32_10(counter, stream, e0 + (unsigned)t, key);
+        float n, unused;
+        normal2(r, n, unused);
+        const float w = 1.f + c * n, v = w * w * w;
+        if (v > 0.f && logf(u01(r.x)) < 0.5f * n * n + d - d * v + d * logf(v)) { g = d * v; break; }
+    }
+    return g;
+}
+
+// One thread per (row, dimension c) of the 2A-wide linear head [alpha_layer ; beta_layer] in outb: alpha = softplus(z[c]) + 1 and
+// beta = softplus(z[A + c]) + 1 with ppo_update_kernel's own softplus (float softplus_t, then + 1 in double), both gammas drawn by
+// this thread, x = Ga / (Ga + Gb) clamped into [FLT_MIN, 1 - 2^-24] so that log(x) and log1p(-x) of the STORED float are finite
+// in the update, the per-dimension log-prob in double as the update recomputes it, and the reference loop's
+// action_ = clip(x * max_action, -max_action, max_action) (:529-530: it maps (0,1) into [0, max_action], kept as the script has it).
+__device__ __forceinline__ void beta_sample_rows(const ActArgs& a, lds_cf outb, int op, int nv, int r0, int p, int A, unsigned long long key) {
+    for (int e = threadIdx.x; e < nv * A; e += kWG) {
+        const int r = e / A, c = e - r * A;
+        const size_t o = ((size_t)p * a.n_rows + r0 + r) * A + c;
+        const double al = (double)softplus_t(outb[r * op + c]) + 1.0, be = (double)softplus_t(outb[r * op + A + c]) + 1.0;
+        const unsigned e0 = (unsigned)((r0 + r) * A + c) * (unsigned)kBetaTries;
+        const float ga = gamma_draw((float)al, a.rng_counter, kStreamGammaA, e0, key);
+        const float gb = gamma_draw((float)be, a.rng_counter, kStreamGammaB, e0, key);
+        const float x = fminf(fmaxf(ga / (ga + gb), 1.17549435e-38f), 1.f - 5.9604645e-8f);
+        a.out[o] = x;
+        if (a.out_logp) a.out_logp[o] = (float)((al - 1.0) * log((double)x) + (be - 1.0) * log1p(-(double)x) - lbeta_d(al, be));
+        if (a.env_out) a.env_out[o] = fminf(fmaxf(x * a.max_action, -a.max_action), a.max_action);
+    }
+}
+
 // Everything after the head's output rows are in LDS (outb[row * op + column], rows r0 .. r0 + nv of learner p): the mode's
 // action rule and, for the collectors, the exploration rule.  Shared by act_kernel (row-chunk forward, Wk parameters) and
-// act_frag_kernel (register-chained forward, fragment-image parameters).
+// act_frag_kernel (register-chained forward, fragment-image parameters).  kBetaHead: compiled with the Beta draw above — act_kernel
+// alone, the one forward a Beta engine's actor takes (PPO engines never hold fragment images); every other kernel's code is as it was.
+template <bool kBetaHead = false>
 __device__ __forceinline__ void act_epilogue(const EngineDesc& D, const ActArgs& a, const NetDesc& N, g_cf theta, lds_f outb, int op,
                                              int nv, int r0, int p, int nout) {
     // device-side draws of this launch: Philox keyed like draw_kernel's (seed, learner), one counter value per launch
     const unsigned long long key = D.seed + 0x9E3779B97F4A7C15ull * (p + 1);
+    if constexpr (kBetaHead) {
+        if (D.beta_actor && a.mode == ACTM_PPO_SAMPLE) { beta_sample_rows(a, outb, op, nv, r0, p, nout / 2, key); return; }
+    }
     auto normal_at = [&](unsigned stream, unsigned e) {
         float n0, n1;
         normal2(philox4x32_10(a.rng_counter, stream, e, key), n0, n1);

@@ -940,7 +940,10 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
                         : (e->h.algo == ALGO_MAPPO_ATT && (net & 1)) ? e->h.rec.obs_total : N.L[head * nl].k;      // (an attention critic of either kind cuts its segments from the joint row)
     if (in_dim != want_in) return fail(FRL_ERR_INVALID, "in_dim %d != layer input %d", in_dim, want_in);
     const bool masac_actor = e->h.algo == ALGO_MASAC && !(net & 1);      // its log_std is the head's second half, not an extra vector
-    if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0 && !(masac_actor && mode == FRL_ACT_SAC_SAMPLE)) return fail(FRL_ERR_INVALID, "net has no log_std");
+    // Actor_Beta has no log_std either: FRL_ACT_PPO_SAMPLE samples its own distribution, Beta(alpha, beta), always from the launch's Philox stream
+    const bool beta_draw = e->h.algo == ALGO_PPO && e->h.beta_actor && net == 0 && mode == FRL_ACT_PPO_SAMPLE;
+    if (beta_draw && eps_dev) return fail(FRL_ERR_INVALID, "FRL_ACT_PPO_SAMPLE on a Beta actor draws on the device (a rejection sampler has no draws to inject): eps must be NULL");
+    if ((mode == FRL_ACT_SAC_SAMPLE || mode == FRL_ACT_PPO_SAMPLE) && N.extra_n == 0 && !(masac_actor && mode == FRL_ACT_SAC_SAMPLE) && !beta_draw) return fail(FRL_ERR_INVALID, "net has no log_std");
     const bool gail_ppo = e->h.algo == ALGO_GAIL_PPO;      // (its sampling modes draw for themselves when no eps is given: below)
     if (mode == FRL_ACT_CAT_SAMPLE && !eps_dev && !(ex && ex->device_eps) && !gail_ppo) return fail(FRL_ERR_INVALID, "FRL_ACT_CAT_SAMPLE needs the Exp(1) draws in eps");
     if (n_rows < 1) return fail(FRL_ERR_INVALID, "n_rows must be >= 1");
@@ -962,6 +965,7 @@ static int launch_act(frl_engine* e, int net, int mode_flags, int head, int use_
         a.scale = ex->scale_dev; a.ou_state = ex->ou_state_dev; a.flags = ex->flags_dev; a.env_out = ex->env_out_dev;
         if (!build_only) a.rng_counter = e->rng_counter++;
     }
+    if (beta_draw && !ex) { a.device_eps = 1; a.rng_counter = e->rng_counter++; }      // frl_act: a counter value per call, as a collector's launch takes one
     a.net = net; a.use_target = use_target; a.mode = mode; a.n_rows = n_rows; a.head = head; a.in_dim = in_dim;
     const int agent = e->h.n_agents > 1 ? net / 2 : 0;            // MADDPG: only the actors (even nets) take a single agent's obs
     a.normalize = (!no_norm && e->h.obs_norm_on && (e->h.n_agents == 1 || net % 2 == 0) && in_dim == e->h.rec.obs_dim[agent]) ? 1 : 0;
@@ -1089,6 +1093,7 @@ extern "C" int frl_act(frl_engine* e, int net, int mode, int head, int use_targe
     int nout = N.L[head * nl + nl - 1].n;
     if (e->h.algo == ALGO_MASAC && !(net & 1) && (mode & ~FRL_ACT_NO_OBSNORM) != FRL_ACT_RAW) nout /= 2;      // an action, not the [mean | log_std] head row
     if (e->h.algo == ALGO_MAAC && (net & 1)) nout = e->h.rec.act_dim[net / 2];      // all_q (the net's last layer is bias_fc2, not the head)
+    if (e->h.algo == ALGO_PPO && e->h.beta_actor && net == 0 && (mode & ~FRL_ACT_NO_OBSNORM) == FRL_ACT_PPO_SAMPLE) nout /= 2;      // a Beta draw, not the [alpha | beta] head row
     const size_t rows = (size_t)e->h.P * n_rows;
     const size_t in_n = rows * in_dim, out_n = rows * nout;
     int rc = act_scratch(e, in_n, out_n);
@@ -1120,6 +1125,7 @@ extern "C" int frl_act_explore(frl_engine* e, int mode, int n_rows, const float*
     if (per_agent_alpha(h.algo)) return fail(FRL_ERR_STATE, "frl_act_explore does not serve a %s engine: %s", algo_traits(h.algo).name, algo_traits(h.algo).act_hint);
     if (h.n_agents != 1) return fail(FRL_ERR_STATE, "frl_act_explore: single-agent engines");
     if (*algo_traits(h.algo).act_hint) return wrong_engine(h, "frl_act_explore");
+    if (h.beta_actor && mode == FRL_ACT_PPO_SAMPLE) return fail(FRL_ERR_INVALID, "frl_act_explore: a Beta actor samples through frl_act or frl_ppo_rollout");      // (refused before the draw existed, too)
     const int O = h.rec.obs_dim[0], nout = h.net[0].L[h.net[0].n_layers / h.net[0].heads - 1].n;
     const bool disc = (mode == FRL_ACT_ARGMAX);
     const size_t rows = (size_t)h.P * n_rows, in_n = rows * O, out_n = rows * nout;

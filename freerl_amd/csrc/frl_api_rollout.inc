@@ -654,7 +654,6 @@ extern "C" int frl_ppo_rollout(frl_engine* e, frl_envpool* p, const frl_ppo_roll
     const EngineDesc& h = e->h;
     const frl::EnvSpec& es = p->pool->spec;
     if (h.algo != ALGO_PPO) return wrong_engine(h, "frl_ppo_rollout");
-    if (h.beta_actor) return fail(FRL_ERR_STATE, "frl_ppo_rollout: Gaussian and Categorical actors only");
     const int E = ra->envs_per_learner, Tseg = ra->steps_per_env, n = p->pool->n, T = E * Tseg;
     if (E < 1 || Tseg < 1 || n != h.P * E) return fail(FRL_ERR_INVALID, "pool has %d envs, engine needs P*E = %d*%d", n, h.P, E);
     if (T != ra->learn.horizon || T > h.capacity) return fail(FRL_ERR_INVALID, "horizon %d != E*steps_per_env = %d (capacity %d)", ra->learn.horizon, T, h.capacity);
@@ -679,7 +678,8 @@ extern "C" int frl_ppo_rollout(frl_engine* e, frl_envpool* p, const frl_ppo_roll
     tally.t0 = std::chrono::steady_clock::now();
     for (int it = 0; it < ra->n_iters; ++it) {
         for (int t = 0; t < Tseg; ++t) {
-            // Normal.sample(): mean + std * N(0,1) (:240-242); Categorical.sample(): argmax(p / q), q ~ Exp(1) (:249-251) — the
+            // Normal.sample(): mean + std * N(0,1) (:240-242); Categorical.sample(): argmax(p / q), q ~ Exp(1) (:249-251);
+            // Beta.sample(): Ga / (Ga + Gb) (:243-247, a beta_actor engine's FRL_ACT_PPO_SAMPLE, A log-prob columns) — the
             // variates come from the launch's Philox stream; action_ = clip(action * max_action) (:529-530) in the same launch
             ActExplore ex;
             ex.x.kind = FRL_EXPLORE_NONE; ex.x.max_action = ma; ex.x.scale = 1.f;

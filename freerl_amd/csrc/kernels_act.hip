@@ -33,9 +33,11 @@ __global__ __launch_bounds__(256) void act_kernel(const EngineDesc* __restrict__
                        as_global(D.obsnorm + (((size_t)p * nag + (nag - 1)) * nag + j) * D.obsnorm_w), D.rec.obs_dim[j]);
     }
     __syncthreads();
-    const int out_act = (a.mode == ACTM_TANH || a.mode == ACTM_PPO_SAMPLE) ? ACT_TANH : ACT_NONE;
+    // (a Beta actor's head [alpha_layer ; beta_layer] stays linear under ACTM_PPO_SAMPLE, as ppo_update_kernel forwards it: the
+    //  softplus is the epilogue's)
+    const int out_act = (a.mode == ACTM_TANH || (a.mode == ACTM_PPO_SAMPLE && !D.beta_actor)) ? ACT_TANH : ACT_NONE;
     mlp_fwd(N, l0, nl, theta, S, out_act);
-    act_epilogue(D, a, N, theta, S.outb, S.op, nv, r0, p, N.L[l0 + nl - 1].n);
+    act_epilogue<true>(D, a, N, theta, S.outb, S.op, nv, r0, p, N.L[l0 + nl - 1].n);
 }
 
 // The same for the engines of the register-chained kernels (NetDesc::frag): device/act_common.hpp's act_frag_body;
